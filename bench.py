@@ -12,6 +12,12 @@ Workload (BASELINE.json configs[1]): NAM A1 WaveNet 'Standard', 1024 batched str
 
 Prints ONE JSON line (rank 0).  PyTorch is plumbing only: device buffers, the stream/event used for
 timing, and torch.distributed (RCCL) for the barrier + max-over-ranks.
+
+A plain run does only what the headline figure needs: set up, ramp and warm up, time the K steps, print the line.  Everything
+else the line can carry -- the oracle spot check of the last timed step, the isolated-step latency probe, the rotation regime,
+the exact-f32 and resident-launch side runs, the host-buffer paths, the CPU baseline -- runs under --full (each still switched
+off by its own --no-* / --rotate 0 option there).  --dump-outputs DIR writes the output rows of the last timed step to
+DIR/output.npy (float32): inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -30,6 +36,7 @@ BLOCK = 128
 MODEL_FILE = os.path.join(ROOT, "tests", "golden", "models", "BossWN-standard.nam")
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s (spec)
 FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense f32 MFMA peak
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: all ranks' files together
 
 
 def usable_cores():
@@ -231,6 +238,19 @@ def parity_spot_check(check_rows, x, y, issued, nbuf, mdir):
     return {"rms": worst, "per_model": per_model}
 
 
+def dump_outputs(path, y, rank, world):
+    """--dump-outputs: what the last timed step wrote to the output array -- the rows a caller of NA_BatchProcessDevice receives --
+    as <path>/output.npy (rank r > 0: output_rank<r>.npy), float32, one row per stream of this rank.  Above DUMP_LIMIT_BYTES over all
+    ranks, a fixed seeded sample of rows (in stream order) is written instead."""
+    import numpy as np
+    out = y.cpu().numpy().astype(np.float32)
+    max_rows = max(1, DUMP_LIMIT_BYTES // world // (out.shape[1] * out.itemsize))
+    if out.shape[0] > max_rows:
+        out = out[np.sort(np.random.default_rng(0).choice(out.shape[0], max_rows, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "output.npy" if rank == 0 else "output_rank%d.npy" % rank), out)
+
+
 def rotation_regime(na, model, local_rank, dev, n_rot, bytes_per_sample, steps=240, warmup=80, resident=False):
     """The metric's own regime: ONE batch of n_rot x 1024 A1 Standard streams, every step visits the whole
     n_rot x 249 MB of ring state once -- nothing survives in the 256 MB Infinity Cache from one step to the next.  Same timed-region
@@ -304,7 +324,7 @@ def resident_launch_figure(streams):
     """The same step on the same box as commands to the opt-in RESIDENT launch (NA_BatchSetResidentLaunch): sustained
     step time and the latency of a lone buffer (host clock around post + wait).  Reported beside the default path, never as `value`."""
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", "600", "--warmup", "100", "--ramp-ms", "200", "--streams", str(streams), "--resident",
-           "--no-cpu-baseline", "--no-host-path", "--no-parity-check", "--rotate", "0", "--no-exact-f32"]
+           "--full", "--no-cpu-baseline", "--no-host-path", "--no-parity-check", "--rotate", "0", "--no-exact-f32"]  # --full: the latency probe
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
         j = json.loads(r.stdout.strip().splitlines()[-1])
@@ -370,7 +390,15 @@ def main():
                     help="standard (default = the BASELINE metric's config) | lite | feather | nano | a2full | a2lite | lstm1x16 | lstm2x8 | "
                          "config3 (Lite+Feather+Nano, 4096 streams) | config4 (LSTM 2x16 + GRU) | config5 (A2 quality sweep, 2048 streams) "
                          "(other BASELINE configs, for DESIGN.md numbers; the driver uses the default)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure (oracle spot check, output_finite, isolated-step latency, "
+                         "rotation regime, exact-f32 and resident-launch side runs, host-buffer paths, CPU baseline); default: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the output rows of the last timed step to DIR/output.npy (float32)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set up, warm up, time the K steps, print the line
+        args.no_cpu_baseline = args.no_parity_check = args.no_host_path = args.no_exact_f32 = True
+        args.rotate = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)
     if args.workload == "mixed3":
@@ -540,6 +568,11 @@ def main():
     # how a step reached the chip: one ordered launch | two free-running half-batch launches | a command to the resident launch (ONE
     # dispatch walks all K timed steps: rocprofv3 shows a single long dispatch per timed window, its duration / steps = the step time)
     launch_mode = "resident" if batch.UsesResidentLaunch() else ("half-batch chains" if batch.UsesHalfLaunches() else "ordered")
+    # The ramp issues whole passes of 256 steps (a multiple of nbuf), so the last timed step reads buffer (warmup + steps - 1) % nbuf
+    # after the same input history however long the ramp ran: a WaveNet's output is a function of its last receptive field of inputs
+    # (a recurrent model's state forgets the ramp: the spot check below replays 600 buffers of it).
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, rank, world)
 
     # Parity spot check (outside the timed region, on what the timed region left behind): `y` holds the output of the LAST timed step.
     # The first stream of every model of the batch is replayed on the CPU oracle over the tail of its known input history -- one
@@ -550,9 +583,9 @@ def main():
         parity = parity_spot_check(check_rows, x, y, issued[0], nbuf, mdir)
 
     # diagnostic only (outside the timed region): steps on their own, each bracketed and waited for
-    nprobe = min(32, args.steps)
+    nprobe = min(32, args.steps) if args.full else 0
     kernel_ms = []
-    if batch.UsesResidentLaunch():
+    if nprobe and batch.UsesResidentLaunch():
         # the resident launch has no launch boundary to bracket (a mark would make it leave and come back): post one buffer, wait for its
         # output rows, host clock around both -- what a real-time caller with ONE buffer in flight sees, command post and completion included
         batch.WaitOutputs()
@@ -570,8 +603,17 @@ def main():
     batch.Synchronize()
     torch.cuda.synchronize(dev)
     kernel_ms.sort()
-
-    finite = bool(torch.isfinite(y).all().item())
+    full_only = {}  # the line's checks and side measurements beside the headline figure
+    if args.full:
+        full_only = {
+            "kernel_ms_median_isolated": kernel_ms[len(kernel_ms) // 2],  # a step on its own (bracketed and waited for)
+            # the north star's "per-buffer latency < 1 ms": one buffer of all streams on its own, device pointers in, outputs valid
+            "latency_per_buffer_ms": kernel_ms[len(kernel_ms) // 2],
+            "output_finite": bool(torch.isfinite(y).all().item()),
+            # oracle spot check of the last timed step (one stream per model; tolerance of the north star: 1e-4 RMS)
+            "parity_rms": parity["rms"] if parity else None,
+            "parity_check": parity,
+        }
 
     if rank == 0:
         samples_per_step = S * BLOCK                      # this rank's launch (roofline bookkeeping)
@@ -638,16 +680,10 @@ def main():
             "launches_per_step": launches_per_step,               # 2: the step ran as two free-running half-batch launches
             "launch_mode": launch_mode,
             "steps_per_dispatch": args.steps if launch_mode == "resident" else 1.0 / launches_per_step,
-            "kernel_ms_median_isolated": kernel_ms[len(kernel_ms) // 2],  # a step on its own (bracketed and waited for)
-            # the north star's "per-buffer latency < 1 ms": one buffer of all streams on its own, device pointers in, outputs valid
-            "latency_per_buffer_ms": kernel_ms[len(kernel_ms) // 2],
+            **full_only,
             "frac_note": ("roofline.frac is from the library's HIP events around the K timed steps; roofline.frac_wall_clock from the clock `value` "
                           "is computed from (comparable with a driver's clock around the run; with few steps it carries the fixed cost of "
                           "opening and closing the timed window)"),
-            "output_finite": finite,
-            # oracle spot check of the last timed step (one stream per model; tolerance of the north star: 1e-4 RMS)
-            "parity_rms": parity["rms"] if parity else None,
-            "parity_check": parity,
             "roofline": {
                 # "mfma" = the FLOP roof: FP32 vector peak == dense f32 MFMA peak on MI355X (157.3 TFLOP/s), one roof
                 "bound": "mfma" if on_fp32_roof else "hbm",

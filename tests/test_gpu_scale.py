@@ -12,6 +12,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import na_oracle as O
@@ -19,12 +20,12 @@ import na_oracle as O
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-SHORT = ["--steps", "40", "--warmup", "10", "--ramp-ms", "20", "--no-cpu-baseline", "--no-host-path", "--rotate", "0", "--no-exact-f32"]
+SHORT = ["--steps", "40", "--warmup", "10", "--ramp-ms", "20", "--full", "--no-cpu-baseline", "--no-host-path", "--rotate", "0", "--no-exact-f32"]
 
 
-def _bench(extra):
+def _bench(extra, args=SHORT):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + SHORT + extra, capture_output=True, text=True, timeout=100, env=env, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + extra, capture_output=True, text=True, timeout=100, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout  # ONE line, from rank 0
@@ -59,6 +60,25 @@ def test_bench_headline_workload_with_two_ranks_on_one_device():
     assert "1024 batched streams per GPU" in two["config"]["workload"]
     assert abs(two["value"] - 2 * 1024 * 128 / (two["ms_per_step"] * 1e-3) / 1e6) / two["value"] < 1e-6
     assert two["parity_rms"] < 1e-4
+
+
+@pytest.mark.watchdog(240)
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """A plain run (no --full) times the steps and prints the line, nothing beside it; --dump-outputs writes the rows of the last
+    timed step, and they are what a --full run of the same arguments writes and checks against the oracle."""
+    plain_args = ["--steps", "40", "--warmup", "10", "--ramp-ms", "20"]
+    plain = _bench(["--dump-outputs", str(tmp_path / "plain")], args=plain_args)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in plain, key
+    assert plain["steps"] == 40 and plain["warmup"] == 10
+    assert abs(plain["value"] - 1024 * 128 / (plain["ms_per_step"] * 1e-3) / 1e6) / plain["value"] < 1e-6
+    for key in ("parity_rms", "output_finite", "latency_per_buffer_ms", "rotation", "exact_f32", "host_buffer_latency_ms", "cpu_baseline"):
+        assert key not in plain, key
+    full = _bench(["--dump-outputs", str(tmp_path / "full")])
+    assert full["parity_rms"] < 1e-4 and full["output_finite"]
+    y, y_full = np.load(tmp_path / "plain" / "output.npy"), np.load(tmp_path / "full" / "output.npy")
+    assert y.dtype == np.float32 and y.shape == (1024, 128) and np.isfinite(y).all() and np.abs(y).max() > 0
+    assert np.array_equal(y, y_full)
 
 
 def test_hostpipebench_two_ranks_over_the_loopback_rccl_table():

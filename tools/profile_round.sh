@@ -16,7 +16,7 @@ KPAT=${2:-WaveNetSpecKernel}
 shift; shift
 BARGS="$@"
 export NA_PMC_BENCH_ARGS="$BARGS"
-python $R/bench.py $BARGS > $OUT/bench.json 2> $OUT/bench.err
+python $R/bench.py --full $BARGS > $OUT/bench.json 2> $OUT/bench.err
 rm -rf $OUT/stats
 # (the traced / counted runs are the timed workload alone: no rotation regime, exact-f32 or resident-launch side runs, whose dispatches of the
 # same kernel would be averaged in)
