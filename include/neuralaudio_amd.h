@@ -213,6 +213,10 @@ NA_EXTERN int NA_DebugClassifyNam(const char* jsonText);
 /* stream packing, host side only: pack factor of the model in a large batch (1: none); flat weights of the packed virtual model into
  * out[capacity] when given; returns their count (0: model does not pack), -1 on failure */
 NA_EXTERN int NA_DebugPackedWeights(NeuralModel* model, int* packFactor, float* out, int capacity);
+/* the f16-split kernels' plan of a WaveNet as an unpacked stream runs it, host side only: 16 ints per stage (WnSplitStage) into
+ * stages[stageCapacity], the A-operand image (f16 bit patterns) into wsplit[wsplitCapacity], its length into *wsplitCount; returns the
+ * stage count, -1 on failure */
+NA_EXTERN int NA_DebugSplitPlan(NeuralModel* model, int* stages, int stageCapacity, unsigned short* wsplit, long long wsplitCapacity, long long* wsplitCount);
 /* tests / tuning: 0 = WaveNet models with a compile-time specialised layer chain run on the stage interpreter instead (same stream state,
  * bit-identical results); process-wide, set it only while no other thread is processing */
 NA_EXTERN void NA_DebugSetWaveNetSpec(int on);

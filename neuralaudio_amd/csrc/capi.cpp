@@ -311,6 +311,29 @@ int NA_DebugPackedWeights(NeuralModel* model, int* packFactor, float* out, int c
 }
 #endif
 
+// The f16-split plan of a WaveNet model as an unpacked batch stream would run it (wavenet_plan.cpp BuildSplit), host side only: 16 ints
+// per stage into stages[stageCapacity] (WnSplitStage), the A-operand image (f16 bit patterns, 512 per operand) into wsplit[wsplitCapacity];
+// returns the stage count, -1 on failure.
+#ifndef NA_RELEASE
+int NA_DebugSplitPlan(NeuralModel* model, int* stages, int stageCapacity, unsigned short* wsplit, long long wsplitCapacity, long long* wsplitCount)
+{
+	int r = -1;
+	Guard([&] {
+		NeuralAudio::GpuModel* gm = model ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+		if (!gm) throw std::runtime_error("NA_DebugSplitPlan: not a model of this library");
+		const auto& lm = gm->GetLoadedModel();
+		if (lm->subModels.size() != 1 || lm->subModels[0].desc->kind != na::MODEL_WAVENET) throw std::runtime_error("NA_DebugSplitPlan: not a WaveNet");
+		const na::WaveNetPlan plan = na::BuildWaveNetPlan(lm->subModels[0].desc->wavenet, true);
+		static_assert(sizeof(na::WnSplitStage) == 16 * sizeof(int), "16 ints per stage");
+		r = (int)plan.sstages.size();
+		if (stages) memcpy(stages, plan.sstages.data(), sizeof(na::WnSplitStage) * (size_t)std::min(r, stageCapacity));
+		if (wsplitCount) *wsplitCount = (long long)plan.wsplit.size();
+		if (wsplit) memcpy(wsplit, plan.wsplit.data(), sizeof(uint16_t) * (size_t)std::min<long long>((long long)plan.wsplit.size(), wsplitCapacity));
+	});
+	return r;
+}
+#endif
+
 void NA_SetDevice(NeuralModelLoader* loader, int device)
 {
 	if (loader) loader->loader->SetDevice(device);

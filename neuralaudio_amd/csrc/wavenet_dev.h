@@ -62,6 +62,7 @@ namespace na
 		WN_FLAG_PUBLISH = 4,     // write the layer output to LDS + the next layer's ring
 		WN_FLAG_BIAS = 8,        // dense/head stage has a bias
 		WN_FLAG_STD_TANH = 16,   // StdMath policy: std::tanh instead of the rational FastMath tanh (Activation.h:37-40)
+		WN_FLAG_FOLD = 32,       // f16-split K = 3 layer with folded lo operands (wavenet_plan.cpp FillSplitFoldAux): 8 MFMAs per tile, not 11
 	};
 
 	struct WnStage

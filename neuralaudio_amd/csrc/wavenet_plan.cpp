@@ -135,6 +135,7 @@ namespace na
 			size_t cursor = 0; // into desc.weights
 
 			int pack = 1; // > 1: `desc` is a packed virtual model (PackWaveNetDesc) of `pack` streams
+			bool foldOk = false; // a natural (neither packed nor padded) model: its K = 3 layers may take the folded operands (WN_FLAG_FOLD)
 			bool exactRings = false; // rings of the f16-split kernels' state format (see AddRing)
 			bool compactOk = false;  // ... and every layer has K <= 3 with dense heads: short histories get compact rings
 
@@ -304,7 +305,8 @@ namespace na
 				return first;
 			}
 
-			void FillSplitBlock(int opHi, int opLo, int rowBase, int kbBase, int cout, int cin, const std::function<float(int, int)>& w)
+			// (loSlot 4: the lo weights go to the second half of each lane's eight k-slots -- the folded operands, FillSplitFoldAux)
+			void FillSplitBlock(int opHi, int opLo, int rowBase, int kbBase, int cout, int cin, const std::function<float(int, int)>& w, int loSlot = 0)
 			{
 				for (int o = 0; o < cout; o++)
 					for (int c = 0; c < cin; c++)
@@ -317,14 +319,14 @@ namespace na
 						const size_t lane = (size_t)q * 16 + row;
 						plan.wsplit[(size_t)opHi * 512 + lane * 8 + r] = hi;
 						plan.wsplit[(size_t)opHi * 512 + lane * 8 + 4 + r] = hi;
-						plan.wsplit[(size_t)opLo * 512 + lane * 8 + r] = lo;
+						plan.wsplit[(size_t)opLo * 512 + lane * 8 + loSlot + r] = lo;
 					}
 			}
 
 			// the same weights for every tile slot of mode Gp (merged block-diagonal operand pair)
-			void FillSplitMerged(int opHi, int Gp, int cout, int cin, const std::function<float(int, int)>& w)
+			void FillSplitMerged(int opHi, int Gp, int cout, int cin, const std::function<float(int, int)>& w, int opLo = -1, int loSlot = 0)
 			{
-				for (int p = 0; p < 4 / Gp; p++) FillSplitBlock(opHi, opHi + 1, 4 * Gp * p, Gp * p, cout, cin, w);
+				for (int p = 0; p < 4 / Gp; p++) FillSplitBlock(opHi, opLo < 0 ? opHi + 1 : opLo, 4 * Gp * p, Gp * p, cout, cin, w, loSlot);
 			}
 
 			// "aux" operand: bias and input mix-in ride in the MFMA too.  The kernel's aux B operand of a frame is the 8 halfs
@@ -350,6 +352,31 @@ namespace na
 						uint16_t* e = &plan.wsplit[(size_t)op * 512 + lane * 8];
 						if (halfGroups && ((o / 2) & 1)) { e[1] = w1h; e[3] = w1l; e[5] = wch; e[6] = wch; e[7] = wcl; }
 						else { e[0] = wch; e[1] = w1h; e[2] = wch; e[3] = w1l; e[4] = wcl; }
+					}
+			}
+
+			// Folded operands (WN_FLAG_FOLD; unpacked K = 3 layers of lane mode 2 or 4): a lo operand [Wl | 0] uses half of its k-slots, and
+			// its B operand's second half (the xl of the split quad) meets only zeros.  The kernels put something useful there instead:
+			//   [Wl_0 | Wl_1] . [xh_0 | xh_1]      conv lo, taps 0 and 1 (operand 1; operand 3 stays unused)
+			//   [Wl_2 | aux ] . [xh_2 | c8  ]      conv lo, unshifted tap + mix-in and conv bias (operand 5; operand 6 unused)
+			//   [W1l  | b1  ] . [zh   | c8  ]      1x1 lo + its bias (operand 8; operand 9 unused)
+			// c8 = [cond_h, 1, cond_l, 1] is the first half of the aux B operand, the same in every k-block.  A row's aux weights against it
+			// are [wc_h, w1_h, wc_h, w1_l] in the first k-block of its tile slot and [wc_l, 0, 0, 0] in the second (the fifth product of
+			// FillSplitAux); the 1x1 bias needs no second one.  Same products as the unfolded layer, summed in fewer MFMAs.
+			void FillSplitFoldAux(int op, int Gp, int cout, int condOff, int oneOff)
+			{
+				if (Gp < 2) throw std::runtime_error("internal: folded aux operand needs two k-blocks per tile slot");
+				for (int p = 0; p < 4 / Gp; p++)
+					for (int o = 0; o < cout; o++)
+					{
+						const float wc = condOff >= 0 ? W(condOff + o) : 0.0f, w1 = oneOff >= 0 ? W(oneOff + o) : 0.0f;
+						const uint16_t wch = FloatToHalfBits(wc), wcl = FloatToHalfBits(wc - HalfBitsToFloat(wch));
+						const uint16_t w1h = FloatToHalfBits(w1), w1l = FloatToHalfBits(w1 - HalfBitsToFloat(w1h));
+						const size_t row = (size_t)(4 * Gp * p + o), kb = (size_t)(Gp * p);
+						uint16_t* e = &plan.wsplit[(size_t)op * 512 + (kb * 16 + row) * 8];
+						uint16_t* e2 = &plan.wsplit[(size_t)op * 512 + ((kb + 1) * 16 + row) * 8];
+						e[4] = wch; e[5] = w1h; e[6] = wch; e[7] = w1l;
+						e2[4] = wcl;
 					}
 			}
 
@@ -512,12 +539,21 @@ namespace na
 						st.a_ops = 2 * K + 4;
 						st.a_off = NewSplitOps(st.a_ops) * 64;
 						const int op0 = st.a_off / 64;
+						// (the folded layout keeps the operand numbering; FillSplitFoldAux)
+						const bool fold = foldOk && pack == 1 && K == 3 && Gp >= 2 && cfg.conditionSize == 1;
 						for (int k = 0; k < K; k++)
-							FillSplitMerged(op0 + 2 * k, Gp, C, C, [&](int o, int c) { return W(wconv + (o * C + c) * K + k); });
-						FillSplitAux(op0 + 2 * K, Gp, C, wmix, bconv, cpad);
+							FillSplitMerged(op0 + 2 * k, Gp, C, C, [&](int o, int c) { return W(wconv + (o * C + c) * K + k); },
+								(fold && k == 1) ? op0 + 1 : -1, (fold && k == 1) ? 4 : 0);
+						if (fold) FillSplitFoldAux(op0 + 2 * K - 1, Gp, C, wmix, bconv);
+						else FillSplitAux(op0 + 2 * K, Gp, C, wmix, bconv, cpad);
 						st.reserved = groupsPerStream;
 						FillSplitMerged(op0 + 2 * K + 1, Gp, C, C, [&](int o, int c) { return W(w1 + o * C + c); });
-						FillSplitAux(op0 + 2 * K + 3, Gp, C, -1, b1);
+						if (fold)
+						{
+							FillSplitFoldAux(op0 + 2 * K + 2, Gp, C, -1, b1);
+							st.flags |= WN_FLAG_FOLD;
+						}
+						else FillSplitAux(op0 + 2 * K + 3, Gp, C, -1, b1);
 						if (needOutput) st.flags |= WN_FLAG_NEED_OUTPUT;
 						SplitRing(st, layerRing[a][l]);
 						if (cfg.activation == ACT_LEAKYRELU) st.flags |= WN_FLAG_LEAKY;
@@ -861,6 +897,7 @@ namespace na
 	WaveNetPlan BuildWaveNetPlan(const WaveNetDesc& desc, bool splitStateFormat)
 	{
 		Builder b(desc, 1, splitStateFormat);
+		b.foldOk = true;
 		b.Build();
 		return std::move(b.plan);
 	}

@@ -74,6 +74,7 @@ namespace na
 			static constexpr int T = 2, CHUNK = 10;
 			static constexpr bool COARSE = false; // (dilations are powers of two: at most three wave classes per layer, 53 KB of code)
 			static constexpr bool GUARDHIST = false;
+			static constexpr bool FOLD = false;   // folded lo operands (WN_FLAG_FOLD): the plans of natural models only (wavenet_plan.cpp)
 			static constexpr int SKEW = 0;
 			static constexpr bool COMPACT = true; // K <= 3 everywhere, dense heads: histories of <= 32 frames live in compact rings (wavenet_plan.cpp AddRing)
 #ifndef NA_A1_NT_DIL
@@ -95,6 +96,7 @@ namespace na
 			// ~1.5 us instead of ~0.5: every slot waits for its light stream (per-slot timeline: both streams done after ~2700 cycles,
 			// barrier released after ~4400).
 			static constexpr int SKEW = NA_SPK_SKEW;
+			static constexpr bool FOLD = true; // (not padded, not packed: every layer takes the folded operands)
 			static constexpr int NA = 2;
 			static constexpr int CH[2] = { 16, 8 };
 			static constexpr int NLA[2] = { 10, 10 };
@@ -136,6 +138,7 @@ namespace na
 			static constexpr int CHUNK = 16;
 			static constexpr bool COARSE = true;
 			static constexpr bool GUARDHIST = true;
+			static constexpr bool FOLD = false;
 			static constexpr int SKEW = 0;
 			static constexpr bool COMPACT = false;
 			static constexpr int NT_DIL = 100;    // (d = 101 and 239)
@@ -166,6 +169,7 @@ namespace na
 			static constexpr bool FirstOfArr(int L) { return InArr(L) == 0; }
 			static constexpr bool LastOfArr(int L) { return InArr(L) == A::NLA[ArrOf(L)] - 1; }
 			static constexpr int KS(int L) { return A::K(ArrOf(L), InArr(L)); }
+			static constexpr bool Fold(int L) { return A::FOLD && KS(L) == 3 && GPof(ArrOf(L)) >= 2; } // == the plan's WN_FLAG_FOLD (Matches)
 			static constexpr int HEADK = A::HEADK;
 			static constexpr int NRINGS = NL + (HEADK > 1 ? 1 : 0); // one per layer (+ the conv head's)
 			// ring L < NL: input history of layer L; ring NL: the head accumulator's (wavenet_plan.cpp AddRing: roundup16((K - 1) d) + 128)
@@ -328,6 +332,7 @@ namespace na
 			static constexpr bool NEXT = !TB::LastOfArr(L); // a layer of the same array follows (its history is requested during this one)
 			static constexpr int LN = NEXT ? L + 1 : L;
 			static constexpr int dn = NEXT ? TB::Dil(LN) : 0, Kn = NEXT ? TB::KS(LN) : 1;
+			static constexpr bool FOLD = TB::Fold(L) && !C::PK;
 			static constexpr unsigned long long Of(int w)
 			{
 				unsigned long long s = 0;
@@ -664,6 +669,19 @@ namespace na
 			return f32x4{ FastTanh(a.x), FastTanh(a.y), FastTanh(a.z), FastTanh(a.w) };
 		}
 
+		// the LDS part of a shifted conv tap (class TAP_LDS or TAP_BOTH) for set i
+		template <class C, int GP>
+		__device__ __forceinline__ u32x4 TapLds(const Ctx& cx, const Lanes<C, GP>& ln, int imgRead, int shift, int i, int cls)
+		{
+			constexpr int P = Geo<GP, C::T>::P;
+			if (NA_ABL & 256) return u32x4{ (unsigned)shift, 0, 0, 0 };
+			if (cls == TAP_LDS) return LdsRead16(ln.img + (unsigned)(imgRead * C::IMG_ONE) + (unsigned)((16 * P * i - shift) * 16));
+			// straddling: lanes whose frame lies before the block read the zero guard quad in front of frame 0
+			int off = C::FW * cx.wave + 16 * P * i + ln.fl - shift;
+			off = off < -1 ? -1 : off;
+			return LdsRead16((unsigned)(C::IMG_OFF + imgRead * C::IMG_ONE + GUARD * 16) + (unsigned)(cx.sub * 2 * C::IMG_ONE) + (unsigned)((ln.cg * PLANE + off) * 16));
+		}
+
 		// One shifted conv tap of ring RG's reader for set i: the frames `shift` back, as classified for wave WR -- ring history (registers),
 		// LDS image, or both (the conv is linear in the operand: the ring part is zero for in-block lanes and vice versa).
 		template <class C, int RG, int GP, int WR>
@@ -678,18 +696,31 @@ namespace na
 			}
 			if (cls != TAP_HIST)
 			{
-				u32x4 b;
-				if (NA_ABL & 256) b = u32x4{ (unsigned)shift, 0, 0, 0 };
-				else if (cls == TAP_LDS) b = LdsRead16(ln.img + (unsigned)(imgRead * C::IMG_ONE) + (unsigned)((16 * P * i - shift) * 16));
-				else
-				{
-					// straddling: lanes whose frame lies before the block read the zero guard quad in front of frame 0
-					int off = C::FW * cx.wave + 16 * P * i + ln.fl - shift;
-					off = off < -1 ? -1 : off;
-					b = LdsRead16((unsigned)(C::IMG_OFF + imgRead * C::IMG_ONE + GUARD * 16) + (unsigned)(cx.sub * 2 * C::IMG_ONE) + (unsigned)((ln.cg * PLANE + off) * 16));
-				}
+				const u32x4 b = TapLds<C, GP>(cx, ln, imgRead, shift, i, cls);
 				acc = Mfma(ah, b, acc);
 				acc = MfmaLo<1>(al, b, acc);
+			}
+			return acc;
+		}
+
+		// The same for a folded layer (LayerSig::FOLD): the hi product only; the tap's h half goes to `th` for the folded lo product
+		// [Wl_0 | Wl_1] . [xh_0 | xh_1] (ring and LDS parts OR-ed: one of the two is zero in every lane)
+		template <class C, int RG, int GP, int WR>
+		__device__ __forceinline__ f32x4 ConvTapFold(const Ctx& cx, const Lanes<C, GP>& ln, int imgRead, int shift, int i, u32x4 ah, u32x4 hist, f32x4 acc, u32x2& th)
+		{
+			constexpr int P = Geo<GP, C::T>::P;
+			const int cls = WaveTapClass<C>(WR, P, i, shift, SmallRing<C, RG>());
+			th = u32x2{ 0, 0 };
+			if (cls != TAP_LDS)
+			{
+				acc = Mfma(ah, hist, acc);
+				th = u32x2{ hist.x, hist.y };
+			}
+			if (cls != TAP_HIST)
+			{
+				const u32x4 b = TapLds<C, GP>(cx, ln, imgRead, shift, i, cls);
+				acc = Mfma(ah, b, acc);
+				th = cls == TAP_LDS ? u32x2{ b.x, b.y } : u32x2{ th.x | b.x, th.y | b.y };
 			}
 			return acc;
 		}
@@ -737,18 +768,30 @@ namespace na
 				for (int i = 0; i < S; i++)
 					if (WaveTapClass<C>(WR, SG::P, i, ShiftOf<C, L>(k), SmallRing<C, L>()) != TAP_LDS) hx[k - (KLO > C::HPF ? KLO : C::HPF)][i] = HistLoadAt<C, L, WR>(cx, ln.ring, ln.fl, ShiftOf<C, L>(k), i);
 			}
+			// folded layer (SG::FOLD, one chunk, K = 3): per set hi tap 0, hi tap 1, [Wl_0 | Wl_1] . [xh_0 | xh_1], then (below) hi unshifted
+			// tap, [Wl_2 | aux] . [xh_2 | c8] and the 1x1's [W1h | W1h] . zs, [W1l | b1] . [zh | c8] -- the interpreter's sequence
+			// (wavenet_split_kernels.hip RunLayers), so that both give the same bits
+			static_assert(!SG::FOLD || (NCH == 1 && K == 3), "folded operands: K = 3 layers in one chunk");
+			u32x2 th[SG::FOLD ? 2 : 1][S];
 #pragma unroll
 			for (int k = KLO; k < KHI; k++)
 			{
-				const u32x4 ah = WOp<C>(cx, s, c, 2 * k), al = WOp<C>(cx, s, c, 2 * k + 1);
+				const u32x4 ah = WOp<C>(cx, s, c, 2 * k), al = SG::FOLD ? ah : WOp<C>(cx, s, c, 2 * k + 1);
 #pragma unroll
 				for (int i = 0; i < S; i++)
 				{
 					u32x4 h = u32x4{ 0, 0, 0, 0 };
 					if (WaveTapClass<C>(WR, SG::P, i, ShiftOf<C, L>(k), SmallRing<C, L>()) != TAP_LDS)
 						h = (k < C::HPF) ? st.hist[k < C::HPF ? k : 0][i] : hx[k >= C::HPF ? k - (KLO > C::HPF ? KLO : C::HPF) : 0][i];
-					acc[i] = ConvTap<C, L, GP, WR>(cx, ln, imgRead, ShiftOf<C, L>(k), i, ah, al, h, acc[i]);
+					if constexpr (SG::FOLD) acc[i] = ConvTapFold<C, L, GP, WR>(cx, ln, imgRead, ShiftOf<C, L>(k), i, ah, h, acc[i], th[k < 2 ? k : 0][i]);
+					else acc[i] = ConvTap<C, L, GP, WR>(cx, ln, imgRead, ShiftOf<C, L>(k), i, ah, al, h, acc[i]);
 				}
+			}
+			if constexpr (SG::FOLD)
+			{
+				const u32x4 al01 = WOp<C>(cx, s, c, 1);
+#pragma unroll
+				for (int i = 0; i < S; i++) acc[i] = Mfma(al01, u32x4{ th[0][i].x, th[0][i].y, th[1][i].x, th[1][i].y }, acc[i]);
 			}
 			if constexpr (OWN)
 			{
@@ -760,16 +803,20 @@ namespace na
 				for (int i = 0; i < S; i++)
 				{
 					acc[i] = Mfma(ah, st.xs[i], acc[i]);
-					acc[i] = MfmaLo<1>(al, st.xs[i], acc[i]);
+					if constexpr (SG::FOLD) acc[i] = Mfma(al, u32x4{ st.xs[i].x, st.xs[i].y, ax[i].x, ax[i].y }, acc[i]);
+					else acc[i] = MfmaLo<1>(al, st.xs[i], acc[i]);
 				}
 			}
 			if constexpr (TAIL)
 			{
 				// aux operand: (mix-in, conv bias) * (cond, 1)   (:288-289, :471); activation (:473-480); head accumulate (:482) on the
 				// matrix pipe: head += I (zh + zl); 1x1 + bias + residual (:486-491)
-				const u32x4 xa = WOp<C>(cx, s, c, 2 * K);
+				if constexpr (!SG::FOLD)
+				{
+					const u32x4 xa = WOp<C>(cx, s, c, 2 * K);
 #pragma unroll
-				for (int i = 0; i < S; i++) acc[i] = Mfma(xa, ax[i], acc[i]);
+					for (int i = 0; i < S; i++) acc[i] = Mfma(xa, ax[i], acc[i]);
+				}
 				SPK_STAMP(s, 1);
 				f32x4 z[S];
 #pragma unroll
@@ -780,7 +827,7 @@ namespace na
 				}
 				SPK_STAMP(s, 2);
 				const u32x4 idop = LdsRead16((unsigned)C::IDOP_OFF + (unsigned)cx.lane * 16u);
-				const u32x4 w1h = WOp<C>(cx, s, c, 2 * K + 1), w1l = WOp<C>(cx, s, c, 2 * K + 2), b1a = WOp<C>(cx, s, c, 2 * K + 3);
+				const u32x4 w1h = WOp<C>(cx, s, c, 2 * K + 1), w1l = WOp<C>(cx, s, c, 2 * K + 2), b1a = SG::FOLD ? w1l : WOp<C>(cx, s, c, 2 * K + 3);
 #pragma unroll
 				for (int i = 0; i < S; i++)
 				{
@@ -790,8 +837,13 @@ namespace na
 					{
 						f32x4 y = st.xc[i];
 						y = Mfma(w1h, zs, y);
-						y = MfmaLo<2>(w1l, zs, y);
-						y = Mfma(b1a, NA_SPK_AUX2 ? AuxRead<C, GP>(ln, i) : ax[i], y);
+						const u32x4 axi = NA_SPK_AUX2 ? AuxRead<C, GP>(ln, i) : ax[i];
+						if constexpr (SG::FOLD) y = Mfma(w1l, u32x4{ zs.x, zs.y, axi.x, axi.y }, y);
+						else
+						{
+							y = MfmaLo<2>(w1l, zs, y);
+							y = Mfma(b1a, axi, y);
+						}
 						st.xc[i] = y;
 						if constexpr (SG::NEXT)
 						{
@@ -1426,6 +1478,7 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 				if (d.type != WN_ST_LAYER || d.Gp != TB::GPof(a) || d.G != TB::GPof(a) || d.ksize != TB::KS(L) || d.dilation != TB::Dil(L)) return false;
 				if (d.ring_id != L || d.ring_off != TB::RingOff(L) || d.ring_frames != TB::RingFrames(L)) return false;
 				if (((d.flags & WN_FLAG_LEAKY) != 0) != A::LEAKY || (d.flags & WN_FLAG_STD_TANH)) return false;
+				if (((d.flags & WN_FLAG_FOLD) != 0) != TB::Fold(L)) return false;
 				if (!TB::LastOfArr(L) && (d.out_ring_id != L + 1 || !(d.flags & WN_FLAG_PUBLISH))) return false;
 			}
 			for (int a = 1; a < TB::NA; a++)

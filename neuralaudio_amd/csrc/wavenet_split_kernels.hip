@@ -317,6 +317,10 @@ namespace na
 				f32x4 acc[S];
 #pragma unroll
 				for (int i = 0; i < S; i++) acc[i] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+				// folded operands (WN_FLAG_FOLD, wavenet_plan.cpp FillSplitFoldAux; K == 3): per set hi tap 0, hi tap 1, [Wl_0 | Wl_1] .
+				// [xh_0 | xh_1], hi unshifted tap, [Wl_2 | aux] . [xh_2 | c8] -- the MFMA sequence of the specialised chains, bit for bit
+				const bool fold = GP >= 2 && (sd.flags & WN_FLAG_FOLD) != 0; // wave-uniform
+				u32x2 th[2][S]; // folded: the h halves of taps 0 and 1
 #pragma unroll
 				for (int k = 0; k < HPF; k++)
 				{
@@ -325,7 +329,8 @@ namespace na
 						const u32x4 ah = wl[WOP(2 * k)], al = wl[WOP(2 * k + 1)];
 						// Where do the frames of this tap lie for this wave?  All before the block start: the ring prefetch is the whole
 						// operand.  All inside the block: the LDS image is.  Otherwise both parts go through the MFMA (the conv is linear
-						// in the operand: the ring part is zero for in-block lanes and vice versa, nothing has to be merged).
+						// in the operand: the ring part is zero for in-block lanes and vice versa, nothing has to be merged -- except the
+						// h halves a folded lo product takes, which are OR-ed: one of the two is zero in every lane).
 						const int shift = d * (K - 1 - k);
 						const int lo = cx.F0 - shift, hi = cx.F0 + 16 * P * S - 1 - shift; // wave-uniform
 						if (hi < 0)
@@ -334,7 +339,8 @@ namespace na
 							for (int i = 0; i < S; i++)
 							{
 								acc[i] = Mfma(ah, hist[k][i], acc[i]);
-								acc[i] = MfmaLo<1>(al, hist[k][i], acc[i]);
+								if (fold) th[k < 2 ? k : 0][i] = u32x2{ hist[k][i].x, hist[k][i].y };
+								else acc[i] = MfmaLo<1>(al, hist[k][i], acc[i]);
 							}
 						}
 						else if (lo >= 0)
@@ -345,7 +351,8 @@ namespace na
 								u32x4 b = imgCur[ImgIdx(cg[i], f[i] - shift)];
 								if (mask) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 }; // no garbage (NaN) into the MFMA
 								acc[i] = Mfma(ah, b, acc[i]);
-								acc[i] = MfmaLo<1>(al, b, acc[i]);
+								if (fold) th[k < 2 ? k : 0][i] = u32x2{ b.x, b.y };
+								else acc[i] = MfmaLo<1>(al, b, acc[i]);
 							}
 						}
 						else
@@ -356,12 +363,19 @@ namespace na
 								u32x4 b = TapInBlock(imgCur, f[i] - shift, cg[i]);
 								if (mask) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 };
 								acc[i] = Mfma(ah, hist[k][i], acc[i]);
-								acc[i] = MfmaLo<1>(al, hist[k][i], acc[i]);
+								if (!fold) acc[i] = MfmaLo<1>(al, hist[k][i], acc[i]);
 								acc[i] = Mfma(ah, b, acc[i]);
-								acc[i] = MfmaLo<1>(al, b, acc[i]);
+								if (fold) th[k < 2 ? k : 0][i] = u32x2{ hist[k][i].x | b.x, hist[k][i].y | b.y };
+								else acc[i] = MfmaLo<1>(al, b, acc[i]);
 							}
 						}
 					}
+				}
+				if (HPF >= 2 && fold) // (both shifted taps are done: the h halves need not live across the history loads below)
+				{
+					const u32x4 al01 = wl[WOP(1)];
+#pragma unroll
+					for (int i = 0; i < S; i++) acc[i] = Mfma(al01, u32x4{ th[0][i].x, th[0][i].y, th[1][i].x, th[1][i].y }, acc[i]);
 				}
 				SP_STAMP(7);
 				// history of the NEXT layer's first HPF taps (the registers are free again)
@@ -387,8 +401,15 @@ namespace na
 						u32x4 b = TapOperandInline(cx, imgCur, sd.ring_off, sd.ring_frames, G, inPos0, f[i], cg[i] < G ? cg[i] : 0, shift, lo, lo + 16 * P - 1);
 						if (mask) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 };
 						acc[i] = Mfma(ah, b, acc[i]);
-						acc[i] = MfmaLo<1>(al, b, acc[i]);
+						if (fold) th[k < 2 ? k : 0][i] = u32x2{ b.x, b.y };
+						else acc[i] = MfmaLo<1>(al, b, acc[i]);
 					}
+				}
+				if (HPF < 2 && fold)
+				{
+					const u32x4 al01 = wl[WOP(1)];
+#pragma unroll
+					for (int i = 0; i < S; i++) acc[i] = Mfma(al01, u32x4{ th[0][i].x, th[0][i].y, th[1][i].x, th[1][i].y }, acc[i]);
 				}
 				{
 					// unshifted tap (the layer input itself, read back from the block image) and the aux operand:
@@ -401,8 +422,12 @@ namespace na
 						if (mask) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 };
 						const u32x4 ax = AuxOf<PK>(cx, f[i], cg[i], gsShift);
 						acc[i] = Mfma(ah, b, acc[i]);
-						acc[i] = MfmaLo<1>(al, b, acc[i]);
-						acc[i] = Mfma(xa, ax, acc[i]);
+						if (fold) acc[i] = Mfma(al, u32x4{ b.x, b.y, ax.x, ax.y }, acc[i]);
+						else
+						{
+							acc[i] = MfmaLo<1>(al, b, acc[i]);
+							acc[i] = Mfma(xa, ax, acc[i]);
+						}
 					}
 				}
 
@@ -449,8 +474,12 @@ namespace na
 						st.hd[i] = Mfma(idop, zs, st.hd[i]);
 						f32x4 y = st.xc[i];
 						y = Mfma(w1h, zs, y);
-						y = MfmaLo<2>(w1l, zs, y);
-						y = Mfma(b1a, ax, y);
+						if (fold) y = Mfma(w1l, u32x4{ zs.x, zs.y, ax.x, ax.y }, y);
+						else
+						{
+							y = MfmaLo<2>(w1l, zs, y);
+							y = Mfma(b1a, ax, y);
+						}
 						st.xc[i] = y;
 						// always one store per set (predicated through the offset): fixed VMEM count per layer
 						Publish(cx, imgNext, SplitOf(cx, st, y), f[i], cg[i], pub && (!GEN || (live[i] && cg[i] < sd.out_G)), sd.out_ring_off, sd.out_ring_frames, sd.out_G, outPos0,
