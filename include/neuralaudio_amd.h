@@ -204,6 +204,53 @@ NA_EXTERN float NA_BatchStreamInputLimit(NA_Batch* batch, int stream);
  * (the stream recovers one receptive field later).  Always 0 for proven models and the f32 kernels.  Synchronises the batch stream: a
  * diagnostic, not for the audio path.  Negative on a bad argument. */
 NA_EXTERN int NA_BatchStreamRangeEvents(NA_Batch* batch, int stream);
+
+/* ---- offline rendering of long signals (csrc/offline_render.cpp) --------------------------------------------------
+ * NA_RenderOffline renders every job's whole signal through its model and writes exactly what a FRESH instance of that model (same
+ * loader settings: quality, math modes, external sample rate) would output after Prewarm() through Process() over the whole signal.
+ * It never reads or writes the stream state of the NeuralModel passed in: it builds a temporary batch from it (as NA_BatchAddStreams).
+ *
+ * WaveNet models have no recurrence -- output t depends only on the inputs in [t - H, t], H the summed history of the stream's rings --
+ * so a long signal is cut into segments that run as the streams of one batch, every segment after the first starting `lead` >= H
+ * samples early (rounded up to 128) and keeping only what follows its lead-in.  Its output is the sequential run's bit for bit where the
+ * segment batch runs the stream on the same kernel as a batch of one (NA_BatchStreamKernelName), else to the kernels' usual tolerance.
+ * Recurrent models (LSTM, GRU, keras stacks) cannot be cut exactly: each recurrent job is one stream run sequentially from its prewarmed
+ * state, and the gain comes only from rendering many jobs in one call.  Jobs of one call share one batch on the device of job 0's
+ * model; all models must be on that device.
+ *
+ * Host pointers, pageable or registered; a job's input and output must not overlap.  Synchronous: every wait is bounded by the wait
+ * limit (NA_BatchSetWaitLimitMs; waitLimitMs); a failure returns non-zero with the reason in NA_GetLastError().  Device memory: about
+ * 3 x 4 bytes per sample of a pass's segment rows plus the batch's stream state; a signal longer than maxSamplesPerPass is rendered in
+ * several passes. */
+typedef struct NA_RenderJob
+{
+	NeuralModel* model;
+	float quality;      /* the submodel of a slimmable model (ignored otherwise) */
+	const float* input;
+	float* output;
+	size_t numSamples;
+} NA_RenderJob;
+typedef struct NA_RenderOptions
+{
+	size_t segmentSamples;    /* kept samples per segment (0: the planner's choice) */
+	size_t maxSamplesPerPass; /* bound of a pass's segment rows in samples, i.e. of its device buffers (0: 64 Mi) */
+	double waitLimitMs;       /* 0: the batch default (NA_WAIT_LIMIT_MS, 2000 ms) */
+} NA_RenderOptions;
+typedef struct NA_RenderPlanInfo
+{
+	long long segments;   /* over all jobs (a recurrent job: 1) */
+	int lead;             /* lead-in of every segment after the first (a multiple of 128; 0 without WaveNet jobs) */
+	long long segmentSamples; /* samples a segment after the first keeps */
+	long long rowSamples; /* samples every stream of the segment batch processes per pass (lead + segmentSamples) */
+	int passes;
+	int streams;          /* streams of the segment batch */
+	double estimatedMs;   /* the planner's estimate of the device time */
+	char kernel[64];      /* with a device: NA_BatchStreamKernelName of job 0's first segment; else "" */
+} NA_RenderPlanInfo;
+/* opts may be NULL (all defaults).  0 on success. */
+NA_EXTERN int NA_RenderOffline(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts);
+/* the plan of NA_RenderOffline without running it (no device needed; with one it also builds the segment batch for info->kernel) */
+NA_EXTERN int NA_RenderPlan(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, NA_RenderPlanInfo* info);
 #ifndef NA_RELEASE
 /* ---- test / tuning hooks: exported by the test build only (csrc/Makefile default target; what tests/ loads).  The release library
  * (make RELEASE=1 -> dist/libNeuralAudioCAPI.so: -DNA_RELEASE -DNA_NO_TUNING, no loopback RCCL table) has none of the NA_Debug* symbols

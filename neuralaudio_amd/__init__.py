@@ -14,7 +14,7 @@ import numpy as np
 from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
-           "NeuralAudioError"]
+           "NeuralAudioError", "render_offline", "render_plan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -473,3 +473,59 @@ class MultiBatch:
             self.close()
         except Exception:
             pass
+
+
+def _render_jobs(model, x, quality):
+    """(model, x, quality) or a list of (model, x[, quality]) -> (ctypes job array, [input arrays], [output arrays], list form?)"""
+    many = isinstance(model, (list, tuple))
+    specs = model if many else [(model, x, quality)]
+    if not specs:
+        raise NeuralAudioError("render_offline: no jobs")
+    jobs = (capi.NA_RenderJob * len(specs))()
+    xs, ys = [], []
+    for i, spec in enumerate(specs):
+        m, xi = spec[0], spec[1]
+        q = float(spec[2]) if len(spec) > 2 else 1.0
+        xi = np.ascontiguousarray(xi, dtype=np.float32).reshape(-1)
+        yi = np.empty_like(xi)
+        xs.append(xi)
+        ys.append(yi)
+        jobs[i].model = m._h if m is not None else None
+        jobs[i].quality = q
+        jobs[i].input = _fptr(xi)
+        jobs[i].output = _fptr(yi)
+        jobs[i].numSamples = xi.size
+    return jobs, xs, ys, many
+
+
+def _render_options(segment_samples, max_samples_per_pass, wait_limit_ms):
+    return capi.NA_RenderOptions(int(segment_samples), int(max_samples_per_pass), float(wait_limit_ms))
+
+
+def render_offline(model, x=None, quality=1.0, segment_samples=0, max_samples_per_pass=0, wait_limit_ms=0.0):
+    """Renders a whole signal through `model` as a fresh, prewarmed instance would (NA_RenderOffline: time-parallel segments for WaveNet
+    models, one sequential stream per recurrent job).  float32 in, float32 out, same length.  List form: render_offline([(model, x,
+    quality), ...]) renders every job in one call and returns the list of outputs.  The model's own stream state is not touched."""
+    jobs, xs, ys, many = _render_jobs(model, x, quality)
+    opts = _render_options(segment_samples, max_samples_per_pass, wait_limit_ms)
+    if capi.load_library().NA_RenderOffline(jobs, len(xs), C.byref(opts)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return ys if many else ys[0]
+
+
+def render_plan(model, x=None, quality=1.0, segment_samples=0, max_samples_per_pass=0):
+    """The plan render_offline would run (NA_RenderPlan; no device needed): segments, lead, segment_samples, row_samples, passes,
+    streams, estimated_ms and -- with a device -- the kernel of the first segment.  `x` may be an array or a sample count."""
+    def as_signal(v):
+        return np.zeros(int(v), dtype=np.float32) if np.isscalar(v) else v
+    if isinstance(model, (list, tuple)):
+        model = [(s[0], as_signal(s[1])) + tuple(s[2:]) for s in model]
+    else:
+        x = as_signal(x)
+    jobs, xs, ys, _ = _render_jobs(model, x, quality)
+    opts = _render_options(segment_samples, max_samples_per_pass, 0.0)
+    info = capi.NA_RenderPlanInfo()
+    if capi.load_library().NA_RenderPlan(jobs, len(xs), C.byref(opts), C.byref(info)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return {"segments": info.segments, "lead": info.lead, "segment_samples": info.segmentSamples, "row_samples": info.rowSamples,
+            "passes": info.passes, "streams": info.streams, "estimated_ms": info.estimatedMs, "kernel": info.kernel.decode()}

@@ -31,7 +31,22 @@ NA_SYMBOLS = [
     "NA_IsQualityChangeRealtimeSafe", "NA_ProcessChecked", "NA_BatchSubmit", "NA_BatchCollect", "NA_BatchNextInput", "NA_BatchOutputView", "NA_BatchIsQualityChangeRealtimeSafe", "NA_DebugClassifyNam", "NA_DebugPackedWeights", "NA_DebugSplitPlan", "NA_ModelKernelInfo", "NA_BatchStreamRangeEvents", "NA_MultiSetFanIn", "NA_MultiGatheredOutput", "NA_RcclAvailable",
     "NA_BatchMarkTime", "NA_BatchWaitMarks", "NA_BatchElapsedMs", "NA_BatchUsesHalfLaunches", "NA_DebugSetRcclApi", "NA_BatchWaitOutputs", "NA_BatchUsesResidentLaunch", "NA_BatchSetResidentLaunch",
     "NA_BatchSetWaitLimitMs", "NA_BatchGetWaitLimitMs", "NA_BatchIsBroken", "NA_DebugStallDevice",
+    "NA_RenderOffline", "NA_RenderPlan",
 ]
+
+
+class NA_RenderJob(C.Structure):
+    _fields_ = [("model", C.c_void_p), ("quality", C.c_float), ("input", C.POINTER(C.c_float)), ("output", C.POINTER(C.c_float)),
+                ("numSamples", C.c_size_t)]
+
+
+class NA_RenderOptions(C.Structure):
+    _fields_ = [("segmentSamples", C.c_size_t), ("maxSamplesPerPass", C.c_size_t), ("waitLimitMs", C.c_double)]
+
+
+class NA_RenderPlanInfo(C.Structure):
+    _fields_ = [("segments", C.c_longlong), ("lead", C.c_int), ("segmentSamples", C.c_longlong), ("rowSamples", C.c_longlong),
+                ("passes", C.c_int), ("streams", C.c_int), ("estimatedMs", C.c_double), ("kernel", C.c_char * 64)]
 
 _lib = None
 
@@ -146,6 +161,8 @@ def load_library():
         "NA_BatchIsQualityChangeRealtimeSafe": (C.c_int, [vp, C.c_int, C.c_float]),
         "NA_DebugClassifyNam": (C.c_int, [C.c_char_p]),
         "NA_DebugPackedWeights": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int]),
+        "NA_RenderOffline": (C.c_int, [C.POINTER(NA_RenderJob), C.c_int, C.POINTER(NA_RenderOptions)]),
+        "NA_RenderPlan": (C.c_int, [C.POINTER(NA_RenderJob), C.c_int, C.POINTER(NA_RenderOptions), C.POINTER(NA_RenderPlanInfo)]),
         "NA_DebugSplitPlan": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_ushort), C.c_longlong, C.POINTER(C.c_longlong)]),
     }
     for name, (res, args) in sig.items():

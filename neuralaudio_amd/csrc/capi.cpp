@@ -7,6 +7,7 @@
 
 #include "neuralaudio_amd.h"
 #include "multi_gpu.h"
+#include "offline_render.h"
 #include "neural_model_impl.h"
 #include "lstm_launch.h"
 #include "wavenet_launch.h"
@@ -783,4 +784,74 @@ int NA_BatchStreamPackFactor(NA_Batch* batch, int stream)
 	catch (...) { return 0; }
 }
 
+// ---------------------------------------------------------------- offline rendering (csrc/offline_render.cpp)
+
+namespace
+{
+	// jobs of the C ABI -> the renderer's, with the device they run on (job 0's model's); throws on a bad argument
+	int RenderJobs(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, std::vector<na::RenderJobDesc>& out, na::RenderOptionsDesc& o)
+	{
+		if (!jobs) throw std::runtime_error("offline render: jobs is NULL");
+		if (numJobs <= 0) throw std::runtime_error("offline render: numJobs must be >= 1");
+		int device = -1;
+		out.clear();
+		for (int j = 0; j < numJobs; j++)
+		{
+			const NA_RenderJob& job = jobs[j];
+			NeuralAudio::GpuModel* gm = job.model ? dynamic_cast<NeuralAudio::GpuModel*>(job.model->model) : nullptr;
+			if (!job.model) throw std::runtime_error("offline render: job " + std::to_string(j) + " has a NULL model");
+			if (!gm) throw std::runtime_error("offline render: job " + std::to_string(j) + ": model was not created by this library");
+			if (device < 0) device = gm->GetDevice();
+			else if (gm->GetDevice() != device) throw std::runtime_error("offline render: the jobs' models are on different devices");
+			na::RenderJobDesc d;
+			d.model = gm->GetLoadedModel();
+			d.quality = job.quality;
+			d.input = job.input;
+			d.output = job.output;
+			d.numSamples = job.numSamples;
+			out.push_back(d);
+		}
+		o = na::RenderOptionsDesc();
+		if (opts)
+		{
+			o.segmentSamples = opts->segmentSamples;
+			o.maxSamplesPerPass = opts->maxSamplesPerPass;
+			o.waitLimitMs = opts->waitLimitMs;
+		}
+		return device;
+	}
+}
+
+int NA_RenderOffline(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts)
+{
+	return Guard([&] {
+		std::vector<na::RenderJobDesc> js;
+		na::RenderOptionsDesc o;
+		const int device = RenderJobs(jobs, numJobs, opts, js, o);
+		na::RenderOffline(js, o, device);
+	});
+}
+
+int NA_RenderPlan(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, NA_RenderPlanInfo* info)
+{
+	return Guard([&] {
+		if (!info) throw std::runtime_error("NA_RenderPlan: info is NULL");
+		std::vector<na::RenderJobDesc> js;
+		na::RenderOptionsDesc o;
+		const int device = RenderJobs(jobs, numJobs, opts, js, o);
+		std::string kernel;
+		const na::RenderPlan p = na::PlanOfflineRenderOn(js, o, device, &kernel);
+		memset(info, 0, sizeof(*info));
+		info->segments = p.segments;
+		info->lead = p.lead;
+		info->segmentSamples = p.stride > 0 ? p.stride : 0;
+		info->rowSamples = p.rowSamples;
+		info->passes = p.passes;
+		info->streams = p.rows;
+		info->estimatedMs = p.estimatedMs;
+		strncpy(info->kernel, kernel.c_str(), sizeof(info->kernel) - 1);
+	});
+}
+
 } // extern "C"
+

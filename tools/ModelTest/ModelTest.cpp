@@ -7,6 +7,8 @@
 // engine, so the RMS line compares two instances of it driven with DIFFERENT call sizes over sin(0.01 n) -- the chunk-invariance
 // the reference's Internal path has (its results do not depend on the 64-frame split, InternalModel.h:104-117).
 // `--streams N` additionally times N copies of the model as one batch (the data-parallel entry point the GPU path adds).
+// `--offline SECONDS` additionally renders that many seconds of sin(0.01 n) through the model twice: sequentially (Process on a fresh
+// instance) and with NA_RenderOffline (time-parallel segments), and prints both times, the speed-up and the largest difference.
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -36,6 +38,7 @@ namespace
 		int blockSize = 64;
 		float quality = 1.0f;
 		int streams = 0;
+		double offlineSeconds = 0.0;
 	};
 
 	void Usage()
@@ -77,6 +80,12 @@ namespace
 				const char* v = value("--streams");
 				if (!v) return false;
 				o.streams = atoi(v);
+			}
+			else if (a == "--offline")
+			{
+				const char* v = value("--offline");
+				if (!v) return false;
+				o.offlineSeconds = atof(v);
 			}
 			else if (a == "-h" || a == "--help") return false;
 			else if (!a.empty() && a[0] == '-')
@@ -186,6 +195,50 @@ namespace
 		DeleteLoader(loader);
 	}
 
+	// `seconds` of sin(0.01 n) through a fresh prewarmed instance (Process, one second per call) and through NA_RenderOffline
+	void TimeOffline(const fs::path& path, const Options& o)
+	{
+		const size_t total = (size_t)(o.offlineSeconds * 48000.0);
+		std::vector<float> x(total), seq(total), par(total);
+		for (size_t i = 0; i < total; i++) x[i] = (float)std::sin((double)i * 0.01);
+		::NeuralModelLoader* loader = CreateLoader();
+		NA_SetDefaultQualityScaleFactor(loader, o.quality);
+		::NeuralModel* model = NA_CreateModelFromFileUtf8(loader, path.string().c_str(), 1);
+		::NeuralModel* fresh = model ? NA_CreateModelFromFileUtf8(loader, path.string().c_str(), 1) : nullptr;
+		NA_RenderJob job = { fresh, o.quality, x.data(), par.data(), std::min<size_t>(total, 48000) };
+		bool ok = model && fresh && NA_RenderOffline(&job, 1, nullptr) == 0; // first call: code objects, allocations
+		double tSeq = 0.0, tPar = 0.0;
+		if (ok)
+		{
+			const auto t0 = std::chrono::steady_clock::now();
+			for (size_t pos = 0; ok && pos < total; pos += 48000)
+				ok = NA_ProcessChecked(model, x.data() + pos, seq.data() + pos, std::min<size_t>(48000, total - pos)) == 0;
+			tSeq = Seconds(t0, std::chrono::steady_clock::now());
+		}
+		if (ok)
+		{
+			job.numSamples = total;
+			const auto t0 = std::chrono::steady_clock::now();
+			ok = NA_RenderOffline(&job, 1, nullptr) == 0;
+			tPar = Seconds(t0, std::chrono::steady_clock::now());
+		}
+		if (!ok) std::cout << "Offline: " << NA_GetLastError() << std::endl;
+		else
+		{
+			double maxDiff = 0.0;
+			for (size_t i = 0; i < total; i++) maxDiff = std::max(maxDiff, (double)std::fabs(seq[i] - par[i]));
+			NA_RenderPlanInfo info = {};
+			NA_RenderPlan(&job, 1, nullptr, &info);
+			PrintBench("Offline sequential (" + std::to_string(total) + " samples)", tSeq, (double)total);
+			PrintBench("Offline NA_RenderOffline", tPar, (double)total);
+			std::cout << "  speed-up: " << tSeq / tPar << "x  max abs diff: " << maxDiff << "  (" << info.segments << " segments, lead " << info.lead
+					  << ", " << info.streams << " streams x " << info.rowSamples << " samples, " << info.passes << " passes, " << info.kernel << ")" << std::endl;
+		}
+		if (fresh) DeleteModel(fresh);
+		if (model) DeleteModel(model);
+		DeleteLoader(loader);
+	}
+
 	// false when the model could not be loaded or run
 	bool RunModel(const fs::path& path, NA::NeuralModelLoader& loader, const Options& o)
 	{
@@ -220,6 +273,7 @@ namespace
 				std::cout << "Internal (block " << o.blockSize << ") vs Internal (block " << otherBlock << ") RMS err: " << rms << std::endl;
 			}
 			if (o.streams > 0) TimeBatch(path, o, o.streams);
+			if (o.offlineSeconds > 0) TimeOffline(path, o);
 		}
 		catch (const std::exception& e)
 		{
