@@ -3,7 +3,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <functional>
 #include <mutex>
 #include <cstdlib>
 #include <cstring>
@@ -368,26 +367,43 @@ namespace na
 		}
 	}
 
-	// How many launches a buffer takes once `leaving` has lost / `entering` has gained an active stream (ProcessDevice's grouping: the
-	// WaveNet launch lists, the fused recurrent launch, everything else on its own)
-	int GpuBatch::LaunchUnitsAfterSwitch(const ModelGroup* leaving, const ModelGroup* entering) const
+	std::vector<LaunchKind> GpuBatch::ActiveKinds(const ModelGroup* leaving, const ModelGroup* entering, std::vector<ModelGroup*>* active) const
 	{
-		bool lists[3] = { false, false, false }, joiner = false, rec = false;
-		int singles = 0;
+		std::vector<LaunchKind> kinds;
 		for (const auto& g : groups)
 		{
-			int active = g->NumActive();
-			if (g.get() == leaving) active -= 1;
-			if (g.get() == entering) active += 1;
-			if (active <= 0) continue;
-			const int c = g->LaunchClass();
-			if (c >= 0 && c <= 2) lists[c] = true;
-			else if (c == -1) joiner = true;
-			else if (c == 3) rec = true;
-			else singles++;
+			if (g->NumActive() - (g.get() == leaving) + (g.get() == entering) <= 0) continue;
+			kinds.push_back(g->Kind());
+			if (active) active->push_back(g.get());
 		}
-		if (joiner && !lists[2]) lists[1] = true; // plain fast-flavour split groups ride in the packed launch when there is one
-		return (int)lists[0] + (int)lists[1] + (int)lists[2] + (int)rec + singles;
+		return kinds;
+	}
+
+	// (every change of which groups have active streams -- AddStreams, RemoveStreams, SetQuality -- is a new topology version)
+	void GpuBatch::UpdatePlan()
+	{
+		if (plan.version == topologyVersion) return;
+		plan.groups.clear();
+		plan.units = PlanLaunches(ActiveKinds(nullptr, nullptr, &plan.groups));
+		plan.version = topologyVersion;
+	}
+
+	// The groups of a frame / split / packed unit as its launch takes them -- a plain group in the packed launch passes its index lists
+	// (launch_plan.h) -- in the unit's order, or in group order (the lists of the half-batch chains and of the resident launch keep the
+	// joiners where they stand).  The unit's kind makes every one of them a WaveNetGroup.
+	std::vector<WnFrameGroup> GpuBatch::WaveNetArgs(const LaunchUnit& unit, bool groupOrder)
+	{
+		std::vector<int> sorted;
+		if (groupOrder)
+		{
+			sorted = unit.groups;
+			std::sort(sorted.begin(), sorted.end());
+		}
+		std::vector<WnFrameGroup> args;
+		args.reserve(unit.groups.size());
+		for (int i : groupOrder ? sorted : unit.groups)
+			args.push_back(static_cast<WaveNetGroup*>(plan.groups[(size_t)i])->LaunchArgs(unit.kind == LaunchKind::SplitPacked));
+		return args;
 	}
 
 	// CompositeModel::IsModelChangeRealtimeSafe (CompositeModel.h:44-50, HadInitialPrewarm): false when the target submodel never had its
@@ -402,7 +418,7 @@ namespace na
 		const int idx = ref.model->ModelIndexFromQuality(quality);
 		if (idx == ref.active) return true;
 		if (!ref.prewarmed[(size_t)idx]) return false;
-		return LaunchUnitsAfterSwitch(ref.members[(size_t)ref.active].first, ref.members[(size_t)idx].first) <= 1;
+		return PlanLaunches(ActiveKinds(ref.members[(size_t)ref.active].first, ref.members[(size_t)idx].first)).size() <= 1;
 	}
 
 	float GpuBatch::GetQuality(int s) const { return streams.at((size_t)s).quality; }
@@ -477,56 +493,22 @@ namespace na
 			for (auto& g : groups) g->Process(dIn, dOut, inStride, outStride, n, launch);
 			return;
 		}
-		// Mixed batch.  Groups that can share a launch are fused: all WaveNet groups on the frame kernel into one launch, all LSTM / GRU
-		// groups with an LDS-free kernel instance into another (the workgroups of all architectures share the chip, no fork/join per
-		// group).  What remains are independent "units" (disjoint rows, disjoint state); one unit runs directly on the batch stream.
-		constexpr int NUM_WN_LISTS = 3; // frame kernel | f16-split kernel | f16-split kernel, packed streams: one launch each
-		std::vector<WnFrameGroup> fusedWn[NUM_WN_LISTS];
-		std::vector<RecurrentGroup> fusedRec;
-		std::vector<ModelGroup*> singles;
-		ModelGroup* wnOwner[NUM_WN_LISTS] = {}; // lends its side stream / event to the fused unit
-		std::vector<std::pair<WnFrameGroup, ModelGroup*>> joiners;
-		ModelGroup* recOwner = nullptr;
-		for (auto& g : groups)
+		// Mixed batch: the launch units of launch_plan.h.  Their arguments are gathered first (changed index lists are uploaded now,
+		// asynchronously on the batch stream: never inside a graph capture).
+		UpdatePlan();
+		const std::vector<LaunchUnit>& units = plan.units;
+		std::vector<std::vector<WnFrameGroup>> wnArgs(units.size());
+		std::vector<RecurrentGroup> recArgs;
+		for (size_t u = 0; u < units.size(); u++)
 		{
-			if (g->NumActive() == 0) continue;
-			WnFrameGroup a = {};
-			RecurrentGroup r;
-			int list = 0;
-			if (g->FusedLaunchArgs(a, list))
-			{
-				if (list < 0)
-				{
-					// a plain fast-flavour split group: joins the packed launch if there is one (decided below), else the plain split launch
-					a.slots = static_cast<WaveNetGroup*>(g.get())->listSlots;
-					joiners.push_back({ a, g.get() });
-					continue;
-				}
-				fusedWn[list].push_back(a);
-				if (!wnOwner[list]) wnOwner[list] = g.get();
-			}
-			else if (g->FusedRecurrentArgs(r))
-			{
-				fusedRec.push_back(r);
-				if (!recOwner) recOwner = g.get();
-			}
-			else
-			{
-				g->SyncActiveLists();
-				singles.push_back(g.get());
-			}
-		}
-		for (auto& j : joiners)
-		{
-			const int list = fusedWn[2].empty() ? 1 : 2;
-			WnFrameGroup a = j.first;
-			if (list == 1 && static_cast<WaveNetGroup*>(j.second)->IsContiguous()) a.slots = nullptr; // the plain kernel's shortcut
-			fusedWn[list].push_back(a);
-			if (!wnOwner[list]) wnOwner[list] = j.second;
+			if (units[u].kind == LaunchKind::Recurrent)
+				for (int i : units[u].groups) recArgs.push_back(static_cast<LstmGroup*>(plan.groups[(size_t)i])->LaunchArgs());
+			else if (units[u].kind == LaunchKind::Own) plan.groups[(size_t)units[u].groups[0]]->SyncActiveLists();
+			else wnArgs[u] = WaveNetArgs(units[u], false);
 		}
 		// prepareOnly: upload the group tables the list's launches will look up and launch nothing (the pass in front of a stream capture)
-		auto launchWnList = [&](int which, hipStream_t s, bool prepareOnly) {
-			const std::vector<WnFrameGroup>& list = fusedWn[which];
+		auto launchWnList = [&](LaunchKind which, const std::vector<WnFrameGroup>& list, hipStream_t s, bool prepareOnly) {
+			WnLaunchTable& table = wnTable[(int)which];
 			bool compact = false;
 			for (const WnFrameGroup& g : list) compact = compact || g.model->compact_rings != 0;
 			size_t offset = 0, left = n;
@@ -535,11 +517,11 @@ namespace na
 				const int chunk = NextWaveNetChunk(left, compact);
 				// more groups than one launch's kernarg table holds (a batch of many different models): ONE launch with the table in device
 				// memory where the chains have one (128-frame blocks of the A1 families), else launches of eight groups each
-				if (which != 0 && list.size() > (size_t)WN_FRAME_MAX_GROUPS)
+				if (which != LaunchKind::Frame && list.size() > (size_t)WN_FRAME_MAX_GROUPS)
 				{
-					wnTable[which].prepareOnly = prepareOnly;
-					const hipError_t te = LaunchWaveNetSpecTable(list.data(), (int)list.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, s, wnTable[which]);
-					wnTable[which].prepareOnly = false;
+					table.prepareOnly = prepareOnly;
+					const hipError_t te = LaunchWaveNetSpecTable(list.data(), (int)list.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, s, table);
+					table.prepareOnly = false;
 					if (te == hipSuccess)
 					{
 						offset += (size_t)chunk;
@@ -558,9 +540,9 @@ namespace na
 				for (size_t first = 0; first < list.size(); first += WN_FRAME_MAX_GROUPS)
 				{
 					const int count = (int)std::min<size_t>(list.size() - first, (size_t)WN_FRAME_MAX_GROUPS);
-					CheckHip(which == 0 ? LaunchWaveNetFrameFused(list.data() + first, count, dIn + offset, dOut + offset, inStride, outStride, chunk, s)
-										: LaunchWaveNetSplitFused(list.data() + first, count, dIn + offset, dOut + offset, inStride, outStride, chunk, s,
-											1 | ((!Tuning::Get().wnNtOff && StateBytes() > ((size_t)Tuning::Get().wnNtFromMB << 20)) ? WN_SHARING_BEYOND_CACHE : 0)),
+					CheckHip(which == LaunchKind::Frame ? LaunchWaveNetFrameFused(list.data() + first, count, dIn + offset, dOut + offset, inStride, outStride, chunk, s)
+														: LaunchWaveNetSplitFused(list.data() + first, count, dIn + offset, dOut + offset, inStride, outStride, chunk, s,
+															1 | WnBeyondCacheBit(StateBytes())),
 						"WaveNet kernel (fused)");
 				}
 				offset += (size_t)chunk;
@@ -572,24 +554,31 @@ namespace na
 			while (left > 0)
 			{
 				const int chunk = (int)std::min<size_t>(left, (size_t)LSTM_MAX_FRAMES);
-				if (fusedRec.size() > (size_t)RECURRENT_MAX_GROUPS)
+				if (recArgs.size() > (size_t)RECURRENT_MAX_GROUPS)
 				{
 					// (many different recurrent models: one launch, the group table in device memory)
-					wnTable[3].prepareOnly = prepareOnly;
-					const hipError_t te = LaunchRecurrentDppTable(fusedRec.data(), (int)fusedRec.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, s, wnTable[3]);
-					wnTable[3].prepareOnly = false;
+					WnLaunchTable& table = wnTable[(int)LaunchKind::Recurrent];
+					table.prepareOnly = prepareOnly;
+					const hipError_t te = LaunchRecurrentDppTable(recArgs.data(), (int)recArgs.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, s, table);
+					table.prepareOnly = false;
 					CheckHip(te, "RecurrentDppKernel (table launch)");
 					offset += (size_t)chunk;
 					left -= (size_t)chunk;
 					continue;
 				}
 				if (prepareOnly) break;
-				for (size_t first = 0; first < fusedRec.size(); first += RECURRENT_MAX_GROUPS)
-					CheckHip(LaunchRecurrentDpp(fusedRec.data() + first, (int)std::min<size_t>(fusedRec.size() - first, (size_t)RECURRENT_MAX_GROUPS),
+				for (size_t first = 0; first < recArgs.size(); first += RECURRENT_MAX_GROUPS)
+					CheckHip(LaunchRecurrentDpp(recArgs.data() + first, (int)std::min<size_t>(recArgs.size() - first, (size_t)RECURRENT_MAX_GROUPS),
 						dIn + offset, dOut + offset, inStride, outStride, chunk, s), "RecurrentDppKernel (fused)");
 				offset += (size_t)chunk;
 				left -= (size_t)chunk;
 			}
+		};
+		auto run = [&](size_t u, hipStream_t s, bool prepareOnly) {
+			const LaunchUnit& unit = units[u];
+			if (unit.kind == LaunchKind::Recurrent) launchRec(s, prepareOnly);
+			else if (unit.kind != LaunchKind::Own) launchWnList(unit.kind, wnArgs[u], s, prepareOnly);
+			else if (!prepareOnly) plan.groups[(size_t)unit.groups[0]]->Process(dIn, dOut, inStride, outStride, n, s);
 		};
 		// group tables of an earlier topology go (their graphs first)
 		if (!graphCache.empty() && graphCache.front().key.version != topologyVersion)
@@ -598,36 +587,34 @@ namespace na
 			graphCache.clear();
 		}
 		for (WnLaunchTable& t : wnTable) t.NewGeneration(topologyVersion);
-		size_t units = (fusedRec.empty() ? 0 : 1) + singles.size();
-		for (int l = 0; l < NUM_WN_LISTS; l++) units += fusedWn[l].empty() ? 0 : 1;
-		if (units == 1)
+		if (units.size() == 1)
 		{
-			for (int l = 0; l < NUM_WN_LISTS; l++)
-				if (!fusedWn[l].empty())
-				{
-					launchWnList(l, launch, false);
-					return;
-				}
-			if (!fusedRec.empty()) launchRec(launch, false);
-			else singles[0]->Process(dIn, dOut, inStride, outStride, n, launch);
+			run(0, launch, false);
 			return;
 		}
+		// tuning knob: the units one after the other on the batch stream instead of concurrently on side streams
+		if (Tuning::Get().batchSerial)
 		{
-			// tuning knob: the units one after the other on the batch stream instead of concurrently on side streams
-			const bool serial = Tuning::Get().batchSerial;
-			if (serial)
-			{
-				for (int l = 0; l < NUM_WN_LISTS; l++)
-					if (!fusedWn[l].empty()) launchWnList(l, stream, false);
-				if (!fusedRec.empty()) launchRec(stream, false);
-				for (ModelGroup* g : singles) g->Process(dIn, dOut, inStride, outStride, n, stream);
-				return;
-			}
+			for (size_t u = 0; u < units.size(); u++) run(u, stream, false);
+			return;
 		}
 		// Several units: fork onto side streams so their kernels share the GPU, then join back into the batch stream.  The fork/join
 		// costs ~5 HIP calls per unit, which would make a buffer host-bound, so the sequence is captured once into a hipGraph and
 		// replayed while the call signature (pointers, n, strides) and the active-stream lists stay the same -- the steady state of a
 		// real-time host.
+		auto forkJoin = [&] {
+			if (!forkEvent) CheckHip(hipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
+			CheckHip(hipEventRecord(forkEvent, stream), "hipEventRecord");
+			for (size_t u = 0; u < units.size(); u++)
+			{
+				ModelGroup* owner = plan.groups[(size_t)units[u].groups[0]];
+				hipStream_t side = owner->SideStream();
+				CheckHip(hipStreamWaitEvent(side, forkEvent, 0), "hipStreamWaitEvent");
+				run(u, side, false);
+				CheckHip(hipEventRecord(owner->DoneEvent(), side), "hipEventRecord");
+				CheckHip(hipStreamWaitEvent(stream, owner->DoneEvent(), 0), "hipStreamWaitEvent");
+			}
+		};
 		// The runtime this process actually runs on may be OLDER than the ROCm 7.2 this library is built against: a host that loads
 		// PyTorch first gets PyTorch's bundled libamdhip64 (HIP 7.0.51831 with torch 2.10+rocm7.0) for the whole process, and that
 		// runtime's graph replay crashes after other graphs of the process were destroyed (hip::Graph::UpdateStreams under
@@ -640,19 +627,7 @@ namespace na
 		}();
 		if (!graphsTrusted)
 		{
-			if (!forkEvent) CheckHip(hipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
-			CheckHip(hipEventRecord(forkEvent, stream), "hipEventRecord");
-			auto direct = [&](ModelGroup* owner, const std::function<void(hipStream_t)>& work) {
-				hipStream_t side = owner->SideStream();
-				CheckHip(hipStreamWaitEvent(side, forkEvent, 0), "hipStreamWaitEvent");
-				work(side);
-				CheckHip(hipEventRecord(owner->DoneEvent(), side), "hipEventRecord");
-				CheckHip(hipStreamWaitEvent(stream, owner->DoneEvent(), 0), "hipStreamWaitEvent");
-			};
-			for (int l = 0; l < NUM_WN_LISTS; l++)
-				if (!fusedWn[l].empty()) direct(wnOwner[l], [&, l](hipStream_t s) { launchWnList(l, s, false); });
-			if (!fusedRec.empty()) direct(recOwner, [&](hipStream_t s) { launchRec(s, false); });
-			for (ModelGroup* g : singles) direct(g, [&](hipStream_t s) { g->Process(dIn, dOut, inStride, outStride, n, s); });
+			forkJoin();
 			return;
 		}
 		hipGraphExec_t graphExec = nullptr;
@@ -666,26 +641,12 @@ namespace na
 				graphCache.erase(graphCache.begin());
 			}
 			// the group tables of the table launches are uploaded here, in front of the capture (WnLaunchTable)
-			for (int l = 0; l < NUM_WN_LISTS; l++)
-				if (!fusedWn[l].empty()) launchWnList(l, stream, true);
-			if (!fusedRec.empty()) launchRec(stream, true);
+			for (size_t u = 0; u < units.size(); u++) run(u, stream, true);
 			hipGraph_t graph = nullptr;
 			CheckHip(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed), "hipStreamBeginCapture");
 			try
 			{
-				if (!forkEvent) CheckHip(hipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
-				CheckHip(hipEventRecord(forkEvent, stream), "hipEventRecord");
-				auto branch = [&](ModelGroup* owner, const std::function<void(hipStream_t)>& work) {
-					hipStream_t side = owner->SideStream();
-					CheckHip(hipStreamWaitEvent(side, forkEvent, 0), "hipStreamWaitEvent");
-					work(side);
-					CheckHip(hipEventRecord(owner->DoneEvent(), side), "hipEventRecord");
-					CheckHip(hipStreamWaitEvent(stream, owner->DoneEvent(), 0), "hipStreamWaitEvent");
-				};
-				for (int l = 0; l < NUM_WN_LISTS; l++)
-					if (!fusedWn[l].empty()) branch(wnOwner[l], [&, l](hipStream_t s) { launchWnList(l, s, false); });
-				if (!fusedRec.empty()) branch(recOwner, [&](hipStream_t s) { launchRec(s, false); });
-				for (ModelGroup* g : singles) branch(g, [&](hipStream_t s) { g->Process(dIn, dOut, inStride, outStride, n, s); });
+				forkJoin();
 			}
 			catch (...)
 			{

@@ -16,6 +16,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "launch_plan.h"
 #include "model_loader.h"
 #include "tuning.h"
 #include "wavenet_launch.h"
@@ -203,7 +204,9 @@ namespace na
 		std::vector<int> retired; // sorted ids of removed streams
 		int AllocateIds(int count);
 		void DropTrailingRetiredRows();
-		int LaunchUnitsAfterSwitch(const ModelGroup* leaving, const ModelGroup* entering) const;
+		// the kinds of the groups that have active streams once `leaving` has lost / `entering` has gained one, in group order (`active`:
+		// those groups)
+		std::vector<LaunchKind> ActiveKinds(const ModelGroup* leaving, const ModelGroup* entering, std::vector<ModelGroup*>* active = nullptr) const;
 		void ZeroRetiredRows(float* hostRows, size_t n, size_t rows) const;
 
 		ModelGroup* GroupFor(const std::shared_ptr<const ModelDesc>& desc, int packHint = 0);
@@ -244,6 +247,15 @@ namespace na
 		};
 		std::vector<GraphEntry> graphCache; // a handful of call signatures (hosts cycle through a few fixed buffers)
 		unsigned long topologyVersion = 0;
+		// the launch units of a buffer (launch_plan.h), planned again when the topology -- which groups have active streams -- changes
+		struct
+		{
+			unsigned long version = ~0ul;
+			std::vector<ModelGroup*> groups; // the groups with active streams, in group order: what the units' indices point at
+			std::vector<LaunchUnit> units;
+		} plan;
+		void UpdatePlan();
+		std::vector<WnFrameGroup> WaveNetArgs(const LaunchUnit& unit, bool groupOrder); // the arguments of a frame / split / packed unit's launch
 		std::vector<std::unique_ptr<ModelGroup>> groups;
 		std::vector<StreamRef> streams;
 		bool peerWeights = false;
@@ -287,7 +299,7 @@ namespace na
 		// ring in pinned host memory -- for the batches the chains serve whose buffer is one launch of 128-frame A1 Standard blocks
 		struct ResidentState;
 		std::unique_ptr<ResidentState> residentState;
-		WnLaunchTable wnTable[4]; // device tables of launch lists with more groups than a launch's kernarg segment holds (gpu_batch.cpp launchWnList; [3]: the recurrent list)
+		WnLaunchTable wnTable[4]; // device tables of launch lists with more groups than a launch's kernarg segment holds (gpu_batch.cpp launchWnList), by LaunchKind
 		bool lastStepResident = false;
 		bool residentWanted = Tuning::Get().residentOn;
 		bool TryResident(const float* dIn, float* dOut, size_t n, long inStride, long outStride);

@@ -157,25 +157,15 @@ namespace na
 		r.unsupported = true;
 		r.topology = topologyVersion;
 		r.list.clear();
-		int active = 0, total = 0;
-		for (const auto& g : groups)
-		{
-			if (g->NumActive() == 0) continue;
-			const int c = g->LaunchClass();
-			if (c != 1 && c != -1) return false; // (plain f16-split launches only)
-			active++;
-		}
-		if (active == 0 || active > WN_FRAME_MAX_GROUPS) return false;
+		UpdatePlan();
+		if (!IsOneSplitLaunch(plan.units, false, WN_FRAME_MAX_GROUPS)) return false;
 		// whatever else this batch has in flight comes first (state resets and prewarms on the batch stream, slot streams, the chains) ...
 		DrainPipeline();
 		WaitStreamBounded(stream, "hipStreamSynchronize");
-		for (const auto& g : groups)
+		int total = 0;
+		for (const WnFrameGroup& a : WaveNetArgs(plan.units[0], true)) // (uploads changed index lists, asynchronously on the batch stream)
 		{
-			if (g->NumActive() == 0) continue;
-			WnFrameGroup a = {};
-			int list = 0;
-			if (!g->FusedLaunchArgs(a, list)) return false; // (uploads a changed index list, asynchronously on the batch stream)
-			if (a.pack > 1 || a.model->spec_arch != WN_SPEC_STD) return false;
+			if (a.model->spec_arch != WN_SPEC_STD) return false;
 			total += a.numStreams;
 			r.list.push_back(a);
 		}
@@ -369,21 +359,17 @@ namespace na
 	bool GpuBatch::PrepareHalves(size_t n)
 	{
 		if (Tuning::Get().hostHalvesOff) return false;
-		bool dirty = false, packed = false, plain = false;
-		int active = 0, kernelStreams = 0;
-		for (const auto& g : groups)
+		UpdatePlan();
+		if (!IsOneSplitLaunch(plan.units, true, WN_FRAME_MAX_GROUPS)) return false;
+		const LaunchUnit& unit = plan.units[0];
+		bool dirty = false;
+		int kernelStreams = 0;
+		for (int i : unit.groups)
 		{
-			const int members = g->NumActive();
-			if (members == 0) continue;
-			const int c = g->LaunchClass(); // 1 / 2 / -1: the f16-split kernels' plain launch / packed launch / either (gpu_batch.cpp LaunchClass)
-			if (c != 1 && c != 2 && c != -1) return false;
-			packed = packed || c == 2;
-			plain = plain || c == 1;
+			const ModelGroup* g = plan.groups[(size_t)i];
 			dirty = dirty || g->ListsDirty();
-			kernelStreams += (members + g->PackFactor() - 1) / g->PackFactor();
-			active++;
+			kernelStreams += (g->NumActive() + g->PackFactor() - 1) / g->PackFactor();
 		}
-		if (active == 0 || active > WN_FRAME_MAX_GROUPS || (packed && plain)) return false; // (two launches per buffer: not split)
 		if (kernelStreams < 512) return false; // (a small batch: nothing below is worth its host time; the exact count is checked at the end)
 		// changed index lists are re-uploaded below (asynchronously, on the batch stream): nothing in flight may still read the old ones
 		if (dirty && (halfChainsUsed || pipelineUsed)) DrainPipeline();
@@ -393,14 +379,8 @@ namespace na
 		hl.listsUploaded = dirty;
 		int total = 0;
 		bool compact = false;
-		for (const auto& g : groups)
+		for (const WnFrameGroup& a : WaveNetArgs(unit, true))
 		{
-			if (g->NumActive() == 0) continue;
-			WnFrameGroup a = {};
-			int list = 0;
-			if (!g->FusedLaunchArgs(a, list)) return false;
-			WaveNetGroup* wg = static_cast<WaveNetGroup*>(g.get());
-			if (list < 0 && packed) a.slots = wg->listSlots; // a plain group in the packed launch passes its index lists
 			total += a.numStreams;
 			compact = compact || a.model->compact_rings != 0;
 			// contiguous parts of whole workgroups (two streams each)
@@ -469,7 +449,7 @@ namespace na
 			{
 				const int chunk = NextWaveNetChunk(left, halfLists->compact);
 				CheckHip(LaunchWaveNetSplitFused(part.data(), (int)part.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, halfStream[h],
-					(hostRows ? 1 : numChains) | ((!Tuning::Get().wnNtOff && StateBytes() > ((size_t)Tuning::Get().wnNtFromMB << 20)) ? WN_SHARING_BEYOND_CACHE : 0)), "WaveNet kernel (half batch)");
+					(hostRows ? 1 : numChains) | WnBeyondCacheBit(StateBytes())), "WaveNet kernel (half batch)");
 				offset += (size_t)chunk;
 				left -= (size_t)chunk;
 			}

@@ -251,7 +251,8 @@ namespace na
 		// buffer's.  The upload of buffer k + 1 (its stream's first operation) overlaps the kernel of buffer k, the download of buffer k
 		// (behind its kernel) overlaps the kernel of buffer k + 1.  Per buffer: 2 copies, 1 launch, 1 event wait, 1 event record --
 		// the round-2 path cost 2 more waits and 2 more records on the compute stream, 15 us per buffer (tools/microbench/host_pipe_probe.cpp).
-		if (LaunchUnitsAfterSwitch(nullptr, nullptr) <= 1)
+		UpdatePlan();
+		if (plan.units.size() <= 1)
 		{
 			JoinHalves(); // (device-pointer steps may have run as half-batch chains: this buffer's kernel comes after both)
 			if (!p.own) CheckHip(hipStreamCreateWithFlags(&p.own, hipStreamNonBlocking), "hipStreamCreate");

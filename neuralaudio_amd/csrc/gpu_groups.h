@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "gpu_batch.h"
+#include "launch_plan.h"
 #include "lstm_launch.h"
 #include "tuning.h"
 #include "wavenet_launch.h"
@@ -163,10 +164,8 @@ namespace na
 		virtual double AlgorithmicBytesPerSample(int blockFrames) const = 0;
 		virtual double MacsPerSample() const = 0;
 		virtual size_t StateBytesPerStream() const = 0;
-		// Which launch of a buffer this group's streams ride in (GpuBatch::ProcessDevice): 0 frame kernel, 1 f16-split kernel, 2 f16-split
-		// kernel with packed streams, -1 split kernel, joins list 2 when the batch has one (else 1), 3 the fused LDS-free recurrent launch,
-		// -2 a launch of its own
-		virtual int LaunchClass() const { return -2; }
+		// which launch of a buffer this group's streams ride in (launch_plan.h); set once, by the constructor
+		LaunchKind Kind() const { return kind; }
 		virtual int PackFactor() const { return 1; } // real streams per kernel-level stream (WaveNet stream packing)
 		// f16-split kernels without a static range proof: (wave, block) pairs in which a value of this member's stream was saturated
 		virtual int RangeEvents(int member) { (void)member; return 0; }
@@ -177,22 +176,6 @@ namespace na
 		virtual void WeightsArrived() {}
 		virtual float InputLimit() const { return INFINITY; } // samples beyond +-limit are clamped by the kernel (f16-split WaveNet kernels)
 		virtual const char* KernelName() const = 0;  // the kernel that runs this group's streams (rocprof name, without template arguments)
-		// WaveNet groups on the frame kernel can share ONE launch with other such groups (a heterogeneous batch without stream
-		// fork/join); fills `out` with this group's part of that launch.  Other groups return false.
-		// `launchList`: which fused launch it joins (0 frame kernel, 1 f16-split kernel, 2 f16-split kernel with packed streams)
-		virtual bool FusedLaunchArgs(WnFrameGroup& out, int& launchList)
-		{
-			(void)out;
-			(void)launchList;
-			return false;
-		}
-
-		// LSTM / GRU groups with an LDS-free kernel instance likewise share one launch (recurrent_dpp_kernels.hip)
-		virtual bool FusedRecurrentArgs(RecurrentGroup& out)
-		{
-			(void)out;
-			return false;
-		}
 
 		bool ListsDirty() const { return activeDirty; }
 
@@ -275,6 +258,7 @@ namespace na
 		}
 
 		hipStream_t stream;
+		LaunchKind kind = LaunchKind::Own;
 		hipStream_t sideStream = nullptr;
 		hipEvent_t doneEvent = nullptr;
 		std::vector<int> memberRow; // member == state slot
@@ -479,6 +463,8 @@ namespace na
 				dev.saturate = plan.splitRangeProven ? 0 : 1;
 				dev.compact_rings = (family == WN_FAMILY_SPLIT && plan.compactRings) ? 1 : 0;
 				dev.spec_arch = family == WN_FAMILY_SPLIT ? WaveNetSpecArchId(plan.sstages.data(), (int)plan.sstages.size(), plan.stateF4, (int)(plan.wsplit.size() / 8)) : WN_SPEC_NONE;
+				if (family == WN_FAMILY_SPLIT) kind = pack > 1 ? LaunchKind::SplitPacked : (plan.splitFastT == 2 ? LaunchKind::SplitJoinsPacked : LaunchKind::Split);
+				else kind = family == WN_FAMILY_GENERIC ? LaunchKind::Own : LaunchKind::Frame;
 			}
 
 			// ChannelHistoryBuffer::AllocBuffer zero-fills (WaveNet.h:38-40)
@@ -564,11 +550,10 @@ namespace na
 					const WnFamily which = family;
 					if (which == WN_FAMILY_SPLIT)
 					{
-						const WnFrameGroup g = { &dev, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive, contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, pack };
+						const WnFrameGroup g = LaunchArgs(false);
 						// (sharing 1; the state of this group's streams alone beyond the Infinity Cache: non-temporal ring traffic for the long dilations)
-						const bool beyondCache = !Tuning::Get().wnNtOff && (size_t)numActive * StateBytesPerStream() > ((size_t)Tuning::Get().wnNtFromMB << 20);
-						CheckHip(LaunchWaveNetSplitFused(&g, 1, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream, 1 | (beyondCache ? WN_SHARING_BEYOND_CACHE : 0)),
-							"WaveNetSplitKernel");
+						CheckHip(LaunchWaveNetSplitFused(&g, 1, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream,
+							1 | WnBeyondCacheBit((size_t)numActive * StateBytesPerStream())), "WaveNetSplitKernel");
 					}
 					else if (which == WN_FAMILY_GENERIC)
 						CheckHip(LaunchWaveNetGeneric(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
@@ -582,33 +567,18 @@ namespace na
 				}
 			}
 
-			bool FusedLaunchArgs(WnFrameGroup& out, int& launchList) override
+			// this group's part of a launch of the frame / f16-split kernels (groups of kind Own never take one); `indexLists`: the slot list
+			// even when the streams are contiguous (a plain group in the packed launch, launch_plan.h)
+			WnFrameGroup LaunchArgs(bool indexLists)
 			{
-				if (family == WN_FAMILY_GENERIC) return false; // its own launch
-				// list 2 = the packed flavour of the split kernel; a plain group whose plan runs the fast flavour may join it (negative list:
-				// "1, or 2 if a packed group is in the batch" -- then it passes its index lists even when its streams are contiguous)
-				launchList = LaunchClass();
-				out.pack = pack;
 				SyncActiveLists();
-				out.model = &dev;
-				out.state = state.Get();
-				out.slots = contiguous ? nullptr : dSlots.Get();
-				out.rows = dRows.Get();
-				out.numStreams = (int)hSlots.size();
-				out.slot0 = contiguous ? hSlots[0] : 0;
-				out.row0 = contiguous ? hRows[0] : 0;
-				listSlots = dSlots.Get();
-				return out.numStreams > 0;
+				return { &dev, state.Get(), (contiguous && !indexLists) ? nullptr : dSlots.Get(), dRows.Get(), (int)hSlots.size(), contiguous ? hSlots[0] : 0,
+					contiguous ? hRows[0] : 0, pack };
 			}
 
 			double AlgorithmicBytesPerSample(int blockFrames) const override { return (plan.isVirtual() ? realPlan : plan).AlgorithmicBytesPerSample(blockFrames); }
 			double MacsPerSample() const override { return (plan.isVirtual() ? realPlan : plan).MacsPerSample(); }
 			size_t StateBytesPerStream() const override { return (size_t)plan.stateF4 * 16 / (size_t)pack; }
-			int LaunchClass() const override
-			{
-				if (family == WN_FAMILY_GENERIC) return -2;
-				return family == WN_FAMILY_SPLIT ? (pack > 1 ? 2 : (plan.splitFastT == 2 ? -1 : 1)) : 0;
-			}
 			int PackFactor() const override { return pack; }
 			float InputLimit() const override { return family == WN_FAMILY_SPLIT ? plan.condLimit : INFINITY; }
 			void WeightsArrived() override
@@ -706,9 +676,6 @@ namespace na
 				CheckHip(hipStreamSynchronize(stream), "hipStreamSynchronize"); // the lists are freed on return
 			}
 
-		public:
-			const int* listSlots = nullptr; // device slot list of the last FusedLaunchArgs (always uploaded, also for contiguous groups)
-		private:
 			bool columnsPending;  // the weight images arrive from a peer device: the prewarm columns are computed then (WeightsArrived)
 			const int pack;       // real streams per virtual stream (1: no packing)
 			const bool dense;     // ... two streams per channel group in the last array (DenseFor)
@@ -803,6 +770,8 @@ namespace na
 				numElems = lstm.numLayers * 2 * lstm.hiddenSize + convRows;
 				dZeros.Alloc(LSTM_MAX_FRAMES);
 				CheckHip(hipMemsetAsync(dZeros.Get(), 0, LSTM_MAX_FRAMES * sizeof(float), stream), "hipMemsetAsync");
+				dpp = !(Tuning::Get().lstmNoDpp || Tuning::Get().gruNoDpp || Tuning::Get().lstmLaneKernel) && RecurrentDppSupported(dev);
+				kind = dpp ? LaunchKind::Recurrent : LaunchKind::Own;
 			}
 
 			// InternalLSTMModelT::Prewarm -> NeuralModelImpl::Prewarm(2048, 64) (InternalModel.h:368-371):
@@ -839,7 +808,7 @@ namespace na
 				if (numActive == 0) return;
 				size_t offset = 0;
 				RecurrentGroup fused;
-				const bool dpp = FusedRecurrentArgs(fused); // the LDS-free kernel, as a launch of one group (with the contiguous-streams shortcut)
+				if (dpp) fused = LaunchArgs(); // the LDS-free kernel, as a launch of one group
 				while (n > 0)
 				{
 					const int chunk = (int)std::min<size_t>(n, (size_t)LSTM_MAX_FRAMES);
@@ -850,20 +819,12 @@ namespace na
 				}
 			}
 
-			bool FusedRecurrentArgs(RecurrentGroup& out) override
+			// this group's part of a launch of the LDS-free kernel (groups of kind Recurrent)
+			RecurrentGroup LaunchArgs()
 			{
-				const bool noDpp = Tuning::Get().lstmNoDpp || Tuning::Get().gruNoDpp || Tuning::Get().lstmLaneKernel;
-				if (noDpp || !RecurrentDppSupported(dev)) return false;
 				SyncActiveLists();
-				out.model = dev;
-				out.state = state.Get();
-				out.capacity = (int)capacity;
-				out.slots = contiguous ? nullptr : dSlots.Get();
-				out.rows = dRows.Get();
-				out.numStreams = (int)hSlots.size();
-				out.slot0 = contiguous ? hSlots[0] : 0;
-				out.row0 = contiguous ? hRows[0] : 0;
-				return out.numStreams > 0;
+				return { dev, state.Get(), (int)capacity, contiguous ? nullptr : dSlots.Get(), dRows.Get(), (int)hSlots.size(), contiguous ? hSlots[0] : 0,
+					contiguous ? hRows[0] : 0 };
 			}
 
 			hipError_t Launch(const int* slots, const int* rows, int count, const float* dIn, float* dOut, long inStride, long outStride, int n, hipStream_t s)
@@ -893,11 +854,6 @@ namespace na
 				if (dWT.Get()) out.push_back({ dWT.Get(), dWT.Count() * sizeof(float) });
 			}
 			size_t StateBytesPerStream() const override { return (size_t)numElems * sizeof(float); }
-			int LaunchClass() const override
-			{
-				const bool noDpp = Tuning::Get().lstmNoDpp || Tuning::Get().gruNoDpp || Tuning::Get().lstmLaneKernel;
-				return (!noDpp && RecurrentDppSupported(dev)) ? 3 : -2;
-			}
 			const char* KernelName() const override
 			{
 				// (four streams per wave from RecurrentQuadMinStreams() streams in ONE launch: a batch of several recurrent models decides on
@@ -927,6 +883,7 @@ namespace na
 			}
 
 		private:
+			bool dpp = false; // the LDS-free kernel runs this model (a launch of kind Recurrent)
 			LstmModelDev dev = {};
 			DevArray<float> dW, dWT, dInit, dZeros;
 			DevArray<float> state;

@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "tuning.h"
 #include "wavenet_dev.h"
 
 namespace na
@@ -42,9 +43,14 @@ namespace na
 	// `sharing` of the fused launches below: the number of launches that share the chip (free-running chains), OR-ed with this bit when the
 	// batch's stream state does not fit the 256 MB Infinity Cache (the chains then mark the long dilations' ring traffic non-temporal)
 	constexpr int WN_SHARING_BEYOND_CACHE = 1 << 16;
-	// ... from this much stream state on (measured, us per 1024 A1 Standard streams with / without the non-temporal bits: 1280 streams =
-	// 311 MB 40.4 / 39.2 -- part of the state still lives in the cache --, 2048 = 498 MB 37.6 / 39.2, 8192 = 2 GB 37.4 - 38.4 / 37.9 - 39.2)
-	constexpr size_t WN_BEYOND_CACHE_BYTES = (size_t)400 << 20;
+	// ... for launches over `stateBytes` of stream state: from NA_WN_NT_MB (400 MiB) on, unless NA_WN_NT=0 (measured, us per 1024 A1
+	// Standard streams with / without the non-temporal bits: 1280 streams = 311 MB 40.4 / 39.2 -- part of the state still lives in the
+	// cache --, 2048 = 498 MB 37.6 / 39.2, 8192 = 2 GB 37.4 - 38.4 / 37.9 - 39.2)
+	inline int WnBeyondCacheBit(size_t stateBytes)
+	{
+		const Tuning& t = Tuning::Get();
+		return (!t.wnNtOff && stateBytes > ((size_t)t.wnNtFromMB << 20)) ? WN_SHARING_BEYOND_CACHE : 0;
+	}
 	hipError_t LaunchWaveNetSpecFused(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
 		hipStream_t stream, int sharing = 1);
 	// test hook (GpuBatch::DebugStallDevice): one wave that keeps `stream` busy for `ms` milliseconds (s_memrealtime, 100 MHz)

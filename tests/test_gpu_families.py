@@ -67,3 +67,17 @@ def test_forced_fallback_passes_the_parity_suite(env):
 @pytest.mark.parametrize("env", SOAK, ids=ident)
 def test_forced_family_passes_parity_fuzz_and_batch_suites(env):
     forced_run(env, [os.path.join(T, "test_gpu_parity.py"), os.path.join(T, "test_gpu_fuzz.py"), os.path.join(T, "test_gpu_batch.py")], 300)
+
+
+# Multi-unit batches (a buffer of several launches on forked side streams): the suite runs on the runtime the library was built for, which
+# replays a captured hipGraph; NA_BATCH_NO_GRAPH issues the fork / join directly every buffer -- the path of an older runtime
+# (NA_TEST_TORCH_FIRST) -- over the tests that process such batches.  They import torch: the child keeps the warm import.
+DIRECT_FORK_JOIN = ["test_gpu_batch.py::test_config4_lstm_2x16_many_streams_and_mixed_with_wavenet",
+                    "test_gpu_batch.py::test_table_launches_inside_a_captured_multi_unit_batch_replay_their_own_tables",
+                    "test_gpu_recurrent_quad.py::test_four_streams_per_wave_kernel_is_right_beside_matrix_waves_of_another_kernel"]
+
+
+@pytest.mark.gpu
+@pytest.mark.watchdog(260)
+def test_multi_unit_batches_pass_with_the_fork_join_issued_directly():
+    forced_run({"NA_BATCH_NO_GRAPH": "1"}, [os.path.join(T, t) for t in DIRECT_FORK_JOIN], 240)

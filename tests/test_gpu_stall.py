@@ -109,7 +109,7 @@ def test_device_pointer_buffers_give_up_at_the_limit(na, std, resident):
     for _ in range(3):
         b.ProcessDevice(x.data_ptr(), y.data_ptr(), n, n, n)
     b.WaitOutputs()
-    if not any(os.environ.get(k) for k in ("NA_WN_KERNEL", "NA_WN_SPEC", "NA_HOST_HALVES", "NA_SP_T", "NA_SP_GEN")):
+    if not any(os.environ.get(k) for k in ("NA_WN_KERNEL", "NA_WN_SPEC", "NA_HOST_HALVES", "NA_SP_T", "NA_SP_GEN", "NA_RESIDENT")):
         assert b.UsesResidentLaunch() == resident and (resident or b.UsesHalfLaunches())
     b.SetWaitLimitMs(LIMIT_MS)
     b.DebugStallDevice(STALL_MS)
