@@ -153,6 +153,33 @@ NA_EXTERN double NA_BatchStateBytes(NA_Batch* batch);
 NA_EXTERN int NA_BatchStreamPackFactor(NA_Batch* batch, int stream);
 /* the kernel that runs the stream (its rocprof name without template arguments; static string, "" on a bad argument) */
 NA_EXTERN const char* NA_BatchStreamKernelName(NA_Batch* batch, int stream);
+/* ---- stream snapshots: save and restore of live stream state (csrc/stream_snapshot.h) ------------
+ * A snapshot is one self-contained, relocatable blob per stream: the history of every conv layer / the recurrent state of every submodel
+ * plus quality, active submodel and prewarmed bits, behind a versioned header with a fingerprint of the model (architecture + weights).
+ * It loads into any stream created from the same model file -- in another batch, on another device, in another process, on another kernel
+ * family -- and the stream then continues where the saved one stopped: bit for bit where the same kernel runs both, else to the kernels'
+ * usual tolerance.  Moving a session between GPUs, parking and resuming it, consolidating batches, rewinding for an A/B comparison.
+ *
+ * Both calls first wait for everything of the batch that is in flight (like NA_BatchRemoveStreams): NOT real-time safe, call them
+ * between buffers, never from the audio callback.  A broken batch refuses both.  Cost: one device launch per model of the listed
+ * streams and one device <-> host copy per call, however many streams the call names. */
+/* bytes NA_BatchSaveStreams writes for this stream (host arithmetic; no device work); negative on a bad argument */
+NA_EXTERN long long NA_BatchStreamSnapshotBytes(NA_Batch* batch, int stream);
+/* the same from a model alone, without a batch or a device */
+NA_EXTERN long long NA_ModelSnapshotBytes(NeuralModel* model);
+/* fingerprint a snapshot of this model carries (host arithmetic): the same for every load of one file whatever the math mode or kernel */
+NA_EXTERN unsigned long long NA_ModelSnapshotFingerprint(NeuralModel* model);
+/* blobs of streams[0..count) back to back into buf; *written = total bytes.  Non-zero (and *written = bytes needed, nothing written to
+ * buf) if capacity is short.  Saving changes nothing: the streams continue as if it had not been called. */
+NA_EXTERN int NA_BatchSaveStreams(NA_Batch* batch, const int* streams, int count, void* buf, size_t capacity, size_t* written);
+/* the inverse: blob i goes to streams[i] (each id at most once).  All-or-nothing: every blob is checked first -- magic, version, size,
+ * model fingerprint against the destination stream's model, submodel count -- and on any mismatch the call returns non-zero with the
+ * reason in NA_GetLastError() and no stream has changed.  The destination keeps its own composite load mode. */
+NA_EXTERN int NA_BatchLoadStreams(NA_Batch* batch, const int* streams, int count, const void* buf, size_t bytes);
+/* the one-stream NeuralModel of the legacy API is a batch of one (call them from the thread that calls Process) */
+NA_EXTERN int NA_SaveModelState(NeuralModel* model, void* buf, size_t capacity, size_t* written);
+NA_EXTERN int NA_LoadModelState(NeuralModel* model, const void* buf, size_t bytes);
+
 /* ---- multi-GPU host: one batch + one host thread + one HIP stream per device ------------------------------------------------
  * The GLOBAL stream list (order of the NA_MultiAddStreams calls: sort it by architecture) is cut into contiguous ranges of near-equal
  * cost, one per entry of `devices` (an index may repeat).  Streams are independent (the reference runs one NeuralModel per stream,
@@ -271,6 +298,8 @@ NA_EXTERN void NA_DebugSetWaveNetSpec(int on);
  * environment NA_REC_QUAD_MIN); returns the previous value.  NA_DebugRecurrentQuadLaunches: launches of that kernel so far. */
 NA_EXTERN int NA_DebugSetRecurrentQuadMin(int streams);
 NA_EXTERN long long NA_DebugRecurrentQuadLaunches(void);
+/* Tests: export / import kernel launches of the stream snapshots so far (one per model group and call, whatever the stream count) */
+NA_EXTERN long long NA_DebugSnapshotLaunches(void);
 /* Tests: which implementation of the NCCL entry points the multi-GPU host binds.  0 = librccl.so (the product).  1 = a loopback table
  * inside this library (csrc/rccl_loopback.cpp): every rank may sit on the SAME device and a transfer is a device-to-device copy, so the
  * multi-rank orchestration (communicators, weight fan-out, gathered fan-in, failure teardown) executes on a one-GPU box; it moves no

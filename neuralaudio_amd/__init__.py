@@ -14,7 +14,7 @@ import numpy as np
 from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
-           "NeuralAudioError", "render_offline", "render_plan"]
+           "NeuralAudioError", "render_offline", "render_plan", "snapshot_bytes", "snapshot_fingerprint"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -127,6 +127,23 @@ class NeuralModel:
             raise NeuralAudioError(capi.last_error())
         return {"kernel": name.value.decode(), "input_limit": float(lim.value), "range_proven": bool(proven.value), "weights_ok": bool(wok.value),
                 "pack": int(pack.value)}
+
+    # -- stream snapshots (include/neuralaudio_amd.h) --------------------------------
+    def SnapshotBytes(self):
+        return snapshot_bytes(self)
+
+    def SaveState(self):
+        """This stream's state as a relocatable blob (bytes); LoadState on a model of the same file continues from it."""
+        buf = C.create_string_buffer(max(self.SnapshotBytes(), 1))
+        written = C.c_size_t(0)
+        if self._lib.NA_SaveModelState(self._h, buf, len(buf), C.byref(written)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return buf.raw[:written.value]
+
+    def LoadState(self, blob):
+        blob = bytes(blob)
+        if self._lib.NA_LoadModelState(self._h, blob, len(blob)) != 0:
+            raise NeuralAudioError(capi.last_error())
 
     def close(self):
         if self._h:
@@ -243,6 +260,31 @@ class Batch:
 
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    # -- stream snapshots: not real-time safe (they wait for everything in flight), call between buffers ---------------------------
+    def StreamSnapshotBytes(self, stream):
+        n = int(self._lib.NA_BatchStreamSnapshotBytes(self._h, int(stream)))
+        if n < 0:
+            raise NeuralAudioError(capi.last_error())
+        return n
+
+    def SaveStreams(self, streams):
+        """The snapshots of `streams` (an id or a sequence of ids) back to back as bytes: one launch per model, one download."""
+        ids = np.atleast_1d(np.asarray(streams, dtype=np.int32))
+        idp = ids.ctypes.data_as(C.POINTER(C.c_int))
+        need = sum(self.StreamSnapshotBytes(int(s)) for s in ids)
+        buf = C.create_string_buffer(max(need, 1))
+        written = C.c_size_t(0)
+        if self._lib.NA_BatchSaveStreams(self._h, idp, ids.size, buf, need, C.byref(written)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return buf.raw[:written.value]
+
+    def LoadStreams(self, streams, blob):
+        """The inverse: snapshot i of `blob` goes to streams[i].  All or nothing: raises (naming the reason) before any stream changed."""
+        ids = np.atleast_1d(np.asarray(streams, dtype=np.int32))
+        blob = bytes(blob)
+        if self._lib.NA_BatchLoadStreams(self._h, ids.ctypes.data_as(C.POINTER(C.c_int)), ids.size, blob, len(blob)) != 0:
             raise NeuralAudioError(capi.last_error())
 
     def IsQualityChangeRealtimeSafe(self, stream, q):
@@ -473,6 +515,19 @@ class MultiBatch:
             self.close()
         except Exception:
             pass
+
+
+def snapshot_bytes(model):
+    """Bytes of one stream snapshot of `model` (host arithmetic: no batch, no device)."""
+    n = int(capi.load_library().NA_ModelSnapshotBytes(model._h))
+    if n < 0:
+        raise NeuralAudioError(capi.last_error())
+    return n
+
+
+def snapshot_fingerprint(model):
+    """The model fingerprint a snapshot carries: architecture + weights of every submodel, nothing kernel-specific."""
+    return int(capi.load_library().NA_ModelSnapshotFingerprint(model._h))
 
 
 def _render_jobs(model, x, quality):

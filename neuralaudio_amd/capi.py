@@ -32,6 +32,8 @@ NA_SYMBOLS = [
     "NA_BatchMarkTime", "NA_BatchWaitMarks", "NA_BatchElapsedMs", "NA_BatchUsesHalfLaunches", "NA_DebugSetRcclApi", "NA_BatchWaitOutputs", "NA_BatchUsesResidentLaunch", "NA_BatchSetResidentLaunch",
     "NA_BatchSetWaitLimitMs", "NA_BatchGetWaitLimitMs", "NA_BatchIsBroken", "NA_DebugStallDevice",
     "NA_RenderOffline", "NA_RenderPlan",
+    "NA_BatchStreamSnapshotBytes", "NA_ModelSnapshotBytes", "NA_ModelSnapshotFingerprint", "NA_BatchSaveStreams", "NA_BatchLoadStreams",
+    "NA_SaveModelState", "NA_LoadModelState", "NA_DebugSnapshotLaunches",
 ]
 
 
@@ -163,6 +165,14 @@ def load_library():
         "NA_DebugPackedWeights": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_int]),
         "NA_RenderOffline": (C.c_int, [C.POINTER(NA_RenderJob), C.c_int, C.POINTER(NA_RenderOptions)]),
         "NA_RenderPlan": (C.c_int, [C.POINTER(NA_RenderJob), C.c_int, C.POINTER(NA_RenderOptions), C.POINTER(NA_RenderPlanInfo)]),
+        "NA_BatchStreamSnapshotBytes": (C.c_longlong, [vp, C.c_int]),
+        "NA_ModelSnapshotBytes": (C.c_longlong, [vp]),
+        "NA_ModelSnapshotFingerprint": (C.c_ulonglong, [vp]),
+        "NA_BatchSaveStreams": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "NA_BatchLoadStreams": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, vp, C.c_size_t]),
+        "NA_SaveModelState": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "NA_LoadModelState": (C.c_int, [vp, vp, C.c_size_t]),
+        "NA_DebugSnapshotLaunches": (C.c_longlong, []),
         "NA_DebugSplitPlan": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_ushort), C.c_longlong, C.POINTER(C.c_longlong)]),
     }
     for name, (res, args) in sig.items():

@@ -8,6 +8,7 @@
 #include "neuralaudio_amd.h"
 #include "multi_gpu.h"
 #include "offline_render.h"
+#include "stream_snapshot.h"
 #include "neural_model_impl.h"
 #include "lstm_launch.h"
 #include "wavenet_launch.h"
@@ -420,6 +421,79 @@ int NA_BatchRemoveStreams(NA_Batch* batch, int first, int count)
 	if (!batch) return -1;
 	return Guard([&] { batch->batch->RemoveStreams(first, count); });
 }
+
+// ---- stream snapshots (csrc/stream_snapshot.h) ----
+namespace
+{
+	NeuralAudio::GpuModel* OwnModel(NeuralModel* model, const char* who)
+	{
+		NeuralAudio::GpuModel* gm = model ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+		if (!gm) throw std::runtime_error(std::string(who) + ": model is null or was not created by this library");
+		return gm;
+	}
+}
+
+long long NA_BatchStreamSnapshotBytes(NA_Batch* batch, int stream)
+{
+	long long n = -1;
+	Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchStreamSnapshotBytes: null batch");
+		n = (long long)batch->batch->StreamSnapshotBytes(stream);
+	});
+	return n;
+}
+
+long long NA_ModelSnapshotBytes(NeuralModel* model)
+{
+	long long n = -1;
+	Guard([&] { n = (long long)na::SnapshotBytes(*OwnModel(model, "NA_ModelSnapshotBytes")->GetLoadedModel()); });
+	return n;
+}
+
+unsigned long long NA_ModelSnapshotFingerprint(NeuralModel* model)
+{
+	unsigned long long f = 0;
+	Guard([&] { f = na::ModelFingerprint(*OwnModel(model, "NA_ModelSnapshotFingerprint")->GetLoadedModel()); });
+	return f;
+}
+
+int NA_BatchSaveStreams(NA_Batch* batch, const int* streams, int count, void* buf, size_t capacity, size_t* written)
+{
+	if (written) *written = 0;
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchSaveStreams: null batch (a batch needs a HIP device: there is no host-side stream state)");
+		const size_t need = batch->batch->SaveStreams(streams, count, buf, capacity);
+		if (written) *written = need;
+		if (need > capacity) throw std::runtime_error("NA_BatchSaveStreams: buffer too small: " + std::to_string(need) + " bytes needed, " + std::to_string(capacity) + " given");
+	});
+}
+
+int NA_BatchLoadStreams(NA_Batch* batch, const int* streams, int count, const void* buf, size_t bytes)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchLoadStreams: null batch (a batch needs a HIP device: there is no host-side stream state)");
+		batch->batch->LoadStreams(streams, count, buf, bytes);
+	});
+}
+
+int NA_SaveModelState(NeuralModel* model, void* buf, size_t capacity, size_t* written)
+{
+	if (written) *written = 0;
+	return Guard([&] {
+		const size_t need = OwnModel(model, "NA_SaveModelState")->SaveState(buf, capacity);
+		if (written) *written = need;
+		if (need > capacity) throw std::runtime_error("NA_SaveModelState: buffer too small: " + std::to_string(need) + " bytes needed, " + std::to_string(capacity) + " given");
+	});
+}
+
+int NA_LoadModelState(NeuralModel* model, const void* buf, size_t bytes)
+{
+	return Guard([&] { OwnModel(model, "NA_LoadModelState")->LoadState(buf, bytes); });
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugSnapshotLaunches(void) { return na::SnapshotKernelLaunches(); }
+#endif
 
 int NA_BatchSetQuality(NA_Batch* batch, int stream, float quality)
 {

@@ -145,6 +145,8 @@ namespace na
 		groups.clear();
 		if (hostStage) (void)hipHostFree(hostStage);
 		if (devStage) (void)hipFree(devStage);
+		if (snapHost) (void)hipHostFree(snapHost);
+		if (snapDev) (void)hipFree(snapDev);
 		for (PipeSlot& p : pipe)
 		{
 			if (p.hostIn) (void)hipHostFree(p.hostIn);

@@ -10,6 +10,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <memory>
 #include <string>
 #include <vector>
@@ -86,6 +87,18 @@ namespace na
 		// Not real-time safe (like AddStreams): call between buffers.
 		void RemoveStreams(int first, int count);
 		bool IsLive(int stream) const { return stream >= 0 && stream < (int)streams.size() && streams[(size_t)stream].live; }
+
+		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
+		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
+		// into `buf` and returns their total size; with `capacity` short of it nothing is written (the caller sizes the buffer from the
+		// return value).  LoadStreams reads blob i into stream ids[i]: every blob is checked against its destination's model before
+		// anything is written (all or nothing; throws naming the reason); the stream takes over quality, active submodel, prewarmed
+		// bits and the state of every submodel, and keeps its own load mode.  Both settle the batch first like RemoveStreams (resident
+		// launch, half-batch chains, pipeline tickets, batch stream): not real-time safe, call between buffers.  One export / import
+		// launch per model group and one device <-> host copy per call, whatever `count`.  SaveStreams changes nothing on the device.
+		size_t StreamSnapshotBytes(int stream) const;
+		size_t SaveStreams(const int* ids, int count, void* buf, size_t capacity);
+		void LoadStreams(const int* ids, int count, const void* buf, size_t bytes);
 
 		int NumStreams() const { return (int)streams.size(); } // rows of the [streams][n] arrays (retired ids included)
 		int NumLiveStreams() const { return (int)streams.size() - (int)retired.size(); }
@@ -261,6 +274,15 @@ namespace na
 		bool peerWeights = false;
 		std::vector<ModelGroup*> awaitingWeights;
 		std::vector<std::pair<ModelGroup*, std::vector<int>>> pendingPrewarm;
+
+		// snapshot staging (SaveStreams / LoadStreams): pinned host + device, 32-bit words, grown on demand
+		uint32_t* snapHost = nullptr;
+		uint32_t* snapDev = nullptr;
+		size_t snapWords = 0;
+		void EnsureSnapshotStaging(size_t words);
+		void SettleForSnapshot(const int* ids, int count, const char* who);
+		std::vector<std::pair<std::shared_ptr<const LoadedModel>, uint64_t>> fingerprints; // of the models of this batch's streams, computed once each
+		uint64_t FingerprintOf(const std::shared_ptr<const LoadedModel>& model);
 
 		float* hostStage = nullptr; // pinned
 		float* devStage = nullptr;

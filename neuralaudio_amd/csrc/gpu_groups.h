@@ -20,6 +20,7 @@
 #include "gpu_batch.h"
 #include "launch_plan.h"
 #include "lstm_launch.h"
+#include "stream_snapshot.h"
 #include "tuning.h"
 #include "wavenet_launch.h"
 #include "wavenet_plan.h"
@@ -176,6 +177,15 @@ namespace na
 		virtual void WeightsArrived() {}
 		virtual float InputLimit() const { return INFINITY; } // samples beyond +-limit are clamped by the kernel (f16-split WaveNet kernels)
 		virtual const char* KernelName() const = 0;  // the kernel that runs this group's streams (rocprof name, without template arguments)
+
+		// Stream snapshots (stream_snapshot.h): the section of every listed member, `SnapshotValues()` words each, back to back in list
+		// order in a device staging buffer.  One launch on the batch stream, asynchronous; the caller has quiesced the batch and copies
+		// / waits.  SaveState reads only.  LoadState: `encodings[i]` is the encoding of member i's section in the staging buffer; it
+		// writes nothing but the listed members' own values (neighbours of a packed virtual stream and the shared cursors stay).
+		size_t SnapshotValues() const { return SnapshotSectionValues(*desc); }
+		virtual uint32_t SnapshotNativeEncoding() const = 0;
+		virtual void SaveState(const std::vector<int>& members, uint32_t* dStaging) = 0;
+		virtual void LoadState(const std::vector<int>& members, const std::vector<uint32_t>& encodings, const uint32_t* dStaging) = 0;
 
 		bool ListsDirty() const { return activeDirty; }
 
@@ -432,6 +442,22 @@ namespace na
 				dRingOff.Upload(ringOff, stream);
 				dRingFrames.Upload(ringFrames, stream);
 				dRingG.Upload(ringG, stream);
+				{
+					// snapshot table (stream_snapshot.h WnSnapshotArgs::snapTab): what of every ring is one REAL stream's history
+					const std::vector<SnapshotRing> real = SnapshotRings(d->wavenet);
+					if (real.size() != plan.rings.size()) throw std::runtime_error("internal: snapshot rings do not match the WaveNet plan");
+					std::vector<int> tab;
+					int words = 0;
+					for (size_t r = 0; r < real.size(); r++)
+					{
+						const WnRingInfo& ri = plan.rings[r];
+						const int owned = pack > 1 ? ri.channels / pack : 4 * ri.G;
+						if (real[r].history > ri.frames || real[r].channels > owned) throw std::runtime_error("internal: snapshot ring exceeds the plan's ring");
+						tab.insert(tab.end(), { real[r].history, real[r].channels, owned, words });
+						words += real[r].history * real[r].channels;
+					}
+					dSnapTab.Upload(tab, stream);
+				}
 
 				// steady-state columns: once per model (WaveNet.h:746-766)
 				dCols.Alloc(plan.rings.size() * WN_COL_STRIDE);
@@ -606,6 +632,19 @@ namespace na
 				CheckHip(hipStreamSynchronize(stream), "hipStreamSynchronize");
 				return count;
 			}
+			uint32_t SnapshotNativeEncoding() const override { return family == WN_FAMILY_SPLIT ? SNAP_SPLIT : SNAP_F32; }
+			void SaveState(const std::vector<int>& members, uint32_t* dStaging) override
+			{
+				if (members.empty()) return;
+				const WnSnapshotArgs a = SnapshotArgs(members, nullptr);
+				CheckHip(LaunchWaveNetSnapshotExport(a, dStaging, stream), "WaveNetSnapshotExportKernel");
+			}
+			void LoadState(const std::vector<int>& members, const std::vector<uint32_t>& encodings, const uint32_t* dStaging) override
+			{
+				if (members.empty()) return;
+				const WnSnapshotArgs a = SnapshotArgs(members, &encodings);
+				CheckHip(LaunchWaveNetSnapshotImport(a, dStaging, stream), "WaveNetSnapshotImportKernel");
+			}
 			const char* KernelName() const override
 			{
 				// (a model with a specialised chain runs it for blocks of 128 / 64 / 32 frames, the interpreter for other lengths)
@@ -665,6 +704,23 @@ namespace na
 			}
 
 		private:
+			// the launch arguments of a snapshot export / import of `members`; uploads their [slot | sub | encoding] lists
+			WnSnapshotArgs SnapshotArgs(const std::vector<int>& members, const std::vector<uint32_t>* encodings)
+			{
+				const size_t n = members.size();
+				std::vector<int> lists(3 * n);
+				for (size_t i = 0; i < n; i++)
+				{
+					if (!InUse(members[i])) throw std::runtime_error("internal: snapshot of a state slot that is not in use");
+					lists[i] = members[i] / pack;
+					lists[n + i] = members[i] % pack;
+					lists[2 * n + i] = encodings ? (int)(*encodings)[i] : (int)SnapshotNativeEncoding();
+				}
+				dSnapLists.Upload(lists, stream);
+				return { state.Get(), plan.stateF4, dSnapLists.Get(), (int)n, (int)plan.rings.size(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
+					dSnapTab.Get(), family == WN_FAMILY_SPLIT ? 1 : 0, pack, (int)SnapshotValues() };
+			}
+
 			void FillPacked(const std::vector<int>& slots, const std::vector<int>& subs, bool zero)
 			{
 				if (slots.empty()) return;
@@ -690,6 +746,7 @@ namespace na
 			DevArray<float> dWeights;
 			DevArray<float> dWeightsGen; // WN_FAMILY_GENERIC: layer convs tap-major
 			DevArray<int> dRingOff, dRingFrames, dRingG;
+			DevArray<int> dSnapTab, dSnapLists; // stream snapshots: the per-ring table, the lists of the current call
 			DevArray<float> dCols;
 			DevArray<WnSplitStage> dSStages;
 			DevArray<uint16_t> dWsplit;
@@ -854,6 +911,12 @@ namespace na
 				if (dWT.Get()) out.push_back({ dWT.Get(), dWT.Count() * sizeof(float) });
 			}
 			size_t StateBytesPerStream() const override { return (size_t)numElems * sizeof(float); }
+			uint32_t SnapshotNativeEncoding() const override { return SNAP_F32; }
+			void SaveState(const std::vector<int>& members, uint32_t* dStaging) override { SnapshotLaunch(members, dStaging, false); }
+			void LoadState(const std::vector<int>& members, const std::vector<uint32_t>&, const uint32_t* dStaging) override
+			{
+				SnapshotLaunch(members, const_cast<uint32_t*>(dStaging), true);
+			}
 			const char* KernelName() const override
 			{
 				// (four streams per wave from RecurrentQuadMinStreams() streams in ONE launch: a batch of several recurrent models decides on
@@ -883,6 +946,18 @@ namespace na
 			}
 
 		private:
+			void SnapshotLaunch(const std::vector<int>& members, uint32_t* dStaging, bool import)
+			{
+				if (members.empty()) return;
+				if ((size_t)numElems != SnapshotValues()) throw std::runtime_error("internal: snapshot section does not match the recurrent state");
+				for (int m : members)
+					if (!InUse(m)) throw std::runtime_error("internal: snapshot of a state slot that is not in use");
+				dSnapLists.Upload(members, stream);
+				CheckHip(LaunchRecurrentSnapshot(state.Get(), (int)capacity, dSnapLists.Get(), (int)members.size(), numElems, dStaging, import, stream),
+					"RecurrentSnapshotKernel");
+			}
+
+			DevArray<int> dSnapLists;
 			bool dpp = false; // the LDS-free kernel runs this model (a launch of kind Recurrent)
 			LstmModelDev dev = {};
 			DevArray<float> dW, dWT, dInit, dZeros;

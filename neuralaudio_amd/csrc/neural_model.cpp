@@ -118,6 +118,29 @@ namespace NeuralAudio
 		PublishPrewarmState();
 	}
 
+	// Stream snapshots: the one stream of this model's batch.  Like Process / Prewarm they create the device state on first use (a
+	// model without a device fails here with the batch's own message: there is no host-side state to save).
+	size_t GpuModel::SaveState(void* buf, size_t capacity)
+	{
+		EnsureDeviceState();
+		ApplyPendingQuality();
+		const int id = 0;
+		return batch->SaveStreams(&id, 1, buf, capacity);
+	}
+
+	void GpuModel::LoadState(const void* buf, size_t bytes)
+	{
+		EnsureDeviceState();
+		ApplyPendingQuality();
+		const int id = 0;
+		batch->LoadStreams(&id, 1, buf, bytes);
+		// the snapshot's quality is this model's now, as if SetQualityScaleFactor had been called and applied
+		appliedQuality = batch->GetQuality(0);
+		quality.store(appliedQuality);
+		activeIndex.store(batch->GetActiveSubModel(0));
+		PublishPrewarmState();
+	}
+
 	// ------------------------------------------------------------------------------------------ loader
 
 	bool NeuralModelLoader::SupportsWaveNetLoadMode(EModelLoadMode mode) { return mode == EModelLoadMode::Internal; }

@@ -31,6 +31,10 @@ namespace NeuralAudio
 		int GetDevice() const { return device; }
 		bool IsOnDemand() const { return onDemand; }
 
+		// stream snapshots (gpu_batch.h SaveStreams / LoadStreams) of this one-stream model; audio thread
+		size_t SaveState(void* buf, size_t capacity);
+		void LoadState(const void* buf, size_t bytes);
+
 	private:
 		void EnsureDeviceState();
 

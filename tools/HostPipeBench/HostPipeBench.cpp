@@ -6,6 +6,8 @@
 //       cost): `streams` is the GLOBAL count; --devices names the device of every shard explicitly (an index may repeat, e.g. 0,0 runs
 //       two shards on one GPU -- the plumbing test on a single-GPU box).  A second model file may follow --mix: the global list is then
 //       half / half (architecture-sorted), which exercises the cost-balanced cut.
+//   HostPipeBench <model file> [streams] [frames] [buffers=64] --migrate K [--devices a,b]
+//       the stream-snapshot example (RunMigrate below): moves K streams half way through and checks the result against an unmoved run.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -13,7 +15,9 @@
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cmath>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "neuralaudio_amd.h"
 
@@ -100,19 +104,118 @@ static int RunMulti(NeuralModelLoader* loader, NeuralModel* model, const char* m
 	return identical ? 0 : 3;
 }
 
+// --migrate K: the complete host example of the stream snapshots (include/neuralaudio_amd.h "stream snapshots").
+// Half way through `buffers` buffers the first K streams are saved (NA_BatchSaveStreams), removed, added again as fresh streams
+// without prewarm -- in a second batch on devices[1] when --devices a,b is given, else in the same batch -- and loaded
+// (NA_BatchLoadStreams); the final buffer of every stream is then compared with a run in which nothing moved.  Also times the two
+// calls (median of 12 after a warm-up call) and, for context, what a host without snapshots does to move a stream and lose its
+// state: NA_BatchRemoveStreams + NA_BatchAddStreams(doPrewarm = 1) of the same count.
+static double Median(std::vector<double> v)
+{
+	std::sort(v.begin(), v.end());
+	return v.empty() ? 0.0 : v[v.size() / 2];
+}
+
+static int RunMigrate(NeuralModel* model, const std::vector<int>& devices, int streams, int frames, int buffers, int K)
+{
+	CHECK(K >= 1 && K <= streams && buffers >= 2);
+	const int dev0 = devices.empty() ? 0 : devices[0];
+	const bool second = devices.size() > 1;
+	const size_t count = (size_t)streams * frames;
+	auto fill = [&](std::vector<float>& in, int buffer) {
+		for (size_t i = 0; i < in.size(); i++) in[i] = 0.5f * (float)((((i + (size_t)buffer * 7919u) * 2654435761u) >> 8) & 0xffff) / 65536.0f - 0.25f;
+	};
+	std::vector<float> in(count), refOut(count), out(count), outB((size_t)K * frames);
+	// the unmigrated run
+	{
+		NA_Batch* ref = NA_BatchCreate(dev0, nullptr);
+		CHECK(ref != nullptr);
+		CHECK(NA_BatchAddStreams(ref, model, 1.0f, streams, 1) >= 0);
+		for (int b = 0; b < buffers; b++)
+		{
+			fill(in, b);
+			CHECK(NA_BatchProcess(ref, in.data(), refOut.data(), (size_t)frames) == 0);
+		}
+		NA_BatchDestroy(ref);
+	}
+	NA_Batch* a = NA_BatchCreate(dev0, nullptr);
+	CHECK(a != nullptr);
+	CHECK(NA_BatchAddStreams(a, model, 1.0f, streams, 1) >= 0);
+	NA_Batch* b2 = second ? NA_BatchCreate(devices[1], nullptr) : a;
+	CHECK(b2 != nullptr);
+	for (int b = 0; b < buffers / 2; b++)
+	{
+		fill(in, b);
+		CHECK(NA_BatchProcess(a, in.data(), out.data(), (size_t)frames) == 0);
+	}
+	std::vector<int> ids((size_t)K);
+	for (int i = 0; i < K; i++) ids[(size_t)i] = i;
+	const long long each = NA_BatchStreamSnapshotBytes(a, 0);
+	CHECK(each > 0 && each == NA_ModelSnapshotBytes(model));
+	std::vector<char> blob((size_t)each * K);
+	size_t written = 0;
+	CHECK(NA_BatchSaveStreams(a, ids.data(), K, blob.data(), blob.size(), &written) == 0 && written == blob.size());
+	const std::string kernelFrom = NA_BatchStreamKernelName(a, 0);
+	CHECK(NA_BatchRemoveStreams(a, 0, K) == 0);
+	const int first = NA_BatchAddStreams(b2, model, 1.0f, K, 0); // fresh, no prewarm: the snapshot brings the state
+	CHECK(first == 0);
+	CHECK(NA_BatchLoadStreams(b2, ids.data(), K, blob.data(), blob.size()) == 0);
+	const std::string kernelTo = NA_BatchStreamKernelName(b2, 0);
+	for (int b = buffers / 2; b < buffers; b++)
+	{
+		fill(in, b);
+		CHECK(NA_BatchProcess(a, in.data(), out.data(), (size_t)frames) == 0);
+		if (second) CHECK(NA_BatchProcess(b2, in.data(), outB.data(), (size_t)frames) == 0); // (rows 0 .. K-1 of the input are the moved streams')
+	}
+	if (second) std::memcpy(out.data(), outB.data(), outB.size() * sizeof(float));
+	double maxDiff = 0.0;
+	for (size_t i = 0; i < count; i++) maxDiff = std::max(maxDiff, (double)std::fabs(out[i] - refOut[i]));
+	const bool identical = std::memcmp(out.data(), refOut.data(), count * sizeof(float)) == 0;
+	const bool ok = identical || (kernelFrom != kernelTo && maxDiff < 1e-4);
+
+	// timings: host to host, median of 12
+	std::vector<double> tSave, tLoad, tRejoin;
+	for (int r = 0; r < 13; r++)
+	{
+		double t0 = Now();
+		CHECK(NA_BatchSaveStreams(b2, ids.data(), K, blob.data(), blob.size(), &written) == 0);
+		if (r) tSave.push_back((Now() - t0) * 1e3);
+		t0 = Now();
+		CHECK(NA_BatchLoadStreams(b2, ids.data(), K, blob.data(), blob.size()) == 0);
+		if (r) tLoad.push_back((Now() - t0) * 1e3);
+	}
+	for (int r = 0; r < 6; r++)
+	{
+		const double t0 = Now();
+		CHECK(NA_BatchRemoveStreams(b2, 0, K) == 0);
+		CHECK(NA_BatchAddStreams(b2, model, 1.0f, K, 1) == 0);
+		CHECK(NA_BatchSynchronize(b2) == 0);
+		if (r) tRejoin.push_back((Now() - t0) * 1e3);
+	}
+	std::printf("{\"migrate\": %d, \"streams\": %d, \"frames\": %d, \"buffers\": %d, \"second_batch\": %s, \"kernel_from\": \"%s\", \"kernel_to\": \"%s\", "
+		"\"snapshot_bytes_per_stream\": %lld, \"identical\": %s, \"max_abs_diff\": %.3g, \"save_ms\": %.3f, \"load_ms\": %.3f, \"remove_add_prewarm_ms\": %.3f}\n",
+		K, streams, frames, buffers, second ? "true" : "false", kernelFrom.c_str(), kernelTo.c_str(), each, identical ? "true" : "false", maxDiff, Median(tSave),
+		Median(tLoad), Median(tRejoin));
+	if (second) NA_BatchDestroy(b2);
+	NA_BatchDestroy(a);
+	return ok ? 0 : 3;
+}
+
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
+	int migrate = 0;
 	for (int i = 1; i < argc; i++)
 	{
 		if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--fan-in") && i + 1 < argc) rcclFanIn = !std::strcmp(argv[++i], "rccl");
 		else if (!std::strcmp(argv[i], "--mix") && i + 1 < argc) mixFile = argv[++i];
+		else if (!std::strcmp(argv[i], "--migrate") && i + 1 < argc) migrate = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
 			// rehearsal on a one-GPU box: the multi-GPU host bound to the library's loopback RCCL table (test build only), so that
@@ -135,6 +238,13 @@ int main(int argc, char** argv)
 	CHECK(loader != nullptr);
 	NeuralModel* model = NA_CreateModelFromFileUtf8(loader, pos[0], 0);
 	CHECK(model != nullptr);
+	if (migrate > 0)
+	{
+		const int rc = RunMigrate(model, devices, streams, frames, pos.size() > 3 ? buffers : 64, migrate);
+		DeleteModel(model);
+		DeleteLoader(loader);
+		return rc;
+	}
 	if (gpus > 0 || !devices.empty())
 	{
 		if (devices.empty())
