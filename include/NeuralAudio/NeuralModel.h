@@ -138,6 +138,12 @@ namespace NeuralAudio
 		EMathMode GetWaveNetMathMode() { return wavenetMath; }
 		void SetLSTMMathMode(EMathMode mode) { lstmMath = mode; }
 		EMathMode GetLSTMMathMode() { return lstmMath; }
+		// Opt-in (default off: the reference's behaviour): a model created while the external sample rate is neither its model-side rate
+		// nor a whole multiple of it (44.1 kHz against a 48 kHz capture) resamples inside Process() -- a resampling batch of one, see
+		// NA_BatchSetResampling in neuralaudio_amd.h; its output is delayed by NA_GetProcessLatencySamples() external samples.
+		void SetResampleToExternalRate(bool on) { resampleToExternalRate = on; }
+		bool GetResampleToExternalRate() { return resampleToExternalRate; }
+		int GetExternalSampleRate() { return externalSampleRate; }
 
 	protected:
 		EModelLoadMode lstmLoadMode = EModelLoadMode::Internal;
@@ -150,5 +156,6 @@ namespace NeuralAudio
 		int device = 0;
 		EMathMode wavenetMath = EMathMode::FastMath;
 		EMathMode lstmMath = EMathMode::FastMath;
+		bool resampleToExternalRate = false;
 	};
 }

@@ -278,6 +278,56 @@ typedef struct NA_RenderPlanInfo
 NA_EXTERN int NA_RenderOffline(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts);
 /* the plan of NA_RenderOffline without running it (no device needed; with one it also builds the segment batch for info->kernel) */
 NA_EXTERN int NA_RenderPlan(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, NA_RenderPlanInfo* info);
+
+/* ---- batch resampling: hosts whose sample rate is not the model's (csrc/resample.h) -------------
+ * Every model has one sample rate; the loader serves whole multiples of it by multiplying the dilations (NA_SetExternalSampleRate), and
+ * every other external rate -- 44.1 kHz against a 48 kHz capture -- would run the model at the wrong rate.  A resampling batch converts
+ * on the device: ONE clock domain per batch (one external rate Fe, one model rate Fm, one phase for all its streams; a server keeps one
+ * batch per client rate).  With Fc = lcm(Fe, Fm), te = Fc / Fe, tm = Fc / Fm, one Kaiser-windowed sinc prototype at Fc of length
+ * K = 48 * max(te, tm) + 1 (pass band to 16 / 22.05 of the lower Nyquist frequency, stop band from that Nyquist frequency, 100 dB)
+ * serves both directions.  The model only ever runs whole multiples of the block quantum q (1, 32, 64 or 128 frames; 0 = the default,
+ * 32): after E external samples it has run P(E) = floor(J(E) / q) * q frames, J(E) = floor((E - 1) * te / tm) + 1 -- with q = 32 and
+ * 128-sample calls at 44.1 kHz the model sees 128, 128, 160, ... frames and never a remainder block.  The output is delayed by a FIXED
+ * whole number of external samples, latencySamples = (48 * max(te, tm) + (q - 1) * tm + pad) / te whatever the call lengths (48 / 77 /
+ * 165 samples at 44.1 kHz for q = 1 / 32 / 128), and it is bit for bit independent of how the signal is cut into calls (any n >= 1).
+ * A NaN input sample reads as silence before the filter.  Pairs whose te or tm exceeds 640 are refused. */
+typedef struct NA_ResampleInfo {
+	int externalRate, modelRate;
+	int ticksExternal, ticksModel;   /* te, tm */
+	int tapsUp, tapsDown;            /* taps per output sample of each stage */
+	int quantum;                     /* q in effect */
+	int latencySamples;              /* external samples; 0 when the rates are equal */
+	int prototypeLength;             /* K */
+} NA_ResampleInfo;
+/* host arithmetic only, no device: the plan for a rate pair (quantum 0: the default); non-zero + NA_GetLastError() if refused */
+NA_EXTERN int NA_ResamplePlan(int externalRate, int modelRate, int quantum, NA_ResampleInfo* info);
+/* the f32 prototype of that plan into buf[capacity] (as many as fit); returns K, negative if the pair is refused */
+NA_EXTERN int NA_ResamplePrototype(int externalRate, int modelRate, float* buf, int capacity);
+/* model frames P(E) run after E external samples (host arithmetic; what a host needs to size anything by); negative if refused */
+NA_EXTERN long long NA_ResampleModelFrames(int externalRate, int modelRate, int quantum, long long externalSamples);
+/* Set-up call, before the first NA_BatchAddStreams of the batch (refused afterwards and on a broken batch): every n of the processing
+ * entry points -- NA_BatchProcess (pageable and registered blocks), NA_BatchProcessDevice (n and strides), NA_BatchSubmit / Collect /
+ * NextInput / OutputView -- now counts EXTERNAL samples per row.  maxFrames: the largest n the host will pass (device buffers are sized
+ * here; a larger n later grows them -- not real-time safe, like any first use of a longer buffer; calls beyond 2048 samples run in
+ * pieces).  externalRate == modelRate is accepted and means "no resampling": the batch behaves bit for bit as without the call and
+ * reports latency 0.  NA_BatchAddStreams then refuses a model whose model-side rate (NA_GetModelProcessRate) is not modelRate.
+ * A resampling batch orders its work on the batch stream -- up kernel, model launches, down kernel -- under either contract of
+ * NA_BatchProcessDevice: it does not use the half-batch launches or the resident launch (NA_BatchUsesHalfLaunches / UsesResidentLaunch
+ * answer 0; NA_BatchSetResidentLaunch is accepted and has no effect).  New, recycled and prewarmed streams (NA_BatchAddStreams,
+ * NA_BatchPrewarm) start from zero filter histories at the batch's current phase; NA_BatchSetQuality keeps them.  Timing marks, bounded
+ * waits and the broken-batch rules are those of every batch.  Not provided: NA_BatchSaveStreams / NA_BatchLoadStreams on a resampling
+ * batch (they fail and say so), NA_RenderOffline and NA_Multi* with resampling, per-stream rates inside one batch. */
+NA_EXTERN int NA_BatchSetResampling(NA_Batch* batch, int externalRate, int modelRate, int quantum, int maxFrames);
+/* the plan in effect; non-zero if NA_BatchSetResampling was never called on the batch */
+NA_EXTERN int NA_BatchGetResampleInfo(NA_Batch* batch, NA_ResampleInfo* info);
+/* loader opt-in for the one-stream NeuralModel (a batch of one): with on != 0, a model created while the loader's external rate is
+ * neither the model's rate nor a whole multiple of it resamples inside Process / NA_ProcessChecked (default quantum; a refused rate
+ * pair fails the load).  Default 0: today's behaviour, which is the reference's. */
+NA_EXTERN void NA_SetResampleToExternalRate(NeuralModelLoader* loader, int on);
+NA_EXTERN int NA_GetProcessLatencySamples(NeuralModel* model);   /* external samples; 0 unless the model resamples */
+/* the model-side rate of this model as loaded: the file's rate times the integer oversampling factor the loader APPLIED -- what to
+ * pass as modelRate (host arithmetic).  0 if the file's rate is not a whole number. */
+NA_EXTERN int NA_GetModelProcessRate(NeuralModel* model);
 #ifndef NA_RELEASE
 /* ---- test / tuning hooks: exported by the test build only (csrc/Makefile default target; what tests/ loads).  The release library
  * (make RELEASE=1 -> dist/libNeuralAudioCAPI.so: -DNA_RELEASE -DNA_NO_TUNING, no loopback RCCL table) has none of the NA_Debug* symbols
@@ -309,6 +359,10 @@ NA_EXTERN void NA_DebugSetRcclApi(int mode, int failSendAt, int rendezvousMs);
 /* Tests: a kernel that keeps the batch's streams busy for `milliseconds` (at most 10 000) behind whatever they hold -- a device that
  * does not answer, as far as the waits of this batch can tell (tests/test_gpu_stall.py drives the wait limit with it). */
 NA_EXTERN int NA_DebugStallDevice(NA_Batch* batch, double milliseconds);
+/* Tests: the model-rate input and output rows ([streams][*frames], rows *frames floats apart) of the LAST processing call of a resampling
+ * batch -- of its last piece where a call longer than 2048 external samples ran in several -- copied to the host; either pointer may be
+ * NULL.  Fails if *frames exceeds capacityPerRow.  Synchronises the batch. */
+NA_EXTERN int NA_DebugResampleTap(NA_Batch* batch, float* modelIn, float* modelOut, long long capacityPerRow, int* frames);
 /* tuning aid: device buffer (long long[stages*4*waves]) that workgroup 0 of the WaveNet kernel stamps with the shader clock; NULL = off */
 NA_EXTERN void NA_DebugSetTraceBuffer(void* deviceBuffer);
 #endif /* NA_RELEASE */

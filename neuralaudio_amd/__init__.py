@@ -14,7 +14,8 @@ import numpy as np
 from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
-           "NeuralAudioError", "render_offline", "render_plan", "snapshot_bytes", "snapshot_fingerprint"]
+           "NeuralAudioError", "render_offline", "render_plan", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
+           "resample_model_frames"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -118,6 +119,14 @@ class NeuralModel:
     def IsQualityChangeRealtimeSafe(self, q):
         return bool(self._lib.NA_IsQualityChangeRealtimeSafe(self._h, float(q)))
 
+    def GetProcessLatencySamples(self):
+        """External samples by which Process delays its output: 0 unless the loader's resampling opt-in applies to this model."""
+        return int(self._lib.NA_GetProcessLatencySamples(self._h))
+
+    def GetModelProcessRate(self):
+        """The model-side rate as loaded: the file's rate times the oversampling factor the loader applied (0: not a whole number)."""
+        return int(self._lib.NA_GetModelProcessRate(self._h))
+
     def KernelInfo(self, quality=1.0, streams=1):
         """Host side only: the kernel family a batch of `streams` streams would run on and the f16-split range proof behind the choice."""
         name = C.create_string_buffer(64)
@@ -183,6 +192,10 @@ class NeuralModelLoader:
 
     def SetExternalSampleRate(self, sr):
         self._lib.NA_SetExternalSampleRate(self._h, int(sr))
+
+    def SetResampleToExternalRate(self, on=True):
+        """Opt-in: models created at an external rate that is neither their rate nor a whole multiple of it resample inside Process."""
+        self._lib.NA_SetResampleToExternalRate(self._h, 1 if on else 0)
 
     def SetDevice(self, device):
         self._lib.NA_SetDevice(self._h, int(device))
@@ -261,6 +274,30 @@ class Batch:
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:
             raise NeuralAudioError(capi.last_error())
+
+    # -- batch resampling (include/neuralaudio_amd.h) ------------------------------------------------------------
+    def SetResampling(self, external_rate, model_rate=48000, quantum=0, max_frames=512):
+        """Set-up call before the first AddStreams: every n of the processing entry points now counts samples at `external_rate`."""
+        if self._lib.NA_BatchSetResampling(self._h, int(external_rate), int(model_rate), int(quantum), int(max_frames)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def ResampleInfo(self):
+        """The resampling plan in effect (see resample_plan); raises if SetResampling was never called."""
+        info = capi.NA_ResampleInfo()
+        if self._lib.NA_BatchGetResampleInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return _resample_info(info)
+
+    def DebugResampleTap(self, capacity=4096):
+        """Test hook: (model_in, model_out), the model-rate rows [streams, frames] of the last processing call (NA_DebugResampleTap)."""
+        rows = self.NumStreams()
+        u = np.zeros((rows, int(capacity)), np.float32)
+        v = np.zeros((rows, int(capacity)), np.float32)
+        frames = C.c_int(0)
+        if self._lib.NA_DebugResampleTap(self._h, _fptr(u), _fptr(v), int(capacity), C.byref(frames)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        f = int(frames.value)
+        return (u.reshape(-1)[:rows * f].reshape(rows, f).copy(), v.reshape(-1)[:rows * f].reshape(rows, f).copy())
 
     # -- stream snapshots: not real-time safe (they wait for everything in flight), call between buffers ---------------------------
     def StreamSnapshotBytes(self, stream):
@@ -515,6 +552,39 @@ class MultiBatch:
             self.close()
         except Exception:
             pass
+
+
+def _resample_info(info):
+    return {"external_rate": info.externalRate, "model_rate": info.modelRate, "te": info.ticksExternal, "tm": info.ticksModel,
+            "taps_up": info.tapsUp, "taps_down": info.tapsDown, "quantum": info.quantum, "latency_samples": info.latencySamples,
+            "prototype_length": info.prototypeLength}
+
+
+def resample_plan(external_rate, model_rate=48000, quantum=0):
+    """The resampling plan of a rate pair (NA_ResamplePlan; host arithmetic, no device): te, tm, taps, quantum, latency, K."""
+    info = capi.NA_ResampleInfo()
+    if capi.load_library().NA_ResamplePlan(int(external_rate), int(model_rate), int(quantum), C.byref(info)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _resample_info(info)
+
+
+def resample_prototype(external_rate, model_rate=48000):
+    """The f32 prototype low-pass of a rate pair at the common rate (NA_ResamplePrototype), as a numpy array of length K."""
+    lib = capi.load_library()
+    k = int(lib.NA_ResamplePrototype(int(external_rate), int(model_rate), None, 0))
+    if k < 0:
+        raise NeuralAudioError(capi.last_error())
+    h = np.zeros(k, np.float32)
+    lib.NA_ResamplePrototype(int(external_rate), int(model_rate), _fptr(h), k)
+    return h
+
+
+def resample_model_frames(external_rate, model_rate, quantum, external_samples):
+    """Model frames P(E) a resampling batch has run after E external samples (NA_ResampleModelFrames)."""
+    f = int(capi.load_library().NA_ResampleModelFrames(int(external_rate), int(model_rate), int(quantum), int(external_samples)))
+    if f < 0:
+        raise NeuralAudioError(capi.last_error())
+    return f
 
 
 def snapshot_bytes(model):

@@ -34,6 +34,8 @@ NA_SYMBOLS = [
     "NA_RenderOffline", "NA_RenderPlan",
     "NA_BatchStreamSnapshotBytes", "NA_ModelSnapshotBytes", "NA_ModelSnapshotFingerprint", "NA_BatchSaveStreams", "NA_BatchLoadStreams",
     "NA_SaveModelState", "NA_LoadModelState", "NA_DebugSnapshotLaunches",
+    "NA_ResamplePlan", "NA_ResamplePrototype", "NA_ResampleModelFrames", "NA_BatchSetResampling", "NA_BatchGetResampleInfo",
+    "NA_SetResampleToExternalRate", "NA_GetProcessLatencySamples", "NA_GetModelProcessRate", "NA_DebugResampleTap",
 ]
 
 
@@ -49,6 +51,12 @@ class NA_RenderOptions(C.Structure):
 class NA_RenderPlanInfo(C.Structure):
     _fields_ = [("segments", C.c_longlong), ("lead", C.c_int), ("segmentSamples", C.c_longlong), ("rowSamples", C.c_longlong),
                 ("passes", C.c_int), ("streams", C.c_int), ("estimatedMs", C.c_double), ("kernel", C.c_char * 64)]
+
+
+class NA_ResampleInfo(C.Structure):
+    _fields_ = [("externalRate", C.c_int), ("modelRate", C.c_int), ("ticksExternal", C.c_int), ("ticksModel", C.c_int),
+                ("tapsUp", C.c_int), ("tapsDown", C.c_int), ("quantum", C.c_int), ("latencySamples", C.c_int),
+                ("prototypeLength", C.c_int)]
 
 _lib = None
 
@@ -173,6 +181,15 @@ def load_library():
         "NA_SaveModelState": (C.c_int, [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
         "NA_LoadModelState": (C.c_int, [vp, vp, C.c_size_t]),
         "NA_DebugSnapshotLaunches": (C.c_longlong, []),
+        "NA_ResamplePlan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(NA_ResampleInfo)]),
+        "NA_ResamplePrototype": (C.c_int, [C.c_int, C.c_int, fp, C.c_int]),
+        "NA_ResampleModelFrames": (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_longlong]),
+        "NA_BatchSetResampling": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "NA_BatchGetResampleInfo": (C.c_int, [vp, C.POINTER(NA_ResampleInfo)]),
+        "NA_SetResampleToExternalRate": (None, [vp, C.c_int]),
+        "NA_GetProcessLatencySamples": (C.c_int, [vp]),
+        "NA_GetModelProcessRate": (C.c_int, [vp]),
+        "NA_DebugResampleTap": (C.c_int, [vp, fp, fp, C.c_longlong, C.POINTER(C.c_int)]),
         "NA_DebugSplitPlan": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_ushort), C.c_longlong, C.POINTER(C.c_longlong)]),
     }
     for name, (res, args) in sig.items():

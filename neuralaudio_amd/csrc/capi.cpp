@@ -8,6 +8,7 @@
 #include "neuralaudio_amd.h"
 #include "multi_gpu.h"
 #include "offline_render.h"
+#include "resample.h"
 #include "stream_snapshot.h"
 #include "neural_model_impl.h"
 #include "lstm_launch.h"
@@ -927,5 +928,97 @@ int NA_RenderPlan(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions*
 	});
 }
 
-} // extern "C"
+// ---------------------------------------------------------------- batch resampling (csrc/resample.cpp)
 
+namespace
+{
+	void FillResampleInfo(const na::ResamplePlan& p, NA_ResampleInfo* info)
+	{
+		memset(info, 0, sizeof(*info));
+		info->externalRate = p.externalRate;
+		info->modelRate = p.modelRate;
+		info->ticksExternal = p.te;
+		info->ticksModel = p.tm;
+		info->tapsUp = p.tapsUp;
+		info->tapsDown = p.tapsDown;
+		info->quantum = p.quantum;
+		info->latencySamples = p.latency;
+		info->prototypeLength = p.K;
+	}
+}
+
+int NA_ResamplePlan(int externalRate, int modelRate, int quantum, NA_ResampleInfo* info)
+{
+	return Guard([&] {
+		if (!info) throw std::runtime_error("NA_ResamplePlan: info is NULL");
+		FillResampleInfo(na::PlanResampling(externalRate, modelRate, quantum), info);
+	});
+}
+
+int NA_ResamplePrototype(int externalRate, int modelRate, float* buf, int capacity)
+{
+	int k = -1;
+	Guard([&] {
+		const na::ResamplePlan p = na::PlanResampling(externalRate, modelRate, 0);
+		const std::vector<float> h = na::ResamplePrototype(p);
+		if (buf && capacity > 0) memcpy(buf, h.data(), sizeof(float) * std::min((size_t)capacity, h.size()));
+		k = (int)h.size();
+	});
+	return k;
+}
+
+long long NA_ResampleModelFrames(int externalRate, int modelRate, int quantum, long long externalSamples)
+{
+	long long frames = -1;
+	Guard([&] {
+		if (externalSamples < 0) throw std::runtime_error("NA_ResampleModelFrames: negative sample count");
+		frames = na::PlanResampling(externalRate, modelRate, quantum).ModelFrames(externalSamples);
+	});
+	return frames;
+}
+
+int NA_BatchSetResampling(NA_Batch* batch, int externalRate, int modelRate, int quantum, int maxFrames)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchSetResampling: null batch");
+		batch->batch->SetResampling(externalRate, modelRate, quantum, maxFrames);
+	});
+}
+
+int NA_BatchGetResampleInfo(NA_Batch* batch, NA_ResampleInfo* info)
+{
+	return Guard([&] {
+		if (!batch || !info) throw std::runtime_error("NA_BatchGetResampleInfo: null argument");
+		FillResampleInfo(batch->batch->ResamplingPlan(), info);
+	});
+}
+
+void NA_SetResampleToExternalRate(NeuralModelLoader* loader, int on)
+{
+	if (loader) loader->loader->SetResampleToExternalRate(on != 0);
+}
+
+int NA_GetProcessLatencySamples(NeuralModel* model)
+{
+	NeuralAudio::GpuModel* gm = model ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+	return gm ? gm->GetProcessLatencySamples() : 0;
+}
+
+int NA_GetModelProcessRate(NeuralModel* model)
+{
+	NeuralAudio::GpuModel* gm = model ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+	return gm ? gm->GetLoadedModel()->ProcessRate() : 0;
+}
+
+#ifndef NA_RELEASE
+int NA_DebugResampleTap(NA_Batch* batch, float* modelIn, float* modelOut, long long capacityPerRow, int* frames)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugResampleTap: null batch");
+		const int f = batch->batch->DebugResampleTap(modelIn, modelOut, capacityPerRow);
+		if (frames) *frames = f;
+	});
+}
+#endif
+
+} // extern "C"

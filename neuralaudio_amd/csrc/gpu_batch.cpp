@@ -138,6 +138,7 @@ namespace na
 		{
 			for (auto& g : groups) (void)g.release();
 			(void)residentState.release();
+			(void)resample.release();
 			for (WnLaunchTable& t : wnTable) t.entries.clear();
 			return;
 		}
@@ -215,6 +216,9 @@ namespace na
 		CheckUsable();
 		if (!model || model->subModels.empty()) throw std::runtime_error("neuralaudio_amd: AddStream with an empty model");
 		if (count < 1) throw std::runtime_error("neuralaudio_amd: AddStreams with count < 1");
+		if (resample && model->ProcessRate() != resample->plan.modelRate)
+			throw std::runtime_error("neuralaudio_amd: AddStreams: the model runs at " + std::to_string(model->ProcessRate()) + " Hz as loaded, the batch resamples to a model rate of " +
+				std::to_string(resample->plan.modelRate) + " Hz");
 		CheckHip(hipSetDevice(device), "hipSetDevice");
 		DrainPipeline(); // (state arrays may be re-allocated below)
 		topologyVersion++;
@@ -265,6 +269,12 @@ namespace na
 				if (waits) pendingPrewarm.push_back({ subGroups[k], newMembers[k] }); // (its weights are not on the device yet: WeightsArrived)
 				else if (now) subGroups[k]->Prewarm(newMembers[k]);
 				for (int i = 0; i < count; i++) streams[(size_t)(first + i)].prewarmed[k] = now ? 1 : 0;
+			}
+			if (Resamples())
+			{
+				// history slots for every row, on this, the set-up side; a new or recycled stream starts from zero histories
+				EnsureResampleRows((int)streams.size());
+				ZeroResampleHistories(first, count);
 			}
 		}
 		catch (...)
@@ -440,6 +450,7 @@ namespace na
 			ref.members[k].first->Prewarm({ ref.members[k].second });
 			ref.prewarmed[k] = 1;
 		}
+		if (Resamples()) ZeroResampleHistories(s, 1);
 	}
 
 	void GpuBatch::ProcessDevice(const float* dIn, float* dOut, size_t n, long inStride, long outStride)
@@ -450,7 +461,7 @@ namespace na
 		// A batch on its own stream that nobody has seen: a buffer of one contiguous WaveNet group runs as two free-running half-batch
 		// launches (the order of work on the internal streams is not observable from outside; Synchronize() and the host-buffer entry
 		// points wait for all of them).  1024 x A1 Standard x 128 frames: 40.1 -> 37.4 us per step.
-		if (ownsStream && !streamObserved)
+		if (ownsStream && !streamObserved && !Resamples()) // (a resampling batch orders up kernel -> model -> down kernel on the batch stream)
 		{
 			if (TryResident(dIn, dOut, n, inStride, outStride)) return;
 			if (PrepareHalves(n))
@@ -488,6 +499,11 @@ namespace na
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{
+		if (resample && !resample->plan.identity && !resample->inside)
+		{
+			ProcessResampledOn(launch, dIn, dOut, n, inStride, outStride);
+			return;
+		}
 		int activeGroups = 0;
 		for (auto& g : groups) activeGroups += (g->NumActive() > 0);
 		if (activeGroups <= 1)

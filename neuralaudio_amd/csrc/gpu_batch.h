@@ -19,6 +19,7 @@
 
 #include "launch_plan.h"
 #include "model_loader.h"
+#include "resample.h"
 #include "tuning.h"
 #include "wavenet_launch.h"
 
@@ -99,6 +100,20 @@ namespace na
 		size_t StreamSnapshotBytes(int stream) const;
 		size_t SaveStreams(const int* ids, int count, void* buf, size_t capacity);
 		void LoadStreams(const int* ids, int count, const void* buf, size_t bytes);
+
+		// Batch resampling (resample.h): a set-up call before the first AddStreams.  From then on every `n` of the processing
+		// entry points counts EXTERNAL samples per row: an up kernel turns them into model frames (whole multiples of the block quantum, the
+		// rest waits), the model runs on them through the ordinary launches, a down kernel produces the n output samples -- all on the
+		// batch stream, in that order (no half-batch chains, no resident launch).  The output is the pipeline's answer delayed by a fixed
+		// whole number of external samples (ResamplingPlan().latency) and does not depend on how the signal is cut into calls.
+		// externalRate == modelRate: accepted, nothing changes.  AddStreams then refuses models whose model-side rate is not modelRate.
+		void SetResampling(int externalRate, int modelRate, int quantum, int maxFrames);
+		bool HasResamplingPlan() const { return resample != nullptr; }
+		bool Resamples() const; // a plan with different rates is in effect
+		const ResamplePlan& ResamplingPlan() const;
+		// test hook (NA_DebugResampleTap): the model-rate input / output rows [streams][frames] of the last processing call (of its last
+		// piece, where a call longer than 2048 external samples ran in several); synchronises
+		int DebugResampleTap(float* modelIn, float* modelOut, long long capacityPerRow);
 
 		int NumStreams() const { return (int)streams.size(); } // rows of the [streams][n] arrays (retired ids included)
 		int NumLiveStreams() const { return (int)streams.size() - (int)retired.size(); }
@@ -342,6 +357,12 @@ namespace na
 		void JoinHalves(); // the half-batch chains are done (host-side wait); the next launches go to the batch stream again
 		hipEvent_t marks[1 + kMaxChains][2] = {};
 		void ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
+		struct ResampleState; // (gpu_batch_internal.h)
+		std::unique_ptr<ResampleState> resample;
+		void ProcessResampledOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
+		void EnsureResampleRows(int rows);           // set-up side only (AddStreams): histories and model-side rows for `rows` rows
+		void EnsureResampleFrames(size_t n);         // model-side buffers for pieces of n external samples
+		void ZeroResampleHistories(int first, int count);
 		// ordering between the batch stream and the slot streams: the stream state makes every kernel launch depend on the previous one
 		bool pipelineUsed = false;
 		hipEvent_t lastKernelEvent = nullptr, mainDone = nullptr;

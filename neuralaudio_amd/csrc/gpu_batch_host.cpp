@@ -252,7 +252,7 @@ namespace na
 		// (behind its kernel) overlaps the kernel of buffer k + 1.  Per buffer: 2 copies, 1 launch, 1 event wait, 1 event record --
 		// the round-2 path cost 2 more waits and 2 more records on the compute stream, 15 us per buffer (tools/microbench/host_pipe_probe.cpp).
 		UpdatePlan();
-		if (plan.units.size() <= 1)
+		if (plan.units.size() <= 1 && !Resamples()) // (a resampling batch: three ordered launches, on the batch stream like a multi-unit batch)
 		{
 			JoinHalves(); // (device-pointer steps may have run as half-batch chains: this buffer's kernel comes after both)
 			if (!p.own) CheckHip(hipStreamCreateWithFlags(&p.own, hipStreamNonBlocking), "hipStreamCreate");

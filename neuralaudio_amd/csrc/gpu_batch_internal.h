@@ -3,6 +3,7 @@
 #pragma once
 
 #include "gpu_groups.h"
+#include "resample.h"
 
 namespace na
 {
@@ -52,6 +53,31 @@ namespace na
 			if (dWgDone) (void)hipFree(dWgDone);
 			if (ctrl) (void)(ctrlInDeviceMemory ? hipFree(ctrl) : hipHostFree(ctrl));
 			if (status) (void)hipHostFree(status);
+		}
+	};
+
+	// a resampling batch (resample.cpp): the plan, the batch's counters, the coefficient tables, the per-row histories
+	// and the fixed model-side buffers
+	struct GpuBatch::ResampleState
+	{
+		ResamplePlan plan;
+		long long E = 0, P = 0;    // external samples taken / model frames run so far: the batch's, not the streams'
+		float* tableUp = nullptr;   // [te][tapsUp]
+		float* tableDown = nullptr; // [tm][tapsDown]
+		float* histUp = nullptr;    // [rowCapacity][plan.histUp]
+		float* histDown = nullptr;  // [rowCapacity][plan.histDown]
+		float* modelIn = nullptr;   // [rowCapacity][modelStride]
+		float* modelOut = nullptr;
+		int rowCapacity = 0;
+		int pieceFrames = 0;        // a longer call runs in pieces of this many external samples (the LDS window of the stages)
+		int sizedFrames = 0;        // external samples per piece the model-side buffers hold
+		int modelStride = 0;
+		bool inside = false;        // the model launches of a resampled call are under way (ProcessDeviceOn)
+		int lastFrames = 0, lastRows = 0; // NA_DebugResampleTap: model frames and rows of the last piece
+		~ResampleState()
+		{
+			for (float* p : { tableUp, tableDown, histUp, histDown, modelIn, modelOut })
+				if (p) (void)hipFree(p);
 		}
 	};
 

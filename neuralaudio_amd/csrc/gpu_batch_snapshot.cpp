@@ -51,6 +51,8 @@ namespace na
 	void GpuBatch::SettleForSnapshot(const int* ids, int count, const char* who)
 	{
 		CheckUsable();
+		// (the v1 blob has no place for the resampler's histories, and the phase is the batch's, not the stream's)
+		if (Resamples()) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": stream snapshots of a resampling batch are not supported");
 		if (count < 0 || (count > 0 && !ids)) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": bad argument");
 		for (int i = 0; i < count; i++)
 			if (!IsLive(ids[i])) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": stream " + std::to_string(ids[i]) + " is not a live stream of the batch");

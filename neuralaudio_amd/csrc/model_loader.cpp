@@ -806,6 +806,13 @@ namespace na
 		}
 	}
 
+	int LoadedModel::ProcessRate() const
+	{
+		const float rate = info.sampleRate;
+		if (!(rate > 0.0f) || rate > 1.0e8f || rate != std::floor(rate)) return 0;
+		return (int)rate * oversample;
+	}
+
 	std::shared_ptr<LoadedModel> LoadModelFromJson(const Json& modelJson, const std::string& extension, const LoaderOptions& opts)
 	{
 		auto model = std::make_shared<LoadedModel>();
@@ -829,6 +836,7 @@ namespace na
 					SubModel sm = loaded->subModels[0];
 					sm.maxValue = sub.At("max_value").AsFloat();
 					sm.info = loaded->info;
+					if (i == 0) model->oversample = loaded->oversample;
 					model->subModels.push_back(sm);
 					model->qualityLevels.push_back({ sm.maxValue, (int)model->subModels.size() - 1 });
 					std::stable_sort(model->qualityLevels.begin(), model->qualityLevels.end(),
@@ -840,7 +848,11 @@ namespace na
 
 			SubModel sm;
 			sm.info = model->info;
-			if (arch == "WaveNet") sm.desc = ReadNAMWaveNet(modelJson, OversampleFactor(modelJson, opts.externalSampleRate), opts);
+			if (arch == "WaveNet")
+			{
+				model->oversample = OversampleFactor(modelJson, opts.externalSampleRate);
+				sm.desc = ReadNAMWaveNet(modelJson, model->oversample, opts);
+			}
 			else if (arch == "LSTM") sm.desc = ReadNAMLSTM(modelJson, opts);
 			else return nullptr;
 			model->subModels.push_back(sm);

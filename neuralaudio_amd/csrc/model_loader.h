@@ -38,6 +38,11 @@ namespace na
 		bool isComposite = false;              // architecture == "SlimmableContainer" (NeuralModel.cpp:350-358)
 		std::vector<SubModel> subModels;       // size 1 when !isComposite; file order
 		std::vector<std::pair<float, int>> qualityLevels; // sorted by max_value (CompositeModel.h:183-194)
+		// the integer oversampling factor the loader APPLIED for the external sample rate (NeuralModel.cpp:92-114: NAM WaveNet files only;
+		// 1 for everything else, whatever the external rate); the submodels of a container share it
+		int oversample = 1;
+		// the model-side rate: what Process of this model expects -- the file's rate times `oversample`; 0 if the file's rate is not whole
+		int ProcessRate() const;
 
 		// CompositeModel.h:200-213: first sorted level with quality <= max_value, else the last
 		int ModelIndexFromQuality(float quality) const;

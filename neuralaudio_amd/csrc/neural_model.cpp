@@ -32,6 +32,16 @@ namespace NeuralAudio
 		activeIndex = model->isComposite ? model->ModelIndexFromQuality(quality) : 0;
 		appliedQuality = quality;
 		onDemand = loader->GetCompositeModelLoadMode() == ECompositeModelLoadMode::OnDemand; // CompositeModel.h:139
+
+		// resampling opt-in: the external rate is neither the model-side rate nor (for the files the loader oversamples) a whole multiple
+		// of the file's -- the plan is made here so that a refused rate pair fails the load, not the first Process()
+		const int modelRate = model->ProcessRate(), externalRate = loader->GetExternalSampleRate();
+		if (loader->GetResampleToExternalRate() && modelRate > 0 && externalRate > 0 && externalRate != modelRate)
+		{
+			processLatency = na::PlanResampling(externalRate, modelRate, 0).latency;
+			resampleExternalRate = externalRate;
+			resampleMaxFrames = std::max(loader->GetDefaultMaxAudioBufferSize(), 1);
+		}
 	}
 
 	GpuModel::~GpuModel() {}
@@ -43,6 +53,7 @@ namespace NeuralAudio
 		// with zero streams behind, or every later Process() would silently write nothing
 		std::unique_ptr<na::GpuBatch> fresh(new na::GpuBatch(device));
 		appliedQuality = quality.load();
+		if (resampleExternalRate > 0) fresh->SetResampling(resampleExternalRate, model->ProcessRate(), 0, resampleMaxFrames);
 		fresh->AddStream(model, appliedQuality, prewarmPending, onDemand);
 		batch = std::move(fresh);
 		prewarmPending = false;

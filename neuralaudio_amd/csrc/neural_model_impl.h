@@ -30,6 +30,8 @@ namespace NeuralAudio
 		const std::shared_ptr<const na::LoadedModel>& GetLoadedModel() const { return model; }
 		int GetDevice() const { return device; }
 		bool IsOnDemand() const { return onDemand; }
+		// the loader's resampling opt-in (NeuralModelLoader::SetResampleToExternalRate): 0 unless Process() resamples
+		int GetProcessLatencySamples() const { return processLatency; }
 
 		// stream snapshots (gpu_batch.h SaveStreams / LoadStreams) of this one-stream model; audio thread
 		size_t SaveState(void* buf, size_t capacity);
@@ -54,5 +56,8 @@ namespace NeuralAudio
 		float appliedQuality = 1.0f; // audio thread only
 		bool onDemand = false;
 		bool prewarmPending;
+		int resampleExternalRate = 0; // > 0: the one-stream batch resamples between this rate and the model's
+		int resampleMaxFrames = 128;
+		int processLatency = 0;
 	};
 }
