@@ -316,7 +316,9 @@ NA_EXTERN long long NA_ResampleModelFrames(int externalRate, int modelRate, int 
  * answer 0; NA_BatchSetResidentLaunch is accepted and has no effect).  New, recycled and prewarmed streams (NA_BatchAddStreams,
  * NA_BatchPrewarm) start from zero filter histories at the batch's current phase; NA_BatchSetQuality keeps them.  Timing marks, bounded
  * waits and the broken-batch rules are those of every batch.  Not provided: NA_BatchSaveStreams / NA_BatchLoadStreams on a resampling
- * batch (they fail and say so), NA_RenderOffline and NA_Multi* with resampling, per-stream rates inside one batch. */
+ * batch (they fail and say so: the v1 blob has no place for the filter histories, and the phase belongs to the batch, not the stream),
+ * per-stream rates inside one batch.  Offline rendering and the multi-GPU host at an external rate: NA_RenderOfflineAtRate and
+ * NA_MultiSetResampling below. */
 NA_EXTERN int NA_BatchSetResampling(NA_Batch* batch, int externalRate, int modelRate, int quantum, int maxFrames);
 /* the plan in effect; non-zero if NA_BatchSetResampling was never called on the batch */
 NA_EXTERN int NA_BatchGetResampleInfo(NA_Batch* batch, NA_ResampleInfo* info);
@@ -328,6 +330,42 @@ NA_EXTERN int NA_GetProcessLatencySamples(NeuralModel* model);   /* external sam
 /* the model-side rate of this model as loaded: the file's rate times the integer oversampling factor the loader APPLIED -- what to
  * pass as modelRate (host arithmetic).  0 if the file's rate is not a whole number. */
 NA_EXTERN int NA_GetModelProcessRate(NeuralModel* model);
+/* ---- offline rendering at an external rate: files at 44.1 kHz through 48 kHz captures (csrc/offline_render.cpp) ------
+ * As NA_RenderOffline, but every job's input, output and numSamples are at externalRate, whatever rate its model runs at.  Job i's
+ * model rate is Fm = NA_GetModelProcessRate(job.model) and its plan NA_ResamplePlan(externalRate, Fm, quantum 1); jobs of one call may
+ * have different model rates.  With L = latencySamples, N = numSamples and M = NA_ResampleModelFrames(externalRate, Fm, 1, N + L) model
+ * frames: out[k] = s[k + L] for k in [0, N), s what a fresh resampling batch of one prewarmed stream (NA_BatchSetResampling(externalRate,
+ * Fm, quantum 1), same loader settings) returns when fed x[0 .. N) followed by L zeros.  The result is therefore LATENCY-COMPENSATED --
+ * out[k] lines up with x[k] -- and the filter's tail is rendered instead of being cut off.  It equals that streaming batch bit for bit
+ * where the segment batch and the batch of one run the stream on the same kernel (NA_BatchStreamKernelName; NA_RenderOffline's own
+ * rule); the two resampling stages are bit-identical to the streaming stages in every case (one shared sum per output sample).  A job
+ * whose model runs at externalRate is rendered exactly as NA_RenderOffline renders it (L = 0).  NaN input reads as silence, +-inf as the
+ * largest finite value.  The model's own loader opt-in (NA_SetResampleToExternalRate) is ignored: the call builds a temporary batch
+ * from the loaded model, as NA_RenderOffline does.  Recurrent jobs stay one sequential stream each, over their M frames.
+ *
+ * Per job: x is uploaded whole, an up kernel makes the model-rate signal u[0 .. M) in device memory, the segment machinery of
+ * NA_RenderOffline renders u to v there, a down kernel makes out, which is downloaded whole.  opts->segmentSamples,
+ * opts->maxSamplesPerPass and every field of NA_RenderPlanInfo count MODEL-RATE frames.  Device memory: NA_RenderOffline's (3 x 4
+ * bytes per frame of a pass's segment rows, which maxSamplesPerPass keeps bounding, plus the stream state) plus whole-signal buffers of
+ * 8 N + 8 M bytes per job (8 M for a job that does not resample) and the coefficient tables (31 + 34 KB at 44.1 / 48 kHz); the call
+ * fails with a message naming the size when they cannot be allocated.  Every wait is bounded as in NA_RenderOffline.
+ * The whole call fails BEFORE any device work on externalRate <= 0, on a pair NA_ResamplePlan refuses (a reduced term above 640), on a
+ * job without a model and on overlapping buffers. */
+NA_EXTERN int NA_RenderOfflineAtRate(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, int externalRate);
+/* the plan of NA_RenderOfflineAtRate without running it (no device needed): NA_RenderPlan of jobs of M model-rate frames each;
+ * resample: the resampling plan of job 0's rate pair, may be NULL */
+NA_EXTERN int NA_RenderPlanAtRate(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, int externalRate,
+                                  NA_RenderPlanInfo* info, NA_ResampleInfo* resample);
+/* ---- multi-GPU host at an external rate ----
+ * Before NA_MultiCommit (refused afterwards, on a refused pair and on a bad quantum; arguments as NA_BatchSetResampling): every
+ * shard's batch becomes a resampling batch of this plan, and every n of NA_MultiProcess, NA_MultiSubmit and NA_MultiCollect counts
+ * EXTERNAL samples.  All shards share one phase, because they are always called with the same n; the library compares their sample
+ * counters after every call and refuses further work on the multi batch if they ever disagree.  A model whose process rate is not
+ * modelRate fails NA_MultiAddStreams (and this call, if it is already on the list) with NA_BatchAddStreams' message.  Both fan-in modes
+ * work: with RCCL fan-in (NA_MultiSetFanIn 1) the gathered buffer is [streams][n] in external samples. */
+NA_EXTERN int NA_MultiSetResampling(NA_MultiBatch* multi, int externalRate, int modelRate, int quantum, int maxFrames);
+/* the plan in effect; non-zero if NA_MultiSetResampling was never called on the multi batch */
+NA_EXTERN int NA_MultiGetResampleInfo(NA_MultiBatch* multi, NA_ResampleInfo* info);
 #ifndef NA_RELEASE
 /* ---- test / tuning hooks: exported by the test build only (csrc/Makefile default target; what tests/ loads).  The release library
  * (make RELEASE=1 -> dist/libNeuralAudioCAPI.so: -DNA_RELEASE -DNA_NO_TUNING, no loopback RCCL table) has none of the NA_Debug* symbols
@@ -363,6 +401,9 @@ NA_EXTERN int NA_DebugStallDevice(NA_Batch* batch, double milliseconds);
  * batch -- of its last piece where a call longer than 2048 external samples ran in several -- copied to the host; either pointer may be
  * NULL.  Fails if *frames exceeds capacityPerRow.  Synchronises the batch. */
 NA_EXTERN int NA_DebugResampleTap(NA_Batch* batch, float* modelIn, float* modelOut, long long capacityPerRow, int* frames);
+/* Tests: the NEXT NA_RenderOfflineAtRate (one call) copies job 0's model-rate input u and output v, M frames each, to these host arrays
+ * (either may be NULL); that call fails before any device work if M > capacity.  Both NULL: off. */
+NA_EXTERN void NA_DebugSetRenderTap(float* modelIn, float* modelOut, long long capacity);
 /* tuning aid: device buffer (long long[stages*4*waves]) that workgroup 0 of the WaveNet kernel stamps with the shader clock; NULL = off */
 NA_EXTERN void NA_DebugSetTraceBuffer(void* deviceBuffer);
 #endif /* NA_RELEASE */

@@ -14,7 +14,7 @@ import numpy as np
 from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
-           "NeuralAudioError", "render_offline", "render_plan", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
+           "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
            "resample_model_frames"]
 
 
@@ -526,6 +526,34 @@ class MultiBatch:
             raise NeuralAudioError(capi.last_error())
         return y
 
+    def SetResampling(self, external_rate, model_rate=48000, quantum=0, max_frames=512):
+        """Before Commit: every shard's batch becomes a resampling batch of this plan; every n then counts samples at `external_rate`."""
+        if self._lib.NA_MultiSetResampling(self._h, int(external_rate), int(model_rate), int(quantum), int(max_frames)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def ResampleInfo(self):
+        """The resampling plan in effect (see resample_plan); raises if SetResampling was never called."""
+        info = capi.NA_ResampleInfo()
+        if self._lib.NA_MultiGetResampleInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return _resample_info(info)
+
+    def Submit(self, x):
+        """Pipelined variant of Process (NA_MultiSubmit, host-rows fan-in): returns a ticket for Collect()."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        assert x.ndim == 2 and x.shape[0] == self.NumStreams(), "expected [streams, n]"
+        t = self._lib.NA_MultiSubmit(self._h, _fptr(x), x.shape[1])
+        if t < 0:
+            raise NeuralAudioError(capi.last_error())
+        return t, x.shape
+
+    def Collect(self, ticket):
+        t, shape = ticket
+        y = np.empty(shape, np.float32)
+        if self._lib.NA_MultiCollect(self._h, int(t), _fptr(y)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return y
+
     def GatheredOutput(self, shard, n):
         """RCCL fan-in: the [streams][n] device buffer of the last Process() on `shard`'s GPU, copied to the host (tests)."""
         ptr = self._lib.NA_MultiGatheredOutput(self._h, int(shard))
@@ -627,20 +655,45 @@ def _render_options(segment_samples, max_samples_per_pass, wait_limit_ms):
     return capi.NA_RenderOptions(int(segment_samples), int(max_samples_per_pass), float(wait_limit_ms))
 
 
-def render_offline(model, x=None, quality=1.0, segment_samples=0, max_samples_per_pass=0, wait_limit_ms=0.0):
+def render_offline(model, x=None, quality=1.0, segment_samples=0, max_samples_per_pass=0, wait_limit_ms=0.0, external_rate=None):
     """Renders a whole signal through `model` as a fresh, prewarmed instance would (NA_RenderOffline: time-parallel segments for WaveNet
     models, one sequential stream per recurrent job).  float32 in, float32 out, same length.  List form: render_offline([(model, x,
-    quality), ...]) renders every job in one call and returns the list of outputs.  The model's own stream state is not touched."""
+    quality), ...]) renders every job in one call and returns the list of outputs.  The model's own stream state is not touched.
+    external_rate: the signals are at this sample rate, whatever rate each model runs at (NA_RenderOfflineAtRate: resampled on the
+    device, latency-compensated; segment_samples and max_samples_per_pass then count model-rate frames).  None: NA_RenderOffline."""
     jobs, xs, ys, many = _render_jobs(model, x, quality)
     opts = _render_options(segment_samples, max_samples_per_pass, wait_limit_ms)
-    if capi.load_library().NA_RenderOffline(jobs, len(xs), C.byref(opts)) != 0:
+    lib = capi.load_library()
+    rc = (lib.NA_RenderOffline(jobs, len(xs), C.byref(opts)) if external_rate is None
+          else lib.NA_RenderOfflineAtRate(jobs, len(xs), C.byref(opts), int(external_rate)))
+    if rc != 0:
         raise NeuralAudioError(capi.last_error())
     return ys if many else ys[0]
 
 
-def render_plan(model, x=None, quality=1.0, segment_samples=0, max_samples_per_pass=0):
+def debug_render_tap(model, x=None, quality=1.0, external_rate=48000, **options):
+    """Test hook (NA_DebugSetRenderTap): render_offline(..., external_rate=...) that also returns job 0's model-rate input and output,
+    (out, u, v)."""
+    lib = capi.load_library()
+    first = model[0] if isinstance(model, (list, tuple)) else (model, x, quality)
+    n = np.asarray(first[1]).size
+    info = resample_plan(external_rate, first[0].GetModelProcessRate(), 1)
+    m = resample_model_frames(external_rate, info["model_rate"], 1, n + info["latency_samples"])
+    u = np.zeros(max(m, 1), np.float32)
+    v = np.zeros(max(m, 1), np.float32)
+    lib.NA_DebugSetRenderTap(_fptr(u), _fptr(v), m)
+    try:
+        out = render_offline(model, x, quality, external_rate=external_rate, **options)
+    finally:
+        lib.NA_DebugSetRenderTap(None, None, 0)
+    return out, u[:m], v[:m]
+
+
+def render_plan(model, x=None, quality=1.0, segment_samples=0, max_samples_per_pass=0, external_rate=None):
     """The plan render_offline would run (NA_RenderPlan; no device needed): segments, lead, segment_samples, row_samples, passes,
-    streams, estimated_ms and -- with a device -- the kernel of the first segment.  `x` may be an array or a sample count."""
+    streams, estimated_ms and -- with a device -- the kernel of the first segment.  `x` may be an array or a sample count.
+    external_rate: the plan of render_offline(..., external_rate=...) (NA_RenderPlanAtRate): the same figures in model-rate frames plus
+    "resample", the resampling plan of job 0's rate pair."""
     def as_signal(v):
         return np.zeros(int(v), dtype=np.float32) if np.isscalar(v) else v
     if isinstance(model, (list, tuple)):
@@ -650,7 +703,14 @@ def render_plan(model, x=None, quality=1.0, segment_samples=0, max_samples_per_p
     jobs, xs, ys, _ = _render_jobs(model, x, quality)
     opts = _render_options(segment_samples, max_samples_per_pass, 0.0)
     info = capi.NA_RenderPlanInfo()
-    if capi.load_library().NA_RenderPlan(jobs, len(xs), C.byref(opts), C.byref(info)) != 0:
+    rs = capi.NA_ResampleInfo()
+    lib = capi.load_library()
+    rc = (lib.NA_RenderPlan(jobs, len(xs), C.byref(opts), C.byref(info)) if external_rate is None
+          else lib.NA_RenderPlanAtRate(jobs, len(xs), C.byref(opts), int(external_rate), C.byref(info), C.byref(rs)))
+    if rc != 0:
         raise NeuralAudioError(capi.last_error())
-    return {"segments": info.segments, "lead": info.lead, "segment_samples": info.segmentSamples, "row_samples": info.rowSamples,
+    plan = {"segments": info.segments, "lead": info.lead, "segment_samples": info.segmentSamples, "row_samples": info.rowSamples,
             "passes": info.passes, "streams": info.streams, "estimated_ms": info.estimatedMs, "kernel": info.kernel.decode()}
+    if external_rate is not None:
+        plan["resample"] = _resample_info(rs)
+    return plan

@@ -36,6 +36,7 @@ NA_SYMBOLS = [
     "NA_SaveModelState", "NA_LoadModelState", "NA_DebugSnapshotLaunches",
     "NA_ResamplePlan", "NA_ResamplePrototype", "NA_ResampleModelFrames", "NA_BatchSetResampling", "NA_BatchGetResampleInfo",
     "NA_SetResampleToExternalRate", "NA_GetProcessLatencySamples", "NA_GetModelProcessRate", "NA_DebugResampleTap",
+    "NA_RenderOfflineAtRate", "NA_RenderPlanAtRate", "NA_DebugSetRenderTap", "NA_MultiSetResampling", "NA_MultiGetResampleInfo",
 ]
 
 
@@ -190,6 +191,12 @@ def load_library():
         "NA_GetProcessLatencySamples": (C.c_int, [vp]),
         "NA_GetModelProcessRate": (C.c_int, [vp]),
         "NA_DebugResampleTap": (C.c_int, [vp, fp, fp, C.c_longlong, C.POINTER(C.c_int)]),
+        "NA_RenderOfflineAtRate": (C.c_int, [C.POINTER(NA_RenderJob), C.c_int, C.POINTER(NA_RenderOptions), C.c_int]),
+        "NA_RenderPlanAtRate": (C.c_int, [C.POINTER(NA_RenderJob), C.c_int, C.POINTER(NA_RenderOptions), C.c_int, C.POINTER(NA_RenderPlanInfo),
+                                          C.POINTER(NA_ResampleInfo)]),
+        "NA_DebugSetRenderTap": (None, [fp, fp, C.c_longlong]),
+        "NA_MultiSetResampling": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int]),
+        "NA_MultiGetResampleInfo": (C.c_int, [vp, C.POINTER(NA_ResampleInfo)]),
         "NA_DebugSplitPlan": (C.c_int, [vp, C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_ushort), C.c_longlong, C.POINTER(C.c_longlong)]),
     }
     for name, (res, args) in sig.items():

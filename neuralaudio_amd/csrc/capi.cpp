@@ -897,6 +897,22 @@ namespace
 	}
 }
 
+namespace
+{
+	void FillRenderPlanInfo(const na::RenderPlan& p, const std::string& kernel, NA_RenderPlanInfo* info)
+	{
+		memset(info, 0, sizeof(*info));
+		info->segments = p.segments;
+		info->lead = p.lead;
+		info->segmentSamples = p.stride > 0 ? p.stride : 0;
+		info->rowSamples = p.rowSamples;
+		info->passes = p.passes;
+		info->streams = p.rows;
+		info->estimatedMs = p.estimatedMs;
+		strncpy(info->kernel, kernel.c_str(), sizeof(info->kernel) - 1);
+	}
+}
+
 int NA_RenderOffline(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts)
 {
 	return Guard([&] {
@@ -915,20 +931,60 @@ int NA_RenderPlan(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions*
 		na::RenderOptionsDesc o;
 		const int device = RenderJobs(jobs, numJobs, opts, js, o);
 		std::string kernel;
-		const na::RenderPlan p = na::PlanOfflineRenderOn(js, o, device, &kernel);
-		memset(info, 0, sizeof(*info));
-		info->segments = p.segments;
-		info->lead = p.lead;
-		info->segmentSamples = p.stride > 0 ? p.stride : 0;
-		info->rowSamples = p.rowSamples;
-		info->passes = p.passes;
-		info->streams = p.rows;
-		info->estimatedMs = p.estimatedMs;
-		strncpy(info->kernel, kernel.c_str(), sizeof(info->kernel) - 1);
+		FillRenderPlanInfo(na::PlanOfflineRenderOn(js, o, device, &kernel), kernel, info);
 	});
 }
 
 // ---------------------------------------------------------------- batch resampling (csrc/resample.cpp)
+
+namespace
+{
+	void FillResampleInfo(const na::ResamplePlan& p, NA_ResampleInfo* info);
+}
+
+int NA_RenderOfflineAtRate(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, int externalRate)
+{
+	return Guard([&] {
+		std::vector<na::RenderJobDesc> js;
+		na::RenderOptionsDesc o;
+		const int device = RenderJobs(jobs, numJobs, opts, js, o);
+		na::RenderOfflineAtRate(js, o, device, externalRate);
+	});
+}
+
+int NA_RenderPlanAtRate(const NA_RenderJob* jobs, int numJobs, const NA_RenderOptions* opts, int externalRate, NA_RenderPlanInfo* info, NA_ResampleInfo* resample)
+{
+	return Guard([&] {
+		if (!info) throw std::runtime_error("NA_RenderPlanAtRate: info is NULL");
+		std::vector<na::RenderJobDesc> js;
+		na::RenderOptionsDesc o;
+		const int device = RenderJobs(jobs, numJobs, opts, js, o);
+		std::string kernel;
+		na::ResamplePlan first;
+		FillRenderPlanInfo(na::PlanOfflineRenderAtRateOn(js, o, device, externalRate, &kernel, &first), kernel, info);
+		if (resample) FillResampleInfo(first, resample);
+	});
+}
+
+#ifndef NA_RELEASE
+void NA_DebugSetRenderTap(float* modelIn, float* modelOut, long long capacity) { na::SetRenderTap(modelIn, modelOut, capacity); }
+#endif
+
+int NA_MultiSetResampling(NA_MultiBatch* mb, int externalRate, int modelRate, int quantum, int maxFrames)
+{
+	return Guard([&] {
+		if (!mb) throw std::runtime_error("NA_MultiSetResampling: null multi batch");
+		mb->multi->SetResampling(externalRate, modelRate, quantum, maxFrames);
+	});
+}
+
+int NA_MultiGetResampleInfo(NA_MultiBatch* mb, NA_ResampleInfo* info)
+{
+	return Guard([&] {
+		if (!mb || !info) throw std::runtime_error("NA_MultiGetResampleInfo: null argument");
+		FillResampleInfo(mb->multi->ResamplingPlan(), info);
+	});
+}
 
 namespace
 {

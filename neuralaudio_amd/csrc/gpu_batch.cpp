@@ -216,9 +216,7 @@ namespace na
 		CheckUsable();
 		if (!model || model->subModels.empty()) throw std::runtime_error("neuralaudio_amd: AddStream with an empty model");
 		if (count < 1) throw std::runtime_error("neuralaudio_amd: AddStreams with count < 1");
-		if (resample && model->ProcessRate() != resample->plan.modelRate)
-			throw std::runtime_error("neuralaudio_amd: AddStreams: the model runs at " + std::to_string(model->ProcessRate()) + " Hz as loaded, the batch resamples to a model rate of " +
-				std::to_string(resample->plan.modelRate) + " Hz");
+		if (resample) CheckResampleModelRate(model->ProcessRate(), resample->plan.modelRate);
 		CheckHip(hipSetDevice(device), "hipSetDevice");
 		DrainPipeline(); // (state arrays may be re-allocated below)
 		topologyVersion++;

@@ -111,6 +111,7 @@ namespace na
 		bool HasResamplingPlan() const { return resample != nullptr; }
 		bool Resamples() const; // a plan with different rates is in effect
 		const ResamplePlan& ResamplingPlan() const;
+		long long ResampleSamplesTaken() const; // external samples the batch has taken so far (its phase); -1 without a plan
 		// test hook (NA_DebugResampleTap): the model-rate input / output rows [streams][frames] of the last processing call (of its last
 		// piece, where a call longer than 2048 external samples ran in several); synchronises
 		int DebugResampleTap(float* modelIn, float* modelOut, long long capacityPerRow);
@@ -363,6 +364,7 @@ namespace na
 		void EnsureResampleRows(int rows);           // set-up side only (AddStreams): histories and model-side rows for `rows` rows
 		void EnsureResampleFrames(size_t n);         // model-side buffers for pieces of n external samples
 		void ZeroResampleHistories(int first, int count);
+		void WaitFresh(float* fresh);                // bounded wait for the set-up of a new block; frees it if the wait fails
 		// ordering between the batch stream and the slot streams: the stream state makes every kernel launch depend on the previous one
 		bool pipelineUsed = false;
 		hipEvent_t lastKernelEvent = nullptr, mainDone = nullptr;

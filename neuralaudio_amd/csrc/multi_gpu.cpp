@@ -53,6 +53,7 @@ namespace na
 	{
 		if (committed) throw std::runtime_error("neuralaudio_amd: MultiGpuBatch::AddStreams after Commit (the shards are fixed)");
 		if (!model || count < 1) throw std::runtime_error("neuralaudio_amd: MultiGpuBatch::AddStreams: bad argument");
+		if (resampling) CheckResampleModelRate(model->ProcessRate(), resamplePlan.modelRate);
 		const int first = total;
 		entries.push_back({ model, quality, count, prewarm, onDemand });
 		total += count;
@@ -164,6 +165,7 @@ namespace na
 			Post([this, fanOut](Shard& s) {
 				if (s.end <= s.begin) return;
 				s.batch.reset(new GpuBatch(s.device));
+				if (resampling) s.batch->SetResampling(resamplePlan.externalRate, resamplePlan.modelRate, resamplePlan.quantum, resampleMaxFrames);
 				int first = 0;
 				for (const Entry& e : entries)
 				{
@@ -192,6 +194,41 @@ namespace na
 	{
 		if (committed) throw std::runtime_error("neuralaudio_amd: MultiGpuBatch::SetFanIn after Commit");
 		fanIn = mode;
+	}
+
+	void MultiGpuBatch::SetResampling(int externalRate, int modelRate, int quantum, int maxFrames)
+	{
+		if (committed) throw std::runtime_error("neuralaudio_amd: MultiGpuBatch::SetResampling after Commit (it is a set-up call)");
+		if (maxFrames < 1) throw std::runtime_error("neuralaudio_amd: SetResampling: maxFrames must be >= 1");
+		const ResamplePlan p = PlanResampling(externalRate, modelRate, quantum);
+		for (const Entry& e : entries) CheckResampleModelRate(e.model->ProcessRate(), p.modelRate);
+		resamplePlan = p;
+		resampleMaxFrames = maxFrames;
+		resampling = true;
+	}
+
+	const ResamplePlan& MultiGpuBatch::ResamplingPlan() const
+	{
+		if (!resampling) throw std::runtime_error("neuralaudio_amd: the multi batch does not resample (NA_MultiSetResampling was not called)");
+		return resamplePlan;
+	}
+
+	// All shards are called with the same n, so their resampling batches have taken the same number of external samples and sit at the
+	// same phase.  A shard that disagrees would return rows of another latency: the object refuses further work.
+	void MultiGpuBatch::CheckInStep()
+	{
+		if (!resampling) return;
+		long long taken = -1;
+		for (const auto& sp : shards)
+		{
+			if (!sp->batch) continue;
+			if (taken < 0) taken = sp->taken;
+			if (sp->taken != taken)
+			{
+				broken = "the shards' resampling batches are out of step";
+				throw std::runtime_error("neuralaudio_amd: MultiGpuBatch: " + broken);
+			}
+		}
 	}
 
 	static void CheckNccl(const rccl::Api* api, rccl::Result r, const char* what)
@@ -360,6 +397,7 @@ namespace na
 			CheckNccl(nccl, closed, "ncclGroupEnd");
 			if (s.rank == 0) CheckHip(hipMemcpyAsync(out, s.gathered, totalFloats * sizeof(float), hipMemcpyDeviceToHost, st), "hipMemcpyAsync D2H");
 			s.batch->WaitStreamBounded(st, "hipStreamSynchronize");
+			s.taken = s.batch->ResampleSamplesTaken();
 		});
 		}
 		catch (const std::exception& e)
@@ -415,11 +453,15 @@ namespace na
 		if (fanIn == FanIn::Rccl)
 		{
 			ProcessGathered(in, out, n);
+			CheckInStep();
 			return;
 		}
 		Post([=](Shard& s) {
-			if (s.batch) s.batch->ProcessHost(in + (size_t)s.begin * n, out + (size_t)s.begin * n, n);
+			if (!s.batch) return;
+			s.batch->ProcessHost(in + (size_t)s.begin * n, out + (size_t)s.begin * n, n);
+			s.taken = s.batch->ResampleSamplesTaken();
 		});
+		CheckInStep();
 	}
 
 	int MultiGpuBatch::Submit(const float* in, size_t n)
@@ -438,6 +480,7 @@ namespace na
 				std::lock_guard<std::mutex> lock(tm);
 				if (ticket >= 0 && ticket != t) throw std::runtime_error("neuralaudio_amd: MultiGpuBatch: shards out of step");
 				ticket = t;
+				s.taken = s.batch->ResampleSamplesTaken();
 			});
 		}
 		catch (const std::exception& e)
@@ -447,6 +490,7 @@ namespace na
 			broken = e.what();
 			throw;
 		}
+		CheckInStep();
 		return ticket;
 	}
 
@@ -454,8 +498,11 @@ namespace na
 	{
 		CheckUsable();
 		Post([=](Shard& s) {
-			if (s.batch) s.batch->Collect(ticket, out ? out + (size_t)s.begin * s.batch->SlotFrames(ticket) : nullptr);
+			if (!s.batch) return;
+			s.batch->Collect(ticket, out ? out + (size_t)s.begin * s.batch->SlotFrames(ticket) : nullptr);
+			s.taken = s.batch->ResampleSamplesTaken();
 		});
+		CheckInStep();
 	}
 
 	void MultiGpuBatch::SetQuality(int stream, float quality)

@@ -52,6 +52,13 @@ namespace na
 		enum class FanIn { HostRows, Rccl };
 		void SetFanIn(FanIn mode);
 		FanIn GetFanIn() const { return fanIn; }
+		// Every shard's batch becomes a resampling batch of this plan (GpuBatch::SetResampling at Commit, before the shard's AddStreams):
+		// from then on every n of Process / Submit / Collect counts EXTERNAL samples, under either fan-in (the gathered buffer is
+		// [streams][n] in external samples).  All shards share one phase because they are always called with the same n; their sample
+		// counters are compared after every call and a disagreement breaks the object.  Before Commit; throws on a refused pair / quantum
+		// and on a model of the list whose process rate is not modelRate (AddStreams refuses such a model from then on).
+		void SetResampling(int externalRate, int modelRate, int quantum, int maxFrames);
+		const ResamplePlan& ResamplingPlan() const; // throws if SetResampling was never called
 		const float* GatheredOutput(int shard) const; // Rccl mode: device pointer to [streams][n] of the last Process() on that shard's GPU
 
 		int NumStreams() const { return total; }
@@ -88,6 +95,7 @@ namespace na
 			rccl::Comm comm = nullptr;
 			float* gathered = nullptr; // device [total][n] (owned by the worker: allocated / freed on its thread)
 			size_t gatheredFloats = 0;
+			long long taken = -1; // external samples the shard's resampling batch has taken (read on the worker after every call)
 		};
 		void Run(Shard& s);
 		void CheckShard(const Shard& s) const;
@@ -102,6 +110,10 @@ namespace na
 		bool committed = false;
 		std::string broken; // set by a submission that only part of the shards took
 		FanIn fanIn = FanIn::HostRows;
+		bool resampling = false; // SetResampling was called: the request, applied to every shard's batch at Commit
+		ResamplePlan resamplePlan;
+		int resampleMaxFrames = 0;
+		void CheckInStep(); // the shards' sample counters agree, else the object breaks
 		const rccl::Api* nccl = nullptr;
 		void InitRccl();          // communicators (one per shard) + weight replication
 		void ReplicateWeights();

@@ -15,6 +15,7 @@
 #include <thread>
 
 #include "gpu_batch.h"
+#include "resample.h"
 
 namespace na
 {
@@ -233,17 +234,36 @@ namespace na
 		return plan;
 	}
 
+	namespace
+	{
+		void CheckHostJobs(const std::vector<RenderJobDesc>& jobs)
+		{
+			for (const RenderJobDesc& j : jobs)
+			{
+				if (!j.model) throw std::runtime_error("offline render: job without a model");
+				if (j.numSamples > 0 && (!j.input || !j.output)) throw std::runtime_error("offline render: job without input or output buffer");
+				if (j.numSamples > 0 && j.input < j.output + j.numSamples && j.output < j.input + j.numSamples)
+					throw std::runtime_error("offline render: a job's input and output overlap");
+			}
+		}
+	}
+
+	static void RenderSegments(GpuBatch& batch, const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device, bool deviceSignals);
+
 	void RenderOffline(const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device)
 	{
-		for (const RenderJobDesc& j : jobs)
-		{
-			if (!j.model) throw std::runtime_error("offline render: job without a model");
-			if (j.numSamples > 0 && (!j.input || !j.output)) throw std::runtime_error("offline render: job without input or output buffer");
-			if (j.numSamples > 0 && j.input < j.output + j.numSamples && j.output < j.input + j.numSamples)
-				throw std::runtime_error("offline render: a job's input and output overlap");
-		}
+		CheckHostJobs(jobs);
 		GpuBatch batch(device); // throws without a device: there is no CPU fallback
 		if (opts.waitLimitMs > 0) batch.SetWaitLimitMs(opts.waitLimitMs);
+		RenderSegments(batch, jobs, opts, device, false);
+	}
+
+	// the segment passes of a render on `batch` (empty so far).  deviceSignals: the jobs' input / output pointers are device memory of
+	// `device` (the model-rate signals of RenderOfflineAtRate) instead of host windows; nothing else differs.
+	static void RenderSegments(GpuBatch& batch, const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device, bool deviceSignals)
+	{
+		const hipMemcpyKind inKind = deviceSignals ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+		const hipMemcpyKind outKind = deviceSignals ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
 		const RenderPlan plan = PlanOfflineRender(jobs, opts, DeviceComputeUnits(device));
 		if (plan.rows == 0) return;
 
@@ -323,7 +343,7 @@ namespace na
 			{
 				const Window& w = win[(size_t)j];
 				if (w.inHi > w.inLo)
-					CheckHip(hipMemcpyAsync(dSig + w.sigBase, jobs[(size_t)j].input + w.inLo, (size_t)(w.inHi - w.inLo) * sizeof(float), hipMemcpyHostToDevice, rs),
+					CheckHip(hipMemcpyAsync(dSig + w.sigBase, jobs[(size_t)j].input + w.inLo, (size_t)(w.inHi - w.inLo) * sizeof(float), inKind, rs),
 						"hipMemcpyAsync (offline render input)");
 			}
 			CheckHip(hipMemcpyAsync(dRows, table.data(), table.size() * sizeof(RenderRow), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (row table)");
@@ -337,10 +357,241 @@ namespace na
 			{
 				const Window& w = win[(size_t)j];
 				if (w.outHi > w.outLo)
-					CheckHip(hipMemcpyAsync(jobs[(size_t)j].output + w.outLo, dOut + w.outBase, (size_t)(w.outHi - w.outLo) * sizeof(float), hipMemcpyDeviceToHost, rs),
+					CheckHip(hipMemcpyAsync(jobs[(size_t)j].output + w.outLo, dOut + w.outBase, (size_t)(w.outHi - w.outLo) * sizeof(float), outKind, rs),
 						"hipMemcpyAsync (offline render output)");
 			}
 			batch.WaitStreamBounded(rs, "offline render: output download");
 		}
+	}
+
+	// ---------------------------------------------------------------------------------- rendering at an external rate
+
+	namespace
+	{
+		struct RenderTap
+		{
+			float* modelIn = nullptr;
+			float* modelOut = nullptr;
+			long long capacity = 0;
+			bool armed = false;
+		};
+		// Test hook only, and NOT thread-safe: one unsynchronised slot, armed by SetRenderTap and taken (and cleared) by the next
+		// RenderOfflineAtRate on whatever thread.  The release library exports no way to arm it (NA_DebugSetRenderTap is compiled out
+		// of its capi.cpp), so there it stays off and concurrent renders only ever copy and clear an empty slot.
+		RenderTap g_renderTap;
+
+		// the jobs as the segment machinery sees them: job i is M_i = J_i(N_i + L_i) model-rate frames (identity pairs: N_i, L_i = 0)
+		struct AtRateLayout
+		{
+			std::vector<ResamplePlan> plans;  // one per distinct model rate
+			std::vector<int> jobPlan;         // index into plans
+			std::vector<long long> frames;    // M per job
+		};
+
+		AtRateLayout LayoutAtRate(const std::vector<RenderJobDesc>& jobs, int externalRate)
+		{
+			if (externalRate <= 0) throw std::runtime_error("offline render: the external sample rate must be positive (" + std::to_string(externalRate) + ")");
+			AtRateLayout lay;
+			for (const RenderJobDesc& j : jobs)
+			{
+				if (!j.model) throw std::runtime_error("offline render: job without a model");
+				const int fm = j.model->ProcessRate();
+				int k = 0;
+				while (k < (int)lay.plans.size() && lay.plans[(size_t)k].modelRate != fm) k++;
+				if (k == (int)lay.plans.size())
+				{
+					ResamplePlan p = PlanResampling(externalRate, fm, 1); // throws on a refused pair
+					if (!p.identity && (OfflineResampleTile(p.tm, p.te, p.tapsUp) == 0 || OfflineResampleTile(p.te, p.tm, p.tapsDown) == 0))
+						throw std::runtime_error("offline render: the filter of " + std::to_string(externalRate) + " Hz against " + std::to_string(fm) + " Hz (" +
+							std::to_string(p.tapsUp) + " / " + std::to_string(p.tapsDown) + " taps) does not fit the stages' window");
+					lay.plans.push_back(p);
+				}
+				const ResamplePlan& p = lay.plans[(size_t)k];
+				lay.jobPlan.push_back(k);
+				lay.frames.push_back(p.ModelFrames((long long)j.numSamples + p.latency)); // (an empty job still renders its L samples of tail)
+			}
+			return lay;
+		}
+
+		std::vector<RenderJobDesc> ModelRateJobs(const std::vector<RenderJobDesc>& jobs, const AtRateLayout& lay)
+		{
+			std::vector<RenderJobDesc> out = jobs;
+			for (size_t j = 0; j < out.size(); j++)
+			{
+				out[j].input = nullptr;
+				out[j].output = nullptr;
+				out[j].numSamples = (size_t)lay.frames[j];
+			}
+			return out;
+		}
+	}
+
+	void SetRenderTap(float* modelIn, float* modelOut, long long capacity)
+	{
+		g_renderTap.modelIn = modelIn;
+		g_renderTap.modelOut = modelOut;
+		g_renderTap.capacity = capacity;
+		g_renderTap.armed = (modelIn || modelOut);
+	}
+
+	RenderPlan PlanOfflineRenderAtRateOn(const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device, int externalRate,
+		std::string* kernelName, ResamplePlan* firstJobPlan)
+	{
+		if (jobs.empty()) throw std::runtime_error("offline render: no jobs");
+		const AtRateLayout lay = LayoutAtRate(jobs, externalRate);
+		if (firstJobPlan) *firstJobPlan = lay.plans[(size_t)lay.jobPlan[0]];
+		return PlanOfflineRenderOn(ModelRateJobs(jobs, lay), opts, device, kernelName);
+	}
+
+	void RenderOfflineAtRate(const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device, int externalRate)
+	{
+		// the tap is for the next call only, whatever becomes of it
+		const RenderTap tap = g_renderTap;
+		g_renderTap = RenderTap();
+		if (jobs.empty()) throw std::runtime_error("offline render: no jobs");
+		// everything that can refuse the call comes before any device work
+		const AtRateLayout lay = LayoutAtRate(jobs, externalRate);
+		CheckHostJobs(jobs);
+		const int numJobs = (int)jobs.size();
+		if (numJobs > kMaxRenderRows) throw std::runtime_error("offline render: more jobs than one segment batch holds (16384)");
+		if (tap.armed && lay.frames[0] > tap.capacity)
+			throw std::runtime_error("offline render: the render tap holds " + std::to_string(tap.capacity) + " frames, job 0 has " + std::to_string(lay.frames[0]));
+
+		GpuBatch batch(device); // throws without a device: there is no CPU fallback
+		if (opts.waitLimitMs > 0) batch.SetWaitLimitMs(opts.waitLimitMs);
+
+		// whole-signal device buffers: x and out at the external rate (resampled jobs only), u and v at the model rate
+		DeviceBuffers mem;
+		mem.batch = &batch;
+		unsigned long long bytes = 0;
+		for (int j = 0; j < numJobs; j++)
+			bytes += 8ULL * (unsigned long long)lay.frames[(size_t)j] + (lay.plans[(size_t)lay.jobPlan[(size_t)j]].identity ? 0ULL : 8ULL * (unsigned long long)jobs[(size_t)j].numSamples);
+		auto alloc = [&](long long floats) -> float* {
+			try
+			{
+				return mem.Alloc<float>((size_t)floats);
+			}
+			catch (const std::exception& e)
+			{
+				throw std::runtime_error("offline render: no device memory for the whole-signal buffers (" + std::to_string(bytes) +
+					" bytes: 8 per sample at the external rate and 8 per model-rate frame of every job): " + e.what());
+			}
+		};
+		std::vector<float*> dX((size_t)numJobs, nullptr), dU((size_t)numJobs, nullptr), dV((size_t)numJobs, nullptr), dY((size_t)numJobs, nullptr);
+		for (int j = 0; j < numJobs; j++)
+		{
+			const long long N = (long long)jobs[(size_t)j].numSamples, M = lay.frames[(size_t)j];
+			if (M == 0) continue;
+			dU[(size_t)j] = alloc(M);
+			dV[(size_t)j] = alloc(M);
+			if (lay.plans[(size_t)lay.jobPlan[(size_t)j]].identity) continue;
+			dX[(size_t)j] = alloc(N);
+			dY[(size_t)j] = alloc(N);
+		}
+		// the coefficient tables of every pair that resamples
+		std::vector<float*> dUp(lay.plans.size(), nullptr), dDown(lay.plans.size(), nullptr);
+		CheckHip(hipStreamCreateWithFlags(&mem.stream, hipStreamNonBlocking), "hipStreamCreate");
+		hipStream_t rs = mem.stream;
+		std::vector<std::vector<float>> tables; // (alive until the uploads are waited for)
+		for (size_t k = 0; k < lay.plans.size(); k++)
+		{
+			const ResamplePlan& p = lay.plans[k];
+			if (p.identity) continue;
+			tables.emplace_back();
+			tables.emplace_back();
+			std::vector<float>&up = tables[tables.size() - 2], &down = tables[tables.size() - 1];
+			ResampleTables(p, ResamplePrototype(p), up, down);
+			dUp[k] = alloc((long long)up.size());
+			dDown[k] = alloc((long long)down.size());
+			CheckHip(hipMemcpyAsync(dUp[k], up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (resample table)");
+			CheckHip(hipMemcpyAsync(dDown[k], down.data(), down.size() * sizeof(float), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (resample table)");
+		}
+
+		// 1 + 2: upload x, up stage -> u (an identity job's x IS its u)
+		std::vector<OfflineResampleJob> up((size_t)numJobs), down((size_t)numJobs);
+		bool resamples = false;
+		for (int j = 0; j < numJobs; j++)
+		{
+			const size_t k = (size_t)lay.jobPlan[(size_t)j];
+			const ResamplePlan& p = lay.plans[k];
+			const long long N = (long long)jobs[(size_t)j].numSamples, M = lay.frames[(size_t)j];
+			OfflineResampleJob& a = up[(size_t)j];
+			OfflineResampleJob& b = down[(size_t)j];
+			a = OfflineResampleJob{ nullptr, nullptr, nullptr, 0, 0, 0, 1, 1, 1, 1, 1, 0.0f };
+			b = a;
+			if (M == 0) continue;
+			if (p.identity)
+			{
+				CheckHip(hipMemcpyAsync(dU[(size_t)j], jobs[(size_t)j].input, (size_t)N * sizeof(float), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (offline render input)");
+				continue;
+			}
+			resamples = true;
+			if (N > 0) CheckHip(hipMemcpyAsync(dX[(size_t)j], jobs[(size_t)j].input, (size_t)N * sizeof(float), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (offline render input)");
+			// u[f]: newest tap at tick f * tm, reads x at tick / te - tap, phase tick % te, gain te
+			a.in = dX[(size_t)j];
+			a.out = dU[(size_t)j];
+			a.table = dUp[k];
+			a.nIn = N;
+			a.nOut = M;
+			a.tick0 = 0;
+			a.step = p.tm;
+			a.period = p.te;
+			a.taps = p.tapsUp;
+			a.tile = OfflineResampleTile(a.step, a.period, a.taps);
+			a.window = (int)OfflineResampleWindow(a.tile, a.step, a.period, a.taps);
+			a.gain = (float)p.te;
+			// out[i] = s[i + L]: newest tap at tick (i + L) * te - S, reads v at tick / tm - tap, phase tick % tm, gain tm
+			b.in = dV[(size_t)j];
+			b.out = dY[(size_t)j];
+			b.table = dDown[k];
+			b.nIn = M;
+			b.nOut = N;
+			b.tick0 = (long long)p.latency * p.te - p.shift;
+			b.step = p.te;
+			b.period = p.tm;
+			b.taps = p.tapsDown;
+			b.tile = OfflineResampleTile(b.step, b.period, b.taps);
+			b.window = (int)OfflineResampleWindow(b.tile, b.step, b.period, b.taps);
+			b.gain = (float)p.tm;
+			// the newest model frame the last output reads was computed: floor(((N + L - 1) * te - S) / tm) <= J(N + L) - 1
+			if (b.tick0 < 0 || (N > 0 && (b.tick0 + (N - 1) * (long long)b.step) / b.period >= M)) throw std::runtime_error("offline render: resampling layout out of range");
+		}
+		OfflineResampleJob* dJobs = nullptr;
+		if (resamples)
+		{
+			void* p = nullptr;
+			CheckHip(hipMalloc(&p, 2 * (size_t)numJobs * sizeof(OfflineResampleJob)), "hipMalloc (offline render)");
+			mem.ptrs.push_back(p);
+			dJobs = (OfflineResampleJob*)p;
+			CheckHip(hipMemcpyAsync(dJobs, up.data(), (size_t)numJobs * sizeof(OfflineResampleJob), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (resample jobs)");
+			CheckHip(hipMemcpyAsync(dJobs + numJobs, down.data(), (size_t)numJobs * sizeof(OfflineResampleJob), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (resample jobs)");
+			CheckHip(LaunchOfflineResampleUp(up.data(), dJobs, numJobs, rs), "OfflineResampleUpKernel");
+		}
+		batch.WaitStreamBounded(rs, "offline render: up stage");
+
+		// 3: the segment machinery over u -> v, both in device memory
+		std::vector<RenderJobDesc> mj = ModelRateJobs(jobs, lay);
+		for (int j = 0; j < numJobs; j++)
+		{
+			mj[(size_t)j].input = dU[(size_t)j];
+			mj[(size_t)j].output = dV[(size_t)j];
+		}
+		RenderSegments(batch, mj, opts, device, true);
+
+		// 4 + 5: down stage -> out, download
+		if (resamples) CheckHip(LaunchOfflineResampleDown(down.data(), dJobs + numJobs, numJobs, rs), "OfflineResampleDownKernel");
+		for (int j = 0; j < numJobs; j++)
+		{
+			const long long N = (long long)jobs[(size_t)j].numSamples;
+			if (N == 0) continue;
+			const float* src = lay.plans[(size_t)lay.jobPlan[(size_t)j]].identity ? dV[(size_t)j] : dY[(size_t)j];
+			CheckHip(hipMemcpyAsync(jobs[(size_t)j].output, src, (size_t)N * sizeof(float), hipMemcpyDeviceToHost, rs), "hipMemcpyAsync (offline render output)");
+		}
+		if (tap.armed && lay.frames[0] > 0)
+		{
+			if (tap.modelIn) CheckHip(hipMemcpyAsync(tap.modelIn, dU[0], (size_t)lay.frames[0] * sizeof(float), hipMemcpyDeviceToHost, rs), "hipMemcpyAsync (render tap)");
+			if (tap.modelOut) CheckHip(hipMemcpyAsync(tap.modelOut, dV[0], (size_t)lay.frames[0] * sizeof(float), hipMemcpyDeviceToHost, rs), "hipMemcpyAsync (render tap)");
+		}
+		batch.WaitStreamBounded(rs, "offline render: output download");
 	}
 }

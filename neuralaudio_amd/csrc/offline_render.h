@@ -71,4 +71,20 @@ namespace na
 	RenderPlan PlanOfflineRenderOn(const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device, std::string* kernelName);
 	// renders every job on `device`; throws std::runtime_error / HipError with the reason (no device, a wait that ran into the limit, ...)
 	void RenderOffline(const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device);
+
+	// ---- the same at an external sample rate (NA_RenderOfflineAtRate): every job's input / output / numSamples are at `externalRate`,
+	// its model runs at its own LoadedModel::ProcessRate().  Per job: plan = PlanResampling(externalRate, model rate, quantum 1),
+	// L = plan.latency, M = J(N + L) model frames; x is uploaded whole, the up stage (offline_resample_kernels.hip) makes u[0, M), the
+	// segment machinery above renders u -> v with both in device memory, the down stage makes out[k] = s[k + L], downloaded whole.
+	// An identity pair skips both stages (u = x, out = v): RenderOffline's result.  Device memory on top of RenderOffline's: 8 N + 8 M
+	// bytes per job (8 M for an identity job) plus the coefficient tables.  Refusals (a rate <= 0, a refused pair, overlapping buffers)
+	// come before any device work.
+	struct ResamplePlan;
+	// segmentSamples / maxSamplesPerPass and every figure of the plan count MODEL-RATE frames; firstJobPlan: job 0's resampling plan
+	RenderPlan PlanOfflineRenderAtRateOn(const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device, int externalRate,
+		std::string* kernelName, ResamplePlan* firstJobPlan);
+	void RenderOfflineAtRate(const std::vector<RenderJobDesc>& jobs, const RenderOptionsDesc& opts, int device, int externalRate);
+	// tests (NA_DebugSetRenderTap): the next RenderOfflineAtRate copies job 0's u and v (M frames each) to these host arrays and fails
+	// before any device work if M > capacity; both NULL: off.  One call only.
+	void SetRenderTap(float* modelIn, float* modelOut, long long capacity);
 }

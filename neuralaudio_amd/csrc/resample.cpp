@@ -49,6 +49,13 @@ namespace na
 		return p;
 	}
 
+	void CheckResampleModelRate(int modelProcessRate, int planModelRate)
+	{
+		if (modelProcessRate != planModelRate)
+			throw std::runtime_error("neuralaudio_amd: AddStreams: the model runs at " + std::to_string(modelProcessRate) + " Hz as loaded, the batch resamples to a model rate of " +
+				std::to_string(planModelRate) + " Hz");
+	}
+
 	namespace
 	{
 		double BesselI0(double x)
@@ -116,6 +123,8 @@ namespace na
 		return resample->plan;
 	}
 
+	long long GpuBatch::ResampleSamplesTaken() const { return resample ? resample->E : -1; }
+
 	void GpuBatch::SetResampling(int externalRate, int modelRate, int quantum, int maxFrames)
 	{
 		CheckUsable();
@@ -148,6 +157,21 @@ namespace na
 		resample = std::move(rs);
 	}
 
+	// waits for the clear / copy into a block that no member owns yet; a wait that fails gives the block back -- unless the batch broke:
+	// the clear may then still be pending, and the block is left alone like everything else of a broken batch (GpuBatch::IsBroken)
+	void GpuBatch::WaitFresh(float* fresh)
+	{
+		try
+		{
+			WaitStreamBounded(stream, "hipStreamSynchronize");
+		}
+		catch (...)
+		{
+			if (!IsBroken()) (void)hipFree(fresh);
+			throw;
+		}
+	}
+
 	// set-up side (AddStreams): rows only ever grow; the histories of the rows that exist move to the new block
 	void GpuBatch::EnsureResampleRows(int rows)
 	{
@@ -159,14 +183,17 @@ namespace na
 		auto grow = [&](float*& block, size_t rowFloats, bool keep) {
 			float* fresh = nullptr;
 			CheckHip(hipMalloc(reinterpret_cast<void**>(&fresh), (size_t)cap * rowFloats * sizeof(float)), "hipMalloc");
-			hipError_t e = hipMemset(fresh, 0, (size_t)cap * rowFloats * sizeof(float));
+			// (on the batch stream, not the legacy stream: another shard of a multi batch may be capturing a graph on its own stream, and
+			// a legacy-stream operation would have to wait for that stream)
+			hipError_t e = hipMemsetAsync(fresh, 0, (size_t)cap * rowFloats * sizeof(float), stream);
 			if (e == hipSuccess && keep && block && r.rowCapacity > 0)
-				e = hipMemcpy(fresh, block, (size_t)r.rowCapacity * rowFloats * sizeof(float), hipMemcpyDeviceToDevice);
+				e = hipMemcpyAsync(fresh, block, (size_t)r.rowCapacity * rowFloats * sizeof(float), hipMemcpyDeviceToDevice, stream);
 			if (e != hipSuccess)
 			{
 				(void)hipFree(fresh);
 				CheckHip(e, "resampling: growing the row blocks");
 			}
+			WaitFresh(fresh);
 			if (block) (void)hipFree(block);
 			block = fresh;
 		};
@@ -189,12 +216,13 @@ namespace na
 		{
 			float* fresh = nullptr;
 			CheckHip(hipMalloc(reinterpret_cast<void**>(&fresh), (size_t)r.rowCapacity * (size_t)stride * sizeof(float)), "hipMalloc");
-			const hipError_t e = hipMemset(fresh, 0, (size_t)r.rowCapacity * (size_t)stride * sizeof(float));
+			const hipError_t e = hipMemsetAsync(fresh, 0, (size_t)r.rowCapacity * (size_t)stride * sizeof(float), stream); // (see EnsureResampleRows)
 			if (e != hipSuccess)
 			{
 				(void)hipFree(fresh);
-				CheckHip(e, "hipMemset");
+				CheckHip(e, "hipMemsetAsync");
 			}
+			WaitFresh(fresh);
 			if (*block) (void)hipFree(*block);
 			*block = fresh;
 		}

@@ -42,6 +42,9 @@ namespace na
 
 	// throws std::runtime_error naming the reason (rate <= 0, a quantum other than 0 / 1 / 32 / 64 / 128, reduced terms beyond 640)
 	ResamplePlan PlanResampling(int externalRate, int modelRate, int quantum);
+	// a model that runs at `modelProcessRate` as loaded does not belong in a batch that resamples to `planModelRate`: throws (the one
+	// message of NA_BatchAddStreams and NA_MultiAddStreams)
+	void CheckResampleModelRate(int modelProcessRate, int planModelRate);
 	// the prototype of a rate pair: designed in double precision, rounded to f32 once
 	std::vector<float> ResamplePrototype(const ResamplePlan& plan);
 	// phase-major coefficient tables of the two stages: up[phase][tap] = h[phase + tap * te] (te phases, tapsUp taps), down[phase][tap] =
@@ -67,4 +70,32 @@ namespace na
 	hipError_t LaunchResampleUp(const ResampleStageArgs& a, hipStream_t stream);
 	hipError_t LaunchResampleDown(const ResampleStageArgs& a, hipStream_t stream);
 	constexpr int kResampleWindowFloats = 12288; // LDS window of a workgroup: history + the samples of one piece (48 KiB)
+
+	// ---- whole-signal stages of NA_RenderOfflineAtRate (offline_resample_kernels.hip): the same sums over a signal of any length.
+	// One workgroup computes `tile` consecutive outputs of one job from a window of the job's input that it stages once in LDS (zero
+	// outside [0, nIn)).  Output o's newest tap sits at tick tick0 + o * step (64-bit: two hours at 44.1 kHz are 5e10 ticks); it reads
+	// the input at tick / period - tap with the coefficients of phase tick % period, exactly as ResampleStageArgs describes.
+	struct OfflineResampleJob
+	{
+		const float* in;    // nIn samples (device)
+		float* out;         // nOut samples (device)
+		const float* table; // [period][taps] (device)
+		long long nIn, nOut;
+		long long tick0;    // >= 0
+		int step, period, taps;
+		int tile;           // outputs per workgroup (OfflineResampleTile)
+		int window;         // floats a workgroup stages (OfflineResampleWindow of the tile)
+		float gain;
+	};
+	constexpr int kOfflineResampleTile = 2048;       // the largest tile; 8 outputs per thread
+	constexpr int kOfflineResampleWindowFloats = 12288;
+	// floats a tile of `tile` outputs stages: taps + floor((period - 1 + (tile - 1) * step) / period), the span from the oldest tap of its
+	// first output to the newest tap of its last one at the worst phase of the first
+	long long OfflineResampleWindow(int tile, int step, int period, int taps);
+	// the largest power of two <= kOfflineResampleTile whose window fits kOfflineResampleWindowFloats; 0 if not even one output does
+	int OfflineResampleTile(int step, int period, int taps);
+	// `jobs` (host copy) and `dJobs` (the same array in device memory, already enqueued on `stream`) describe numJobs jobs; the launcher
+	// checks every job's integers -- the window indices its kernel will form -- before it launches one grid of (tiles, jobs)
+	hipError_t LaunchOfflineResampleUp(const OfflineResampleJob* jobs, const OfflineResampleJob* dJobs, int numJobs, hipStream_t stream);
+	hipError_t LaunchOfflineResampleDown(const OfflineResampleJob* jobs, const OfflineResampleJob* dJobs, int numJobs, hipStream_t stream);
 }

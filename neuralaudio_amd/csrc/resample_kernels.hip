@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include "resample.h"
+#include "resample_tap.h"
 
 namespace na
 {
@@ -33,11 +34,7 @@ namespace na
 				else
 				{
 					v = in[i - a.histLen];
-					if (CLEAN)
-					{
-						// NaN reads as silence, before the filter so that it cannot smear; infinities become the largest finite value
-						v = __builtin_isnan(v) ? 0.0f : fminf(fmaxf(v, -3.0e38f), 3.0e38f);
-					}
+					if (CLEAN) v = ResampleCleanSample(v);
 				}
 				win[i] = v;
 			}
@@ -48,10 +45,8 @@ namespace na
 				const int tick = a.tick0 + o * a.step;
 				const int idx = tick / a.period;
 				const int phase = tick - idx * a.period;
-				const float* __restrict__ c = a.table + (long)phase * a.taps;
-				float acc = 0.0f;
-				for (int t = 0; t < a.taps; t++) acc = fmaf(c[t], win[idx - t], acc);
-				out[o] = acc * a.gain;
+				// (the sum itself is shared with the offline stages: resample_tap.h)
+				out[o] = ResampleTapSum(a.table + (long)phase * a.taps, win, idx, a.taps, a.gain);
 			}
 			// (every read of the old history happened in front of the barrier)
 			for (int i = (int)threadIdx.x; i < a.histLen; i += kResampleThreads) hist[i] = win[a.nIn + i];
