@@ -58,7 +58,7 @@ namespace na
 		const WnFamily fam = isVirtual ? WN_FAMILY_SPLIT : FamilyFor(real);
 		info.pack = pack;
 		info.kernel = fam == WN_FAMILY_SPLIT ? "f16-split" : (fam == WN_FAMILY_GENERIC ? "generic" : "frame");
-		if (fam != WN_FAMILY_SPLIT) info.inputLimit = INFINITY;
+		if (fam != WN_FAMILY_SPLIT && fam != WN_FAMILY_GENERIC) info.inputLimit = INFINITY;
 		return info;
 	}
 

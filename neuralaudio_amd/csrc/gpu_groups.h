@@ -583,7 +583,7 @@ namespace na
 					}
 					else if (which == WN_FAMILY_GENERIC)
 						CheckHip(LaunchWaveNetGeneric(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
-							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
+							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, plan.condLimit, !plan.splitRangeProven, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
 							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetGenericKernel");
 					else
 						CheckHip(LaunchWaveNetFrame(dev, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive, dIn + offset, dOut + offset,
@@ -606,7 +606,7 @@ namespace na
 			double MacsPerSample() const override { return (plan.isVirtual() ? realPlan : plan).MacsPerSample(); }
 			size_t StateBytesPerStream() const override { return (size_t)plan.stateF4 * 16 / (size_t)pack; }
 			int PackFactor() const override { return pack; }
-			float InputLimit() const override { return family == WN_FAMILY_SPLIT ? plan.condLimit : INFINITY; }
+			float InputLimit() const override { return (family == WN_FAMILY_SPLIT || family == WN_FAMILY_GENERIC) ? plan.condLimit : INFINITY; }
 			void WeightsArrived() override
 			{
 				if (!columnsPending) return;
@@ -625,7 +625,9 @@ namespace na
 			}
 			int RangeEvents(int member) override
 			{
-				if (family != WN_FAMILY_SPLIT || !dev.saturate || !InUse(member)) return 0;
+				// (the runtime-shaped kernels count where the header has a free word)
+				const bool counts = dev.saturate && (family == WN_FAMILY_SPLIT || (family == WN_FAMILY_GENERIC && plan.rings.size() <= (size_t)WN_RANGE_EVENT_SLOT));
+				if (!counts || !InUse(member)) return 0;
 				int count = 0;
 				const float* slot = state.Get() + (size_t)(member / pack) * (size_t)plan.stateF4 * 4;
 				CheckHip(hipMemcpyAsync(&count, reinterpret_cast<const int*>(slot) + WN_RANGE_EVENT_SLOT, sizeof(int), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync D2H");

@@ -1,6 +1,7 @@
 // model_loader.cpp -- see model_loader.h.
 #include "model_loader.h"
 #include "lstm_dev.h"
+#include "wavenet_plan.h"
 
 #include <cstdlib>
 #include <algorithm>
@@ -234,6 +235,7 @@ namespace na
 			// the reference throws "Wrong number of weights" inside CreateFromJson (WaveNet.h:704-709); so does this loader, together with
 			// the limits of the gfx950 kernels, instead of deferring them to the first device use on the audio thread
 			ValidateWaveNetDesc(desc->wavenet);
+			CheckWaveNetRunnable(desc->wavenet);
 			return desc;
 		}
 

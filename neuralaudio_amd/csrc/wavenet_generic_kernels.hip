@@ -18,6 +18,11 @@
 //   a layer = publish X to its ring, load the ring history its taps need -> per tap: stage the tap's matrix, read the tap's input where
 //   the mat-mul wants it (X for in-block frames, the prefetched ring history for earlier ones), MFMA into register accumulators -> bias + mix-in + activation + head accumulate in the result lanes (the
 //   activation's split quad IS the 1x1's B operand: no LDS round trip) -> stage the 1x1 -> MFMA -> residual into X.
+//
+// Range contract, the one of the shaped f16-split kernels: the input is clamped to the plan's condLimit (NaN reads as
+// silence); a model with the static range proof then keeps every operand inside the f16 range, a model without one (LeakyReLU chains)
+// splits its operands with saturation and counts the event in the state header.  The weights fit the operand format or the model was
+// refused at load (CheckWaveNetRunnable): these widths have no f32 kernel.
 #include "device_once.h"
 #include <algorithm>
 #include <cstdlib>
@@ -65,6 +70,9 @@ namespace na
 			const int* ringG;
 			int nrings, stateF4, maxC;
 			float headScale;
+			float condLimit; // input samples are clamped to +-condLimit (WaveNetPlan::condLimit), NaN reads as silence
+			int saturate;    // no static range proof: operands saturate (SplitOperand)
+			int countEvents; // ... and the state header has a free word for the range-event count (fewer than WN_MAX_RINGS rings)
 			float* state;
 			const int* slots; // nullptr: contiguous (slot0 + i, row0 + i)
 			const int* rows;
@@ -168,6 +176,38 @@ namespace na
 			}
 		}
 
+		// The B operand of a mat-mul from f32 values of the chain (residual stream, head accumulator, activations).  The state of these
+		// kernels is f32; what can leave the f16 range is the operand.  `sat` (workgroup-uniform): the model has no static range proof
+		// (WaveNetPlan::splitRangeProven) -- the split saturates at +-65504 and the lane remembers that it did; with the proof and the
+		// input clamp nothing gets there, and the split is the plain one.  Inside the range both are the same bits.
+		__device__ __forceinline__ u32x4 SplitOperand(f32x4 v, bool sat, int& hit)
+		{
+			if (sat) return sp::SplitQuadSatLoose(v, hit);
+			return sp::SplitQuad(v);
+		}
+
+		__device__ __forceinline__ float AbsMax4(f32x4 v)
+		{
+			return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)), __builtin_fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w)));
+		}
+		// Block exponent of a frame's head accumulator, for models without a range proof.  The head accumulator is the sum of every
+		// layer's activations -- the first value of a LeakyReLU chain to leave the f16 range (24 / 12 channels, 40 samples at 31 114: 91 492,
+		// with the residual stream at 56 534) -- and its one consumer, the head mat-mul, sums over the channels of ONE frame: a frame whose
+		// peak (`top`: the lane's own quads; the frame's four lanes j, j + 16, j + 32, j + 48 agree on the largest) lies beyond 65504 is
+		// split as v 2^-k with the peak below 32768 and the mat-mul's result multiplied by 2^k, both exact.  The lane notes the range
+		// event.  k = 0 -- every frame of a signal inside the range -- leaves the bits as they were.  (inf / NaN: 0, the saturating
+		// split deals with those.)
+		__device__ __forceinline__ int HeadExponent(float top, int& hit)
+		{
+			top = __builtin_fmaxf(top, __shfl_xor(top, 16));
+			top = __builtin_fmaxf(top, __shfl_xor(top, 32));
+			if (!(top > 65504.0f) || !(top <= 3.0e38f)) return 0;
+			hit |= 1;
+			int e;
+			(void)frexpf(top, &e); // top < 2^e
+			return e - 15;
+		}
+
 		__device__ __forceinline__ f32x4 Load4(const float* __restrict__ w, int off, int c0, int count)
 		{
 			f32x4 v;
@@ -205,7 +245,7 @@ namespace na
 			float* st = a.state + (size_t)slot * (size_t)a.stateF4 * 4;
 			f32x4* stq = reinterpret_cast<f32x4*>(st);
 			int* header = reinterpret_cast<int*>(st);
-			if (cq == 0) condL[f] = (f < n) ? in[(size_t)row * inStride + f] : 0.0f; // WaveNet.h:770 (input -> condition)
+			if (cq == 0) condL[f] = (f < n) ? sp::ClampCond(in[(size_t)row * inStride + f], a.condLimit) : 0.0f; // WaveNet.h:770 (input -> condition)
 			for (int g = cq; g < GQ; g += 4)
 			{
 				X[g * FRAMES + f] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
@@ -213,6 +253,8 @@ namespace na
 			}
 			__syncthreads();
 			const float cond = condL[tf];
+			const bool sat = a.saturate != 0; // range contract: SplitOperand
+			int hit = 0;
 
 			const float* __restrict__ w = a.w;
 			StagedRegs<NB> pre;   // weights of the next mat-mul, under way while the current one runs
@@ -256,7 +298,7 @@ namespace na
 							u32x4 b[NB];
 #pragma unroll
 							for (int kb = 0; kb < NB; kb++)
-								b[kb] = (kb < nbk && 4 * kb + q < Gin) ? sp::SplitQuad(X[(4 * kb + q) * FRAMES + tf]) : u32x4{ 0, 0, 0, 0 };
+								b[kb] = (kb < nbk && 4 * kb + q < Gin) ? SplitOperand(X[(4 * kb + q) * FRAMES + tf], sat, hit) : u32x4{ 0, 0, 0, 0 };
 							__syncthreads(); // operands staged; every wave has read its own frames of the old X
 							sp::f32x4 acc[NB];
 #pragma unroll
@@ -320,7 +362,7 @@ namespace na
 						for (int kb = 0; kb < NB; kb++)
 						{
 							const int g = 4 * kb + q;
-							b[kb] = (kb < nb && g < Gl) ? sp::SplitQuad(src >= 0 ? X[g * FRAMES + src] : h[kb]) : u32x4{ 0, 0, 0, 0 };
+							b[kb] = (kb < nb && g < Gl) ? SplitOperand(src >= 0 ? X[g * FRAMES + src] : h[kb], sat, hit) : u32x4{ 0, 0, 0, 0 };
 						}
 						MatMul<NB>(ops, nb, nb, lane, b, acc);
 					};
@@ -355,7 +397,7 @@ namespace na
 							zv.z = (4 * g + 2 < cin) ? Activate(acc[rb].z + bc.z + wm.z * cond, L.act) : 0.0f;
 							zv.w = (4 * g + 3 < cin) ? Activate(acc[rb].w + bc.w + wm.w * cond, L.act) : 0.0f;
 							HEAD[g * FRAMES + tf] += zv;
-							zs[rb] = sp::SplitQuad(sp::f32x4{ zv.x, zv.y, zv.z, zv.w });
+							zs[rb] = SplitOperand(sp::f32x4{ zv.x, zv.y, zv.z, zv.w }, sat, hit);
 						}
 					}
 					// 1x1 + bias + residual (:486-491); the last layer's output feeds the next array's rechannel (or nothing)
@@ -444,15 +486,27 @@ namespace na
 					{
 						u32x4* ops = ops0 + (par++ & 1) * OPS_ONE;
 						StageMatrix<NB>(ops, w, L.wconv, L.cout, L.cin, nbo, nbk);
+						f32x4 hv[NB];
+						float top = 0.0f;
+#pragma unroll
+						for (int kb = 0; kb < NB; kb++)
+						{
+							hv[kb] = (kb < nbk && 4 * kb + q < Gin) ? HEAD[(4 * kb + q) * FRAMES + tf] : f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+							top = __builtin_fmaxf(top, AbsMax4(hv[kb]));
+						}
+						const int hexp = sat ? HeadExponent(top, hit) : 0;
+						const float hscale = ldexpf(1.0f, -hexp), hback = ldexpf(1.0f, hexp);
 						u32x4 b[NB];
 #pragma unroll
 						for (int kb = 0; kb < NB; kb++)
-							b[kb] = (kb < nbk && 4 * kb + q < Gin) ? sp::SplitQuad(HEAD[(4 * kb + q) * FRAMES + tf]) : u32x4{ 0, 0, 0, 0 };
+							b[kb] = (kb < nbk && 4 * kb + q < Gin) ? SplitOperand(hv[kb] * hscale, sat, hit) : u32x4{ 0, 0, 0, 0 };
 						__syncthreads();
 						sp::f32x4 acc[NB];
 #pragma unroll
 						for (int rb = 0; rb < NB; rb++) acc[rb] = sp::f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
 						MatMul<NB>(ops, nbo, nbk, lane, b, acc);
+#pragma unroll
+						for (int rb = 0; rb < NB; rb++) acc[rb] *= hback;
 						if (last)
 						{
 							if (q == 0 && tf < n) out[(size_t)row * outStride + tf] = a.headScale * (acc[0].x + ((L.bconv >= 0) ? w[L.bconv] : 0.0f)); // :793-798
@@ -490,6 +544,7 @@ namespace na
 				if (p >= R) p -= R;
 				header[tid] = p;
 			}
+			if (a.countEvents) sp::CountRangeEvent(header, hit, lane, true);
 		}
 
 		// ------------------------------------------------------------------------------------------------------------------------------
@@ -522,11 +577,13 @@ namespace na
 			float* st = a.state + (size_t)slot * (size_t)a.stateF4 * 4;
 			f32x4* stq = reinterpret_cast<f32x4*>(st);
 			int* header = reinterpret_cast<int*>(st);
-			if (cq == 0) condL[f] = (f < n) ? in[(size_t)row * inStride + f] : 0.0f;
+			if (cq == 0) condL[f] = (f < n) ? sp::ClampCond(in[(size_t)row * inStride + f], a.condLimit) : 0.0f;
 			for (int g = cq; g < GQ; g += 4) X[g * FRAMES + f] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
 			__syncthreads();
 			const float cond = condL[tf];
 			const float* __restrict__ w = a.w;
+			const bool sat = a.saturate != 0;
+			int hit = 0; // a split of this lane saturated (as in the kernel above)
 			f32x4 head[HB][NB]; // the lane's head accumulator: group 16 h + 4 rb + q of frame tf (:772 headArray.SetZero())
 #pragma unroll
 			for (int h = 0; h < HB; h++)
@@ -579,7 +636,7 @@ namespace na
 								for (int kb = 0; kb < NB; kb++)
 								{
 									const int g = 16 * ih + 4 * kb + q;
-									bq[ih][kb] = (g < Gin) ? sp::SplitQuad(X[g * FRAMES + tf]) : u32x4{ 0, 0, 0, 0 };
+									bq[ih][kb] = (g < Gin) ? SplitOperand(X[g * FRAMES + tf], sat, hit) : u32x4{ 0, 0, 0, 0 };
 								}
 #pragma unroll
 							for (int oh = 0; oh < HB; oh++)
@@ -635,7 +692,7 @@ namespace na
 								for (int kb = 0; kb < NB; kb++)
 								{
 									const int g = 16 * ih + 4 * kb + q;
-									b[kb] = (g < Gl) ? sp::SplitQuad(src >= 0 ? X[g * FRAMES + src] : stq[RingQuad(roff, G, p, g)]) : u32x4{ 0, 0, 0, 0 };
+									b[kb] = (g < Gl) ? SplitOperand(src >= 0 ? X[g * FRAMES + src] : stq[RingQuad(roff, G, p, g)], sat, hit) : u32x4{ 0, 0, 0, 0 };
 								}
 								subMatMul(L.wconv + k * cin * cin, cin, cin, oh, ih, b, acc);
 							}
@@ -654,7 +711,7 @@ namespace na
 								zv.z = (4 * g + 2 < cin) ? Activate(acc[rb].z + bc.z + wm.z * cond, L.act) : 0.0f;
 								zv.w = (4 * g + 3 < cin) ? Activate(acc[rb].w + bc.w + wm.w * cond, L.act) : 0.0f;
 								head[oh][rb] += zv;
-								zq[oh][rb] = sp::SplitQuad(sp::f32x4{ zv.x, zv.y, zv.z, zv.w });
+								zq[oh][rb] = SplitOperand(sp::f32x4{ zv.x, zv.y, zv.z, zv.w }, sat, hit);
 							}
 						}
 					}
@@ -686,12 +743,20 @@ namespace na
 					// head rechannel (:658-660), dense (K = 1): the next array's head accumulator (:785-789) or, for the last array, the output
 					const bool last = (li == a.numLayers - 1);
 					const int Gin = (L.cin + 3) / 4, Gout = (L.cout + 3) / 4, nhi = (L.cin + 63) / 64, nho = (L.cout + 63) / 64;
+					float top = 0.0f;
+#pragma unroll
+					for (int ih = 0; ih < HB; ih++)
+#pragma unroll
+						for (int kb = 0; kb < NB; kb++)
+							if (16 * ih + 4 * kb + q < Gin) top = __builtin_fmaxf(top, AbsMax4(head[ih][kb]));
+					const int hexp = sat ? HeadExponent(top, hit) : 0;
+					const float hscale = ldexpf(1.0f, -hexp), hback = ldexpf(1.0f, hexp);
 					u32x4 bq[HB][NB];
 #pragma unroll
 					for (int ih = 0; ih < HB; ih++)
 #pragma unroll
 						for (int kb = 0; kb < NB; kb++)
-							bq[ih][kb] = (16 * ih + 4 * kb + q < Gin) ? sp::SplitQuad(sp::f32x4{ head[ih][kb].x, head[ih][kb].y, head[ih][kb].z, head[ih][kb].w }) : u32x4{ 0, 0, 0, 0 };
+							bq[ih][kb] = (16 * ih + 4 * kb + q < Gin) ? SplitOperand(head[ih][kb] * hscale, sat, hit) : u32x4{ 0, 0, 0, 0 };
 #pragma unroll
 					for (int oh = 0; oh < HB; oh++)
 					{
@@ -703,6 +768,8 @@ namespace na
 #pragma unroll
 							for (int ih = 0; ih < HB; ih++)
 								if (ih < nhi) subMatMul(L.wconv, L.cout, L.cin, oh, ih, bq[ih], acc);
+#pragma unroll
+							for (int rb = 0; rb < NB; rb++) acc[rb] *= hback;
 						}
 						if (last)
 						{
@@ -737,12 +804,13 @@ namespace na
 				if (p >= R) p -= R;
 				header[tid] = p;
 			}
+			if (a.countEvents) sp::CountRangeEvent(header, hit, lane, true);
 		}
 	}
 
 	hipError_t LaunchWaveNetGeneric(const WnPrewarmLayer* layers, int numLayers, const float* weights, const int* ringOffF4, const int* ringFrames,
-		const int* ringG, int nrings, int stateF4, int maxChannels, float headScale, float* state, const int* slots, const int* rows, int numStreams,
-		int slot0, int row0, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
+		const int* ringG, int nrings, int stateF4, int maxChannels, float headScale, float condLimit, bool saturate, float* state, const int* slots, const int* rows,
+		int numStreams, int slot0, int row0, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
 	{
 		if (numStreams <= 0 || n <= 0) return hipSuccess;
 		if (n > WN_MAX_FRAMES || maxChannels > WN_GENERIC_MAX_CHANNELS) return hipErrorInvalidValue;
@@ -757,6 +825,9 @@ namespace na
 		a.stateF4 = stateF4;
 		a.maxC = maxChannels;
 		a.headScale = headScale;
+		a.condLimit = condLimit;
+		a.saturate = saturate ? 1 : 0;
+		a.countEvents = (saturate && nrings <= WN_RANGE_EVENT_SLOT) ? 1 : 0;
 		a.state = state;
 		a.slots = slots;
 		a.rows = rows;

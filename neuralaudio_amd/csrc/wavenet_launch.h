@@ -185,9 +185,12 @@ namespace na
 
 	// The runtime-shaped block kernel (wavenet_generic_kernels.hip): up to 64 channels per layer array, dense heads; walks the
 	// natural-layout tensor table (WaveNetPlan::prewarm) over the flat reference-order weights; frame-kernel stream-state format.
+	// Its operands are f16 (hi, lo) pairs: input samples are clamped to +-condLimit; `saturate` (a model without a static range proof):
+	// every operand split saturates, and a saturated split is counted in header[WN_RANGE_EVENT_SLOT] of the stream (models with
+	// WN_MAX_RINGS rings have no free header word: not counted).
 	hipError_t LaunchWaveNetGeneric(const WnPrewarmLayer* layers, int numLayers, const float* weights, const int* ringOffF4, const int* ringFrames,
-		const int* ringG, int nrings, int stateF4, int maxChannels, float headScale, float* state, const int* slots, const int* rows, int numStreams,
-		int slot0, int row0, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
+		const int* ringG, int nrings, int stateF4, int maxChannels, float headScale, float condLimit, bool saturate, float* state, const int* slots, const int* rows,
+		int numStreams, int slot0, int row0, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
 
 	// slots == nullptr: the active streams are contiguous -- stream i uses state slot slot0 + i and matrix row row0 + i (saves the
 	// kernel a dependent global load before it can touch the stream's state)

@@ -285,7 +285,11 @@ namespace na
 			// (|f(v)| <= |v|) multiply: for them G grows with the worst-case row sums of every layer.
 			double rangeGain = 1.0, rangeAdd = 0.0;       // |x| <= rangeGain * L + rangeAdd
 			double rangeHeadGain = 0.0, rangeHeadAdd = 0.0; // |head accumulator| likewise
-			double linearGain = 1.0, linearGainMax = 0.0;   // the rechannel path alone (input -> array inputs)
+			// the rechannel path alone (input -> array inputs) is linear in the condition and composed exactly: channel o of the current
+			// array carries linearPath[o] * cond from it (the product of the arrays' row sums overstates a 128-channel rechannel six
+			// times); whatever the layers add on top is bounded through row sums (rangeNonlinear * L + rangeAdd)
+			std::vector<double> linearPath;
+			double rangeNonlinear = 0.0, linearGainMax = 0.0;
 			std::vector<std::pair<double, double>> rangeCons;
 			double weightAbsMax = 0.0;      // largest |w| of the model
 			double matrixPeakMin = 1e300;   // smallest max|w| over its (non-zero) weight matrices
@@ -296,6 +300,126 @@ namespace na
 				for (size_t i = 0; i < count; i++) peak = std::max(peak, std::fabs((double)W(off + (int)i)));
 				weightAbsMax = std::max(weightAbsMax, peak);
 				if (matrix && peak > 0.0) matrixPeakMin = std::min(matrixPeakMin, peak);
+			}
+
+			// The bookkeeping itself, one call per tensor group in weight-walk order: shared by the stage program of the shaped kernels
+			// (BuildSplit) and the tensor table of the runtime-shaped ones (BuildGenericOnly), whose operands are the same (hi, lo) pairs.
+			// |residual stream| <= gain * |cond| + add through this array's rechannel
+			void RangeRechannel(int a, const WnArrayCfg& cfg, int rechOff)
+			{
+				const int C = cfg.channels;
+				if (a == 0) linearPath.assign((size_t)cfg.inputSize, 1.0); // (input_size == 1: the condition itself)
+				std::vector<double> next((size_t)C, 0.0);
+				double rowMax = 0.0, linearPeak = 0.0;
+				for (int o = 0; o < C; o++)
+				{
+					double row = 0.0;
+					for (int c = 0; c < cfg.inputSize; c++)
+					{
+						const double wv = (double)W(rechOff + o * cfg.inputSize + c);
+						row += std::fabs(wv);
+						next[(size_t)o] += wv * linearPath[(size_t)c];
+					}
+					rowMax = std::max(rowMax, row);
+					linearPeak = std::max(linearPeak, std::fabs(next[(size_t)o]));
+				}
+				linearPath.swap(next);
+				rangeNonlinear = (a == 0 ? 0.0 : rangeNonlinear) * rowMax;
+				rangeGain = linearPeak + rangeNonlinear;
+				rangeAdd = (a == 0 ? 0.0 : rangeAdd) * rowMax;
+				RangeNote(rangeGain, rangeAdd);
+				linearGainMax = std::max(linearGainMax, linearPeak);
+				NoteTensor(rechOff, (size_t)C * cfg.inputSize, true);
+			}
+
+			void RangeLayer(bool firstOfModel, const WnArrayCfg& cfg, int K, int wconv, int bconv, int wmix, int w1, int b1, bool needOutput)
+			{
+				const int C = cfg.channels;
+				NoteTensor(wconv, (size_t)C * C * K, true);
+				NoteTensor(bconv, (size_t)C, false);
+				NoteTensor(wmix, (size_t)C * cfg.conditionSize, true);
+				NoteTensor(w1, (size_t)C * C, needOutput); // (the very last 1x1 is dead, WaveNet.h:643,785: trained files hold denormals there)
+				NoteTensor(b1, (size_t)C, false);
+				// |z| <= zG * L + zA: 1.0081 for the rational tanh (the StdMath one: 1); LeakyReLU passes the conv's worst case on
+				double zG = 0.0, zA = 1.0081;
+				if (cfg.activation == ACT_LEAKYRELU)
+				{
+					double convRow = 0.0, mixMax = 0.0, biasMax = 0.0;
+					for (int o = 0; o < C; o++)
+					{
+						double row = 0.0;
+						for (int c = 0; c < C * K; c++) row += std::fabs((double)W(wconv + o * C * K + c));
+						convRow = std::max(convRow, row);
+						double mix = 0.0;
+						for (int c = 0; c < cfg.conditionSize; c++) mix += std::fabs((double)W(wmix + o * cfg.conditionSize + c));
+						mixMax = std::max(mixMax, mix);
+						biasMax = std::max(biasMax, std::fabs((double)W(bconv + o)));
+					}
+					zG = convRow * rangeGain + mixMax;
+					zA = convRow * rangeAdd + biasMax;
+				}
+				RangeNote(zG, zA);
+				rangeHeadGain = (firstOfModel ? 0.0 : rangeHeadGain) + zG;
+				rangeHeadAdd = (firstOfModel ? 0.0 : rangeHeadAdd) + zA;
+				RangeNote(rangeHeadGain, rangeHeadAdd);
+				// the 1x1 adds at most max_o (sum_c |w1[o][c]| * |z| + |b1[o]|) to the residual stream
+				double rowMax = 0.0, b1Max = 0.0;
+				for (int o = 0; o < C; o++)
+				{
+					double row = 0.0;
+					for (int c = 0; c < C; c++) row += std::fabs((double)W(w1 + o * C + c));
+					rowMax = std::max(rowMax, row);
+					b1Max = std::max(b1Max, std::fabs((double)W(b1 + o)));
+				}
+				rangeNonlinear += rowMax * zG;
+				rangeGain += rowMax * zG;
+				rangeAdd += rowMax * zA + b1Max;
+				RangeNote(rangeGain, rangeAdd);
+			}
+
+			void RangeHead(const WnArrayCfg& cfg, int wh, int bh, bool lastArray)
+			{
+				const int C = cfg.channels;
+				NoteTensor(wh, (size_t)cfg.headSize * C * cfg.headKernelSize, true);
+				if (bh >= 0) NoteTensor(bh, (size_t)cfg.headSize, false);
+				if (lastArray) return;
+				// the head rechannel's output is the next array's head accumulator (WaveNet.h:785-789)
+				double rowMax = 0.0, bMax = 0.0;
+				for (int o = 0; o < cfg.headSize; o++)
+				{
+					double row = 0.0;
+					for (int c = 0; c < C * cfg.headKernelSize; c++) row += std::fabs((double)W(wh + o * C * cfg.headKernelSize + c));
+					rowMax = std::max(rowMax, row);
+					if (bh >= 0) bMax = std::max(bMax, std::fabs((double)W(bh + o)));
+				}
+				rangeHeadGain *= rowMax;
+				rangeHeadAdd = rangeHeadAdd * rowMax + bMax;
+				RangeNote(rangeHeadGain, rangeHeadAdd);
+			}
+
+			// Range contract of the f16-split kernels: the hi half of every value is an f16 (|v| <= 65504).  With the input clamped to
+			// +-condLimit every split value stays below half of that: G * limit + A <= 32752 for every (G, A) collected above.  A model
+			// of up to 16 channels for which that leaves less than kSplitMinInputLimit -- or whose weights do not fit the operand format --
+			// is not run by the f16-split kernels at all (splitRangeProven / splitWeightsOk -> the f32 frame kernel, gpu_batch.cpp
+			// FamilyFor); a wider one has no f32 kernel and is refused at load (CheckWaveNetRunnable).
+			void FinishRange()
+			{
+				double limit = 32752.0;
+				for (const auto& c : rangeCons)
+				{
+					const double room = 32752.0 - c.second;
+					limit = std::min(limit, room <= 0.0 ? 0.0 : (c.first > 0.0 ? room / c.first : 32752.0));
+				}
+				plan.splitRangeProven = limit >= kSplitMinInputLimit;
+				// no proof (in practice: LeakyReLU models, whose worst case grows with the product of every layer's row sums): the limit
+				// then covers the rechannel path only, and the kernels that still run such a model -- the official A2 chains and the
+				// runtime-shaped kernels -- saturate at the f16 range and count the event instead of overflowing
+				// (wavenet_split_dev.h SplitQuadSat)
+				plan.condLimit = (float)(plan.splitRangeProven ? limit : std::min(32752.0, 32752.0 / std::max(1e-6, linearGainMax)));
+				// weights: |w| <= half the f16 range (hi + lo never overflow); every live weight MATRIX has its largest entry above
+				// 2^-12 -- a split value carries an absolute error of 2^-25 (f16 subnormals), so the entries that matter keep >= 13
+				// bits and nothing that matters is flushed to zero (|w| < 2^-25 is)
+				plan.splitWeightsOk = weightAbsMax <= 32752.0 && (matrixPeakMin >= 1.0 / 4096.0 || matrixPeakMin == 1e300);
 			}
 
 			int NewSplitOps(int count)
@@ -420,22 +544,7 @@ namespace na
 					const int cpad = pack > 1 ? C / pack : (1 << 20); // channels per packed stream (a multiple of 4; 2 in a dense pack)
 					const int groupsPerStream = pack > 1 ? cpad / 4 : 4; // (0: two streams per channel group)
 					const int rechOff = Take((size_t)C * cfg.inputSize);
-					{
-						// range bookkeeping for condLimit: |residual stream| <= gain * |cond| + add through this array's rechannel
-						double rowMax = 0.0;
-						for (int o = 0; o < C; o++)
-						{
-							double row = 0.0;
-							for (int c = 0; c < cfg.inputSize; c++) row += std::fabs((double)W(rechOff + o * cfg.inputSize + c));
-							rowMax = std::max(rowMax, row);
-						}
-						rangeGain = (a == 0 ? 1.0 : rangeGain) * rowMax;
-						rangeAdd = (a == 0 ? 0.0 : rangeAdd) * rowMax;
-						RangeNote(rangeGain, rangeAdd);
-						linearGain = (a == 0 ? 1.0 : linearGain) * rowMax;
-						linearGainMax = std::max(linearGainMax, linearGain);
-						NoteTensor(rechOff, (size_t)C * cfg.inputSize, true);
-					}
+					RangeRechannel(a, cfg, rechOff);
 					if (a == 0)
 					{
 						// x = w_re * cond (WaveNet.h:637, input_size == 1): the aux operand with weights (w_re, 0)
@@ -489,47 +598,7 @@ namespace na
 						const int b1 = Take((size_t)C);
 						const bool lastLayer = (l == numLayers - 1);
 						const bool needOutput = !(lastLayer && lastArray);
-						{
-							NoteTensor(wconv, (size_t)C * C * K, true);
-							NoteTensor(bconv, (size_t)C, false);
-							NoteTensor(wmix, (size_t)C * cfg.conditionSize, true);
-							NoteTensor(w1, (size_t)C * C, needOutput); // (the very last 1x1 is dead, WaveNet.h:643,785: trained files hold denormals there)
-							NoteTensor(b1, (size_t)C, false);
-							// |z| <= zG * L + zA: 1.0081 for the rational tanh (the StdMath one: 1); LeakyReLU passes the conv's worst case on
-							double zG = 0.0, zA = 1.0081;
-							if (cfg.activation == ACT_LEAKYRELU)
-							{
-								double convRow = 0.0, mixMax = 0.0, biasMax = 0.0;
-								for (int o = 0; o < C; o++)
-								{
-									double row = 0.0;
-									for (int c = 0; c < C * K; c++) row += std::fabs((double)W(wconv + o * C * K + c));
-									convRow = std::max(convRow, row);
-									double mix = 0.0;
-									for (int c = 0; c < cfg.conditionSize; c++) mix += std::fabs((double)W(wmix + o * cfg.conditionSize + c));
-									mixMax = std::max(mixMax, mix);
-									biasMax = std::max(biasMax, std::fabs((double)W(bconv + o)));
-								}
-								zG = convRow * rangeGain + mixMax;
-								zA = convRow * rangeAdd + biasMax;
-							}
-							RangeNote(zG, zA);
-							rangeHeadGain = (l == 0 && a == 0 ? 0.0 : rangeHeadGain) + zG;
-							rangeHeadAdd = (l == 0 && a == 0 ? 0.0 : rangeHeadAdd) + zA;
-							RangeNote(rangeHeadGain, rangeHeadAdd);
-							// the 1x1 adds at most max_o (sum_c |w1[o][c]| * |z| + |b1[o]|) to the residual stream
-							double rowMax = 0.0, b1Max = 0.0;
-							for (int o = 0; o < C; o++)
-							{
-								double row = 0.0;
-								for (int c = 0; c < C; c++) row += std::fabs((double)W(w1 + o * C + c));
-								rowMax = std::max(rowMax, row);
-								b1Max = std::max(b1Max, std::fabs((double)W(b1 + o)));
-							}
-							rangeGain += rowMax * zG;
-							rangeAdd += rowMax * zA + b1Max;
-							RangeNote(rangeGain, rangeAdd);
-						}
+						RangeLayer(a == 0 && l == 0, cfg, K, wconv, bconv, wmix, w1, b1, needOutput);
 
 						WnSplitStage st = EmptySplit(WN_ST_LAYER);
 						st.G = G; st.Gp = Gp; st.ksize = K; st.dilation = cfg.dilations[l];
@@ -568,23 +637,7 @@ namespace na
 
 					const int wh = Take((size_t)cfg.headSize * C * cfg.headKernelSize);
 					const int bh = cfg.hasHeadBias ? Take((size_t)cfg.headSize) : -1;
-					NoteTensor(wh, (size_t)cfg.headSize * C * cfg.headKernelSize, true);
-					if (bh >= 0) NoteTensor(bh, (size_t)cfg.headSize, false);
-					if (!lastArray)
-					{
-						// the head rechannel's output is the next array's head accumulator (WaveNet.h:785-789)
-						double rowMax = 0.0, bMax = 0.0;
-						for (int o = 0; o < cfg.headSize; o++)
-						{
-							double row = 0.0;
-							for (int c = 0; c < C * cfg.headKernelSize; c++) row += std::fabs((double)W(wh + o * C * cfg.headKernelSize + c));
-							rowMax = std::max(rowMax, row);
-							if (bh >= 0) bMax = std::max(bMax, std::fabs((double)W(bh + o)));
-						}
-						rangeHeadGain *= rowMax;
-						rangeHeadAdd = rangeHeadAdd * rowMax + bMax;
-						RangeNote(rangeHeadGain, rangeHeadAdd);
-					}
+					RangeHead(cfg, wh, bh, lastArray);
 					if (lastArray)
 					{
 						// only head channel 0 reaches the output (WaveNet.h:793-798): one output row per tile slot
@@ -616,27 +669,7 @@ namespace na
 					}
 				}
 				for (const WnSplitStage& st : plan.sstages) plan.maxSplitOps = std::max(plan.maxSplitOps, st.a_ops);
-				// Range contract of the f16-split kernels: the hi half of every value is an f16 (|v| <= 65504).  With the input clamped to
-				// +-condLimit every split value stays below half of that: G * limit + A <= 32752 for every (G, A) collected above.  A model
-				// for which that leaves less than kSplitMinInputLimit -- or whose weights do not fit the operand format -- is not run by
-				// the f16-split kernels at all (splitRangeProven / splitWeightsOk -> the f32 frame kernel, gpu_batch.cpp FamilyFor).
-				{
-					double limit = 32752.0;
-					for (const auto& c : rangeCons)
-					{
-						const double room = 32752.0 - c.second;
-						limit = std::min(limit, room <= 0.0 ? 0.0 : (c.first > 0.0 ? room / c.first : 32752.0));
-					}
-					plan.splitRangeProven = limit >= kSplitMinInputLimit;
-					// no proof (in practice: LeakyReLU models, whose worst case grows with the product of every layer's row sums): the limit
-					// then covers the rechannel path only, and the kernels that still run such a model -- the official A2 chains -- saturate
-					// at the f16 range and count the event instead of overflowing (wavenet_split_dev.h SplitQuadSat)
-					plan.condLimit = (float)(plan.splitRangeProven ? limit : std::min(32752.0, 32752.0 / std::max(1e-6, linearGainMax)));
-					// weights: |w| <= half the f16 range (hi + lo never overflow); every live weight MATRIX has its largest entry above
-					// 2^-12 -- a split value carries an absolute error of 2^-25 (f16 subnormals), so the entries that matter keep >= 13
-					// bits and nothing that matters is flushed to zero (|w| < 2^-25 is)
-					plan.splitWeightsOk = weightAbsMax <= 32752.0 && (matrixPeakMin >= 1.0 / 4096.0 || matrixPeakMin == 1e300);
-				}
+				FinishRange();
 				// fast instantiation of the kernel: K == 3 everywhere, every array fills its lane mode (G == Gp), 1x1 heads, weight blocks
 				// within the fixed 16 KB staging part
 				plan.splitFastT = 2;
@@ -649,6 +682,7 @@ namespace na
 
 			// Models wider than the shaped kernels take (> 16 channels): rings and the natural-layout tensor table only -- what the prewarm
 			// kernel and the runtime-shaped block kernel (wavenet_generic_kernels.hip) walk.  Same weight order as Build() (WaveNet.h:700-719).
+			// Those kernels split their operands like the shaped ones, so the range bookkeeping runs here too.
 			void BuildGenericOnly()
 			{
 				const int numArrays = (int)desc.arrays.size();
@@ -659,6 +693,7 @@ namespace na
 					const int C = cfg.channels;
 					const int numLayers = (int)cfg.kernelSizes.size();
 					const int rechOff = Take((size_t)C * cfg.inputSize);
+					RangeRechannel(a, cfg, rechOff);
 					for (int l = 0; l < numLayers; l++)
 					{
 						const int K = cfg.kernelSizes[l];
@@ -678,6 +713,7 @@ namespace na
 						pw.rech_in = cfg.inputSize;
 						pw.dilation = cfg.dilations[l];
 						plan.prewarm.push_back(pw);
+						RangeLayer(a == 0 && l == 0, cfg, K, pw.wconv, pw.bconv, pw.wmix, pw.w1, pw.b1, !(l == numLayers - 1 && a == numArrays - 1));
 					}
 					WnPrewarmLayer pw = {};
 					pw.kind = 1;
@@ -689,9 +725,11 @@ namespace na
 					pw.rechannel = -1;
 					pw.dilation = cfg.headDilation;
 					plan.prewarm.push_back(pw);
+					RangeHead(cfg, pw.wconv, pw.bconv, a == numArrays - 1);
 				}
 				plan.headScale = W(Take(1));
 				plan.stateF4 = CeilDiv(plan.stateF4, 16) * 16;
+				FinishRange();
 			}
 
 			void Build()
@@ -900,6 +938,28 @@ namespace na
 		b.foldOk = true;
 		b.Build();
 		return std::move(b.plan);
+	}
+
+	void CheckWaveNetRunnable(const WaveNetDesc& desc)
+	{
+		const WaveNetPlan plan = BuildWaveNetPlan(desc);
+		if (!plan.genericOnly) return;
+		const std::string who = "WaveNet with layer arrays wider than 16 channels (f16-split arithmetic only): ";
+		if (!plan.splitWeightsOk)
+			throw std::runtime_error(who + "the weights do not fit the (hi, lo) f16 operand format (a weight beyond 32752, or a weight matrix whose largest entry is below 2^-12)");
+		// No static proof: LeakyReLU chains (the worst case is the product of every layer's row sums) run all the same -- the kernels
+		// saturate and count the event -- as long as the rechannel path alone leaves an input limit.  A model with tanh layers that fails
+		// the proof fails it because those layers can ADD more than the f16 range holds, at any input level: saturating would be wrong
+		// silently.
+		bool allLeaky = true;
+		for (const WnArrayCfg& cfg : desc.arrays) allLeaky = allLeaky && cfg.activation == ACT_LEAKYRELU;
+		if ((!plan.splitRangeProven && !allLeaky) || plan.condLimit < kSplitMinInputLimit)
+		{
+			std::stringstream str;
+			str << who << "the static range bound leaves no input limit of at least " << kSplitMinInputLimit
+			    << " (the layers can drive the residual stream or the head accumulator beyond the f16 range)";
+			throw std::runtime_error(str.str());
+		}
 	}
 
 	// ---- stream packing ------------------------------------------------------------------------------------------------------

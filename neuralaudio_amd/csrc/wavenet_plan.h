@@ -44,7 +44,8 @@ namespace na
 		float headScale = 0.0f;
 		float condLimit = 32752.0f; // f16-split kernels: input samples are clamped to +-condLimit (range contract)
 		// static proof of that contract (wavenet_plan.cpp): with inputs inside +-condLimit >= kSplitMinInputLimit no value of the chain leaves
-		// the f16 range, and the weights fit the f16-split operand format.  A plan that fails either runs on the f32 frame kernel.
+		// the f16 range, and the weights fit the f16-split operand format.  A plan that fails either runs on the f32 frame kernel
+		// (genericOnly plans have none: CheckWaveNetRunnable).
 		bool compactRings = false;  // some ring is a compact one: launches take buffer lengths of WnCompactSafeFrames() only
 		bool splitRangeProven = true;
 		bool splitWeightsOk = true;
@@ -61,6 +62,10 @@ namespace na
 	// splitStateFormat: the stream state is laid out for the f16-split kernels (rings of layers with a dilation >= 128 are exactly
 	// (K - 1) d frames long, wavenet_plan.cpp AddRing); false: for the frame / runtime-shaped kernels (every ring roundup16 + 128)
 	WaveNetPlan BuildWaveNetPlan(const WaveNetDesc& desc, bool splitStateFormat = false);
+	// Layer arrays wider than 16 channels run on the runtime-shaped kernels only, whose operands are f16 (hi, lo) pairs and which have no
+	// f32 fallback: throws std::runtime_error at LOAD time for a model whose weights do not fit that format or whose range bound leaves
+	// an input limit below kSplitMinInputLimit.  Narrower models always have a kernel: nothing to check.
+	void CheckWaveNetRunnable(const WaveNetDesc& desc);
 	// Stream packing (wavenet_plan.cpp): how many streams of this model fit one virtual stream of the f16-split kernel (1: none),
 	// the virtual model, and its plan (WaveNetPlan::pack = P; arrays / rings / stages describe the VIRTUAL model).
 	int WaveNetPackFactor(const WaveNetDesc& desc);

@@ -35,8 +35,12 @@ def _shift(h, s):
     return out
 
 
-def wavenet_forward(arrays, weights, x, lead_in=None, tanh=fast_tanh):
-    """Returns y for signal x assuming the model was prewarmed (zero-input steady state) before x."""
+def wavenet_forward(arrays, weights, x, lead_in=None, tanh=fast_tanh, peaks=None):
+    """Returns y for signal x assuming the model was prewarmed (zero-input steady state) before x.
+
+    peaks: an optional dict that receives the largest magnitudes of what the f16-split kernels turn into (hi, lo) operands -- "h" the
+    residual stream (every layer input), "z" the activations, "head" the head accumulator (as the layers add to it and as a head
+    rechannel hands it to the next array) -- over the whole evaluation, lead-in included."""
     w = np.asarray(weights, dtype=np.float64)
     pos = 0
 
@@ -56,11 +60,17 @@ def wavenet_forward(arrays, weights, x, lead_in=None, tanh=fast_tanh):
     cond = sig[None, :]
     layer_in = cond
     head = None
-    for a in arrays:
+
+    def note(name, v):
+        if peaks is not None:
+            peaks[name] = max(peaks.get(name, 0.0), float(np.abs(v).max()))
+
+    for ai, a in enumerate(arrays):
         c = a["channels"]
         act = leaky_relu if a["activation"] == 1 else tanh
         w_re = take(c * a["input_size"]).reshape(c, a["input_size"])
         h = w_re @ layer_in
+        note("h", h)
         if head is None:
             head = np.zeros((c, T))
         for k, d in zip(a["kernel_sizes"], a["dilations"]):
@@ -75,6 +85,9 @@ def wavenet_forward(arrays, weights, x, lead_in=None, tanh=fast_tanh):
             z = act(z)
             head = head + z
             h = w1 @ z + b1[:, None] + h
+            note("z", z)
+            note("head", head)
+            note("h", h)
         kh = a["head_kernel_size"]
         wh = take(a["head_size"] * c * kh).reshape(a["head_size"], c, kh)
         out = np.zeros((a["head_size"], T))
@@ -83,6 +96,8 @@ def wavenet_forward(arrays, weights, x, lead_in=None, tanh=fast_tanh):
         if a["has_head_bias"]:
             out = out + take(a["head_size"])[:, None]
         head = out
+        if ai + 1 < len(arrays):
+            note("head", head)
         layer_in = h
     scale = take(1)[0]
     assert pos == w.size, "weights left over"

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import na_oracle as O
+import wide_cases as WC
 
 pytestmark = pytest.mark.gpu
 
@@ -55,7 +56,8 @@ def _kernel(na, name, quality, streams, rate=None):
     return k
 
 
-CASES = [("BossWN-standard.nam", 1.0), ("BossWN-lite.nam", 1.0), ("BossWN-feather.nam", 1.0), ("BossWN-nano.nam", 1.0),
+WIDE = {"wide-40/20": (40, 20), "wide-72/36": (72, 36)}  # synthetic models of the runtime-shaped kernels (> 16 channels)
+CASES = [("BossWN-standard.nam", 1.0), ("BossWN-lite.nam", 1.0), ("wide-40/20", 1.0), ("wide-72/36", 1.0), ("BossWN-feather.nam", 1.0), ("BossWN-nano.nam", 1.0),
          ("BossWN-a2.nam", 0.0), ("BossWN-a2.nam", 1.0), ("BossLSTM-1x16.nam", 1.0), ("BossLSTM-2x8.nam", 1.0),
          ("synthetic_gru_1x16.json", 1.0)]
 
@@ -64,14 +66,20 @@ CASES = [("BossWN-standard.nam", 1.0), ("BossWN-lite.nam", 1.0), ("BossWN-feathe
 def test_every_sample_model_matches_the_sequential_run(na, name, quality):
     """~90 segment boundaries (segmentSamples = 512 over 48 000 samples of clipped noise): bit-identical to the sequential run where both
     batches run the stream on the same kernel; within the WaveNet tolerance of the oracle in every case."""
-    if name == "BossWN-lite.nam":
-        # (no A1 Lite capture among the sample models: a synthetic A1 Lite stands in for it)
-        arrays = O.a1_arrays(12, 6)
-        text = O.nam_json_wavenet_a1(12, 6, O.synth_wavenet_weights(arrays, seed=41))
+    if name == "BossWN-lite.nam" or name in WIDE:
+        if name in WIDE:
+            arrays = WC.two_array(*WIDE[name])
+            w = O.synth_wavenet_weights(arrays, seed=WIDE[name][0])
+            text = O.nam_json_wavenet_generic(arrays, w)
+        else:
+            # (no A1 Lite capture among the sample models: a synthetic A1 Lite stands in for it)
+            arrays = O.a1_arrays(12, 6)
+            w = O.synth_wavenet_weights(arrays, seed=41)
+            text = O.nam_json_wavenet_a1(12, 6, w)
         loader = na.NeuralModelLoader()
         m = loader.CreateFromString(text, ".nam", doPrewarm=False)
         seq_m = loader.CreateFromString(text, ".nam", doPrewarm=True)
-        ora = O.OracleWaveNet(arrays, O.synth_wavenet_weights(arrays, seed=41))
+        ora = O.OracleWaveNet(arrays, w)
         x = O.signal_noise(48000, seed=5)
         y = na.render_offline(m, x, quality=quality, segment_samples=512)
         ys = np.concatenate([seq_m.Process(x[i:i + CHUNK]) for i in range(0, x.size, CHUNK)])

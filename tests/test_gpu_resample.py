@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 import na_oracle as O
+import wide_cases as WC
 
 pytestmark = pytest.mark.gpu
 
@@ -42,7 +43,11 @@ def _model(na, name, quality=1.0, external_rate=None, opt_in=False, prewarm=Fals
         loader.SetExternalSampleRate(external_rate)
     if opt_in:
         loader.SetResampleToExternalRate(True)
-    m = loader.CreateFromFile(os.path.join(O.MODELS_DIR, name), doPrewarm=prewarm)
+    if name == "wide-40/20":  # a synthetic model of the runtime-shaped kernels (layer arrays wider than 16 channels)
+        arrays = WC.two_array(40, 20)
+        m = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, O.synth_wavenet_weights(arrays, seed=40)), ".nam", doPrewarm=prewarm)
+    else:
+        m = loader.CreateFromFile(os.path.join(O.MODELS_DIR, name), doPrewarm=prewarm)
     assert m is not None
     _loaders.append(loader)
     return m
@@ -189,7 +194,7 @@ def test_each_stage_is_within_the_rounding_bound_of_its_dot_product_and_the_mode
 # ---------------------------------------------------------------------------------------------------- 6
 
 CHUNK_CASES = [("standard", [("BossWN-standard.nam", 1.0, 3)]), ("nano-packed", [("BossWN-nano.nam", 1.0, 8)]), ("a2-q0.3", [("BossWN-a2.nam", 0.3, 2)]),
-               ("a2-q1.0", [("BossWN-a2.nam", 1.0, 2)]), ("lstm-1x16", [("BossLSTM-1x16.nam", 1.0, 3)]),
+               ("a2-q1.0", [("BossWN-a2.nam", 1.0, 2)]), ("lstm-1x16", [("BossLSTM-1x16.nam", 1.0, 3)]), ("wide-40/20", [("wide-40/20", 1.0, 2)]),
                ("mixed", [("BossWN-standard.nam", 1.0, 2), ("BossWN-nano.nam", 1.0, 4), ("BossWN-a2.nam", 0.3, 1), ("BossWN-a2.nam", 1.0, 1),
                           ("BossLSTM-1x16.nam", 1.0, 2)])]
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import na_oracle as O
+import wide_cases as WC
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +42,9 @@ def _model(na, name, quality=1.0, on_demand=False):
     if name == "lite":  # (no A1 Lite capture among the sample models: a synthetic one, as tests/test_gpu_offline.py builds it)
         arrays = O.a1_arrays(12, 6)
         m = loader.CreateFromString(O.nam_json_wavenet_a1(12, 6, O.synth_wavenet_weights(arrays, seed=41)), ".nam", doPrewarm=False)
+    elif name in WIDE:  # layer arrays wider than 16 channels: the runtime-shaped kernels (WaveNetGenericKernel / WaveNetWideKernel)
+        arrays = WC.two_array(*WIDE[name])
+        m = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, O.synth_wavenet_weights(arrays, seed=WIDE[name][0])), ".nam", doPrewarm=False)
     else:
         m = loader.CreateFromFile(os.path.join(O.MODELS_DIR, name), doPrewarm=False)
     assert m is not None
@@ -72,7 +76,8 @@ def _control_bound(y):
 
 # ---------------------------------------------------------------------------------------------------------------- 1
 
-CASES = [("BossWN-standard.nam", 1.0), ("lite", 1.0), ("BossWN-feather.nam", 1.0), ("BossWN-nano.nam", 1.0), ("BossWN-a2.nam", 0.0),
+WIDE = {"wide-40/20": (40, 20), "wide-72/36": (72, 36)}
+CASES = [("BossWN-standard.nam", 1.0), ("lite", 1.0), ("wide-40/20", 1.0), ("wide-72/36", 1.0), ("BossWN-feather.nam", 1.0), ("BossWN-nano.nam", 1.0), ("BossWN-a2.nam", 0.0),
          ("BossWN-a2.nam", 1.0), ("BossLSTM-1x16.nam", 1.0), ("BossLSTM-2x8.nam", 1.0), ("synthetic_gru_1x16.json", 1.0), (CONV_TAIL_STACK, 1.0)]
 
 

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 
 import na_oracle as O
+import ref_np
+import wide_cases as WC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -827,3 +829,87 @@ def test_bench_cpu_baseline_legs_run(na):
                                                                               rng.uniform(-a, a, (2, 3 * H)).tolist()]},
                       {"type": "dense", "shape": [None, None, 1], "weights": [rng.uniform(-a, a, (H, 1)).tolist(), [0.0]]}]}
     assert bench.mixed_cpu_baseline([("lstm", lstm), ("gru", gru)], 0.3)["value"] > 0
+
+
+def test_every_wide_fuzz_seed_loads(na):
+    """tests/test_gpu_wide.py runs every seed of its architecture fuzz and every fixed case without a skip, so the generator must produce
+    loadable shapes only -- proven here without a GPU -- and must reach what it is for: every channel count of the edge list, both
+    orders of a wide array beside a narrower one, one to three arrays, both activations, conv heads, every kernel on both sides of 64."""
+    loader = na.NeuralModelLoader()
+    assert WC.NUM_FUZZ_SEEDS >= len(WC.EDGE_CHANNELS)
+    seen, orders, counts, acts, kernels, conv_heads, ks, ds = set(), set(), set(), set(), set(), 0, set(), set()
+    cases = [WC.fuzz_case(seed) for seed in range(WC.NUM_FUZZ_SEEDS)] + [(WC.fixed_case(c, act), None) for c, act in WC.FIXED_CASES]
+    for arrays, sizes in cases:
+        ch = [a["channels"] for a in arrays]
+        assert max(ch) > 16 and 1 <= len(arrays) <= 3, ch
+        for i, a in enumerate(arrays):
+            assert a["head_size"] == (arrays[i + 1]["channels"] if i + 1 < len(arrays) else 1)
+        w = O.synth_wavenet_weights(arrays, seed=1)
+        m = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, w), ".nam", doPrewarm=False)
+        assert m is not None, arrays
+        info = m.KernelInfo(1.0, 1)
+        assert info["kernel"] == "generic" and info["weights_ok"] and 8.0 <= info["input_limit"] <= 32752.0, (arrays, info)
+        assert m.GetReceptiveFieldSize() == sum((k - 1) * d for a in arrays for k, d in zip(a["kernel_sizes"], a["dilations"])) + \
+            (arrays[-1]["head_kernel_size"] - 1) * arrays[-1]["head_dilation"]
+        if sizes is None:
+            continue
+        assert sizes[:3] == [1, 1, 17] and sum(sizes) == WC.FUZZ_SAMPLES and WC.fuzz_work(arrays) <= WC.FUZZ_WORK_CAP
+        seen.update(ch)
+        counts.add(len(arrays))
+        acts.add(arrays[0]["activation"])
+        kernels.add(WC.max_channels(arrays) > 64)
+        conv_heads += arrays[-1]["head_kernel_size"] > 1
+        for a in arrays:
+            ks.update(a["kernel_sizes"])
+            ds.update(a["dilations"])
+        for a, b in zip(ch, ch[1:]):
+            if max(a, b) > 16 and a != b:
+                orders.add("wide->narrow" if a > b else "narrow->wide")
+    assert seen >= set(WC.EDGE_CHANNELS), sorted(set(WC.EDGE_CHANNELS) - seen)
+    assert orders == {"wide->narrow", "narrow->wide"} and counts == {1, 2, 3} and acts == {O.ACT_TANH, O.ACT_LEAKYRELU}
+    assert kernels == {False, True} and conv_heads >= 1 and ks == set(WC.KERNEL_SIZES) and ds == set(WC.DILATIONS)
+
+
+def test_wide_range_tests_stand_on_the_side_of_the_f16_boundary_they_claim(na):
+    """The range-contract tests of tests/test_gpu_wide.py call some inputs "inside" and some "outside" the f16 range of the split
+    operands.  A float64 evaluation (ref_np.wavenet_forward, peaks of the residual stream h, the activations z and the head accumulator)
+    says which is which: the hot inputs stay under 32 752 (half the range: what the static proof allows), the loud ones exceed 65 504
+    -- also after the kernel's own clamp at the model's input limit, which is what the chain then sees -- and the reference's output
+    is finite either way (its f32 chain holds 3e38)."""
+    loader = na.NeuralModelLoader()
+    noise = O.signal_noise(1024, 5)
+    for name in ("32/8 tanh", "128/64 tanh", "24/12 leaky", "128/128 leaky"):
+        arrays, w = WC.range_model(name)
+        limit = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, w), ".nam", doPrewarm=False).KernelInfo(1.0, 1)["input_limit"]
+        for amp in (30.0, 1000.0, 10000.0):
+            x = (amp * noise).astype(np.float32)
+            assert np.abs(x).max() < limit, (name, amp, limit)  # nothing is clamped
+            peaks = {}
+            y, _ = ref_np.wavenet_forward(arrays, w, x, peaks=peaks)
+            assert max(peaks.values()) < WC.SPLIT_SAFE and np.all(np.isfinite(y)), (name, amp, peaks)
+        loud = 1e5 if "tanh" in name else 6e4
+        for clamp in (np.inf, limit):
+            peaks = {}
+            y, _ = ref_np.wavenet_forward(arrays, w, (loud * noise).astype(np.float32).clip(-clamp, clamp), peaks=peaks)
+            assert np.all(np.isfinite(y)), name
+            if clamp == np.inf or "leaky" in name:  # (a proven tanh model is inside the range once its input is clamped: that is the proof)
+                assert max(peaks.values()) > WC.F16_MAX, (name, loud, clamp, peaks)
+            else:
+                assert max(peaks.values()) < WC.SPLIT_SAFE, (name, loud, clamp, peaks)
+
+
+@pytest.mark.parametrize("name", ["32/8 tanh", "80/72 tanh"])
+def test_wide_models_outside_the_operand_format_fail_at_load(na, name):
+    """Layer arrays wider than 16 channels have no f32 kernel: a model whose weights do not fit the (hi, lo) f16 operands, or whose tanh
+    layers can add more than the f16 range holds, is a load error that names the reason (narrow models with the same weights load and
+    run on the f32 frame kernel: test_models_without_a_range_proof_run_on_the_f32_kernel)."""
+    loader = na.NeuralModelLoader()
+    arrays, w = WC.range_model(name)
+    m = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, w), ".nam", doPrewarm=False)
+    info = m.KernelInfo(1.0, 1)
+    assert info["kernel"] == "generic" and info["range_proven"] and info["weights_ok"] and 8.0 <= info["input_limit"] <= 32752.0
+    expect = {"mix-in x 1e5": "weights do not fit", "1x1 x 4000": "no input limit of at least 8", "all x 1e-3": "weights do not fit"}
+    for case, factors in WC.WEIGHT_SCALINGS.items():
+        ws = O.scale_wavenet_tensors(arrays, w, factors)
+        with pytest.raises(na.NeuralAudioError, match=expect[case]):
+            loader.CreateFromString(O.nam_json_wavenet_generic(arrays, ws), ".nam", doPrewarm=False)
