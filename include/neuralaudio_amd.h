@@ -67,7 +67,35 @@ NA_EXTERN int NA_BatchAddStreams(NA_Batch* batch, NeuralModel* model, float qual
  * output zero -- except trailing retired rows, which leave the arrays (check NA_BatchNumStreams afterwards).  Waits for the batch's
  * stream; call it between buffers, not from the audio callback.  Fails (negative) on ids that are out of range or already removed. */
 NA_EXTERN int NA_BatchRemoveStreams(NA_Batch* batch, int first, int count);
-NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired ids included */
+/* ---- the stream pool: join and leave for a batch that never stops ----
+ * NA_BatchReserveStreams is the set-up side (NOT real-time safe, like NA_BatchAddStreams): it creates `count` PARKED streams of `model`
+ * and returns the first id (ids consecutive, retired ids recycled first, negative on failure).  Everything such a stream will ever need
+ * on the device is created here -- rows, state slots of every submodel, index-list capacity, resampling histories, the half-batch
+ * chains' streams, the staging of the re-arm -- and every parked stream is ARMED: its state is what NA_BatchAddStreams(count = 1,
+ * doPrewarm) leaves behind, for every submodel of a slimmable model whatever the loader's composite load mode.  Stream packing of narrow
+ * WaveNets is decided from `count` as NA_BatchAddStreams decides it, when this call creates the model group.
+ * A parked stream keeps its row of the [streams][n] arrays like a retired one -- input ignored, host output zero, device output row left
+ * alone; NA_BatchNumStreams does not change on activate / park -- and is not live: NA_BatchIsLive 0, not in NA_BatchNumLiveStreams;
+ * NA_BatchSetQuality, NA_BatchPrewarm(stream), NA_BatchSaveStreams / LoadStreams fail on it ("... is parked"), NA_BatchPrewarm(-1) skips
+ * it, NA_BatchRemoveStreams frees it like any stream (not real-time safe).
+ * NA_BatchActivateStream (parked -> live, `quality` picks the submodel; fails on an id that is not parked) and NA_BatchParkStream (live
+ * -> parked; fails on a stream that did not come from the pool) are REAL-TIME SAFE: host bookkeeping only.  The processing call that
+ * follows enqueues the device work on the batch stream in front of the model launches -- the index-list upload, one re-arm launch per
+ * model group, for a resampling batch the zeroing of the row's filter histories -- with no device or pinned allocation or free, no
+ * stream or event creation and no host-side wait.  Three exceptions, all shared with NA_BatchSetQuality: a batch running its half-batch
+ * chains or the resident launch drains them first (bounded by the wait limit); a batch of several launch units per buffer
+ * re-captures its hipGraph; and a batch that runs more than eight different models of one kernel family (their launch takes its
+ * group table from device memory) uploads that table again: a device free, an allocation and a blocking copy -- keep such a batch's
+ * joins and leaves on the set-up side.  From its first sample an activated stream computes what a stream freshly added with
+ * NA_BatchAddStreams(model, quality, 1, doPrewarm) computes, after every park -> activate cycle: a parked stream carries nothing over.
+ * Streams that did not join or leave never notice.  A broken batch refuses all three calls. */
+NA_EXTERN int NA_BatchReserveStreams(NA_Batch* batch, NeuralModel* model, int count, int doPrewarm);
+NA_EXTERN int NA_BatchActivateStream(NA_Batch* batch, int stream, float quality);
+NA_EXTERN int NA_BatchParkStream(NA_Batch* batch, int stream);
+NA_EXTERN int NA_BatchIsParked(NA_Batch* batch, int stream);
+NA_EXTERN int NA_BatchFindParked(NA_Batch* batch, NeuralModel* model); /* the lowest parked id of that model, -1: none */
+NA_EXTERN int NA_BatchNumParked(NA_Batch* batch);
+NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);
 NA_EXTERN int NA_BatchSetQuality(NA_Batch* batch, int stream, float quality);
@@ -397,6 +425,9 @@ NA_EXTERN void NA_DebugSetRcclApi(int mode, int failSendAt, int rendezvousMs);
 /* Tests: a kernel that keeps the batch's streams busy for `milliseconds` (at most 10 000) behind whatever they hold -- a device that
  * does not answer, as far as the waits of this batch can tell (tests/test_gpu_stall.py drives the wait limit with it). */
 NA_EXTERN int NA_DebugStallDevice(NA_Batch* batch, double milliseconds);
+/* Tests: hipMalloc / hipFree / hipHostMalloc / hipHostFree / hipStreamCreate* / hipEventCreate* calls the library has made in this process
+ * so far -- a real-time safe call leaves the count where it was (tests/test_gpu_pool.py) */
+NA_EXTERN long long NA_DebugDeviceResourceCalls(void);
 /* Tests: the model-rate input and output rows ([streams][*frames], rows *frames floats apart) of the LAST processing call of a resampling
  * batch -- of its last piece where a call longer than 2048 external samples ran in several -- copied to the host; either pointer may be
  * NULL.  Fails if *frames exceeds capacityPerRow.  Synchronises the batch. */

@@ -271,6 +271,31 @@ class Batch:
         if self._lib.NA_BatchRemoveStreams(self._h, int(first), int(count)) != 0:
             raise NeuralAudioError(capi.last_error())
 
+    # -- the stream pool: ReserveStreams is set-up side; ActivateStream / ParkStream are real-time safe (include/neuralaudio_amd.h) ----
+    def ReserveStreams(self, model, count=1, doPrewarm=True):
+        """`count` parked, armed streams of `model`; returns the first id."""
+        first = self._lib.NA_BatchReserveStreams(self._h, model._h, int(count), 1 if doPrewarm else 0)
+        if first < 0:
+            raise NeuralAudioError(capi.last_error())
+        return first
+
+    def ActivateStream(self, stream, quality=1.0):
+        if self._lib.NA_BatchActivateStream(self._h, int(stream), float(quality)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def ParkStream(self, stream):
+        if self._lib.NA_BatchParkStream(self._h, int(stream)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def IsParked(self, stream):
+        return bool(self._lib.NA_BatchIsParked(self._h, int(stream)))
+
+    def FindParked(self, model):
+        return int(self._lib.NA_BatchFindParked(self._h, model._h))
+
+    def NumParked(self):
+        return int(self._lib.NA_BatchNumParked(self._h))
+
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:
             raise NeuralAudioError(capi.last_error())

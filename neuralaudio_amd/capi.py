@@ -37,6 +37,8 @@ NA_SYMBOLS = [
     "NA_ResamplePlan", "NA_ResamplePrototype", "NA_ResampleModelFrames", "NA_BatchSetResampling", "NA_BatchGetResampleInfo",
     "NA_SetResampleToExternalRate", "NA_GetProcessLatencySamples", "NA_GetModelProcessRate", "NA_DebugResampleTap",
     "NA_RenderOfflineAtRate", "NA_RenderPlanAtRate", "NA_DebugSetRenderTap", "NA_MultiSetResampling", "NA_MultiGetResampleInfo",
+    "NA_BatchReserveStreams", "NA_BatchActivateStream", "NA_BatchParkStream", "NA_BatchIsParked", "NA_BatchFindParked", "NA_BatchNumParked",
+    "NA_DebugDeviceResourceCalls",
 ]
 
 
@@ -140,6 +142,13 @@ def load_library():
         "NA_UnregisterHostBuffer": (C.c_int, [C.c_void_p]),
         "NA_BatchStreamInputLimit": (C.c_float, [vp, C.c_int]),
         "NA_BatchRemoveStreams": (C.c_int, [vp, C.c_int, C.c_int]),
+        "NA_BatchReserveStreams": (C.c_int, [vp, vp, C.c_int, C.c_int]),
+        "NA_BatchActivateStream": (C.c_int, [vp, C.c_int, C.c_float]),
+        "NA_BatchParkStream": (C.c_int, [vp, C.c_int]),
+        "NA_BatchIsParked": (C.c_int, [vp, C.c_int]),
+        "NA_BatchFindParked": (C.c_int, [vp, vp]),
+        "NA_BatchNumParked": (C.c_int, [vp]),
+        "NA_DebugDeviceResourceCalls": (C.c_longlong, []),
         "NA_MultiCreate": (vp, [C.POINTER(C.c_int), C.c_int]),
         "NA_MultiDestroy": (None, [vp]),
         "NA_MultiAddStreams": (C.c_int, [vp, vp, C.c_float, C.c_int, C.c_int]),

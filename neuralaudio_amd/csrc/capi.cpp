@@ -411,6 +411,50 @@ int NA_BatchAddStreams(NA_Batch* batch, NeuralModel* model, float quality, int c
 	return rc == 0 ? first : -1;
 }
 
+// ---- the stream pool (gpu_batch.h ReserveStreams / ActivateStream / ParkStream) ----
+int NA_BatchReserveStreams(NA_Batch* batch, NeuralModel* model, int count, int doPrewarm)
+{
+	int first = -1;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchReserveStreams: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		if (!model || count < 1) throw std::runtime_error("NA_BatchReserveStreams: bad argument");
+		NeuralAudio::GpuModel* gm = dynamic_cast<NeuralAudio::GpuModel*>(model->model);
+		if (!gm) throw std::runtime_error("NA_BatchReserveStreams: model was not created by this library");
+		first = batch->batch->ReserveStreams(gm->GetLoadedModel(), count, doPrewarm != 0);
+	});
+	return rc == 0 ? first : -1;
+}
+
+int NA_BatchActivateStream(NA_Batch* batch, int stream, float quality)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchActivateStream: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->ActivateStream(stream, quality);
+	});
+}
+
+int NA_BatchParkStream(NA_Batch* batch, int stream)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchParkStream: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->ParkStream(stream);
+	});
+}
+
+int NA_BatchIsParked(NA_Batch* batch, int stream) { return (batch && batch->batch->IsParked(stream)) ? 1 : 0; }
+
+int NA_BatchFindParked(NA_Batch* batch, NeuralModel* model)
+{
+	NeuralAudio::GpuModel* gm = (batch && model) ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+	return gm ? batch->batch->FindParked(gm->GetLoadedModel().get()) : -1;
+}
+
+int NA_BatchNumParked(NA_Batch* batch) { return batch ? batch->batch->NumParked() : -1; }
+
+#ifndef NA_RELEASE
+long long NA_DebugDeviceResourceCalls(void) { return na::DeviceResourceCalls(); }
+#endif
+
 int NA_BatchNumStreams(NA_Batch* batch) { return batch ? batch->batch->NumStreams() : -1; }
 
 int NA_BatchNumLiveStreams(NA_Batch* batch) { return batch ? batch->batch->NumLiveStreams() : -1; }
@@ -524,7 +568,8 @@ int NA_BatchPrewarm(NA_Batch* batch, int stream)
 	return Guard([&] {
 		if (stream >= 0) batch->batch->Prewarm(stream);
 		else
-			for (int s = 0; s < batch->batch->NumStreams(); s++) batch->batch->Prewarm(s);
+			for (int s = 0; s < batch->batch->NumStreams(); s++)
+				if (!batch->batch->IsParked(s)) batch->batch->Prewarm(s); // (a parked stream is armed already)
 	});
 }
 

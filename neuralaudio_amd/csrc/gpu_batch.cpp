@@ -2,6 +2,7 @@
 #include "gpu_batch.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <mutex>
 #include <cstdlib>
@@ -18,6 +19,10 @@ namespace na
 	{
 		if (e != hipSuccess) throw HipError(e, what);
 	}
+
+	static std::atomic<long long> gDeviceResourceCalls{ 0 };
+	void CountDeviceResourceCall() { gDeviceResourceCalls.fetch_add(1, std::memory_order_relaxed); }
+	long long DeviceResourceCalls() { return gDeviceResourceCalls.load(std::memory_order_relaxed); }
 
 	int VisibleDeviceCount()
 	{
@@ -105,7 +110,7 @@ namespace na
 		}
 		else
 		{
-			CheckHip(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
+			CheckHip(CountedHipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
 		}
 		numChains = std::min(std::max(Tuning::Get().hostChains, 2), kMaxChains);
 	}
@@ -144,15 +149,15 @@ namespace na
 		}
 		residentState.reset();
 		groups.clear();
-		if (hostStage) (void)hipHostFree(hostStage);
-		if (devStage) (void)hipFree(devStage);
-		if (snapHost) (void)hipHostFree(snapHost);
-		if (snapDev) (void)hipFree(snapDev);
+		if (hostStage) (void)CountedHipHostFree(hostStage);
+		if (devStage) (void)CountedHipFree(devStage);
+		if (snapHost) (void)CountedHipHostFree(snapHost);
+		if (snapDev) (void)CountedHipFree(snapDev);
 		for (PipeSlot& p : pipe)
 		{
-			if (p.hostIn) (void)hipHostFree(p.hostIn);
-			if (p.hostOut) (void)hipHostFree(p.hostOut);
-			if (p.dev) (void)hipFree(p.dev);
+			if (p.hostIn) (void)CountedHipHostFree(p.hostIn);
+			if (p.hostOut) (void)CountedHipHostFree(p.hostOut);
+			if (p.dev) (void)CountedHipFree(p.dev);
 			if (p.uploaded) (void)hipEventDestroy(p.uploaded);
 			if (p.computed) (void)hipEventDestroy(p.computed);
 			if (p.downloaded) (void)hipEventDestroy(p.downloaded);
@@ -213,10 +218,17 @@ namespace na
 
 	int GpuBatch::AddStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand)
 	{
+		return CreateStreams(model, quality, count, prewarm, onDemand, false);
+	}
+
+	// `pool`: the streams are created PARKED and armed (ReserveStreams) -- no member active, every submodel prewarmed or none
+	int GpuBatch::CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool)
+	{
 		CheckUsable();
 		if (!model || model->subModels.empty()) throw std::runtime_error("neuralaudio_amd: AddStream with an empty model");
 		if (count < 1) throw std::runtime_error("neuralaudio_amd: AddStreams with count < 1");
 		if (resample) CheckResampleModelRate(model->ProcessRate(), resample->plan.modelRate);
+		if (pool && (peerWeights || AwaitsWeights())) throw std::runtime_error("neuralaudio_amd: ReserveStreams: the batch takes its weights from a peer device (pools are not part of the multi-GPU host)");
 		CheckHip(hipSetDevice(device), "hipSetDevice");
 		DrainPipeline(); // (state arrays may be re-allocated below)
 		topologyVersion++;
@@ -252,7 +264,9 @@ namespace na
 				}
 				ref.members = partial;
 				partial.clear();
-				ref.members[(size_t)active].first->SetActive(ref.members[(size_t)active].second, row);
+				ref.pooled = ref.parked = pool;
+				ref.poolPrewarm = pool && prewarm;
+				if (!pool) ref.members[(size_t)active].first->SetActive(ref.members[(size_t)active].second, row);
 				streams[(size_t)row] = ref;
 				built = i + 1;
 			}
@@ -261,6 +275,12 @@ namespace na
 			for (size_t k = 0; k < numSub; k++)
 			{
 				std::sort(newMembers[k].begin(), newMembers[k].end());
+				if (pool)
+				{
+					subGroups[k]->ArmReserved(newMembers[k], prewarm);
+					for (int i = 0; i < count; i++) streams[(size_t)(first + i)].prewarmed[k] = prewarm ? 1 : 0;
+					continue;
+				}
 				subGroups[k]->Reset(newMembers[k]);
 				const bool now = prewarm && (!onDemand || (int)k == active);
 				const bool waits = now && std::find(awaitingWeights.begin(), awaitingWeights.end(), subGroups[k]) != awaitingWeights.end();
@@ -294,8 +314,97 @@ namespace na
 		// the half-batch chains' streams on this, the set-up side (creating a HIP stream takes ~13 ms: not inside the first buffer)
 		if (ownsStream && !streamObserved && streams.size() >= 512)
 			for (int h = 0; h < numChains; h++)
-				if (!halfStream[h]) CheckHip(hipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
+				if (!halfStream[h]) CheckHip(CountedHipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
+		if (pool)
+		{
+			numParked += count;
+			// what a later activation or park may be the first to need: the side streams and events of a batch of several launch units,
+			// and the pipelined interface's streams and events for either number of units (an activation may add a unit, a park take one away)
+			if (groups.size() > 1)
+			{
+				for (auto& g : groups)
+				{
+					(void)g->SideStream();
+					(void)g->DoneEvent();
+				}
+				if (!forkEvent) CheckHip(CountedHipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
+			}
+			EnsurePoolPipeline();
+			pendingHistoryZero.reserve(streams.size());
+		}
 		return first;
+	}
+
+	int GpuBatch::ReserveStreams(const std::shared_ptr<const LoadedModel>& model, int count, bool prewarm)
+	{
+		return CreateStreams(model, 1.0f, count, prewarm, false, true);
+	}
+
+	int GpuBatch::FindParked(const LoadedModel* model) const
+	{
+		for (size_t s = 0; s < streams.size(); s++)
+			if (streams[s].parked && streams[s].model.get() == model) return (int)s;
+		return -1;
+	}
+
+	// Real-time safe: host bookkeeping only.  The device work -- list upload, re-arm, zero histories -- is enqueued by the next processing
+	// call (FlushRearms, SyncActiveLists).
+	void GpuBatch::ActivateStream(int s, float quality)
+	{
+		CheckUsable();
+		if (!IsParked(s)) throw std::runtime_error("neuralaudio_amd: ActivateStream: stream " + std::to_string(s) + " is not a parked stream of the batch");
+		StreamRef& ref = streams[(size_t)s];
+		ref.quality = quality;
+		ref.active = ref.model->isComposite ? ref.model->ModelIndexFromQuality(quality) : 0;
+		// It must start armed.  A stream that ran since it was armed is armed again, every submodel (a quality switch may have run any of
+		// them); so is every member of a packed group: its virtual stream may have been running for its neighbours, with this
+		// position's channel groups taking zero input along
+		for (auto& gm : ref.members)
+			if (ref.used || gm.first->PackFactor() > 1)
+			{
+				gm.first->QueueRearm(gm.second, ref.poolPrewarm);
+				rearmPending = true;
+			}
+		for (size_t k = 0; k < ref.prewarmed.size(); k++) ref.prewarmed[k] = ref.poolPrewarm ? 1 : 0;
+		ref.members[(size_t)ref.active].first->SetActive(ref.members[(size_t)ref.active].second, s);
+		if (Resamples())
+		{
+			pendingHistoryZero.push_back(s); // (a joining stream starts from zero filter histories at the batch's current phase)
+			rearmPending = true;
+		}
+		ref.parked = false;
+		ref.used = true;
+		numParked--;
+		topologyVersion++;
+	}
+
+	void GpuBatch::ParkStream(int s)
+	{
+		CheckUsable();
+		if (IsParked(s)) throw std::runtime_error("neuralaudio_amd: ParkStream: stream " + std::to_string(s) + " is parked already");
+		if (!IsLive(s)) throw std::runtime_error("neuralaudio_amd: ParkStream: stream " + std::to_string(s) + " is not a live stream of the batch");
+		StreamRef& ref = streams[(size_t)s];
+		if (!ref.pooled) throw std::runtime_error("neuralaudio_amd: ParkStream: stream " + std::to_string(s) + " did not come from ReserveStreams (it leaves through RemoveStreams)");
+		ref.members[(size_t)ref.active].first->SetActive(ref.members[(size_t)ref.active].second, -1);
+		pendingHistoryZero.erase(std::remove(pendingHistoryZero.begin(), pendingHistoryZero.end(), s), pendingHistoryZero.end());
+		ref.parked = true;
+		numParked++;
+		topologyVersion++;
+	}
+
+	// The device side of ActivateStream, on the batch stream in front of the model launches (and of the list uploads): one re-arm launch
+	// per model group with members waiting, the asynchronous zeroing of the activated rows' filter histories.  Behind whatever of the
+	// batch may still touch those slots: the pipelined slots' kernels by an event; half-batch chains and the resident launch are drained
+	// (the one host-side wait, shared with a quality switch on such a batch -- bounded by the wait limit).
+	void GpuBatch::FlushRearms()
+	{
+		if (!rearmPending) return;
+		JoinHalves();
+		if (pipelineUsed && lastKernelEvent && lastKernelStream != stream) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
+		for (auto& g : groups) g->FlushRearm();
+		for (int s : pendingHistoryZero) ZeroResampleHistories(s, 1);
+		pendingHistoryZero.clear();
+		rearmPending = false;
 	}
 
 	// trailing retired rows leave the [streams][n] arrays altogether (their ids are the largest entries of the sorted `retired` list)
@@ -325,6 +434,7 @@ namespace na
 		if (count < 1 || first < 0 || (size_t)first + (size_t)count > streams.size()) throw std::runtime_error("neuralaudio_amd: RemoveStreams: id range outside the batch");
 		for (int i = 0; i < count; i++)
 			if (!streams[(size_t)(first + i)].live) throw std::runtime_error("neuralaudio_amd: RemoveStreams: stream was already removed");
+		// (a parked stream is freed like any other: its slots, its pending re-arm, its place in the pool)
 		CheckHip(hipSetDevice(device), "hipSetDevice");
 		// the slots may be handed out again right away: nothing of theirs may still be in flight
 		Quiesce();
@@ -333,6 +443,8 @@ namespace na
 		{
 			StreamRef& ref = streams[(size_t)(first + i)];
 			for (auto& gm : ref.members) gm.first->RemoveMember(gm.second);
+			if (ref.parked) numParked--;
+			pendingHistoryZero.erase(std::remove(pendingHistoryZero.begin(), pendingHistoryZero.end(), first + i), pendingHistoryZero.end());
 			ref = StreamRef();
 			ref.live = false;
 			retired.insert(std::lower_bound(retired.begin(), retired.end(), first + i), first + i);
@@ -352,6 +464,9 @@ namespace na
 	{
 		for (int id : retired)
 			if ((size_t)id < rows) memset(hostRows + (size_t)id * n, 0, n * sizeof(float));
+		if (numParked > 0)
+			for (size_t id = 0; id < rows && id < streams.size(); id++)
+				if (streams[id].parked) memset(hostRows + id * n, 0, n * sizeof(float));
 	}
 
 	void GpuBatch::SetQuality(int s, float quality)
@@ -359,6 +474,7 @@ namespace na
 		CheckUsable();
 		StreamRef& ref = streams.at((size_t)s);
 		if (!ref.live) throw std::runtime_error("neuralaudio_amd: stream was removed");
+		if (ref.parked) throw std::runtime_error("neuralaudio_amd: SetQuality: stream " + std::to_string(s) + " is parked (ActivateStream takes the quality)");
 		ref.quality = quality;
 		if (!ref.model->isComposite) return;
 		const int idx = ref.model->ModelIndexFromQuality(quality);
@@ -423,7 +539,7 @@ namespace na
 	bool GpuBatch::IsQualityChangeRealtimeSafe(int s, float quality) const
 	{
 		const StreamRef& ref = streams.at((size_t)s);
-		if (!ref.live) return false;
+		if (!ref.live || ref.parked) return false;
 		if (!ref.model->isComposite) return true;
 		const int idx = ref.model->ModelIndexFromQuality(quality);
 		if (idx == ref.active) return true;
@@ -437,6 +553,7 @@ namespace na
 	void GpuBatch::Prewarm(int s)
 	{
 		CheckUsable();
+		if (IsParked(s)) throw std::runtime_error("neuralaudio_amd: Prewarm: stream " + std::to_string(s) + " is parked (a parked stream is armed already)");
 		CheckHip(hipSetDevice(device), "hipSetDevice");
 		DrainPipeline();
 		StreamRef& ref = streams.at((size_t)s);
@@ -456,6 +573,7 @@ namespace na
 		CheckUsable();
 		if (n == 0 || streams.empty()) return;
 		CheckHip(hipSetDevice(device), "hipSetDevice");
+		FlushRearms();
 		// A batch on its own stream that nobody has seen: a buffer of one contiguous WaveNet group runs as two free-running half-batch
 		// launches (the order of work on the internal streams is not observable from outside; Synchronize() and the host-buffer entry
 		// points wait for all of them).  1024 x A1 Standard x 128 frames: 40.1 -> 37.4 us per step.
@@ -487,7 +605,7 @@ namespace na
 		if (pipelineUsed)
 		{
 			// ... and the next submitted buffer after this call's
-			if (!mainDone) CheckHip(hipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
+			if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
 			CheckHip(hipEventRecord(mainDone, stream), "hipEventRecord");
 			lastKernelEvent = mainDone;
 			lastKernelStream = stream;
@@ -619,7 +737,7 @@ namespace na
 		// replayed while the call signature (pointers, n, strides) and the active-stream lists stay the same -- the steady state of a
 		// real-time host.
 		auto forkJoin = [&] {
-			if (!forkEvent) CheckHip(hipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
+			if (!forkEvent) CheckHip(CountedHipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
 			CheckHip(hipEventRecord(forkEvent, stream), "hipEventRecord");
 			for (size_t u = 0; u < units.size(); u++)
 			{

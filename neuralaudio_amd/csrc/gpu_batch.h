@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "device_resources.h"
 #include "launch_plan.h"
 #include "model_loader.h"
 #include "resample.h"
@@ -87,7 +88,23 @@ namespace na
 		// one -- before it appends new rows, and recycled state slots start from the same fresh / prewarmed state as new ones.
 		// Not real-time safe (like AddStreams): call between buffers.
 		void RemoveStreams(int first, int count);
-		bool IsLive(int stream) const { return stream >= 0 && stream < (int)streams.size() && streams[(size_t)stream].live; }
+		bool IsLive(int stream) const { return stream >= 0 && stream < (int)streams.size() && streams[(size_t)stream].live && !streams[(size_t)stream].parked; }
+
+		// The stream pool: join and leave for a batch that never stops.  ReserveStreams is the set-up side (like AddStreams:
+		// not real-time safe): `count` PARKED streams of `model` with everything they will ever need on the device -- rows, state slots of
+		// every submodel, list capacity, resampling histories, the chains' streams, the re-arm staging -- each ARMED: in the state
+		// AddStreams(count = 1, prewarm) leaves, every submodel prewarmed whatever the load mode.  A parked stream keeps its row (input
+		// ignored, host output zero, device output row left alone) and is not live.  ActivateStream / ParkStream are host bookkeeping --
+		// a member row, dirty lists, a pending re-arm -- and the processing call that follows enqueues, on the batch stream in front of
+		// the model launches, the list upload, one re-arm launch per model group and (resampling) the zeroing of the row's histories: no
+		// allocation, no stream or event creation, no host-side wait (a batch on its half-batch chains or the resident launch drains
+		// them first, as after SetQuality).  A stream that was parked carries nothing over: it is re-armed before it runs again.
+		int ReserveStreams(const std::shared_ptr<const LoadedModel>& model, int count, bool prewarm);
+		void ActivateStream(int stream, float quality);
+		void ParkStream(int stream); // only streams that came from ReserveStreams; the others leave through RemoveStreams
+		bool IsParked(int stream) const { return stream >= 0 && stream < (int)streams.size() && streams[(size_t)stream].parked; }
+		int FindParked(const LoadedModel* model) const; // the lowest parked id of that model, -1: none
+		int NumParked() const { return numParked; }
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -117,7 +134,7 @@ namespace na
 		int DebugResampleTap(float* modelIn, float* modelOut, long long capacityPerRow);
 
 		int NumStreams() const { return (int)streams.size(); } // rows of the [streams][n] arrays (retired ids included)
-		int NumLiveStreams() const { return (int)streams.size() - (int)retired.size(); }
+		int NumLiveStreams() const { return (int)streams.size() - (int)retired.size() - numParked; }
 		unsigned StreamPrewarmedMask(int stream) const; // bit k: submodel k of the stream had its prewarm
 
 		// ScalableCompositeModel::SetQualityScaleFactor (CompositeModel.h:176-181): switches the active submodel,
@@ -228,9 +245,17 @@ namespace na
 			float quality = 1.0f;
 			bool onDemand = false;
 			bool live = true;
+			// the pool: `pooled` came from ReserveStreams; `parked` holds state slots but no member is active; `used` has run (or may have)
+			// since it was last armed; `poolPrewarm` is the doPrewarm it was reserved with
+			bool pooled = false, parked = false, used = false, poolPrewarm = false;
 			std::vector<char> prewarmed; // per submodel: had its initial prewarm
 		};
 		std::vector<int> retired; // sorted ids of removed streams
+		int numParked = 0;
+		bool rearmPending = false;           // a group has members queued for re-arm / rows wait for zero histories: FlushRearms
+		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
+		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
+		void FlushRearms(); // top of every processing entry point, outside any graph capture
 		int AllocateIds(int count);
 		void DropTrailingRetiredRows();
 		// the kinds of the groups that have active streams once `leaving` has lost / `entering` has gained one, in group order (`active`:
@@ -312,6 +337,7 @@ namespace na
 			float* dev = nullptr;
 			size_t floats = 0, n = 0;
 			size_t rows = 0; // rows of the [streams][n] block this slot was submitted with
+			std::vector<int> parkedRows; // ... and the rows that were parked then (host output zero)
 			hipEvent_t uploaded = nullptr, computed = nullptr, downloaded = nullptr;
 			hipStream_t own = nullptr; // upload, kernel and download of this slot's buffer, in order (batches that run as one launch)
 			bool onOwnStream = false;
@@ -374,5 +400,6 @@ namespace na
 		hipStream_t copyIn = nullptr, copyOut = nullptr;
 		int nextSlot = 0;
 		void EnsurePipeSlot(PipeSlot& s, size_t floats);
+		void EnsurePoolPipeline(); // ReserveStreams: what Submit / Collect would create on first use, whatever the number of launch units
 	};
 }

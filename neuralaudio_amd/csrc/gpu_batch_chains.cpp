@@ -144,7 +144,7 @@ namespace na
 		int grid = 0;
 		CheckHip(LaunchWaveNetSpecResident(r.list.data(), (int)r.list.size(), WN_MAX_FRAMES, ra, stream, &grid), "WaveNet resident launch");
 		if (grid != r.grid) throw std::runtime_error("neuralaudio_amd: internal: resident grid changed inside a generation");
-		if (!r.gen) CheckHip(hipEventCreateWithFlags(&r.gen, hipEventDisableTiming), "hipEventCreate");
+		if (!r.gen) CheckHip(CountedHipEventCreateWithFlags(&r.gen, hipEventDisableTiming), "hipEventCreate");
 		CheckHip(hipEventRecord(r.gen, stream), "hipEventRecord");
 		r.launched = true;
 	}
@@ -179,7 +179,7 @@ namespace na
 			// the command block: device memory the host can write, where the BAR covers it (wavenet_launch.h ResidentCtrl)
 			int largeBar = 0;
 			if (!Tuning::Get().residentHostRing && hipDeviceGetAttribute(&largeBar, hipDeviceAttributeIsLargeBar, device) == hipSuccess && largeBar &&
-				hipExtMallocWithFlags(reinterpret_cast<void**>(&r.ctrl), sizeof(ResidentCtrl), hipDeviceMallocFinegrained) == hipSuccess)
+				CountedHipExtMallocWithFlags(reinterpret_cast<void**>(&r.ctrl), sizeof(ResidentCtrl), hipDeviceMallocFinegrained) == hipSuccess)
 			{
 				r.ctrlInDeviceMemory = true;
 				r.dCtrl = r.ctrl;
@@ -189,23 +189,23 @@ namespace na
 			{
 				(void)hipGetLastError();
 				r.ctrl = nullptr;
-				CheckHip(hipHostMalloc(reinterpret_cast<void**>(&r.ctrl), sizeof(ResidentCtrl), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc (command ring)");
+				CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&r.ctrl), sizeof(ResidentCtrl), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc (command ring)");
 				memset(r.ctrl, 0, sizeof(ResidentCtrl));
 				CheckHip(hipHostGetDevicePointer(reinterpret_cast<void**>(&r.dCtrl), r.ctrl, 0), "hipHostGetDevicePointer");
 			}
 			HostStore(&r.ctrl->exitAfter, kNever);
-			CheckHip(hipHostMalloc(reinterpret_cast<void**>(&r.status), sizeof(ResidentStatus), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc (resident status)");
+			CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&r.status), sizeof(ResidentStatus), hipHostMallocMapped | hipHostMallocCoherent), "hipHostMalloc (resident status)");
 			memset(r.status, 0, sizeof(ResidentStatus));
 			CheckHip(hipHostGetDevicePointer(reinterpret_cast<void**>(&r.dStatus), r.status, 0), "hipHostGetDevicePointer");
-			CheckHip(hipMalloc(reinterpret_cast<void**>(&r.dDone), RESIDENT_RING * sizeof(unsigned)), "hipMalloc");
+			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&r.dDone), RESIDENT_RING * sizeof(unsigned)), "hipMalloc");
 			CheckHip(hipMemsetAsync(r.dDone, 0, RESIDENT_RING * sizeof(unsigned), stream), "hipMemsetAsync");
 		}
 		if (grid > r.wgCapacity)
 		{
-			if (r.dWgDone) (void)hipFree(r.dWgDone);
+			if (r.dWgDone) (void)CountedHipFree(r.dWgDone);
 			r.dWgDone = nullptr;
 			r.wgCapacity = 0;
-			CheckHip(hipMalloc(reinterpret_cast<void**>(&r.dWgDone), (size_t)grid * sizeof(unsigned)), "hipMalloc");
+			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&r.dWgDone), (size_t)grid * sizeof(unsigned)), "hipMalloc");
 			r.wgCapacity = grid;
 		}
 		CheckHip(hipMemsetAsync(r.dWgDone, 0, (size_t)grid * sizeof(unsigned), stream), "hipMemsetAsync"); // (the launch is ordered behind it)
@@ -418,10 +418,10 @@ namespace na
 		for (int h = 0; h < numChains; h++)
 		{
 			if (halfStream[h]) continue;
-			CheckHip(hipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
+			CheckHip(CountedHipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
 			if (markOpen)
 			{
-				if (!marks[1 + h][0]) CheckHip(hipEventCreate(&marks[1 + h][0]), "hipEventCreate");
+				if (!marks[1 + h][0]) CheckHip(CountedHipEventCreate(&marks[1 + h][0]), "hipEventCreate");
 				CheckHip(hipEventRecord(marks[1 + h][0], halfStream[h]), "hipEventRecord");
 			}
 		}
@@ -484,7 +484,7 @@ namespace na
 		{
 			hipStream_t s = i == 0 ? stream : halfStream[i - 1];
 			if (!s || (which == 1 && !marks[i][0])) continue;
-			if (!marks[i][which]) CheckHip(hipEventCreate(&marks[i][which]), "hipEventCreate");
+			if (!marks[i][which]) CheckHip(CountedHipEventCreate(&marks[i][which]), "hipEventCreate");
 			CheckHip(hipEventRecord(marks[i][which], s), "hipEventRecord");
 		}
 	}

@@ -21,13 +21,13 @@ namespace na
 	void GpuBatch::EnsureStaging(size_t floats)
 	{
 		if (floats <= stageFloats) return;
-		if (hostStage) (void)hipHostFree(hostStage);
-		if (devStage) (void)hipFree(devStage);
+		if (hostStage) (void)CountedHipHostFree(hostStage);
+		if (devStage) (void)CountedHipFree(devStage);
 		hostStage = nullptr;
 		devStage = nullptr;
 		stageFloats = 0;
-		CheckHip(hipHostMalloc(reinterpret_cast<void**>(&hostStage), floats * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
-		CheckHip(hipMalloc(reinterpret_cast<void**>(&devStage), floats * sizeof(float)), "hipMalloc");
+		CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&hostStage), floats * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+		CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&devStage), floats * sizeof(float)), "hipMalloc");
 		stageFloats = floats;
 	}
 
@@ -100,6 +100,7 @@ namespace na
 		CheckUsable();
 		if (n == 0 || streams.empty()) return;
 		CheckHip(hipSetDevice(device), "hipSetDevice");
+		FlushRearms();
 		const size_t total = streams.size() * n;
 		if (HostDirect())
 		{
@@ -163,6 +164,7 @@ namespace na
 		const size_t total = streams.size() * n;
 		// the previous call's kernels may still be reading the pinned block
 		WaitStreamBounded(stream, "hipStreamSynchronize");
+		FlushRearms();
 		EnsureStaging(total);
 		memcpy(hostStage, in, total * sizeof(float));
 		float* dStage = nullptr;
@@ -179,23 +181,47 @@ namespace na
 	{
 		if (!p.uploaded)
 		{
-			CheckHip(hipEventCreateWithFlags(&p.uploaded, hipEventDisableTiming), "hipEventCreate");
-			CheckHip(hipEventCreateWithFlags(&p.computed, hipEventDisableTiming), "hipEventCreate");
-			CheckHip(hipEventCreateWithFlags(&p.downloaded, hipEventDisableTiming), "hipEventCreate");
+			CheckHip(CountedHipEventCreateWithFlags(&p.uploaded, hipEventDisableTiming), "hipEventCreate");
+			CheckHip(CountedHipEventCreateWithFlags(&p.computed, hipEventDisableTiming), "hipEventCreate");
+			CheckHip(CountedHipEventCreateWithFlags(&p.downloaded, hipEventDisableTiming), "hipEventCreate");
 			// the set-up side of the pipelined interface: the half-batch chains' streams too (creating a HIP stream takes ~13 ms)
 			for (int h = 0; h < numChains; h++)
-				if (!halfStream[h]) CheckHip(hipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
+				if (!halfStream[h]) CheckHip(CountedHipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
 		}
 		if (floats <= p.floats) return;
-		if (p.hostIn) (void)hipHostFree(p.hostIn);
-		if (p.hostOut) (void)hipHostFree(p.hostOut);
-		if (p.dev) (void)hipFree(p.dev);
+		if (p.hostIn) (void)CountedHipHostFree(p.hostIn);
+		if (p.hostOut) (void)CountedHipHostFree(p.hostOut);
+		if (p.dev) (void)CountedHipFree(p.dev);
 		p.hostIn = p.hostOut = p.dev = nullptr;
 		p.floats = 0;
-		CheckHip(hipHostMalloc(reinterpret_cast<void**>(&p.hostIn), floats * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
-		CheckHip(hipHostMalloc(reinterpret_cast<void**>(&p.hostOut), floats * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
-		CheckHip(hipMalloc(reinterpret_cast<void**>(&p.dev), floats * sizeof(float)), "hipMalloc");
+		CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&p.hostIn), floats * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+		CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&p.hostOut), floats * sizeof(float), hipHostMallocDefault), "hipHostMalloc");
+		CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&p.dev), floats * sizeof(float)), "hipMalloc");
 		p.floats = floats;
+	}
+
+	// The pool's share of the pipelined interface's set-up side: every stream and event that Submit / Collect, or an ordered call behind
+	// them, creates on first use.  Which of them a buffer needs depends on the number of launch units (one: the slots' own streams;
+	// several, or a resampling batch: the copy streams), and an activation or a park may change that number on a running batch.
+	void GpuBatch::EnsurePoolPipeline()
+	{
+		for (PipeSlot& p : pipe)
+		{
+			if (!p.uploaded)
+			{
+				CheckHip(CountedHipEventCreateWithFlags(&p.uploaded, hipEventDisableTiming), "hipEventCreate");
+				CheckHip(CountedHipEventCreateWithFlags(&p.computed, hipEventDisableTiming), "hipEventCreate");
+				CheckHip(CountedHipEventCreateWithFlags(&p.downloaded, hipEventDisableTiming), "hipEventCreate");
+			}
+			if (!p.own) CheckHip(CountedHipStreamCreateWithFlags(&p.own, hipStreamNonBlocking), "hipStreamCreate");
+			for (int h = 0; h < numChains; h++)
+				if (!p.halfDone[h]) CheckHip(CountedHipEventCreateWithFlags(&p.halfDone[h], hipEventDisableTiming), "hipEventCreate");
+		}
+		for (int h = 0; h < numChains; h++)
+			if (!halfStream[h]) CheckHip(CountedHipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
+		if (!copyIn) CheckHip(CountedHipStreamCreateWithFlags(&copyIn, hipStreamNonBlocking), "hipStreamCreate");
+		if (!copyOut) CheckHip(CountedHipStreamCreateWithFlags(&copyOut, hipStreamNonBlocking), "hipStreamCreate");
+		if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
 	}
 
 	int GpuBatch::Submit(const float* in, size_t n)
@@ -206,10 +232,15 @@ namespace na
 		const int ticket = nextSlot;
 		PipeSlot& p = pipe[ticket];
 		if (p.busy) throw std::runtime_error("neuralaudio_amd: Submit with every pipeline slot in flight (Collect the oldest ticket first)");
+		FlushRearms();
 		const size_t total = streams.size() * n;
 		EnsurePipeSlot(p, total);
 		p.n = n;
 		p.rows = streams.size(); // Collect sizes its copy by THIS (AddStreams / RemoveStreams may run while the ticket is in flight)
+		p.parkedRows.clear(); // (a stream may join or leave while the ticket is in flight: the rows parked NOW are this buffer's silent ones)
+		if (numParked > 0)
+			for (size_t r = 0; r < streams.size(); r++)
+				if (streams[r].parked) p.parkedRows.push_back((int)r);
 		if (in) memcpy(p.hostIn, in, total * sizeof(float)); // nullptr: the caller filled NextInput() in place
 		const bool direct = HostDirect(); // (see ProcessHost)
 		float *dIn = nullptr, *dOut = nullptr;
@@ -225,7 +256,7 @@ namespace na
 			{
 				// two free-running half-batch chains (see halfStream): each half in submission order on its own stream
 				for (int h = 0; h < numChains; h++)
-					if (!p.halfDone[h]) CheckHip(hipEventCreateWithFlags(&p.halfDone[h], hipEventDisableTiming), "hipEventCreate");
+					if (!p.halfDone[h]) CheckHip(CountedHipEventCreateWithFlags(&p.halfDone[h], hipEventDisableTiming), "hipEventCreate");
 				LaunchHalves(dIn, dOut, n, (long)n, (long)n, p.halfDone, true);
 				halfChainsUsed = true;
 				pipelineUsed = true;
@@ -255,7 +286,7 @@ namespace na
 		if (plan.units.size() <= 1 && !Resamples()) // (a resampling batch: three ordered launches, on the batch stream like a multi-unit batch)
 		{
 			JoinHalves(); // (device-pointer steps may have run as half-batch chains: this buffer's kernel comes after both)
-			if (!p.own) CheckHip(hipStreamCreateWithFlags(&p.own, hipStreamNonBlocking), "hipStreamCreate");
+			if (!p.own) CheckHip(CountedHipStreamCreateWithFlags(&p.own, hipStreamNonBlocking), "hipStreamCreate");
 			bool listsChanged = false, dirty = false;
 			for (auto& g : groups) dirty = dirty || (g->NumActive() > 0 && g->ListsDirty());
 			if (dirty)
@@ -268,7 +299,7 @@ namespace na
 			if (listsChanged || submitTopology != topologyVersion || !pipelineUsed)
 			{
 				// everything the batch stream still has in flight for this batch (state resets of new streams, index lists) comes first
-				if (!mainDone) CheckHip(hipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
+				if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
 				CheckHip(hipEventRecord(mainDone, stream), "hipEventRecord");
 				CheckHip(hipStreamWaitEvent(p.own, mainDone, 0), "hipStreamWaitEvent");
 				submitTopology = topologyVersion;
@@ -290,8 +321,8 @@ namespace na
 		// several launch units per buffer (a captured hipGraph on the batch stream): copies on the copy streams, events in between
 		if (!copyIn)
 		{
-			CheckHip(hipStreamCreateWithFlags(&copyIn, hipStreamNonBlocking), "hipStreamCreate");
-			CheckHip(hipStreamCreateWithFlags(&copyOut, hipStreamNonBlocking), "hipStreamCreate");
+			CheckHip(CountedHipStreamCreateWithFlags(&copyIn, hipStreamNonBlocking), "hipStreamCreate");
+			CheckHip(CountedHipStreamCreateWithFlags(&copyOut, hipStreamNonBlocking), "hipStreamCreate");
 		}
 		CheckHip(hipMemcpyAsync(p.dev, p.hostIn, total * sizeof(float), hipMemcpyHostToDevice, copyIn), "hipMemcpyAsync H2D");
 		CheckHip(hipEventRecord(p.uploaded, copyIn), "hipEventRecord");
@@ -320,7 +351,9 @@ namespace na
 		else if (p.onOwnStream) WaitStreamBounded(p.own, "hipStreamSynchronize"); // the download is the stream's last operation
 		else WaitEventBounded(p.downloaded, "hipEventSynchronize");
 		// the slot holds the rows the batch had at Submit: ids retired since then are zeroed only inside that block
-		if (!retired.empty()) ZeroRetiredRows(p.hostOut, p.n, p.rows);
+		for (int id : retired)
+			if ((size_t)id < p.rows) memset(p.hostOut + (size_t)id * p.n, 0, p.n * sizeof(float));
+		for (int r : p.parkedRows) memset(p.hostOut + (size_t)r * p.n, 0, p.n * sizeof(float));
 		if (out) memcpy(out, p.hostOut, p.rows * p.n * sizeof(float)); // nullptr: the caller reads OutputView() in place
 		p.busy = false;
 	}

@@ -49,10 +49,10 @@ namespace na
 		~ResidentState()
 		{
 			if (gen) (void)hipEventDestroy(gen);
-			if (dDone) (void)hipFree(dDone);
-			if (dWgDone) (void)hipFree(dWgDone);
-			if (ctrl) (void)(ctrlInDeviceMemory ? hipFree(ctrl) : hipHostFree(ctrl));
-			if (status) (void)hipHostFree(status);
+			if (dDone) (void)CountedHipFree(dDone);
+			if (dWgDone) (void)CountedHipFree(dWgDone);
+			if (ctrl) (void)(ctrlInDeviceMemory ? CountedHipFree(ctrl) : CountedHipHostFree(ctrl));
+			if (status) (void)CountedHipHostFree(status);
 		}
 	};
 
@@ -77,7 +77,7 @@ namespace na
 		~ResampleState()
 		{
 			for (float* p : { tableUp, tableDown, histUp, histDown, modelIn, modelOut })
-				if (p) (void)hipFree(p);
+				if (p) (void)CountedHipFree(p);
 		}
 	};
 

@@ -31,18 +31,19 @@ namespace na
 	void GpuBatch::EnsureSnapshotStaging(size_t words)
 	{
 		if (words <= snapWords) return;
-		if (snapHost) (void)hipHostFree(snapHost);
-		if (snapDev) (void)hipFree(snapDev);
+		if (snapHost) (void)CountedHipHostFree(snapHost);
+		if (snapDev) (void)CountedHipFree(snapDev);
 		snapHost = nullptr;
 		snapDev = nullptr;
 		snapWords = 0;
-		CheckHip(hipHostMalloc(reinterpret_cast<void**>(&snapHost), words * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
-		CheckHip(hipMalloc(reinterpret_cast<void**>(&snapDev), words * sizeof(uint32_t)), "hipMalloc");
+		CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&snapHost), words * sizeof(uint32_t), hipHostMallocDefault), "hipHostMalloc");
+		CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&snapDev), words * sizeof(uint32_t)), "hipMalloc");
 		snapWords = words;
 	}
 
 	size_t GpuBatch::StreamSnapshotBytes(int s) const
 	{
+		if (IsParked(s)) throw std::runtime_error("neuralaudio_amd: StreamSnapshotBytes: stream " + std::to_string(s) + " is parked");
 		if (!IsLive(s)) throw std::runtime_error("neuralaudio_amd: StreamSnapshotBytes: no such stream");
 		return SnapshotBytes(*streams[(size_t)s].model);
 	}
@@ -54,6 +55,8 @@ namespace na
 		// (the v1 blob has no place for the resampler's histories, and the phase is the batch's, not the stream's)
 		if (Resamples()) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": stream snapshots of a resampling batch are not supported");
 		if (count < 0 || (count > 0 && !ids)) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": bad argument");
+		for (int i = 0; i < count; i++)
+			if (IsParked(ids[i])) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": stream " + std::to_string(ids[i]) + " is parked (a parked stream has no state of its own: it is armed)");
 		for (int i = 0; i < count; i++)
 			if (!IsLive(ids[i])) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": stream " + std::to_string(ids[i]) + " is not a live stream of the batch");
 		CheckHip(hipSetDevice(device), "hipSetDevice");

@@ -42,7 +42,7 @@ namespace na
 			{
 				Free();
 				if (n == 0) return;
-				CheckHip(hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)), "hipMalloc");
+				CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)), "hipMalloc");
 				count = n;
 			}
 
@@ -66,7 +66,7 @@ namespace na
 
 			void Free()
 			{
-				if (ptr) (void)hipFree(ptr);
+				if (ptr) (void)CountedHipFree(ptr);
 				ptr = nullptr;
 				count = 0;
 			}
@@ -98,21 +98,23 @@ namespace na
 			if (doneEvent) (void)hipEventDestroy(doneEvent);
 			for (int b = 0; b < 2; b++)
 			{
-				if (pinnedLists[b]) (void)hipHostFree(pinnedLists[b]);
+				if (pinnedLists[b]) (void)CountedHipHostFree(pinnedLists[b]);
 				if (listEvent[b]) (void)hipEventDestroy(listEvent[b]);
+				if (pinnedRearm[b]) (void)CountedHipHostFree(pinnedRearm[b]);
+				if (rearmEvent[b]) (void)hipEventDestroy(rearmEvent[b]);
 			}
 		}
 
 		// created on first use: lets independent model groups of a mixed batch run concurrently
 		hipStream_t SideStream()
 		{
-			if (!sideStream) CheckHip(hipStreamCreateWithFlags(&sideStream, hipStreamNonBlocking), "hipStreamCreate");
+			if (!sideStream) CheckHip(CountedHipStreamCreateWithFlags(&sideStream, hipStreamNonBlocking), "hipStreamCreate");
 			return sideStream;
 		}
 
 		hipEvent_t DoneEvent()
 		{
-			if (!doneEvent) CheckHip(hipEventCreateWithFlags(&doneEvent, hipEventDisableTiming), "hipEventCreate");
+			if (!doneEvent) CheckHip(CountedHipEventCreateWithFlags(&doneEvent, hipEventDisableTiming), "hipEventCreate");
 			return doneEvent;
 		}
 
@@ -140,6 +142,7 @@ namespace na
 		void RemoveMember(int member)
 		{
 			SetActive(member, -1);
+			DropRearm(member);
 			memberInUse[(size_t)member] = 0;
 			freeMembers.insert(std::lower_bound(freeMembers.begin(), freeMembers.end(), member), member);
 		}
@@ -187,6 +190,46 @@ namespace na
 		virtual void SaveState(const std::vector<int>& members, uint32_t* dStaging) = 0;
 		virtual void LoadState(const std::vector<int>& members, const std::vector<uint32_t>& encodings, const uint32_t* dStaging) = 0;
 
+		// ---- the stream pool (GpuBatch::ReserveStreams / ActivateStream / ParkStream) ----
+		// Set-up side: `members` (new, ascending) end up ARMED -- the state AddStreams(count = 1, prewarm) leaves behind -- and the staging
+		// of the re-arm below is sized for every member of the group.
+		virtual void ArmReserved(const std::vector<int>& members, bool prewarm)
+		{
+			Reset(members);
+			if (prewarm) Prewarm(members);
+			EnsureRearmCapacity(memberRow.size());
+		}
+		// Real-time side, host bookkeeping only: `member` is armed again (fill: prewarmed, else fresh) before the next launch of the batch
+		void QueueRearm(int member, bool fill)
+		{
+			if ((size_t)member >= rearmQueued.size() || (!rearmQueued[(size_t)member] && rearmList.size() >= rearmCapacity))
+				throw std::runtime_error("internal: re-arm of a member the pool never sized for");
+			if (!rearmQueued[(size_t)member]) rearmList.push_back(member);
+			rearmQueued[(size_t)member] = fill ? 2 : 1;
+		}
+		bool HasPendingRearm() const { return !rearmList.empty(); }
+		// ... and its device work: the list goes up from one of two pinned, event-guarded staging buffers (like UploadLists) and ONE launch on
+		// the batch stream re-arms every listed member.  No allocation, no synchronisation.  Never called inside a graph capture.
+		void FlushRearm()
+		{
+			if (rearmList.empty()) return;
+			rearmFlip ^= 1;
+			int* pin = pinnedRearm[rearmFlip];
+			if (rearmUsed[rearmFlip]) CheckHip(hipEventSynchronize(rearmEvent[rearmFlip]), "hipEventSynchronize"); // (the copy of two flushes ago)
+			for (size_t i = 0; i < rearmList.size(); i++)
+			{
+				const int m = rearmList[i];
+				pin[i] = m * 2 + (rearmQueued[(size_t)m] == 2 ? 1 : 0);
+				rearmQueued[(size_t)m] = 0;
+			}
+			const int count = (int)rearmList.size();
+			rearmList.clear();
+			CheckHip(hipMemcpyAsync(dRearm.Get(), pin, (size_t)count * sizeof(int), hipMemcpyHostToDevice, stream), "hipMemcpyAsync H2D");
+			CheckHip(hipEventRecord(rearmEvent[rearmFlip], stream), "hipEventRecord");
+			rearmUsed[rearmFlip] = true;
+			LaunchRearm(dRearm.Get(), count);
+		}
+
 		bool ListsDirty() const { return activeDirty; }
 
 		int NumActive() const
@@ -227,6 +270,37 @@ namespace na
 
 	protected:
 		virtual void EnsureCapacity(int members) = 0;
+		// one launch on the batch stream: every entry (= member * 2 + fill) of the device list is armed (the family's re-arm kernel)
+		virtual void LaunchRearm(const int* dEntries, int count) = 0;
+
+		void DropRearm(int member)
+		{
+			if ((size_t)member >= rearmQueued.size() || !rearmQueued[(size_t)member]) return;
+			rearmQueued[(size_t)member] = 0;
+			rearmList.erase(std::find(rearmList.begin(), rearmList.end(), member));
+		}
+
+		// re-arm staging (device list + two pinned buffers + their events) for `members` entries: grown on the ReserveStreams side only
+		void EnsureRearmCapacity(size_t members)
+		{
+			for (int b = 0; b < 2; b++)
+				if (!rearmEvent[b]) CheckHip(CountedHipEventCreateWithFlags(&rearmEvent[b], hipEventDisableTiming), "hipEventCreate");
+			rearmQueued.resize(std::max(rearmQueued.size(), members), 0);
+			if (members <= rearmCapacity) return;
+			const size_t cap = std::max<size_t>(members, std::max<size_t>(rearmCapacity * 2, 64));
+			CheckHip(hipStreamSynchronize(stream), "hipStreamSynchronize"); // (a copy from the old buffers may be in flight)
+			dRearm.Alloc(cap);
+			for (int b = 0; b < 2; b++)
+			{
+				if (pinnedRearm[b]) (void)CountedHipHostFree(pinnedRearm[b]);
+				pinnedRearm[b] = nullptr;
+				CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&pinnedRearm[b]), cap * sizeof(int), hipHostMallocDefault), "hipHostMalloc");
+				rearmUsed[b] = false;
+			}
+			rearmList.reserve(cap);
+			rearmQueued.reserve(cap);
+			rearmCapacity = cap;
+		}
 
 		// hSlots / hRows -> the device lists through one of two pinned staging buffers, asynchronously on the batch stream.  Real-time
 		// safe: buffers and both events were created on the AddStreams side (EnsureListCapacity).
@@ -248,7 +322,7 @@ namespace na
 		void EnsureListCapacity(size_t members)
 		{
 			for (int b = 0; b < 2; b++)
-				if (!listEvent[b]) CheckHip(hipEventCreateWithFlags(&listEvent[b], hipEventDisableTiming), "hipEventCreate");
+				if (!listEvent[b]) CheckHip(CountedHipEventCreateWithFlags(&listEvent[b], hipEventDisableTiming), "hipEventCreate");
 			if (members <= listCapacity) return;
 			const size_t cap = std::max<size_t>(members, std::max<size_t>(listCapacity * 2, 64));
 			CheckHip(hipStreamSynchronize(stream), "hipStreamSynchronize");
@@ -256,9 +330,9 @@ namespace na
 			dRows.Alloc(cap);
 			for (int b = 0; b < 2; b++)
 			{
-				if (pinnedLists[b]) (void)hipHostFree(pinnedLists[b]);
+				if (pinnedLists[b]) (void)CountedHipHostFree(pinnedLists[b]);
 				pinnedLists[b] = nullptr;
-				CheckHip(hipHostMalloc(reinterpret_cast<void**>(&pinnedLists[b]), 2 * cap * sizeof(int), hipHostMallocDefault), "hipHostMalloc");
+				CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&pinnedLists[b]), 2 * cap * sizeof(int), hipHostMallocDefault), "hipHostMalloc");
 			}
 			hSlots.reserve(cap);
 			hRows.reserve(cap);
@@ -283,6 +357,15 @@ namespace na
 		int listFlip = 0;
 		bool contiguous = false; // active streams are slot0+i / row0+i: kernels may skip the index arrays
 		bool activeDirty = true;
+		// the pool's re-arm: members waiting for it (rearmQueued: 0 no, 1 fresh, 2 prewarmed), the device list, its pinned double buffer
+		std::vector<int> rearmList;
+		std::vector<char> rearmQueued;
+		DevArray<int> dRearm;
+		int* pinnedRearm[2] = { nullptr, nullptr };
+		hipEvent_t rearmEvent[2] = { nullptr, nullptr };
+		bool rearmUsed[2] = { false, false };
+		size_t rearmCapacity = 0;
+		int rearmFlip = 0;
 	};
 
 	inline namespace groups
@@ -705,6 +788,12 @@ namespace na
 				capacity = newCap;
 			}
 
+			void LaunchRearm(const int* dEntries, int count) override
+			{
+				CheckHip(LaunchWaveNetRearm(state.Get(), plan.stateF4, dEntries, count, (int)plan.rings.size(), dRingOff.Get(), dRingFrames.Get(),
+					dRingG.Get(), dCols.Get(), stream, family == WN_FAMILY_SPLIT, pack), "WaveNetRearmKernel");
+			}
+
 		private:
 			// the launch arguments of a snapshot export / import of `members`; uploads their [slot | sub | encoding] lists
 			WnSnapshotArgs SnapshotArgs(const std::vector<int>& members, const std::vector<uint32_t>* encodings)
@@ -860,6 +949,26 @@ namespace na
 				CheckHip(hipStreamSynchronize(stream), "hipStreamSynchronize");
 			}
 
+			// The armed state of a recurrent model is the same for every stream: the first reserved member is prewarmed the existing way, alone
+			// (the one-stream launch of AddStreams(count = 1)), its column is kept as the group's template, and the re-arm kernel broadcasts
+			// it -- here to every new member, later to whoever is activated again.  The 2048-zero prewarm runs once per group.
+			void ArmReserved(const std::vector<int>& members, bool prewarm) override
+			{
+				if (members.empty()) return;
+				EnsureRearmCapacity(memberRow.size());
+				if (prewarm && dArmed.Count() == 0)
+				{
+					const std::vector<int> one = { members[0] };
+					Reset(one);
+					Prewarm(one);
+					dArmed.Alloc((size_t)numElems);
+					CheckHip(hipMemcpy2DAsync(dArmed.Get(), sizeof(float), state.Get() + members[0], capacity * sizeof(float), sizeof(float), (size_t)numElems,
+						hipMemcpyDeviceToDevice, stream), "hipMemcpy2DAsync");
+				}
+				for (int m : members) QueueRearm(m, prewarm);
+				FlushRearm();
+			}
+
 			void Process(const float* dIn, float* dOut, long inStride, long outStride, size_t n, hipStream_t launchStream) override
 			{
 				SyncActiveLists();
@@ -947,6 +1056,12 @@ namespace na
 				capacity = newCap;
 			}
 
+			void LaunchRearm(const int* dEntries, int count) override
+			{
+				CheckHip(LaunchRecurrentRearm(state.Get(), (int)capacity, dEntries, count, dInit.Get(), dArmed.Count() ? dArmed.Get() : dInit.Get(), numElems, stream),
+					"RecurrentRearmKernel");
+			}
+
 		private:
 			void SnapshotLaunch(const std::vector<int>& members, uint32_t* dStaging, bool import)
 			{
@@ -963,6 +1078,7 @@ namespace na
 			bool dpp = false; // the LDS-free kernel runs this model (a launch of kind Recurrent)
 			LstmModelDev dev = {};
 			DevArray<float> dW, dWT, dInit, dZeros;
+			DevArray<float> dArmed; // the pool's template: [numElems], the state a one-stream prewarm leaves (empty until a prewarmed reserve)
 			DevArray<float> state;
 			std::vector<float> init;
 			int numElems = 0;

@@ -669,6 +669,17 @@ namespace na
 		for (int k = 0; k < numElems; k++) state[(size_t)k * capacity + slot] = init[k];
 	}
 
+	// Pool re-arm (lstm_launch.h LaunchRecurrentRearm): grid = (entries / 256, min(numElems, 65535)), the elements strided over grid y
+	__global__ void __launch_bounds__(256) RecurrentRearmKernel(float* __restrict__ state, int capacity, const int* __restrict__ entries, int numEntries,
+		const float* __restrict__ init, const float* __restrict__ armed, int numElems)
+	{
+		const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+		if (idx >= numEntries) return;
+		const int entry = entries[idx];
+		const float* __restrict__ from = (entry & 1) ? armed : init;
+		for (int k = blockIdx.y; k < numElems; k += gridDim.y) state[(size_t)k * capacity + (entry >> 1)] = from[k];
+	}
+
 	template <int H>
 	static hipError_t LaunchH(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
 		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
@@ -825,6 +836,15 @@ namespace na
 		if (numStreams <= 0) return hipSuccess;
 		hipLaunchKernelGGL(LstmInitStateKernel, dim3((unsigned)((numStreams + 255) / 256)), dim3(256), 0, stream, state, capacity, slots,
 			numStreams, init, numElems);
+		return hipGetLastError();
+	}
+
+	hipError_t LaunchRecurrentRearm(float* state, int capacity, const int* entries, int numEntries, const float* init, const float* armed,
+		int numElems, hipStream_t stream)
+	{
+		if (numEntries <= 0 || numElems <= 0) return hipSuccess;
+		hipLaunchKernelGGL(RecurrentRearmKernel, dim3((unsigned)((numEntries + 255) / 256), (unsigned)(numElems < 65535 ? numElems : 65535)), dim3(256), 0, stream, state,
+			capacity, entries, numEntries, init, armed, numElems);
 		return hipGetLastError();
 	}
 }

@@ -48,4 +48,9 @@ namespace na
 	// state[k*capacity + slot] = init[k] for the listed slots
 	hipError_t LaunchLstmInitState(float* state, int capacity, const int* slots, int numStreams, const float* init, int numElems,
 		hipStream_t stream);
+
+	// Pool re-arm: entry = member * 2 + prewarmed; state[k*capacity + member] = (prewarmed ? armed : init)[k] -- the armed state of a
+	// recurrent model is the same for every stream, so one column per group (kept from a one-stream prewarm) serves them all
+	hipError_t LaunchRecurrentRearm(float* state, int capacity, const int* entries, int numEntries, const float* init, const float* armed,
+		int numElems, hipStream_t stream);
 }

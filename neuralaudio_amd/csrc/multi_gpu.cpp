@@ -96,7 +96,7 @@ namespace na
 		if (s.gathered)
 		{
 			(void)hipSetDevice(s.device);
-			(void)hipFree(s.gathered);
+			(void)CountedHipFree(s.gathered);
 			s.gathered = nullptr;
 		}
 		if (s.comm && nccl) (void)nccl->CommDestroy(s.comm);
@@ -368,10 +368,10 @@ namespace na
 			CheckHip(hipSetDevice(s.device), "hipSetDevice");
 			if (s.gatheredFloats < totalFloats)
 			{
-				if (s.gathered) (void)hipFree(s.gathered);
+				if (s.gathered) (void)CountedHipFree(s.gathered);
 				s.gathered = nullptr;
 				s.gatheredFloats = 0;
-				CheckHip(hipMalloc(reinterpret_cast<void**>(&s.gathered), totalFloats * sizeof(float)), "hipMalloc");
+				CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&s.gathered), totalFloats * sizeof(float)), "hipMalloc");
 				s.gatheredFloats = totalFloats;
 			}
 			hipStream_t st = s.batch->GetStream();

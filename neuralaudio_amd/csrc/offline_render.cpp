@@ -44,7 +44,7 @@ namespace na
 			T* Alloc(size_t count)
 			{
 				void* p = nullptr;
-				CheckHip(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)), "hipMalloc (offline render)");
+				CheckHip(CountedHipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)), "hipMalloc (offline render)");
 				ptrs.push_back(p);
 				return (T*)p;
 			}
@@ -62,7 +62,7 @@ namespace na
 						std::this_thread::sleep_for(std::chrono::microseconds(50));
 					}
 				}
-				for (void* p : ptrs) (void)hipFree(p);
+				for (void* p : ptrs) (void)CountedHipFree(p);
 				if (stream) (void)hipStreamDestroy(stream);
 			}
 		};
@@ -283,7 +283,7 @@ namespace na
 		float* dSig = mem.Alloc<float>((size_t)windowFloats);
 		float* dOut = mem.Alloc<float>((size_t)windowFloats);
 		RenderRow* dRows = mem.Alloc<RenderRow>((size_t)rows);
-		CheckHip(hipStreamCreateWithFlags(&mem.stream, hipStreamNonBlocking), "hipStreamCreate");
+		CheckHip(CountedHipStreamCreateWithFlags(&mem.stream, hipStreamNonBlocking), "hipStreamCreate");
 		hipStream_t rs = mem.stream;
 
 		std::vector<RenderRow> table((size_t)rows);
@@ -490,7 +490,7 @@ namespace na
 		}
 		// the coefficient tables of every pair that resamples
 		std::vector<float*> dUp(lay.plans.size(), nullptr), dDown(lay.plans.size(), nullptr);
-		CheckHip(hipStreamCreateWithFlags(&mem.stream, hipStreamNonBlocking), "hipStreamCreate");
+		CheckHip(CountedHipStreamCreateWithFlags(&mem.stream, hipStreamNonBlocking), "hipStreamCreate");
 		hipStream_t rs = mem.stream;
 		std::vector<std::vector<float>> tables; // (alive until the uploads are waited for)
 		for (size_t k = 0; k < lay.plans.size(); k++)
@@ -560,7 +560,7 @@ namespace na
 		if (resamples)
 		{
 			void* p = nullptr;
-			CheckHip(hipMalloc(&p, 2 * (size_t)numJobs * sizeof(OfflineResampleJob)), "hipMalloc (offline render)");
+			CheckHip(CountedHipMalloc(&p, 2 * (size_t)numJobs * sizeof(OfflineResampleJob)), "hipMalloc (offline render)");
 			mem.ptrs.push_back(p);
 			dJobs = (OfflineResampleJob*)p;
 			CheckHip(hipMemcpyAsync(dJobs, up.data(), (size_t)numJobs * sizeof(OfflineResampleJob), hipMemcpyHostToDevice, rs), "hipMemcpyAsync (resample jobs)");

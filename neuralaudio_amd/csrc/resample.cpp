@@ -147,8 +147,8 @@ namespace na
 			const std::vector<float> h = ResamplePrototype(p);
 			std::vector<float> up, down;
 			ResampleTables(p, h, up, down);
-			CheckHip(hipMalloc(reinterpret_cast<void**>(&rs->tableUp), up.size() * sizeof(float)), "hipMalloc");
-			CheckHip(hipMalloc(reinterpret_cast<void**>(&rs->tableDown), down.size() * sizeof(float)), "hipMalloc");
+			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&rs->tableUp), up.size() * sizeof(float)), "hipMalloc");
+			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&rs->tableDown), down.size() * sizeof(float)), "hipMalloc");
 			CheckHip(hipMemcpy(rs->tableUp, up.data(), up.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
 			CheckHip(hipMemcpy(rs->tableDown, down.data(), down.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
 			rs->sizedFrames = std::min(maxFrames, piece);
@@ -167,7 +167,7 @@ namespace na
 		}
 		catch (...)
 		{
-			if (!IsBroken()) (void)hipFree(fresh);
+			if (!IsBroken()) (void)CountedHipFree(fresh);
 			throw;
 		}
 	}
@@ -182,7 +182,7 @@ namespace na
 		WaitStreamBounded(stream, "hipStreamSynchronize");
 		auto grow = [&](float*& block, size_t rowFloats, bool keep) {
 			float* fresh = nullptr;
-			CheckHip(hipMalloc(reinterpret_cast<void**>(&fresh), (size_t)cap * rowFloats * sizeof(float)), "hipMalloc");
+			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&fresh), (size_t)cap * rowFloats * sizeof(float)), "hipMalloc");
 			// (on the batch stream, not the legacy stream: another shard of a multi batch may be capturing a graph on its own stream, and
 			// a legacy-stream operation would have to wait for that stream)
 			hipError_t e = hipMemsetAsync(fresh, 0, (size_t)cap * rowFloats * sizeof(float), stream);
@@ -190,11 +190,11 @@ namespace na
 				e = hipMemcpyAsync(fresh, block, (size_t)r.rowCapacity * rowFloats * sizeof(float), hipMemcpyDeviceToDevice, stream);
 			if (e != hipSuccess)
 			{
-				(void)hipFree(fresh);
+				(void)CountedHipFree(fresh);
 				CheckHip(e, "resampling: growing the row blocks");
 			}
 			WaitFresh(fresh);
-			if (block) (void)hipFree(block);
+			if (block) (void)CountedHipFree(block);
 			block = fresh;
 		};
 		grow(r.histUp, (size_t)p.histUp, true);
@@ -215,15 +215,15 @@ namespace na
 		for (float** block : { &r.modelIn, &r.modelOut })
 		{
 			float* fresh = nullptr;
-			CheckHip(hipMalloc(reinterpret_cast<void**>(&fresh), (size_t)r.rowCapacity * (size_t)stride * sizeof(float)), "hipMalloc");
+			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&fresh), (size_t)r.rowCapacity * (size_t)stride * sizeof(float)), "hipMalloc");
 			const hipError_t e = hipMemsetAsync(fresh, 0, (size_t)r.rowCapacity * (size_t)stride * sizeof(float), stream); // (see EnsureResampleRows)
 			if (e != hipSuccess)
 			{
-				(void)hipFree(fresh);
+				(void)CountedHipFree(fresh);
 				CheckHip(e, "hipMemsetAsync");
 			}
 			WaitFresh(fresh);
-			if (*block) (void)hipFree(*block);
+			if (*block) (void)CountedHipFree(*block);
 			*block = fresh;
 		}
 		r.sizedFrames = (int)n;

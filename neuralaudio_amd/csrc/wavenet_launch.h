@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "device_resources.h"
 #include "tuning.h"
 #include "wavenet_dev.h"
 
@@ -80,7 +81,7 @@ namespace na
 		void Clear()
 		{
 			for (Entry& e : entries)
-				if (e.dev) (void)hipFree(e.dev);
+				if (e.dev) (void)CountedHipFree(e.dev);
 			entries.clear();
 		}
 		void NewGeneration(unsigned long g)
@@ -102,12 +103,12 @@ namespace na
 			if (capturing != hipStreamCaptureStatusNone) return hipErrorStreamCaptureUnsupported; // (the prepare pass has not seen this table: a bug)
 			if (entries.size() >= 16) Clear(); // contents that change without a topology change: keep the table bounded
 			Entry e;
-			hipError_t err = hipMalloc(&e.dev, bytes);
+			hipError_t err = CountedHipMalloc(&e.dev, bytes);
 			if (err != hipSuccess) return err;
 			err = hipMemcpy(e.dev, fresh, bytes, hipMemcpyHostToDevice);
 			if (err != hipSuccess)
 			{
-				(void)hipFree(e.dev);
+				(void)CountedHipFree(e.dev);
 				return err;
 			}
 			e.host.assign(static_cast<const char*>(fresh), static_cast<const char*>(fresh) + bytes);
@@ -210,4 +211,9 @@ namespace na
 	hipError_t LaunchWaveNetFillRings(float* state, int stateF4, const int* slots, int numStreams, int numRings, const int* ringOffF4,
 		const int* ringFrames, const int* ringG, const float* cols, hipStream_t stream, bool splitFormat, const int* sub = nullptr, int pack = 1,
 		bool zero = false); // packed groups: (slots[i], sub[i]) = one real stream, only its channel groups are written (see the kernel)
+
+	// Pool re-arm in one launch: every entry (= member * 2 + fill) ends up as Reset + Prewarm (fill) or Reset alone leaves a state slot --
+	// whole slot for an unpacked member, its own channel groups of the virtual stream for a packed one (WaveNetRearmKernel).
+	hipError_t LaunchWaveNetRearm(float* state, int stateF4, const int* entries, int numEntries, int numRings, const int* ringOffF4,
+		const int* ringFrames, const int* ringG, const float* cols, hipStream_t stream, bool splitFormat, int pack);
 }

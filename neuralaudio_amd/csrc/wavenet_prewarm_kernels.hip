@@ -109,18 +109,14 @@ namespace na
 		return f32x4{ __builtin_bit_cast(float, h01), __builtin_bit_cast(float, h23), __builtin_bit_cast(float, l01), __builtin_bit_cast(float, l23) };
 	}
 
-	// grid = (streams to fill, rings), block = 256: fill ring r of stream slot with its steady-state column.
+	// Ring r of the stream state `st` takes its steady-state column (zero != 0: zeros), block = 256 threads.
 	// split == 0: f32 quads in the tile layout (frame kernel); split == 1: split quads, frame-major rings (f16-split kernel).
-	// Packed groups (pack > 1, split format): entry i names one REAL stream = (virtual stream slots[i], position sub[i]); only the
-	// channel groups of that position are written and the cursors -- shared by the streams of a virtual stream -- are left alone (a
-	// steady-state column fills every ring position, so where the cursor stands does not matter).  zero != 0: zeros instead of the column.
-	__global__ void __launch_bounds__(256) WaveNetFillRingsKernel(f32x4* __restrict__ state, int stateF4, const int* __restrict__ slots,
-		const int* __restrict__ ringOffF4, const int* __restrict__ ringFrames, const int* __restrict__ ringG, const float* __restrict__ cols, int split,
-		const int* __restrict__ sub, int pack, int zero)
+	// Packed groups (pack > 1, split format): one REAL stream = position `sub` of the virtual stream; only the channel groups of that
+	// position are written and the cursors -- shared by the streams of a virtual stream -- are left alone (a steady-state column fills
+	// every ring position, so where the cursor stands does not matter).
+	__device__ __forceinline__ void FillRing(f32x4* __restrict__ st, int r, const int* __restrict__ ringOffF4, const int* __restrict__ ringFrames,
+		const int* __restrict__ ringG, const float* __restrict__ cols, int split, int sub, int pack, int zero)
 	{
-		const int slot = slots[blockIdx.x];
-		const int r = blockIdx.y;
-		f32x4* st = state + (size_t)slot * (size_t)stateF4;
 		const int G = ringG[r];
 		const int nF4 = (ringFrames[r] / 16) * G * 16;
 		f32x4* ring = st + ringOffF4[r];
@@ -130,7 +126,7 @@ namespace na
 			// a dense pack (wavenet_plan.cpp PackWaveNetDesc): G x 4 / pack = 2 channels per stream, two streams per channel group.  Of a
 			// split quad [h0 h1 | h2 h3 | l0 l1 | l2 l3] the first stream of a pair owns dwords 0 and 2, the second one dwords 1 and 3:
 			// plain dword stores (streams of one virtual stream may be filled by different workgroups of this launch)
-			const int cgOwn = sub[blockIdx.x] >> 1, half = sub[blockIdx.x] & 1;
+			const int cgOwn = sub >> 1, half = sub & 1;
 			float* ringW = reinterpret_cast<float*>(ring);
 			for (int idx = threadIdx.x; idx < nF4; idx += blockDim.x)
 			{
@@ -140,9 +136,9 @@ namespace na
 				ringW[(size_t)idx * 4 + half] = half ? v.y : v.x;
 				ringW[(size_t)idx * 4 + 2 + half] = half ? v.w : v.z;
 			}
-			return; // (packed: the cursors are left alone)
+			return;
 		}
-		const int cgFirst = pack > 1 ? sub[blockIdx.x] * gs : 0;
+		const int cgFirst = pack > 1 ? sub * gs : 0;
 		for (int idx = threadIdx.x; idx < nF4; idx += blockDim.x)
 		{
 			const int cg = split ? (idx % G) : ((idx >> 4) % G);
@@ -151,7 +147,53 @@ namespace na
 			const f32x4 v = zero ? f32x4{ 0.0f, 0.0f, 0.0f, 0.0f } : f32x4{ c[0], c[1], c[2], c[3] };
 			ring[idx] = split ? SplitQuadBits(v) : v;
 		}
+	}
+
+	// grid = (streams to fill, rings), block = 256: fill ring r of stream slot with its steady-state column (FillRing).
+	// Packed groups: entry i names one REAL stream = (virtual stream slots[i], position sub[i]).  zero != 0: zeros instead of the column.
+	__global__ void __launch_bounds__(256) WaveNetFillRingsKernel(f32x4* __restrict__ state, int stateF4, const int* __restrict__ slots,
+		const int* __restrict__ ringOffF4, const int* __restrict__ ringFrames, const int* __restrict__ ringG, const float* __restrict__ cols, int split,
+		const int* __restrict__ sub, int pack, int zero)
+	{
+		const int slot = slots[blockIdx.x];
+		const int r = blockIdx.y;
+		f32x4* st = state + (size_t)slot * (size_t)stateF4;
+		FillRing(st, r, ringOffF4, ringFrames, ringG, cols, split, pack > 1 ? sub[blockIdx.x] : 0, pack, zero);
 		if (pack <= 1 && r == 0 && threadIdx.x < WN_MAX_RINGS) reinterpret_cast<int*>(st)[threadIdx.x] = 0; // cursors
+	}
+
+	// Pool re-arm (GpuBatch::ActivateStream): ONE launch that leaves every listed member in the state a Reset + Prewarm
+	// pair (or a Reset alone) leaves.  grid = (entries, rings + 1), block = 256; entry = member * 2 + fill (fill == 0: cleared, not
+	// prewarmed).  Workgroup (i, r < rings) writes ring r -- column or zeros; workgroup (i, rings) clears what lies outside the rings: the
+	// header (cursors, the range-event word) and the gaps between rings.  The two sets of quads are disjoint, so the workgroups need no
+	// order.  Packed groups (pack > 1): a member owns channel groups -- in a dense pack two dwords of a shared split quad -- of a virtual
+	// stream whose other members may be running: only those are written, header and cursors stay (workgroup (i, rings) has nothing to do).
+	__global__ void __launch_bounds__(256) WaveNetRearmKernel(f32x4* __restrict__ state, int stateF4, const int* __restrict__ entries, int numRings,
+		const int* __restrict__ ringOffF4, const int* __restrict__ ringFrames, const int* __restrict__ ringG, const float* __restrict__ cols, int split, int pack)
+	{
+		const int entry = entries[blockIdx.x];
+		const int member = entry >> 1, zero = (entry & 1) ? 0 : 1;
+		const int r = blockIdx.y;
+		f32x4* st = state + (size_t)(member / pack) * (size_t)stateF4;
+		if (r < numRings)
+		{
+			FillRing(st, r, ringOffF4, ringFrames, ringG, cols, split, member % pack, pack, zero);
+			return;
+		}
+		if (pack > 1) return;
+		__shared__ int lo[WN_MAX_RINGS], hi[WN_MAX_RINGS];
+		if (threadIdx.x < numRings)
+		{
+			lo[threadIdx.x] = ringOffF4[threadIdx.x];
+			hi[threadIdx.x] = ringOffF4[threadIdx.x] + (ringFrames[threadIdx.x] / 16) * ringG[threadIdx.x] * 16;
+		}
+		__syncthreads();
+		for (int idx = threadIdx.x; idx < stateF4; idx += blockDim.x)
+		{
+			bool inRing = false;
+			for (int q = 0; q < numRings; q++) inRing = inRing || (idx >= lo[q] && idx < hi[q]);
+			if (!inRing) st[idx] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+		}
 	}
 
 	// ------------------------------------------------------------------------------------------ launchers
@@ -173,6 +215,16 @@ namespace na
 		if (numStreams <= 0) return hipSuccess;
 		hipLaunchKernelGGL(WaveNetFillRingsKernel, dim3((unsigned)numStreams, (unsigned)numRings), dim3(256), 0, stream,
 			reinterpret_cast<f32x4*>(state), stateF4, slots, ringOffF4, ringFrames, ringG, cols, splitFormat ? 1 : 0, sub, pack, zero ? 1 : 0);
+		return hipGetLastError();
+	}
+
+	hipError_t LaunchWaveNetRearm(float* state, int stateF4, const int* entries, int numEntries, int numRings, const int* ringOffF4,
+		const int* ringFrames, const int* ringG, const float* cols, hipStream_t stream, bool splitFormat, int pack)
+	{
+		if (numEntries <= 0) return hipSuccess;
+		if (numRings > WN_MAX_RINGS) return hipErrorInvalidValue;
+		hipLaunchKernelGGL(WaveNetRearmKernel, dim3((unsigned)numEntries, (unsigned)numRings + 1u), dim3(256), 0, stream,
+			reinterpret_cast<f32x4*>(state), stateF4, entries, numRings, ringOffF4, ringFrames, ringG, cols, splitFormat ? 1 : 0, pack);
 		return hipGetLastError();
 	}
 

@@ -8,6 +8,9 @@
 //       half / half (architecture-sorted), which exercises the cost-balanced cut.
 //   HostPipeBench <model file> [streams] [frames] [buffers=64] --migrate K [--devices a,b]
 //       the stream-snapshot example (RunMigrate below): moves K streams half way through and checks the result against an unmoved run.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --churn K [--churn-legacy] [--churn-every E=10]
+//       join and leave on a batch that never stops (RunChurn below): every E-th buffer K streams leave or come back -- through the pool
+//       (NA_BatchParkStream / NA_BatchActivateStream) or, with --churn-legacy, through NA_BatchRemoveStreams / NA_BatchAddStreams.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -201,21 +204,129 @@ static int RunMigrate(NeuralModel* model, const std::vector<int>& devices, int s
 	return ok ? 0 : 3;
 }
 
+// --churn K: `streams` streams run `buffers` buffers through the pipelined host interface (two tickets in flight); in front of every
+// E-th buffer the first K streams leave, E buffers later they come back, and so on.  Pool variant: the streams come from
+// NA_BatchReserveStreams and move with NA_BatchParkStream / NA_BatchActivateStream; --churn-legacy: NA_BatchRemoveStreams /
+// NA_BatchAddStreams(doPrewarm = 1) (the ids are recycled).  Prints the cost of the calls (host wall time per event of K streams), the
+// mean and the longest buffer period (Collect to Collect) of the run and of the same run without churn, and -- pool variant -- the mean
+// period with the K streams parked (holes: index lists instead of the contiguous fast path) against all streams active.  The final
+// buffer of the last stream, which never moved, must equal the run without churn bit for bit (exit code 3 otherwise).
+struct ChurnRun
+{
+	double meanUs = 0.0, maxUs = 0.0, leaveUs = 0.0, joinUs = 0.0, leaveMaxUs = 0.0, joinMaxUs = 0.0, holesUs = 0.0, fullUs = 0.0;
+	std::vector<float> lastRow;
+};
+
+static int RunChurnVariant(NeuralModel* model, int streams, int frames, int buffers, int K, int every, int variant /* 0 none, 1 pool, 2 legacy */, ChurnRun& result)
+{
+	NA_Batch* batch = NA_BatchCreate(0, nullptr);
+	CHECK(batch != nullptr);
+	if (variant == 1)
+	{
+		CHECK(NA_BatchReserveStreams(batch, model, streams, 1) == 0);
+		for (int s = 0; s < streams; s++) CHECK(NA_BatchActivateStream(batch, s, 1.0f) == 0);
+	}
+	else CHECK(NA_BatchAddStreams(batch, model, 1.0f, streams, 1) == 0);
+	const size_t count = (size_t)streams * frames;
+	std::vector<std::vector<float>> in(8, std::vector<float>(count));
+	for (size_t b = 0; b < in.size(); b++)
+		for (size_t i = 0; i < count; i++) in[b][i] = 0.5f * (float)((((i + b * 7919u) * 2654435761u) >> 8) & 0xffff) / 65536.0f - 0.25f;
+	std::vector<float> out(count);
+	std::vector<double> tLeave, tJoin;
+	bool away = false;
+	auto event = [&]() -> int {
+		const double t0 = Now();
+		if (variant == 1)
+			for (int s = 0; s < K; s++) CHECK((away ? NA_BatchActivateStream(batch, s, 1.0f) : NA_BatchParkStream(batch, s)) == 0);
+		else if (away) CHECK(NA_BatchAddStreams(batch, model, 1.0f, K, 1) == 0);
+		else CHECK(NA_BatchRemoveStreams(batch, 0, K) == 0);
+		(away ? tJoin : tLeave).push_back((Now() - t0) * 1e6);
+		away = !away;
+		return 0;
+	};
+	auto loop = [&](int n, int firstBuffer, bool churn, double& meanUs, double& maxUs) -> int {
+		int pending = NA_BatchSubmit(batch, in[(size_t)firstBuffer % in.size()].data(), (size_t)frames);
+		CHECK(pending >= 0);
+		double last = Now(), sum = 0.0;
+		maxUs = 0.0;
+		for (int i = 1; i <= n; i++)
+		{
+			if (churn && variant != 0 && i % every == 0 && i < n && event() != 0) return 1;
+			int next = -1;
+			if (i < n)
+			{
+				next = NA_BatchSubmit(batch, in[(size_t)(firstBuffer + i) % in.size()].data(), (size_t)frames);
+				CHECK(next >= 0);
+			}
+			CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
+			const double now = Now();
+			if (i > 20) // (the first buffers: first-use set-up of the pipelined interface)
+			{
+				sum += (now - last) * 1e6;
+				maxUs = std::max(maxUs, (now - last) * 1e6);
+			}
+			last = now;
+			pending = next;
+		}
+		meanUs = sum / std::max(1, n - 20);
+		return 0;
+	};
+	if (loop(buffers, 0, true, result.meanUs, result.maxUs) != 0) return 1;
+	if (away && event() != 0) return 1; // everybody is back for the final buffer
+	CHECK(NA_BatchProcess(batch, in[1].data(), out.data(), (size_t)frames) == 0);
+	result.lastRow.assign(out.begin() + (long)((size_t)(streams - 1) * frames), out.end());
+	if (variant == 1)
+	{
+		double ignored = 0.0;
+		if (loop(std::max(buffers / 4, 40), 0, false, result.fullUs, ignored) != 0) return 1;
+		for (int s = 0; s < K; s++) CHECK(NA_BatchParkStream(batch, s * 2 + 1) == 0); // (holes, not a prefix: RunChurn holds K to half the streams)
+		if (loop(std::max(buffers / 4, 40), 0, false, result.holesUs, ignored) != 0) return 1;
+	}
+	result.leaveUs = Median(tLeave);
+	result.joinUs = Median(tJoin);
+	result.leaveMaxUs = tLeave.empty() ? 0.0 : *std::max_element(tLeave.begin(), tLeave.end());
+	result.joinMaxUs = tJoin.empty() ? 0.0 : *std::max_element(tJoin.begin(), tJoin.end());
+	NA_BatchDestroy(batch);
+	return 0;
+}
+
+static int RunChurn(NeuralModel* model, int streams, int frames, int buffers, int K, int every, bool legacy)
+{
+	CHECK(K >= 1 && 2 * K <= streams && every >= 1 && buffers > 2 * every + 20);
+	ChurnRun quiet, churned;
+	if (RunChurnVariant(model, streams, frames, buffers, K, every, 0, quiet) != 0) return 1;
+	if (RunChurnVariant(model, streams, frames, buffers, K, every, legacy ? 2 : 1, churned) != 0) return 1;
+	const bool identical = quiet.lastRow.size() == churned.lastRow.size() &&
+		std::memcmp(quiet.lastRow.data(), churned.lastRow.data(), quiet.lastRow.size() * sizeof(float)) == 0;
+	std::printf("{\"churn\": %d, \"variant\": \"%s\", \"every\": %d, \"streams\": %d, \"frames\": %d, \"buffers\": %d, "
+		"\"leave_us\": {\"p50\": %.1f, \"max\": %.1f}, \"join_us\": {\"p50\": %.1f, \"max\": %.1f}, "
+		"\"buffer_period_us\": {\"mean\": %.1f, \"max\": %.1f}, \"no_churn_buffer_period_us\": {\"mean\": %.1f, \"max\": %.1f}, ",
+		K, legacy ? "remove + add" : "pool", every, streams, frames, buffers, churned.leaveUs, churned.leaveMaxUs, churned.joinUs, churned.joinMaxUs,
+		churned.meanUs, churned.maxUs, quiet.meanUs, quiet.maxUs);
+	if (!legacy) std::printf("\"all_active_buffer_period_us\": %.1f, \"with_%d_parked_holes_buffer_period_us\": %.1f, ", churned.fullUs, K, churned.holesUs);
+	std::printf("\"unchurned_stream_identical\": %s}\n", identical ? "true" : "false");
+	return identical ? 0 : 3;
+}
+
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
-	int migrate = 0;
+	int migrate = 0, churn = 0, churnEvery = 10;
+	bool churnLegacy = false;
 	for (int i = 1; i < argc; i++)
 	{
 		if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--fan-in") && i + 1 < argc) rcclFanIn = !std::strcmp(argv[++i], "rccl");
 		else if (!std::strcmp(argv[i], "--mix") && i + 1 < argc) mixFile = argv[++i];
 		else if (!std::strcmp(argv[i], "--migrate") && i + 1 < argc) migrate = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--churn") && i + 1 < argc) churn = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--churn-every") && i + 1 < argc) churnEvery = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--churn-legacy")) churnLegacy = true;
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
 			// rehearsal on a one-GPU box: the multi-GPU host bound to the library's loopback RCCL table (test build only), so that
@@ -241,6 +352,13 @@ int main(int argc, char** argv)
 	if (migrate > 0)
 	{
 		const int rc = RunMigrate(model, devices, streams, frames, pos.size() > 3 ? buffers : 64, migrate);
+		DeleteModel(model);
+		DeleteLoader(loader);
+		return rc;
+	}
+	if (churn > 0)
+	{
+		const int rc = RunChurn(model, streams, frames, buffers, churn, churnEvery, churnLegacy);
 		DeleteModel(model);
 		DeleteLoader(loader);
 		return rc;
