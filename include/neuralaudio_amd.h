@@ -414,6 +414,15 @@ NA_EXTERN void NA_DebugSetWaveNetSpec(int on);
  * environment NA_REC_QUAD_MIN); returns the previous value.  NA_DebugRecurrentQuadLaunches: launches of that kernel so far. */
 NA_EXTERN int NA_DebugSetRecurrentQuadMin(int streams);
 NA_EXTERN long long NA_DebugRecurrentQuadLaunches(void);
+/* Tests: how the runtime-shaped recurrent kernel (RecurrentWaveRtKernel) runs a recurrent model, host side only (no device needed):
+ * out = { 1 if the model runs on that kernel, waves per stream (1: wave fences; 2 .. 16: a workgroup with barriers), gate rows per lane,
+ * 1 if the gate weights are streamed from L2 (0: they sit in LDS), 1 if the head is evaluated inside the sample loop, dynamic LDS bytes };
+ * the launcher reads the same plan.  Returns 0, or -1 when the model is not a single LSTM / GRU / keras stack. */
+NA_EXTERN int NA_DebugRecurrentPlan(NeuralModel* model, int out[6]);
+/* ... and for a shape alone (cell: 0 LSTM, 1 GRU; tailLayers / tailWidth / tailHistory: the dense / conv1d chain of a keras stack, zeros for
+ * the classic head), with rpl > 0 / forceL2w >= 0 in place of the tuning knobs NA_REC_RPL / NA_REC_L2W (0 / -1: the knobs).  Returns 1 if
+ * the loader's shape predicate of this kernel admits the shape, 0 if not, -1 on a bad argument. */
+NA_EXTERN int NA_DebugRecurrentShapePlan(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, int rpl, int forceL2w, int out[6]);
 /* Tests: export / import kernel launches of the stream snapshots so far (one per model group and call, whatever the stream count) */
 NA_EXTERN long long NA_DebugSnapshotLaunches(void);
 /* Tests: which implementation of the NCCL entry points the multi-GPU host binds.  0 = librccl.so (the product).  1 = a loopback table

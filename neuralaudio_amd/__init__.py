@@ -52,6 +52,22 @@ def debug_set_rccl_api(mode, fail_send_at=0, rendezvous_ms=0):
     capi.load_library().NA_DebugSetRcclApi(int(mode), int(fail_send_at), int(rendezvous_ms))
 
 
+def _recurrent_plan_dict(out):
+    return {"runs": bool(out[0]), "waves": int(out[1]), "rows_per_lane": int(out[2]), "l2w": bool(out[3]), "head_in_loop": bool(out[4]),
+            "lds_bytes": int(out[5])}
+
+
+def recurrent_shape_plan(kind, hidden, layers=1, tail_layers=0, tail_width=0, tail_history=0, rpl=0, force_l2w=-1):
+    """Test hook, host side only (NA_DebugRecurrentShapePlan): how the runtime-shaped recurrent kernel would run an "lstm" / "gru" of this
+    shape; rpl > 0 / force_l2w >= 0 stand in for the tuning knobs.  "admitted": the loader's shape predicate of that kernel takes it."""
+    out = (C.c_int * 6)()
+    r = capi.load_library().NA_DebugRecurrentShapePlan(1 if kind == "gru" else 0, int(hidden), int(layers), int(tail_layers), int(tail_width),
+                                                       int(tail_history), int(rpl), int(force_l2w), out)
+    if r < 0:
+        raise NeuralAudioError("NA_DebugRecurrentShapePlan: bad argument")
+    return dict(_recurrent_plan_dict(out), admitted=bool(r))
+
+
 def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
@@ -136,6 +152,13 @@ class NeuralModel:
             raise NeuralAudioError(capi.last_error())
         return {"kernel": name.value.decode(), "input_limit": float(lim.value), "range_proven": bool(proven.value), "weights_ok": bool(wok.value),
                 "pack": int(pack.value)}
+
+    def RecurrentPlan(self):
+        """Test hook, host side only (NA_DebugRecurrentPlan): how the runtime-shaped recurrent kernel runs this LSTM / GRU / keras stack."""
+        out = (C.c_int * 6)()
+        if self._lib.NA_DebugRecurrentPlan(self._h, out) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return _recurrent_plan_dict(out)
 
     # -- stream snapshots (include/neuralaudio_amd.h, DESIGN.md 2.7) --------------------------------
     def SnapshotBytes(self):

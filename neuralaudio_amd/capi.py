@@ -38,7 +38,7 @@ NA_SYMBOLS = [
     "NA_SetResampleToExternalRate", "NA_GetProcessLatencySamples", "NA_GetModelProcessRate", "NA_DebugResampleTap",
     "NA_RenderOfflineAtRate", "NA_RenderPlanAtRate", "NA_DebugSetRenderTap", "NA_MultiSetResampling", "NA_MultiGetResampleInfo",
     "NA_BatchReserveStreams", "NA_BatchActivateStream", "NA_BatchParkStream", "NA_BatchIsParked", "NA_BatchFindParked", "NA_BatchNumParked",
-    "NA_DebugDeviceResourceCalls",
+    "NA_DebugDeviceResourceCalls", "NA_DebugRecurrentPlan", "NA_DebugRecurrentShapePlan",
 ]
 
 
@@ -149,6 +149,8 @@ def load_library():
         "NA_BatchFindParked": (C.c_int, [vp, vp]),
         "NA_BatchNumParked": (C.c_int, [vp]),
         "NA_DebugDeviceResourceCalls": (C.c_longlong, []),
+        "NA_DebugRecurrentPlan": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "NA_DebugRecurrentShapePlan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
         "NA_MultiCreate": (vp, [C.POINTER(C.c_int), C.c_int]),
         "NA_MultiDestroy": (None, [vp]),
         "NA_MultiAddStreams": (C.c_int, [vp, vp, C.c_float, C.c_int, C.c_int]),

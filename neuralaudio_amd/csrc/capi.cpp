@@ -337,6 +337,43 @@ int NA_DebugSplitPlan(NeuralModel* model, int* stages, int stageCapacity, unsign
 }
 #endif
 
+// The same plan for a shape alone (cell: 0 LSTM, 1 GRU; tail*: the dense / conv1d chain of a keras stack, zeros for the classic head), with
+// rpl > 0 / forceL2w >= 0 in place of the tuning knobs NA_REC_RPL / NA_REC_L2W.  Returns 1 if the loader's shape predicate for this
+// kernel admits the shape (lstm_dev.h RecurrentWaveShape), 0 if not, -1 on a bad argument.
+#ifndef NA_RELEASE
+int NA_DebugRecurrentShapePlan(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, int rpl, int forceL2w, int out[6])
+{
+	if (!out || (cell != 0 && cell != 1) || hidden < 1 || numLayers < 0 || tailLayers < 0) return -1;
+	const na::RecurrentPlan p = na::RecurrentWavePlan(cell == 1 ? na::LSTM_CELL_GRU : na::LSTM_CELL_LSTM, hidden, numLayers, tailLayers, tailWidth, tailHistory, true, rpl, forceL2w);
+	out[0] = p.runs; out[1] = p.waves; out[2] = p.rowsPerLane; out[3] = p.l2w; out[4] = p.headInLoop; out[5] = (int)p.ldsBytes;
+	return na::RecurrentWaveShape(hidden, numLayers, tailLayers > 0 ? tailWidth : 0, tailLayers > 0 ? tailHistory : 0) ? 1 : 0;
+}
+#endif
+
+// The runtime-shaped recurrent kernel's plan for a recurrent model (lstm_dev.h RecurrentWavePlan -- what the launcher reads), host side
+// only: out = { runs on RecurrentWaveRtKernel, waves per stream, gate rows per lane, weights streamed from L2, head inside the sample
+// loop, dynamic LDS bytes }; 0, or -1 when the model is not a single recurrent one.
+#ifndef NA_RELEASE
+int NA_DebugRecurrentPlan(NeuralModel* model, int out[6])
+{
+	int r = -1;
+	Guard([&] {
+		NeuralAudio::GpuModel* gm = model ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+		if (!gm || !out) throw std::runtime_error("NA_DebugRecurrentPlan: not a model of this library");
+		const auto& lm = gm->GetLoadedModel();
+		if (lm->subModels.size() != 1 || lm->subModels[0].desc->kind != na::MODEL_LSTM) throw std::runtime_error("NA_DebugRecurrentPlan: not a recurrent model");
+		const na::LSTMDesc& d = lm->subModels[0].desc->lstm;
+		int tailWidth = 0, tailHistory = 0;
+		na::RecurrentTailDims(d, tailWidth, tailHistory);
+		const na::RecurrentPlan p = na::RecurrentWavePlan(d.cell == na::CELL_GRU ? na::LSTM_CELL_GRU : na::LSTM_CELL_LSTM, d.hiddenSize, d.numLayers, (int)d.tail.size(),
+			tailWidth, tailHistory);
+		out[0] = p.runs; out[1] = p.waves; out[2] = p.rowsPerLane; out[3] = p.l2w; out[4] = p.headInLoop; out[5] = (int)p.ldsBytes;
+		r = 0;
+	});
+	return r;
+}
+#endif
+
 void NA_SetDevice(NeuralModelLoader* loader, int device)
 {
 	if (loader) loader->loader->SetDevice(device);

@@ -865,9 +865,7 @@ namespace na
 				w.insert(w.end(), lstm.headWeights.begin(), lstm.headWeights.begin() + lstm.hiddenSize);
 				w.push_back(lstm.headBias);
 				dev.tailLayers = (int)lstm.tail.size(); // generic keras stack: a chain of dense / conv1d layers instead of the head
-				dev.tailWidth = 0;
-				dev.tailHistMax = 0;
-				for (const DenseLayerDesc& dl : lstm.tail) dev.tailHistMax = std::max(dev.tailHistMax, dl.History());
+				RecurrentTailDims(lstm, dev.tailWidth, dev.tailHistMax); // (model_desc.h)
 				int convRows = 0; // rows of conv1d input history behind the recurrent state's rows (zero at reset, like RTNeural's model->reset())
 				for (size_t t = 0; t < lstm.tail.size(); t++)
 				{
@@ -880,7 +878,6 @@ namespace na
 					dev.tailDil[t] = dl.dilation;
 					dev.tailHistRow[t] = lstm.numLayers * 2 * lstm.hiddenSize + convRows;
 					convRows += dl.History() * dl.in;
-					dev.tailWidth = std::max(dev.tailWidth, dev.tailHistMax > 0 ? std::max(dl.in, dl.out) : dl.out);
 					w.insert(w.end(), dl.w.begin(), dl.w.end());
 					w.insert(w.end(), dl.b.begin(), dl.b.end());
 					tailMacs += (double)dl.RowLen() * dl.out;
@@ -892,7 +889,7 @@ namespace na
 				{
 					// the gate matrices once more, transposed into [quad of inputs][row][4] (lstm_dev.h: LstmModelDev::wT)
 					const int H = lstm.hiddenSize, gateRows = ((lstm.cell == CELL_GRU) ? 3 : 4) * H;
-					dev.waves = RecurrentWaveWaves(gateRows);
+					dev.waves = RecurrentWavePlan(lstm.cell == CELL_GRU ? LSTM_CELL_GRU : LSTM_CELL_LSTM, H, lstm.numLayers, dev.tailLayers, dev.tailWidth, dev.tailHistMax).waves;
 					dev.rowsPad = (gateRows + 64 * dev.waves - 1) / (64 * dev.waves) * (64 * dev.waves);
 					std::vector<float> wt;
 					for (int l = 0; l < lstm.numLayers; l++)

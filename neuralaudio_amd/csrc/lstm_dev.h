@@ -38,32 +38,106 @@ namespace na
 	//   units the 1-unit head is evaluated inside the sample loop (no [samples][H] buffer) and a dense tail needs that buffer to fit.
 	constexpr int RECURRENT_WAVE_MAX_HIDDEN = 1024;
 	constexpr int RECURRENT_HEAD_IN_LOOP_FROM = 129; // hidden sizes from here on: classic head inside the sample loop
+	constexpr long RECURRENT_LDS_BYTES = 160L * 1024;
+#ifdef __HIPCC__
+#define NA_HOST_DEVICE __host__ __device__
+#else
+#define NA_HOST_DEVICE
+#endif
+	// the classic 1-unit head inside the sample loop (no [samples][H] buffer): wide layers without a dense / conv1d tail
+	NA_HOST_DEVICE inline bool RecurrentHeadInLoop(int hidden, bool hasTail) { return hidden >= RECURRENT_HEAD_IN_LOOP_FROM && !hasTail; }
+	// gate rows per lane of a stream's threads (the kernel's GateRowsL2Dispatch case; the LDS path strides its rows the same way)
+	NA_HOST_DEVICE inline int RecurrentRowsPerLane(int gateRows, int threads) { return (gateRows + threads - 1) / threads; }
 	// waves per stream of the runtime-shaped kernel: one gate row per lane up to 16 waves (the kernel is bound by the latency of its
 	// weight loads from L2, and more waves keep more of them in flight: LSTM 1x256 x 64 streams 2.32 / 1.63 / 1.34 ms per 128-sample
 	// block at four / two / one row per lane, LSTM 1x128 1.22 / 0.90 / 0.68; round 3, one wave: 2.0)
-	inline int RecurrentWaveWaves(int gateRows)
+	inline int RecurrentWaveWaves(int gateRows, int rpl)
 	{
-		const int rpl = Tuning::Get().recRpl; // tuning knob: gate rows per lane
 		int waves = 1;
 		while (waves < 16 && gateRows > 64 * rpl * waves) waves *= 2;
 		return waves;
 	}
 	// tailHistory > 0: the tail has conv1d layers -- it is evaluated layer by layer over the whole block (recurrent_tail.h ConvTail) and its two
 	// scratch arrays are [tailWidth][tailHistory + 128] (tailWidth then covers the widest INPUT of a tail layer as well)
-#ifdef __HIPCC__
-	__host__ __device__
-#endif
-	inline long RecurrentTailScratchFloats(int tailWidth, int tailHistory) { return tailHistory > 0 ? 2L * tailWidth * (tailHistory + LSTM_MAX_FRAMES) : 2L * tailWidth * 64; }
+	NA_HOST_DEVICE inline long RecurrentTailScratchFloats(int tailWidth, int tailHistory) { return tailHistory > 0 ? 2L * tailWidth * (tailHistory + LSTM_MAX_FRAMES) : 2L * tailWidth * 64; }
+	// LDS floats of RecurrentWaveRtKernel (its layout: lstm_kernels.hip), with or without the gate weights of all layers
+	// (tailWidth / tailHistory: 0 without a tail)
+	inline long RecurrentWaveLdsFloats(int cell, int hidden, int numLayers, int tailWidth, int tailHistory, bool hasTail, bool weightsInLds)
+	{
+		const long H = hidden, L = numLayers;
+		const long rowsPerLayer = (cell == LSTM_CELL_GRU ? 3 : 4) * H, biases = (cell == LSTM_CELL_GRU ? 6 : 4) * H;
+		const bool hseq = !RecurrentHeadInLoop(hidden, hasTail);
+		long f = LSTM_MAX_FRAMES + 2 * L * H + 6 * H + (hseq ? 2 * (L > 0 ? H : 1) * 64 : 0) + RecurrentTailScratchFloats(tailWidth, tailHistory);
+		if (weightsInLds)
+			for (int l = 0; l < numLayers; l++) f += rowsPerLayer * (long)(((l == 0 ? 1 : hidden) + hidden) | 1) + biases;
+		return f;
+	}
 	inline bool RecurrentWaveShape(int hidden, int numLayers, int tailWidth, int tailHistory = 0)
 	{
 		if (!(hidden >= 1 && hidden <= RECURRENT_WAVE_MAX_HIDDEN && numLayers >= (tailWidth > 0 ? 0 : 1) && numLayers <= LSTM_MAX_LAYERS &&
 			tailWidth <= std::max(LSTM_MAX_TAIL_WIDTH, tailHistory > 0 ? hidden : 0) && tailHistory <= LSTM_MAX_TAIL_HISTORY)) return false;
 		// LDS without the weights (they stream from L2 when they do not fit): xin | h, c | gates | [samples][H] of the last layer (small models
 		// and dense tails) | tail scratch
-		const bool hseq = hidden < RECURRENT_HEAD_IN_LOOP_FROM || tailWidth > 0;
+		const bool hseq = !RecurrentHeadInLoop(hidden, tailWidth > 0);
 		const long floats = LSTM_MAX_FRAMES + 2L * numLayers * hidden + 6L * hidden + (hseq ? 2L * (numLayers > 0 ? hidden : 1) * 64 : 0) +
 			RecurrentTailScratchFloats(tailWidth, tailHistory) + 64;
-		return floats * 4 <= 160L * 1024;
+		return floats * 4 <= RECURRENT_LDS_BYTES;
+	}
+	// shapes of the LDS-free kernels (recurrent_dpp_kernels.hip RecurrentDppSupported): hidden sizes below a layout (8 or 16 units per gate
+	// block) are padded into it: 12 (the reference's static 1x12 / 2x12) runs as 16 ... and one-layer LSTMs (the reference's static 1x24) /
+	// keras GRUs of 17 .. 32 units on the 32-unit layout
+	inline bool RecurrentDppShape(int cell, int hidden, int numLayers, int tailLayers)
+	{
+		if (tailLayers != 0) return false; // generic keras stacks run on the runtime-shaped kernels
+		if (cell != LSTM_CELL_LSTM && cell != LSTM_CELL_GRU) return false;
+		if (numLayers == 1 && hidden > 16 && hidden <= 32) return !Tuning::Get().recNoDpp32;
+		return hidden >= 1 && hidden <= 16 && (numLayers == 1 || numLayers == 2);
+	}
+
+	// THE decision of how a recurrent model runs on the runtime-shaped kernel (RecurrentWaveRtKernel), in one place: the launcher, the
+	// group that lays the weights out and the test hook (NA_DebugRecurrentPlan) all read it; the kernel shares RecurrentHeadInLoop /
+	// RecurrentRowsPerLane / RecurrentWaveLdsFloats' layout.  No HIP types: it works without a device.
+	struct RecurrentPlan
+	{
+		int runs;        // 1: the model runs on this kernel (0: a shaped / LDS-free kernel or a lane = stream kernel takes it; the rest is then what this kernel WOULD do)
+		int waves;       // waves per stream: 1 = RecurrentWaveRtKernel<64> (wave fences), 2 .. 16 = <1024> (barriers)
+		int rowsPerLane; // gate rows per lane, 1 .. 8
+		int l2w;         // 1: the gate weights are streamed transposed from L2, 0: they sit in LDS
+		int headInLoop;  // 1: the 1-unit head is evaluated inside the sample loop by the first wave
+		long ldsBytes;   // dynamic LDS of the launch
+	};
+	// haveWT: the transposed weight image exists (LstmModelDev::wT).  rpl > 0 / forceL2w >= 0: these instead of the tuning knobs NA_REC_RPL /
+	// NA_REC_L2W (tests ask for the default plan of a shape whatever the environment says)
+	inline RecurrentPlan RecurrentWavePlan(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, bool haveWT = true,
+		int rpl = 0, int forceL2w = -1)
+	{
+		const Tuning& t = Tuning::Get();
+		if (rpl <= 0) rpl = t.recRpl > 0 ? t.recRpl : 1; // tuning knob: gate rows per lane
+		const bool forceL2 = forceL2w >= 0 ? forceL2w != 0 : t.recL2w;
+		const bool gru = cell == LSTM_CELL_GRU, hasTail = tailLayers > 0, convTail = hasTail && tailHistory > 0;
+		const int gateRows = (gru ? 3 : 4) * hidden;
+		RecurrentPlan p = {};
+		p.waves = RecurrentWaveWaves(gateRows, rpl);
+		p.rowsPerLane = RecurrentRowsPerLane(gateRows, 64 * p.waves);
+		p.headInLoop = RecurrentHeadInLoop(hidden, hasTail) ? 1 : 0;
+		const int tw = hasTail ? tailWidth : 0, th = hasTail ? tailHistory : 0;
+		p.ldsBytes = RecurrentWaveLdsFloats(cell, hidden, numLayers, tw, th, hasTail, true) * 4;
+		// weights larger than the LDS (LSTM 2x64: 197 KB): streamed from L2, transposed for coalesced reads (NA_REC_L2W=1 forces the mode)
+		p.l2w = (p.ldsBytes > RECURRENT_LDS_BYTES || (forceL2 && numLayers > 0)) ? 1 : 0;
+		if (p.l2w) p.ldsBytes = RecurrentWaveLdsFloats(cell, hidden, numLayers, tw, th, hasTail, false) * 4;
+		// who runs first: without a tail the LDS-free kernels and the shaped one-wave instances (LstmWaveKernel: 8 .. 32 units, GruWaveKernel:
+		// 8 .. 20, one or two layers) take their shapes; tuning knobs send LSTMs to the lane = stream kernels -- except tails with conv1d
+		// layers, which only this kernel evaluates
+		bool shapedFirst = false;
+		if (!hasTail)
+		{
+			const bool listed = hidden == 8 || hidden == 12 || hidden == 16 || hidden == 20 || (!gru && (hidden == 24 || hidden == 32));
+			shapedFirst = (!(gru ? t.gruNoDpp : t.lstmNoDpp) && RecurrentDppShape(cell, hidden, numLayers, tailLayers)) || (listed && (numLayers == 1 || numLayers == 2));
+		}
+		const bool off = (t.lstmNoWaveRt || (!gru && t.lstmLaneKernel)) && !convTail;
+		p.runs = (!shapedFirst && !off && hidden >= 1 && hidden <= RECURRENT_WAVE_MAX_HIDDEN && numLayers >= 0 && !(numLayers == 0 && !hasTail) &&
+			(!p.l2w || haveWT) && p.ldsBytes <= RECURRENT_LDS_BYTES) ? 1 : 0;
+		return p;
 	}
 	// the lane = stream kernels' bound (LstmGenericKernel / GruGenericKernel: state of 64 streams in LDS)
 	inline bool LstmLaneKernelShape(int hidden, int numLayers, int tailWidth = 0)
@@ -116,6 +190,6 @@ namespace na
 		const float* wT;
 		int layerOffT[LSTM_MAX_LAYERS]; // float offsets into wT
 		int rowsPad; // (a multiple of 64 x waves)
-		int waves;   // waves per stream of the runtime-shaped kernel (RecurrentWaveWaves)
+		int waves;   // waves per stream of the runtime-shaped kernel (RecurrentWavePlan)
 	};
 }

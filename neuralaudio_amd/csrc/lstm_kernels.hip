@@ -344,18 +344,6 @@ namespace na
 	// ------------------------------------------------------------------------------------------------------------
 	__device__ __forceinline__ int OddStride(int w) { return w | 1; }
 
-	static size_t RecurrentWaveRtLdsFloats(const LstmModelDev& m, bool weightsInLds = true)
-	{
-		const int H = m.hidden, L = m.numLayers;
-		const int rowsPerLayer = (m.cell == LSTM_CELL_GRU ? 3 : 4) * H, biases = (m.cell == LSTM_CELL_GRU ? 6 : 4) * H;
-		const bool hseq = H < RECURRENT_HEAD_IN_LOOP_FROM || m.tailLayers > 0; // (else the head is evaluated inside the sample loop)
-		size_t f = (size_t)LSTM_MAX_FRAMES + (size_t)2 * L * H + (size_t)6 * H + (hseq ? (size_t)2 * (L > 0 ? H : 1) * 64 : 0) +
-			(size_t)RecurrentTailScratchFloats(m.tailLayers > 0 ? m.tailWidth : 0, m.tailLayers > 0 ? m.tailHistMax : 0);
-		if (weightsInLds)
-			for (int l = 0; l < L; l++) f += (size_t)rowsPerLayer * (size_t)(((l == 0 ? 1 : H) + H) | 1) + (size_t)biases;
-		return f;
-	}
-
 	// The dot products of the lane's gate rows r = lane + 64 i (i < RPL) from the transposed L2-resident weights (LstmModelDev::wT), all
 	// rows of the lane side by side: per quad of inputs RPL independent 1 KB weight loads per wave and one set of broadcast state reads
 	// (the rows of a lane were evaluated one after the other at first: LSTM 2x64 2.97 ms per block; side by side the loads of all rows
@@ -440,7 +428,7 @@ namespace na
 
 	__device__ __forceinline__ void GateRowsL2Dispatch(const LstmModelDev& m, int l, int lane, int nt, const float* sIn, const float* sH, float* gates)
 	{
-		const int rpl = (((m.cell == LSTM_CELL_GRU) ? 3 : 4) * m.hidden + nt - 1) / nt;
+		const int rpl = RecurrentRowsPerLane(((m.cell == LSTM_CELL_GRU) ? 3 : 4) * m.hidden, nt);
 		switch (rpl)
 		{
 		case 1: GateRowsL2<1>(m, l, lane, nt, sIn, sH, gates); break;
@@ -476,7 +464,7 @@ namespace na
 		float* hvec = xin + LSTM_MAX_FRAMES;   // [L][H]
 		float* cvec = hvec + L * H;            // [L][H] (LSTM)
 		float* gates = cvec + L * H;           // LSTM: [4H] activated gates; GRU: ai[3H] | ah[3H]
-		const bool headInLoop = H >= RECURRENT_HEAD_IN_LOOP_FROM && m.tailLayers == 0; // (no [samples][H] buffer then)
+		const bool headInLoop = RecurrentHeadInLoop(H, m.tailLayers > 0); // (no [samples][H] buffer then)
 		float* hseq = gates + 6 * H;           // [2][Hs][64]
 		float* tailA = hseq + (headInLoop ? 0 : (size_t)2 * Hs * 64);
 		const size_t tailOne = (size_t)RecurrentTailScratchFloats(m.tailLayers > 0 ? m.tailWidth : 0, m.tailLayers > 0 ? m.tailHistMax : 0) / 2;
@@ -628,19 +616,11 @@ namespace na
 	bool LaunchRecurrentWaveRt(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
 		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream, hipError_t& err)
 	{
-		// tuning knob / tests: the lane = stream kernels for every shape -- except tails with conv1d layers, which only this kernel evaluates
-		const bool off = Tuning::Get().lstmNoWaveRt && !(m.tailLayers > 0 && m.tailHistMax > 0);
-		if (off || m.hidden > RECURRENT_WAVE_MAX_HIDDEN || m.numLayers < 0 || (m.numLayers == 0 && m.tailLayers == 0)) return false;
-		size_t ldsBytes = RecurrentWaveRtLdsFloats(m) * sizeof(float);
-		// weights larger than the LDS (LSTM 2x64: 197 KB): streamed from L2, transposed for coalesced reads (NA_REC_L2W=1 forces the mode)
-		const bool forceL2 = Tuning::Get().recL2w;
-		const int l2w = (ldsBytes > 160 * 1024 || (forceL2 && m.numLayers > 0)) ? 1 : 0;
-		if (l2w)
-		{
-			if (m.wT == nullptr) return false;
-			ldsBytes = RecurrentWaveRtLdsFloats(m, false) * sizeof(float);
-			if (ldsBytes > 160 * 1024) return false;
-		}
+		// (lstm_dev.h RecurrentWavePlan: tuning knobs, LDS or L2-streamed weights, the LDS size)
+		const RecurrentPlan plan = RecurrentWavePlan(m.cell, m.hidden, m.numLayers, m.tailLayers, m.tailWidth, m.tailHistMax, m.wT != nullptr);
+		if (!plan.runs) return false;
+		const size_t ldsBytes = (size_t)plan.ldsBytes;
+		const int l2w = plan.l2w;
 		static PerDeviceOnce attr, attrBlock; // (hipFuncSetAttribute applies to the current device's copy of the kernel)
 		const int waves = m.waves > 1 ? m.waves : 1;
 		if (waves == 1)

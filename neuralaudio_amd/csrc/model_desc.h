@@ -83,6 +83,20 @@ namespace na
 		int mathMode = MATH_FAST; // LSTM only (the GRU follows RTNeural's accurate maths)
 	};
 
+	// what the kernels size their tail scratch by: the widest layer of the tail (with conv1d layers: the widest input or output of a tail
+	// layer) and the longest conv1d input history (0: no conv1d layer)
+	inline void RecurrentTailDims(const LSTMDesc& d, int& tailWidth, int& tailHistory)
+	{
+		tailWidth = 0;
+		tailHistory = 0;
+		for (const DenseLayerDesc& dl : d.tail) tailHistory = tailHistory > dl.History() ? tailHistory : dl.History();
+		for (const DenseLayerDesc& dl : d.tail)
+		{
+			const int w = (tailHistory > 0 && dl.in > dl.out) ? dl.in : dl.out;
+			tailWidth = tailWidth > w ? tailWidth : w;
+		}
+	}
+
 	// load-time checks (throw std::runtime_error): weight count (WaveNet.h:704-709) and the shapes the gfx950 kernels accept
 	void ValidateWaveNetDesc(const WaveNetDesc& desc);   // wavenet_plan.cpp
 	void ValidateRecurrentDesc(const LSTMDesc& desc);    // model_loader.cpp

@@ -1448,12 +1448,7 @@ namespace na
 
 	bool RecurrentDppSupported(const LstmModelDev& m)
 	{
-		// hidden sizes below a layout (8 or 16 units per gate block) are padded into it: 12 (the reference's static 1x12 / 2x12) runs as 16
-		// ... and one-layer LSTMs (the reference's static 1x24) / keras GRUs of 17 .. 32 units on the 32-unit layout
-		const bool no32 = Tuning::Get().recNoDpp32;
-		if (m.tailLayers != 0) return false; // generic keras stacks run on the runtime-shaped kernels
-		if ((m.cell == LSTM_CELL_LSTM || m.cell == LSTM_CELL_GRU) && m.numLayers == 1 && m.hidden > 16 && m.hidden <= 32) return !no32;
-		return m.hidden >= 1 && m.hidden <= 16 && (m.numLayers == 1 || m.numLayers == 2) && (m.cell == LSTM_CELL_LSTM || m.cell == LSTM_CELL_GRU);
+		return RecurrentDppShape(m.cell, m.hidden, m.numLayers, m.tailLayers); // (lstm_dev.h)
 	}
 
 	hipError_t LaunchRecurrentDppTable(const RecurrentGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,

@@ -644,6 +644,8 @@ struct na_oracle_gru {
 	float** bi;   /* per layer: [3H] input bias    */
 	float** bh;   /* per layer: [3H] recurrent bias */
 	float** h;    /* per layer: [H] */
+	float* ai;    /* [3H] scratch of one layer step: input-side pre-activations (then the new h) */
+	float* ah;    /* [3H] scratch: recurrent-side pre-activations */
 	float* head_w; float head_b;
 };
 
@@ -667,6 +669,7 @@ na_oracle_gru* na_oracle_gru_create_keras(int num_layers, int hidden, const floa
 		for (int j = 0; j < H; j++) for (int i = 0; i < R; i++) m->wh[l][(size_t)i * H + j] = recurrents[l][(size_t)j * R + i];
 		for (int i = 0; i < R; i++) { m->bi[l][i] = biases[l][i]; m->bh[l][i] = biases[l][R + i]; }
 	}
+	m->ai = (float*)calloc((size_t)R, sizeof(float)); m->ah = (float*)calloc((size_t)R, sizeof(float));
 	m->head_w = (float*)calloc((size_t)H, sizeof(float));
 	for (int i = 0; i < H; i++) m->head_w[i] = head_weights[i];
 	m->head_b = head_bias;
@@ -677,13 +680,14 @@ void na_oracle_gru_free(na_oracle_gru* m)
 {
 	if (!m) return;
 	for (int l = 0; l < m->num_layers; l++) { free(m->wi[l]); free(m->wh[l]); free(m->bi[l]); free(m->bh[l]); free(m->h[l]); }
-	free(m->wi); free(m->wh); free(m->bi); free(m->bh); free(m->h); free(m->head_w); free(m);
+	free(m->wi); free(m->wh); free(m->bi); free(m->bh); free(m->h); free(m->ai); free(m->ah); free(m->head_w); free(m);
 }
 
 static void gru_layer_step(na_oracle_gru* m, int l, const float* x)
 {
 	const int H = m->hidden, I = (l == 0) ? 1 : H;
-	float ai[3 * 256], ah[3 * 256]; /* H <= 256 */
+	float* ai = m->ai; /* (heap scratch sized from the hidden size at create: any H) */
+	float* ah = m->ah;
 	float* h = m->h[l];
 	for (int r = 0; r < 3 * H; r++) {
 		float a = 0.0f, b = 0.0f;

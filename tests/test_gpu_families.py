@@ -17,7 +17,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = os.path.join(ROOT, "tests")
 KNOBS = ("NA_WN_KERNEL", "NA_LSTM_NO_DPP", "NA_LSTM_LANE_KERNEL", "NA_REC_NOSKEW", "NA_WN_PACK", "NA_LSTM_NO_WAVE_RT", "NA_WN_SPEC", "NA_HOST_DIRECT",
-         "NA_REC_QUAD_MIN", "NA_HOST_HALVES", "NA_REC_RPL", "NA_WN_DENSE", "NA_BATCH_NO_GRAPH", "NA_REC_NOPIPE")
+         "NA_REC_QUAD_MIN", "NA_HOST_HALVES", "NA_REC_RPL", "NA_WN_DENSE", "NA_BATCH_NO_GRAPH", "NA_REC_NOPIPE", "NA_REC_L2W")
 
 SOAK = [{"NA_WN_SPEC": "0"}, {"NA_WN_KERNEL": "split"}, {"NA_WN_KERNEL": "split", "NA_SP_T": "4"}, {"NA_WN_KERNEL": "split", "NA_SP_GEN": "1"},
         {"NA_WN_KERNEL": "frame"}, {"NA_WN_KERNEL": "frame", "NA_FR_PF": "2"}, {"NA_WN_KERNEL": "frame", "NA_FR_PF": "0"},
@@ -29,6 +29,7 @@ SOAK = [{"NA_WN_SPEC": "0"}, {"NA_WN_KERNEL": "split"}, {"NA_WN_KERNEL": "split"
         {"NA_WN_DENSE": "0"},       # four Nano streams at 16 / 16 virtual channels (default: 16 / 8, two streams per channel group)
         {"NA_REC_RPL": "4"},        # runtime-shaped recurrent kernel: four gate rows per lane (a quarter of the waves per stream)
         {"NA_BATCH_NO_GRAPH": "1"}, # multi-unit batches: fork / join issued directly every buffer (the path of a runtime older than the build's)
+        {"NA_REC_L2W": "1"},        # runtime-shaped recurrent kernel: gate weights streamed from L2 also where they fit the LDS
         {"NA_REC_NOPIPE": "1"}]     # two-layer 16-unit LSTMs on one wave per stream (default: one wave per layer below 1536 waves)
 
 # the four fallbacks a deployment can actually land on, over the direct parity file only: part of -m gpu, a few seconds each
@@ -60,6 +61,19 @@ def test_forced_fallback_passes_the_parity_suite(env):
     # (the parity file needs no torch: the child skips the warm import -- 16 s on a good box; one r06 run on a box with slow storage
     # spent more than 100 s before the child's first test, hence the generous limit)
     forced_run(dict(env, NA_TEST_NO_WARM="1"), [os.path.join(T, "test_gpu_parity.py")], 240)
+
+
+# the runtime-shaped recurrent kernel's two forced regimes over its own file: every shape on L2-streamed weights (also the one-wave
+# shapes whose weights fit the LDS), and eight gate rows per lane (LSTMs of 600-odd, 769 and 1024 units reach dispatch cases 5, 7 and 8).
+# The regime assertions of that file skip under a knob; the parity assertions do not.
+RECURRENT_RT = [{"NA_REC_L2W": "1"}, {"NA_REC_RPL": "8"}]
+
+
+@pytest.mark.gpu
+@pytest.mark.watchdog(260)
+@pytest.mark.parametrize("env", RECURRENT_RT, ids=ident)
+def test_forced_recurrent_regime_passes_the_runtime_shaped_kernel_suite(env):
+    forced_run(dict(env, NA_TEST_NO_WARM="1"), [os.path.join(T, "test_gpu_recurrent_rt.py")], 240)
 
 
 @pytest.mark.gpu_soak

@@ -18,6 +18,7 @@ import pytest
 
 import na_oracle as O
 import ref_np
+import recurrent_cases as RC
 import wide_cases as WC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -334,7 +335,7 @@ def test_lstm_shapes_accepted_or_rejected_at_load(na, tmp_path):
     """Any hidden size the reference's dynamic LSTM takes loads (runtime-shaped kernel); what has no kernel fails at load, with a reason."""
     loader = na.NeuralModelLoader()
     path = tmp_path / "m.nam"
-    # (up to 1024 units whatever the weight size: streamed from L2, a workgroup of up to 16 waves per stream from 257 gate rows on)
+    # (up to 1024 units whatever the weight size: streamed from L2, a workgroup of up to 16 waves per stream from 65 gate rows on)
     for layers, hidden in ((1, 3), (1, 18), (3, 16), (2, 64), (3, 128), (2, 192), (1, 512)):
         path.write_text(O.nam_json_lstm(layers, hidden, O.synth_lstm_weights(layers, hidden, seed=hidden)))
         assert loader.CreateFromFile(str(path), doPrewarm=False) is not None
@@ -913,3 +914,87 @@ def test_wide_models_outside_the_operand_format_fail_at_load(na, name):
         ws = O.scale_wavenet_tensors(arrays, w, factors)
         with pytest.raises(na.NeuralAudioError, match=expect[case]):
             loader.CreateFromString(O.nam_json_wavenet_generic(arrays, ws), ".nam", doPrewarm=False)
+
+
+# ---- the runtime-shaped recurrent kernel's test shapes (tests/recurrent_cases.py, run by tests/test_gpu_recurrent_rt.py) --------------
+
+def _recurrent_knob_free():
+    if RC.knob_set():
+        pytest.skip("a recurrent tuning knob is set: the plan is not the default one")
+
+
+@pytest.mark.parametrize("c", RC.edge_cases(), ids=RC.case_id)
+def test_every_recurrent_case_loads_and_sits_in_the_regime_it_is_named_for(na, c):
+    """Without a GPU: the loader takes the case, and NA_DebugRecurrentPlan -- the plan the launcher reads -- says that it runs on the
+    runtime-shaped kernel with the wave count, rows per lane, weight path and head placement the case was generated for; at an edge
+    h - 1 | h the named field differs between the two sides."""
+    _recurrent_knob_free()
+    m = RC.Built(c).load(na)
+    p = m.RecurrentPlan()
+    assert p["runs"] and {f: int(p[f]) for f in RC.FIELDS} == c["regime"], (RC.case_id(c), p)
+    assert p["lds_bytes"] <= 160 * 1024
+    gate_rows = (3 if c["kind"] == "gru" else 4) * c["hidden"]
+    assert p["rows_per_lane"] == -(-gate_rows // (64 * p["waves"])) and (p["waves"] == 16 or p["rows_per_lane"] == 1)
+    assert p["head_in_loop"] == (c["hidden"] >= 129)
+    if " edge " in c["why"]:
+        field, _, pair = c["why"].split(" ")
+        lo, hi = (int(v) for v in pair.split("|"))
+        assert RC.regime(c["kind"], lo, c["layers"])[field] != RC.regime(c["kind"], hi, c["layers"])[field], c["why"]
+    m.close()
+
+
+def test_recurrent_cases_reach_every_regime_of_the_kernel(na):
+    """The set of cases (the keras stacks with tails included) reaches every wave count, every rows-per-lane count a cell type can have
+    (a GRU has 3 x 1024 gate rows at most: three per lane), both weight paths on one and on several waves, both head placements and
+    every H % 4 on both weight paths, for both cell types; the tail stacks load and sit where tests/test_gpu_recurrent_rt.py expects."""
+    _recurrent_knob_free()
+    import json
+    regimes = [(c["kind"], c["hidden"], c["regime"]) for c in RC.edge_cases()]
+    for spec in RC.TAIL_STACKS:
+        kind, hidden = RC.stack_dims(spec)[:2]
+        regimes.append((kind, hidden, RC.stack_regime(spec)))
+        m = na.NeuralModelLoader().CreateFromString(json.dumps(ref_np.synth_keras_stack(spec, seed=40 + len(spec))), ".json", doPrewarm=False)
+        assert m is not None and m.RecurrentPlan()["runs"], spec
+        assert {f: int(m.RecurrentPlan()[f]) for f in RC.FIELDS} == RC.stack_regime(spec), spec
+    for kind in ("lstm", "gru"):
+        mine = [(h, r) for k, h, r in regimes if k == kind]
+        assert {r["waves"] for _, r in mine} == {1, 2, 4, 8, 16}, kind
+        assert {r["rows_per_lane"] for _, r in mine} == ({1, 2, 3, 4} if kind == "lstm" else {1, 2, 3}), kind
+        assert {r["head_in_loop"] for _, r in mine} == {0, 1}, kind
+        for l2w in (0, 1):
+            assert {h % 4 for h, r in mine if r["l2w"] == l2w} == {0, 1, 2, 3}, (kind, l2w)
+            assert any(r["waves"] > 1 and r["l2w"] == l2w for _, r in mine), (kind, l2w)
+    both = [r for _, _, r in regimes]
+    assert {(r["waves"] == 1, r["l2w"]) for r in both} == {(True, 0), (True, 1), (False, 0), (False, 1)}
+    # the shapes of the batch / snapshot / pool / level tests are multi-wave shapes of this kernel
+    for kind, layers, hidden in RC.BATCH_SHAPES + RC.SNAPSHOT_SHAPES + RC.POOL_SHAPES + RC.LEVEL_SHAPES + [("lstm", 1, 40)]:
+        p = RC.shape_plan(kind, hidden, layers)
+        assert p["runs"] and p["waves"] > 1, (kind, layers, hidden)
+    assert RC.shape_plan("lstm", 64, 2)["l2w"] and RC.shape_plan("lstm", 257, 1)["rows_per_lane"] == 2
+    # call sizes: n = 1 and a call above LSTM_MAX_FRAMES in every partition
+    for samples in (150, 300):
+        sizes = RC.call_sizes(samples, 1)
+        assert sum(sizes) == samples and sizes[0] == 1 and max(sizes) > 128 and set(sizes) <= set(RC.CALL_SIZES) | {sizes[-1]}
+    # eight rows per lane forced: the LSTMs of 613, 769 and 1024 units reach dispatch cases 5, 7 and 8
+    assert [na.recurrent_shape_plan("lstm", h, 1, rpl=8, force_l2w=0)["rows_per_lane"] for h in (613, 769, 1024)] == [5, 7, 8]
+    # the widest recurrent layer with a dense tail: admitted, and the next one up is not
+    for kind in ("lstm", "gru"):
+        h = RC.widest_with_dense_tail(kind)
+        assert RC.shape_plan(kind, h, 1, 2, RC.TAIL_DENSE, 0)["admitted"] and not RC.shape_plan(kind, h + 1, 1, 2, RC.TAIL_DENSE, 0)["admitted"]
+
+
+HEADROOM_CASES = [c for c in RC.edge_cases() if c["hidden"] <= 256 or (c["kind"], c["hidden"]) in (("lstm", 513), ("gru", 342))]
+
+
+@pytest.mark.parametrize("c", HEADROOM_CASES, ids=RC.case_id)
+def test_recurrent_oracle_keeps_its_headroom_under_the_gpu_bound(c):
+    """The GPU tests hold the kernel to 5e-6 * max(1, rms(want)) against the C oracle: the oracle (float32) itself is within a tenth of
+    that bound of the float64 restatement at unit amplitude and within a quarter at amplitude 1000, so the bound measures the kernel.
+    (Above 256 units: one LSTM and one GRU, to keep CPU time down.)"""
+    b = RC.Built(c)
+    for amp, share in ((1.0, 0.1), (1000.0, 0.25)):
+        x = RC.signal(c, amp)
+        got, want = b.oracle().process(x), b.f64(x)
+        err = O.rms(got - want)
+        print("%s amplitude %g: oracle-float64 rms %.3g, bound %.3g" % (RC.case_id(c), amp, err, RC.bound(want)))
+        assert np.all(np.isfinite(got)) and err <= share * RC.bound(want), (RC.case_id(c), amp, err, RC.bound(want))

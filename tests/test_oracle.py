@@ -269,6 +269,27 @@ def test_gru_oracle_chunking_and_prewarm():
     assert np.array_equal(a, c.process(x))
 
 
+@pytest.mark.parametrize("kind,hidden", [("gru", 342), ("gru", 683), ("gru", 1024), ("lstm", 1024)])
+def test_recurrent_oracles_of_any_width_match_the_float64_restatement(kind, hidden):
+    """The oracle is the reference of the GPU tests up to 1024 units (tests/test_gpu_recurrent_rt.py), so it has to be right there itself:
+    the GRU step keeps its scratch on the heap, sized from the hidden size (it was a stack array for up to 256 units: 342 smashed it).
+    Bound: a tenth of the GPU tests' 5e-6 * max(1, rms(want)) -- float32 sums of up to 1025 terms of magnitude below 1 / sqrt(H) each
+    carry about 1e-7 of relative rounding, through gates of slope below 1.  No prewarm on either side."""
+    x = O.signal_noise(100, seed=13)
+    if kind == "gru":
+        j = O.synth_keras_gru(1, hidden, seed=hidden)
+        got = O.OracleGRU(j, prewarm=False).process(x)
+        want = R.gru_forward_keras(j, x, prewarm=0)
+    else:
+        w = O.synth_lstm_weights(1, hidden, seed=hidden)
+        got = O.OracleLSTM.from_nam(1, hidden, w, prewarm=False).process(x)
+        want = R.lstm_forward_nam(1, hidden, w, x, prewarm=0)
+    assert np.all(np.isfinite(got)) and O.rms(want) > 1e-3
+    err = O.rms(got - want)
+    print("%s 1x%d: oracle-float64 rms %.3g" % (kind, hidden, err))
+    assert err < 5e-7 * max(1.0, O.rms(want)), (kind, hidden, err)
+
+
 def test_gru_oracle_matches_committed_torch_vectors():
     """tests/golden/gru_torch.npz: torch.nn.GRU output for the committed synthetic keras GRU model (make_golden.py)."""
     g = np.load(os.path.join(GOLDEN, "gru_torch.npz"))
