@@ -95,6 +95,48 @@ NA_EXTERN int NA_BatchParkStream(NA_Batch* batch, int stream);
 NA_EXTERN int NA_BatchIsParked(NA_Batch* batch, int stream);
 NA_EXTERN int NA_BatchFindParked(NA_Batch* batch, NeuralModel* model); /* the lowest parked id of that model, -1: none */
 NA_EXTERN int NA_BatchNumParked(NA_Batch* batch);
+/* ---- the output stage: ramped stream gains and the click-free model switch ----
+ * The output rows of NA_BatchProcessDevice and of the host-buffer paths never pass through host code that could scale or cross-fade
+ * them; this is the place for it: a per-stream stage on the device, ONE launch per buffer behind the model launches, over the streams
+ * that need it only.  A batch that enabled it and uses none of it launches exactly what it launched before.
+ * NA_BatchEnableOutputStage is the set-up side (allocates; idempotent): it creates the stage's device + pinned tables for the batch's
+ * current capacity; later NA_BatchAddStreams / NA_BatchReserveStreams grow them on the set-up side.  Every call below fails ("output
+ * stage not enabled") before it.
+ * Arithmetic -- all of it f32; positions count the samples the caller sees (in a resampling batch: external samples):
+ *   Gain ramp.  A set call at the moment the stream's gain is g_a, with target g_b and length R, gives the k-th sample after the call
+ *     (k = 0, 1, ...) the gain g_a + (g_b - g_a) * ((min(k, R-1) + 1) / R).  R = 0 means g_b from k = 0.  A set call during a ramp starts
+ *     from the value the ramp has reached (g_a = the gain of the last sample produced): the gain never jumps.  `gain` must be finite
+ *     and >= 0.  R and fadeSamples lie in [0, 1 << 20]: k + 1 is then exact in f32 and the ratio is one rounding.
+ *   Fade.  For the k-th sample after NA_BatchHandover, w = (min(k, N-1) + 1) / N, and row `to` becomes
+ *     (1 - w) * (g_from * y_from) + w * (g_to * y_to): y_* are the models' outputs, g_* the two streams' own (possibly ramping) gains.
+ *     N = 0 means w = 1 at once: activate + park with nothing in between.  Row `from` keeps carrying g_from * y_from until it is
+ *     parked.  The cross-fade is equal-gain, not equal-power: the two signals are two amps on the same input (correlated), so equal
+ *     power would bump by 3 dB in the middle.
+ *   Position.  w and the ramp value are computed from the absolute position, never accumulated sample to sample: the samples out do not
+ *     depend on how the signal was cut into calls.
+ * Host contract: from the call after NA_BatchHandover feed both rows the same input and listen to row `to`.  Nothing happens to the
+ * session at the end of the fade except that `from` turns silent and returns to the pool, re-armed, as NA_BatchParkStream leaves it:
+ * it is parked by the first processing call after the one that held the fade's last sample.  The incoming stream starts from its armed
+ * (silence-prewarmed) state, as every joiner does; no input history is kept to warm it on the session's real past.
+ * Rules (each fails with a message that names it, NA_GetLastError): `from` must be live and from the pool (NA_BatchParkStream refuses
+ * others, and the hand-over ends in a park); `to` must be parked; neither may be part of a running fade, nor `from` a
+ * stream whose fade has produced its last sample (the next processing call parks it); from != to; a broken batch refuses all the calls.  NA_BatchParkStream (or NA_BatchRemoveStreams, not real-time safe) on either stream of a running fade ends the
+ * fade at the next buffer and the other stream carries on alone at its own gain: parking `to` cancels the fade, parking `from`
+ * completes it at once.  Parking resets the stream's gain to 1: a parked stream carries nothing over.  Gains are not part of a
+ * NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves the destination's gain alone.
+ * NA_BatchSetStreamGain and NA_BatchHandover are REAL-TIME SAFE: host arithmetic.  While an entry exists -- a stream with a gain != 1
+ * or a running ramp, or a fade -- every processing call runs its launches in order on one stream (as a resampling batch does: no
+ * half-batch chains, no resident launch; entering that path drains them under the wait limit, like a quality switch), enqueues one
+ * table upload from a ring of pinned tables and the stage's launch, and host buffers go through the library's device staging block (a
+ * registered block too; its first buffer of a new size allocates that block, as NA_BatchProcess on plain memory does).  No device or
+ * pinned allocation besides, no stream or event creation, no unbounded wait; the activate and the later park follow the rules of
+ * NA_BatchActivateStream / NA_BatchParkStream, exceptions included.  An entry retires when its ramp is finished at gain 1 and its
+ * fade is over; with the last one the free-running modes come back. */
+NA_EXTERN int NA_BatchEnableOutputStage(NA_Batch* batch);
+NA_EXTERN int NA_BatchSetStreamGain(NA_Batch* batch, int stream, float gain, int rampSamples);
+NA_EXTERN float NA_BatchGetStreamGain(NA_Batch* batch, int stream); /* the target; 1 for a stream that never had one; < 0: bad id */
+NA_EXTERN int NA_BatchHandover(NA_Batch* batch, int from, int to, float quality, int fadeSamples);
+NA_EXTERN int NA_BatchHandoverRemaining(NA_Batch* batch, int stream); /* samples left of the fade `stream` is part of (either side); 0: none; < 0: stage not enabled / bad id */
 NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);

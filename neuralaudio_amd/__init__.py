@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames"]
+           "resample_model_frames", "db_to_gain"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -40,6 +40,12 @@ class ECompositeModelLoadMode:
 
 def device_count():
     return capi.device_count()
+
+
+def db_to_gain(db):
+    """Decibels as the linear gain Batch.SetStreamGain takes: 10 ** (db / 20), 0.0 at -inf (GetRecommendedOutputDBAdjustment is in dB)."""
+    db = float(db)
+    return 0.0 if db == float("-inf") else 10.0 ** (db / 20.0)
 
 
 def rccl_available():
@@ -318,6 +324,33 @@ class Batch:
 
     def NumParked(self):
         return int(self._lib.NA_BatchNumParked(self._h))
+
+    # -- the output stage: EnableOutputStage is set-up side; SetStreamGain / Handover are real-time safe (include/neuralaudio_amd.h) ----
+    def EnableOutputStage(self):
+        if self._lib.NA_BatchEnableOutputStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def SetStreamGain(self, stream, gain, rampSamples=0):
+        """Linear output gain of a live stream, reached over `rampSamples` samples (db_to_gain turns decibels into it)."""
+        if self._lib.NA_BatchSetStreamGain(self._h, int(stream), float(gain), int(rampSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamGain(self, stream):
+        gain = float(self._lib.NA_BatchGetStreamGain(self._h, int(stream)))
+        if gain < 0:
+            raise NeuralAudioError(capi.last_error())
+        return gain
+
+    def Handover(self, src, dst, quality=1.0, fadeSamples=0):
+        """Activates the parked stream `dst`; from the next buffer on its row carries the cross-fade from `src`'s output to its own."""
+        if self._lib.NA_BatchHandover(self._h, int(src), int(dst), float(quality), int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def HandoverRemaining(self, stream):
+        left = int(self._lib.NA_BatchHandoverRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
 
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:

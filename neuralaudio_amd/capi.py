@@ -39,6 +39,7 @@ NA_SYMBOLS = [
     "NA_RenderOfflineAtRate", "NA_RenderPlanAtRate", "NA_DebugSetRenderTap", "NA_MultiSetResampling", "NA_MultiGetResampleInfo",
     "NA_BatchReserveStreams", "NA_BatchActivateStream", "NA_BatchParkStream", "NA_BatchIsParked", "NA_BatchFindParked", "NA_BatchNumParked",
     "NA_DebugDeviceResourceCalls", "NA_DebugRecurrentPlan", "NA_DebugRecurrentShapePlan",
+    "NA_BatchEnableOutputStage", "NA_BatchSetStreamGain", "NA_BatchGetStreamGain", "NA_BatchHandover", "NA_BatchHandoverRemaining",
 ]
 
 
@@ -149,6 +150,11 @@ def load_library():
         "NA_BatchFindParked": (C.c_int, [vp, vp]),
         "NA_BatchNumParked": (C.c_int, [vp]),
         "NA_DebugDeviceResourceCalls": (C.c_longlong, []),
+        "NA_BatchEnableOutputStage": (C.c_int, [vp]),
+        "NA_BatchSetStreamGain": (C.c_int, [vp, C.c_int, C.c_float, C.c_int]),
+        "NA_BatchGetStreamGain": (C.c_float, [vp, C.c_int]),
+        "NA_BatchHandover": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_int]),
+        "NA_BatchHandoverRemaining": (C.c_int, [vp, C.c_int]),
         "NA_DebugRecurrentPlan": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "NA_DebugRecurrentShapePlan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
         "NA_MultiCreate": (vp, [C.POINTER(C.c_int), C.c_int]),

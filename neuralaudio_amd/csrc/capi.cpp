@@ -488,6 +488,51 @@ int NA_BatchFindParked(NA_Batch* batch, NeuralModel* model)
 
 int NA_BatchNumParked(NA_Batch* batch) { return batch ? batch->batch->NumParked() : -1; }
 
+// ---- the output stage (gpu_batch.h EnableOutputStage / SetStreamGain / Handover) ----
+int NA_BatchEnableOutputStage(NA_Batch* batch)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchEnableOutputStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->EnableOutputStage();
+	});
+}
+
+int NA_BatchSetStreamGain(NA_Batch* batch, int stream, float gain, int rampSamples)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchSetStreamGain: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->SetStreamGain(stream, gain, rampSamples);
+	});
+}
+
+float NA_BatchGetStreamGain(NA_Batch* batch, int stream)
+{
+	float gain = -1.0f;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchGetStreamGain: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		gain = batch->batch->GetStreamGain(stream);
+	});
+	return rc == 0 ? gain : -1.0f;
+}
+
+int NA_BatchHandover(NA_Batch* batch, int from, int to, float quality, int fadeSamples)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchHandover: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->Handover(from, to, quality, fadeSamples);
+	});
+}
+
+int NA_BatchHandoverRemaining(NA_Batch* batch, int stream)
+{
+	int left = 0;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchHandoverRemaining: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		left = batch->batch->HandoverRemaining(stream);
+	});
+	return rc == 0 ? left : -1;
+}
+
 #ifndef NA_RELEASE
 long long NA_DebugDeviceResourceCalls(void) { return na::DeviceResourceCalls(); }
 #endif

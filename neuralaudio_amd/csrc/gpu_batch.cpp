@@ -332,6 +332,7 @@ namespace na
 			EnsurePoolPipeline();
 			pendingHistoryZero.reserve(streams.size());
 		}
+		if (outStage) EnsureStageRows((int)streams.size());
 		return first;
 	}
 
@@ -387,6 +388,7 @@ namespace na
 		if (!ref.pooled) throw std::runtime_error("neuralaudio_amd: ParkStream: stream " + std::to_string(s) + " did not come from ReserveStreams (it leaves through RemoveStreams)");
 		ref.members[(size_t)ref.active].first->SetActive(ref.members[(size_t)ref.active].second, -1);
 		pendingHistoryZero.erase(std::remove(pendingHistoryZero.begin(), pendingHistoryZero.end(), s), pendingHistoryZero.end());
+		StageLeave(s);
 		ref.parked = true;
 		numParked++;
 		topologyVersion++;
@@ -398,6 +400,7 @@ namespace na
 	// (the one host-side wait, shared with a quality switch on such a batch -- bounded by the wait limit).
 	void GpuBatch::FlushRearms()
 	{
+		if (outStage) StageParkFinished();
 		if (!rearmPending) return;
 		JoinHalves();
 		if (pipelineUsed && lastKernelEvent && lastKernelStream != stream) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
@@ -445,6 +448,7 @@ namespace na
 			for (auto& gm : ref.members) gm.first->RemoveMember(gm.second);
 			if (ref.parked) numParked--;
 			pendingHistoryZero.erase(std::remove(pendingHistoryZero.begin(), pendingHistoryZero.end(), first + i), pendingHistoryZero.end());
+			StageLeave(first + i);
 			ref = StreamRef();
 			ref.live = false;
 			retired.insert(std::lower_bound(retired.begin(), retired.end(), first + i), first + i);
@@ -577,7 +581,8 @@ namespace na
 		// A batch on its own stream that nobody has seen: a buffer of one contiguous WaveNet group runs as two free-running half-batch
 		// launches (the order of work on the internal streams is not observable from outside; Synchronize() and the host-buffer entry
 		// points wait for all of them).  1024 x A1 Standard x 128 frames: 40.1 -> 37.4 us per step.
-		if (ownsStream && !streamObserved && !Resamples()) // (a resampling batch orders up kernel -> model -> down kernel on the batch stream)
+		// (a resampling batch orders up kernel -> model -> down kernel on the batch stream; so does a batch whose output stage has entries)
+		if (ownsStream && !streamObserved && !Resamples() && !StageHasEntries())
 		{
 			if (TryResident(dIn, dOut, n, inStride, outStride)) return;
 			if (PrepareHalves(n))
@@ -615,6 +620,23 @@ namespace na
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{
+		if (outStage && !outStage->inside && outStage->book.HasEntries())
+		{
+			// the output stage: behind everything this call launches -- the join of the units, the graph replay, the down
+			// kernel of a resampling batch -- on the same stream, outside any capture
+			struct Inside
+			{
+				bool& flag;
+				explicit Inside(bool& f) : flag(f) { flag = true; }
+				~Inside() { flag = false; }
+			};
+			{
+				Inside inside(outStage->inside);
+				ProcessDeviceOn(launch, dIn, dOut, n, inStride, outStride);
+			}
+			RunOutputStage(launch, dOut, n, outStride);
+			return;
+		}
 		if (resample && !resample->plan.identity && !resample->inside)
 		{
 			ProcessResampledOn(launch, dIn, dOut, n, inStride, outStride);

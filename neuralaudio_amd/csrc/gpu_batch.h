@@ -20,6 +20,7 @@
 #include "device_resources.h"
 #include "launch_plan.h"
 #include "model_loader.h"
+#include "output_stage.h"
 #include "resample.h"
 #include "tuning.h"
 #include "wavenet_launch.h"
@@ -105,6 +106,20 @@ namespace na
 		bool IsParked(int stream) const { return stream >= 0 && stream < (int)streams.size() && streams[(size_t)stream].parked; }
 		int FindParked(const LoadedModel* model) const; // the lowest parked id of that model, -1: none
 		int NumParked() const { return numParked; }
+
+		// The output stage (output_stage.h): per-stream ramped output gains and the cross-fade that hands a session from a
+		// live stream to a parked one of another model.  EnableOutputStage is the set-up side: the device and pinned tables for the rows
+		// the batch has (CreateStreams grows them).  SetStreamGain / Handover are host arithmetic on those tables; while an entry exists --
+		// a gain != 1, a running ramp, a fade -- every processing call runs on the ordered path and enqueues, behind the join of its model
+		// launches (behind the down kernel of a resampling batch, in front of the device-to-host copy of a host buffer), ONE table upload
+		// from a ring of pinned tables and ONE launch that works in place on the rows the caller sees.  Without an entry the batch
+		// launches exactly what it launches without the stage.
+		void EnableOutputStage();
+		bool HasOutputStage() const { return outStage != nullptr; }
+		void SetStreamGain(int stream, float gain, int rampSamples);
+		float GetStreamGain(int stream) const; // the target; < 0: not a live or parked stream of the batch
+		void Handover(int from, int to, float quality, int fadeSamples);
+		int HandoverRemaining(int stream) const;
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -256,6 +271,13 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
+		struct OutputStage; // (gpu_batch_internal.h)
+		std::unique_ptr<OutputStage> outStage;
+		bool StageHasEntries() const;
+		void EnsureStageRows(int rows);  // set-up side: tables for `rows` rows
+		void StageParkFinished();        // top of every processing call: the `from` streams of the fades that ended in the last one are parked
+		void StageLeave(int stream);     // park / removal: its fade ends, its gain is 1 again
+		void RunOutputStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + launch + the host mirror's advance
 		int AllocateIds(int count);
 		void DropTrailingRetiredRows();
 		// the kinds of the groups that have active streams once `leaving` has lost / `entering` has gained one, in group order (`active`:
@@ -395,6 +417,7 @@ namespace na
 		bool pipelineUsed = false;
 		hipEvent_t lastKernelEvent = nullptr, mainDone = nullptr;
 		hipStream_t lastKernelStream = nullptr;
+		bool lastSubmitOnBatchStream = false; // the last Submit ran its kernel on the batch stream (pinned blocks read in place), with no event behind it
 		unsigned long submitTopology = 0;
 		PipeSlot pipe[kPipelineSlots];
 		hipStream_t copyIn = nullptr, copyOut = nullptr;

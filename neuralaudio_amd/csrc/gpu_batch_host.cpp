@@ -107,7 +107,9 @@ namespace na
 			// blocks the caller registered: the kernels run on them as they are (no staging copies: 81 -> ~62 us for 1024 x 128)
 			float* dIn = static_cast<float*>(RegisteredDevicePointer(in, total * sizeof(float)));
 			float* dOut = static_cast<float*>(RegisteredDevicePointer(out, total * sizeof(float)));
-			if (dIn && dOut)
+			// (while the output stage has entries the rows go through the staging block below: the stage works in place on device memory,
+			// not as a read-modify-write over the bus)
+			if (dIn && dOut && !StageHasEntries())
 			{
 				ProcessDeviceOrdered(dIn, dOut, n, (long)n, (long)n);
 				WaitStreamBounded(stream, "hipStreamSynchronize");
@@ -117,7 +119,8 @@ namespace na
 		}
 		EnsureStaging(total);
 		float* dStage = nullptr;
-		const bool direct = HostDirect() && hipHostGetDevicePointer(reinterpret_cast<void**>(&dStage), hostStage, 0) == hipSuccess && dStage != nullptr;
+		// (output stage entries: the copy engines and the device block, for the same reason)
+		const bool direct = HostDirect() && !StageHasEntries() && hipHostGetDevicePointer(reinterpret_cast<void**>(&dStage), hostStage, 0) == hipSuccess && dStage != nullptr;
 		if (direct && PrepareHalves(n) && halfLists->RowRangesOnly())
 		{
 			// The blocking call in two halves: the rows of the first half are staged and launched, the second half is staged while the
@@ -242,7 +245,7 @@ namespace na
 			for (size_t r = 0; r < streams.size(); r++)
 				if (streams[r].parked) p.parkedRows.push_back((int)r);
 		if (in) memcpy(p.hostIn, in, total * sizeof(float)); // nullptr: the caller filled NextInput() in place
-		const bool direct = HostDirect(); // (see ProcessHost)
+		const bool direct = HostDirect() && !StageHasEntries(); // (see ProcessHost)
 		float *dIn = nullptr, *dOut = nullptr;
 		if (direct && hipHostGetDevicePointer(reinterpret_cast<void**>(&dIn), p.hostIn, 0) == hipSuccess && dIn != nullptr &&
 			hipHostGetDevicePointer(reinterpret_cast<void**>(&dOut), p.hostOut, 0) == hipSuccess && dOut != nullptr)
@@ -269,7 +272,11 @@ namespace na
 				return ticket;
 			}
 			JoinHalves(); // back on the batch stream: the half chains first
+			// (the buffer before this one ran on its slot's own stream while the output stage had entries: this buffer's kernel, and any
+			// index list it uploads again, come behind that one's)
+			if (lastKernelEvent && lastKernelStream != stream) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
 			ProcessDeviceOn(stream, dIn, dOut, n, (long)n, (long)n);
+			lastSubmitOnBatchStream = true;
 			CheckHip(hipEventRecord(p.downloaded, stream), "hipEventRecord");
 			p.onOwnStream = false;
 			p.onHalfStreams = false;
@@ -296,13 +303,15 @@ namespace na
 				for (auto& g : groups)
 					if (g->NumActive() > 0) listsChanged = g->SyncActiveLists() || listsChanged;
 			}
-			if (listsChanged || submitTopology != topologyVersion || !pipelineUsed)
+			if (listsChanged || submitTopology != topologyVersion || !pipelineUsed || lastSubmitOnBatchStream)
 			{
-				// everything the batch stream still has in flight for this batch (state resets of new streams, index lists) comes first
+				// everything the batch stream still has in flight for this batch (state resets of new streams, index lists, the buffer
+				// before this one where it ran there: the output stage's first entry moves the buffers of a direct batch over here) comes first
 				if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
 				CheckHip(hipEventRecord(mainDone, stream), "hipEventRecord");
 				CheckHip(hipStreamWaitEvent(p.own, mainDone, 0), "hipStreamWaitEvent");
 				submitTopology = topologyVersion;
+				lastSubmitOnBatchStream = false;
 			}
 			pipelineUsed = true;
 			CheckHip(hipMemcpyAsync(p.dev, p.hostIn, total * sizeof(float), hipMemcpyHostToDevice, p.own), "hipMemcpyAsync H2D");

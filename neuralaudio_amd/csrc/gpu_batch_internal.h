@@ -81,5 +81,30 @@ namespace na
 		}
 	};
 
+	// the output stage of a batch (output_stage.h): the host mirror and the ring of entry tables
+	struct GpuBatch::OutputStage
+	{
+		// one table more than buffers can be in flight (Submit): the table a call takes was read by a launch whose ticket has been collected
+		static constexpr int kTables = GpuBatch::kPipelineSlots + 1;
+		OutputStageBook book;
+		OutStageEntry* host[kTables] = {}; // pinned
+		OutStageEntry* dev[kTables] = {};
+		hipEvent_t done[kTables] = {};     // the launch that read dev[i] (and the upload that read host[i]) is over
+		bool used[kTables] = {};
+		int next = 0;
+		int capacity = 0;             // entries per table
+		bool inside = false;          // the model launches of a call with entries are under way (ProcessDeviceOn)
+		~OutputStage()
+		{
+			for (int i = 0; i < kTables; i++)
+			{
+				if (host[i]) (void)CountedHipHostFree(host[i]);
+				if (dev[i]) (void)CountedHipFree(dev[i]);
+				if (done[i]) (void)hipEventDestroy(done[i]);
+			}
+		}
+	};
+	hipError_t LaunchOutputStage(const OutStageLaunch& L, hipStream_t stream); // (output_stage_kernels.hip)
+
 	bool HostDirect(); // (gpu_batch_host.cpp) the kernels read / write pinned host blocks themselves instead of the copy engines
 }

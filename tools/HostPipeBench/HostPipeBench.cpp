@@ -11,6 +11,9 @@
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --churn K [--churn-legacy] [--churn-every E=10]
 //       join and leave on a batch that never stops (RunChurn below): every E-th buffer K streams leave or come back -- through the pool
 //       (NA_BatchParkStream / NA_BatchActivateStream) or, with --churn-legacy, through NA_BatchRemoveStreams / NA_BatchAddStreams.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --handover K [--mix <model 2>] [--fade N=256]
+//       the click-free model switch on a batch that never stops (RunHandover below): every K-th buffer one of 16 sessions is handed over
+//       (NA_BatchHandover) to a parked stream of the other model (--mix), with one model to a second stream of it.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -308,15 +311,147 @@ static int RunChurn(NeuralModel* model, int streams, int frames, int buffers, in
 	return identical ? 0 : 3;
 }
 
+// --handover K: `streams` pooled streams run `buffers` buffers through the pipelined host interface (two tickets in flight).  Sixteen of
+// them are sessions with a parked spare each -- of the --mix model, else of the same one; in front of every K-th buffer the next session
+// in turn is handed over to its other stream with a fade of N samples and a level gain on the incoming one (a session whose last
+// hand-over has not ended in its park yet is skipped and counted).  Prints the cost of the calls (host wall time), the mean and the
+// longest buffer period (Collect to Collect) of that run and of the same run without the stage, and the mean period of steady states:
+// stage enabled with no entry, 16 gain entries, a gain entry on every stream, 16 concurrent fades.  The final buffer of the last
+// stream, which never took part, must equal the run without hand-overs bit for bit (exit code 3 otherwise).
+struct HandoverRun
+{
+	double meanUs = 0.0, maxUs = 0.0, handoverUs = 0.0, handoverMaxUs = 0.0, gainUs = 0.0, gainMaxUs = 0.0;
+	double idleUs = 0.0, gain16Us = 0.0, gainAllUs = 0.0, fades16Us = 0.0;
+	int events = 0, skipped = 0;
+	std::vector<float> lastRow;
+};
+
+static int RunHandoverVariant(NeuralModel* model, NeuralModel* other, int streams, int frames, int buffers, int K, int fade, bool stage, HandoverRun& result)
+{
+	const int sessions = 16;
+	NA_Batch* batch = NA_BatchCreate(0, nullptr);
+	CHECK(batch != nullptr);
+	CHECK(NA_BatchReserveStreams(batch, model, streams, 1) == 0);
+	CHECK(NA_BatchReserveStreams(batch, other, sessions, 1) == streams);
+	for (int s = 0; s < streams; s++) CHECK(NA_BatchActivateStream(batch, s, 1.0f) == 0);
+	if (stage) CHECK(NA_BatchEnableOutputStage(batch) == 0);
+	const int rows = streams + sessions;
+	const size_t count = (size_t)rows * frames;
+	std::vector<std::vector<float>> in(8, std::vector<float>(count));
+	for (size_t b = 0; b < in.size(); b++)
+	{
+		for (size_t i = 0; i < (size_t)streams * frames; i++) in[b][i] = 0.5f * (float)((((i + b * 7919u) * 2654435761u) >> 8) & 0xffff) / 65536.0f - 0.25f;
+		// (both streams of a session take the same input: the host contract of a hand-over)
+		for (int j = 0; j < sessions; j++) std::memcpy(&in[b][(size_t)(streams + j) * frames], &in[b][(size_t)j * frames], (size_t)frames * sizeof(float));
+	}
+	std::vector<float> out(count);
+	std::vector<double> tHandover, tGain;
+	const float level = (float)std::pow(10.0, (GetRecommendedOutputDBAdjustment(other) - GetRecommendedOutputDBAdjustment(model)) / 20.0);
+	std::vector<char> onSpare((size_t)sessions, 0);
+	int turn = 0;
+	auto event = [&]() -> int {
+		const int j = turn++ % sessions;
+		const int from = onSpare[(size_t)j] ? streams + j : j, to = onSpare[(size_t)j] ? j : streams + j;
+		if (NA_BatchHandoverRemaining(batch, from) != 0 || !NA_BatchIsParked(batch, to)) { result.skipped++; return 0; }
+		double t0 = Now();
+		CHECK(NA_BatchHandover(batch, from, to, 1.0f, fade) == 0);
+		tHandover.push_back((Now() - t0) * 1e6);
+		t0 = Now();
+		CHECK(NA_BatchSetStreamGain(batch, to, onSpare[(size_t)j] ? 1.0f : level, 0) == 0);
+		tGain.push_back((Now() - t0) * 1e6);
+		onSpare[(size_t)j] = !onSpare[(size_t)j];
+		result.events++;
+		return 0;
+	};
+	auto loop = [&](int n, bool handovers, double& meanUs, double& maxUs) -> int {
+		int pending = NA_BatchSubmit(batch, in[0].data(), (size_t)frames);
+		CHECK(pending >= 0);
+		double last = Now(), sum = 0.0;
+		maxUs = 0.0;
+		for (int i = 1; i <= n; i++)
+		{
+			if (handovers && stage && i % K == 0 && i < n && event() != 0) return 1;
+			int next = -1;
+			if (i < n)
+			{
+				next = NA_BatchSubmit(batch, in[(size_t)i % in.size()].data(), (size_t)frames);
+				CHECK(next >= 0);
+			}
+			CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
+			const double now = Now();
+			if (i > 20) // (the first buffers: first-use set-up of the pipelined interface, the change of steady state)
+			{
+				sum += (now - last) * 1e6;
+				maxUs = std::max(maxUs, (now - last) * 1e6);
+			}
+			last = now;
+			pending = next;
+		}
+		meanUs = sum / std::max(1, n - 20);
+		return 0;
+	};
+	if (loop(buffers, true, result.meanUs, result.maxUs) != 0) return 1;
+	CHECK(NA_BatchProcess(batch, in[1].data(), out.data(), (size_t)frames) == 0);
+	result.lastRow.assign(out.begin() + (long)((size_t)(streams - 1) * frames), out.begin() + (long)((size_t)streams * frames));
+	if (stage)
+	{
+		// steady states.  First everything back to "no entry": the fades run out, every session's live stream at gain 1
+		const int quiet = std::max(buffers / 4, 60), settle = fade / frames + 3;
+		double ignored = 0.0;
+		if (loop(settle + 21, false, ignored, ignored) != 0) return 1;
+		for (int s = 0; s < rows; s++)
+			if (NA_BatchIsLive(batch, s)) CHECK(NA_BatchSetStreamGain(batch, s, 1.0f, 0) == 0);
+		if (loop(quiet, false, result.idleUs, ignored) != 0) return 1;
+		for (int s = 0; s < sessions; s++) CHECK(NA_BatchSetStreamGain(batch, streams - 1 - s, 0.5f, 0) == 0);
+		if (loop(quiet, false, result.gain16Us, ignored) != 0) return 1;
+		for (int s = 0; s < rows; s++)
+			if (NA_BatchIsLive(batch, s)) CHECK(NA_BatchSetStreamGain(batch, s, 0.5f, 0) == 0);
+		if (loop(quiet, false, result.gainAllUs, ignored) != 0) return 1;
+		for (int s = 0; s < rows; s++)
+			if (NA_BatchIsLive(batch, s)) CHECK(NA_BatchSetStreamGain(batch, s, 1.0f, 0) == 0);
+		for (int j = 0; j < sessions; j++)
+		{
+			const int from = onSpare[(size_t)j] ? streams + j : j, to = onSpare[(size_t)j] ? j : streams + j;
+			CHECK(NA_BatchHandover(batch, from, to, 1.0f, 1 << 20) == 0); // (longer than the measurement: sixteen fades throughout)
+		}
+		if (loop(quiet, false, result.fades16Us, ignored) != 0) return 1;
+	}
+	result.handoverUs = Median(tHandover);
+	result.gainUs = Median(tGain);
+	result.handoverMaxUs = tHandover.empty() ? 0.0 : *std::max_element(tHandover.begin(), tHandover.end());
+	result.gainMaxUs = tGain.empty() ? 0.0 : *std::max_element(tGain.begin(), tGain.end());
+	NA_BatchDestroy(batch);
+	return 0;
+}
+
+static int RunHandover(NeuralModel* model, NeuralModel* other, int streams, int frames, int buffers, int K, int fade)
+{
+	CHECK(K >= 1 && streams >= 33 && fade >= 0 && fade <= (1 << 20) && buffers > 60);
+	HandoverRun quiet, moved;
+	if (RunHandoverVariant(model, other, streams, frames, buffers, K, fade, false, quiet) != 0) return 1;
+	if (RunHandoverVariant(model, other, streams, frames, buffers, K, fade, true, moved) != 0) return 1;
+	const bool identical = quiet.lastRow.size() == moved.lastRow.size() &&
+		std::memcmp(quiet.lastRow.data(), moved.lastRow.data(), quiet.lastRow.size() * sizeof(float)) == 0;
+	std::printf("{\"handover\": %d, \"fade\": %d, \"mixed\": %s, \"streams\": %d, \"frames\": %d, \"buffers\": %d, \"events\": %d, \"skipped\": %d, "
+		"\"handover_call_us\": {\"p50\": %.1f, \"max\": %.1f}, \"set_gain_call_us\": {\"p50\": %.1f, \"max\": %.1f}, "
+		"\"buffer_period_us\": {\"mean\": %.1f, \"max\": %.1f}, \"no_stage_buffer_period_us\": {\"mean\": %.1f, \"max\": %.1f}, "
+		"\"steady_buffer_period_us\": {\"no_entry\": %.1f, \"gain_entries_16\": %.1f, \"gain_entries_all\": %.1f, \"fades_16\": %.1f}, "
+		"\"untouched_stream_identical\": %s}\n",
+		K, fade, other != model ? "true" : "false", streams, frames, buffers, moved.events, moved.skipped, moved.handoverUs, moved.handoverMaxUs, moved.gainUs,
+		moved.gainMaxUs, moved.meanUs, moved.maxUs, quiet.meanUs, quiet.maxUs, moved.idleUs, moved.gain16Us, moved.gainAllUs, moved.fades16Us,
+		identical ? "true" : "false");
+	return identical ? 0 : 3;
+}
+
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
-	int migrate = 0, churn = 0, churnEvery = 10;
+	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256;
 	bool churnLegacy = false;
 	for (int i = 1; i < argc; i++)
 	{
@@ -327,6 +462,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--churn") && i + 1 < argc) churn = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--churn-every") && i + 1 < argc) churnEvery = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--churn-legacy")) churnLegacy = true;
+		else if (!std::strcmp(argv[i], "--handover") && i + 1 < argc) handover = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--fade") && i + 1 < argc) fade = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
 			// rehearsal on a one-GPU box: the multi-GPU host bound to the library's loopback RCCL table (test build only), so that
@@ -359,6 +496,16 @@ int main(int argc, char** argv)
 	if (churn > 0)
 	{
 		const int rc = RunChurn(model, streams, frames, buffers, churn, churnEvery, churnLegacy);
+		DeleteModel(model);
+		DeleteLoader(loader);
+		return rc;
+	}
+	if (handover > 0)
+	{
+		NeuralModel* second = mixFile ? NA_CreateModelFromFileUtf8(loader, mixFile, 0) : nullptr;
+		CHECK(!mixFile || second != nullptr);
+		const int rc = RunHandover(model, second ? second : model, streams, frames, buffers, handover, fade);
+		if (second) DeleteModel(second);
 		DeleteModel(model);
 		DeleteLoader(loader);
 		return rc;
