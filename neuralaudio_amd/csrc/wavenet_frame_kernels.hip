@@ -29,6 +29,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "frame_lds.h"
 #include "wavenet_dev.h"
 #include "wavenet_launch.h"
 
@@ -154,12 +155,12 @@ namespace na
 		// Channels [4*cg, 4*cg+4) of the frame `off` frames from the block start (off < 0: history) for this lane.
 		// lo/hi: range of `off` over the wave (scalar) -> whole wave in block / whole wave in history / mixed.
 		// float4 per thread staged per stage by WeightStager (>= 6 KB per workgroup >= any official stage; larger blocks use its tail loop)
-		constexpr int StagerWcopy(int nwaves) { return (384 + 64 * nwaves - 1) / (64 * nwaves); }
+		constexpr int StagerWcopy(int nwaves) { return FrameStagerWcopy(nwaves); }
 
 		// HPF = number of shifted taps (most shifted first) whose ring history is requested one layer ahead: 2 covers every tap of the K = 3
 		// architectures; runs of narrow layers (G <= 2) of models with larger kernels (A2: K = 6 / 15) use HPF_WIDE, the rest of their taps
 		// load in line.  HPF_LDS sizes the per-wave LDS history buffers of the PF == 2 variant.
-		constexpr int HPF_NARROW = 2, HPF_WIDE = 5, HPF_LDS = 2;
+		constexpr int HPF_NARROW = 2, HPF_WIDE = 5, HPF_LDS = FRAME_HPF_LDS;
 
 		// history part of one tap for this lane's frame: channels of frame (pos0 + off) from the ring (lanes inside the block: nothing)
 		// = frame (f - shift) of the block for the lanes with f < shift, when `valid` (wave-uniform); all other lanes load nothing.
@@ -991,11 +992,9 @@ namespace na
 		template <int WPS, int PF, int SPB>
 		static hipError_t Launch(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
 		{
-			// stride of the two LDS weight buffers: the LDS-DMA staging always writes WCOPY * NTHREADS float4 slots (zeros past the block)
-			constexpr int NT = 64 * WPS * SPB;
 			FrLaunchArgs args = {};
 			args.numGroups = numGroups;
-			int maxA4F4 = WeightStager<WPS * SPB>::WCOPY * NT;
+			int maxA4Floats = 0; // the largest staged block among the launch's groups: every workgroup gets the same LDS
 			int blocks = 0;
 			for (int i = 0; i < numGroups; i++)
 			{
@@ -1010,16 +1009,19 @@ namespace na
 				a.maxKsize = m.max_ksize;
 				a.firstBlock = blocks;
 				blocks += (g.numStreams + SPB - 1) / SPB;
-				maxA4F4 = std::max(maxA4F4, (m.max_a4_floats + 3) / 4);
+				maxA4Floats = std::max(maxA4Floats, m.max_a4_floats);
 			}
-			const size_t lds = (size_t)SPB * 2 * WPS * 4 * 64 * 16 + (size_t)2 * maxA4F4 * 16 + (PF == 2 ? (size_t)WPS * SPB * HPF_LDS * 4 * 64 * 16 : 0);
-			if (lds > 160 * 1024) return hipErrorInvalidValue;
+			// stride of the two LDS weight buffers: the LDS-DMA staging always writes WCOPY * NTHREADS float4 slots (zeros past the block)
+			static_assert(FrameWeightStrideF4(0, WPS, SPB) == WeightStager<WPS * SPB>::WCOPY * 64 * WPS * SPB, "frame_lds.h restates the stager");
+			const int maxA4F4 = FrameWeightStrideF4(maxA4Floats, WPS, SPB);
+			const size_t lds = FrameLaunchLdsBytes(maxA4Floats, WPS, SPB, PF);
+			if (lds > FRAME_LDS_LIMIT) return hipErrorInvalidValue; // (the callers below choose a shape that fits; a loaded model has one)
 			auto kernel = WaveNetFrameKernel<WPS, PF, SPB>;
 			if (lds > 64 * 1024)
 			{
 				// per instantiation and device: the whole LDS of a CU once (granting it does not change what a launch uses)
 				static PerDeviceOnce attr;
-				const hipError_t e = attr.Run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+				const hipError_t e = attr.Run([&] { return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FRAME_LDS_LIMIT); });
 				if (e != hipSuccess) return e;
 			}
 			hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * WPS * SPB), lds, stream, args, maxA4F4, in, out, inStride, outStride, n,
@@ -1034,12 +1036,12 @@ namespace na
 		if (n <= 0 || numGroups <= 0) return hipSuccess;
 		if (n > WN_MAX_FRAMES || numGroups > WN_FRAME_MAX_GROUPS) return hipErrorInvalidValue;
 		int total = 0;
-		size_t ldsWeights = 0;
+		int maxA4 = 0; // the launch's LDS follows the largest staged block among its groups
 		for (int i = 0; i < numGroups; i++)
 		{
 			if (groups[i].numStreams <= 0) return hipErrorInvalidValue;
 			total += groups[i].numStreams;
-			ldsWeights = std::max(ldsWeights, (size_t)2 * ((groups[i].model->max_a4_floats + 3) / 4) * 16);
+			maxA4 = std::max(maxA4, groups[i].model->max_a4_floats);
 		}
 		const int prefetch = Tuning::Get().frPrefetch; // tuning knob: 0 none, 1 history prefetch into registers, 2 into LDS (LDS-DMA)
 		const int spbEnv = Tuning::Get().frSpb;            // tuning knob: streams per workgroup (1, 2, 4)
@@ -1048,11 +1050,19 @@ namespace na
 		const int spb = spbEnv > 0 ? spbEnv : (total >= 512 ? 2 : 1);
 		if (n > 64)
 		{
+			// ... the largest count up to that wish whose LDS fits (frame_lds.h): large kernels leave room for fewer block images beside
+			// their staged weights, and the LDS history buffers of prefetch 2 give way to the register prefetch before a launch fails.
+			// Precedence under NA_FR_PF=2: the knob asks for the LDS prefetch, so it is kept over the second stream -- <2,2,2>, then
+			// <2,2,1>, and only where neither fits the register prefetch <2,1,2> / <2,1,1>.  One stream per workgroup with the register
+			// prefetch fits every model that loaded (CheckWaveNetRunnable).
 			if (!prefetch) return fr::Launch<2, 0, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
-			if (spb >= 4 && ldsWeights + 4 * 16384 <= 160 * 1024) return fr::Launch<2, 1, 4>(groups, numGroups, in, out, inStride, outStride, n, stream);
-			if (prefetch == 2) return spb >= 2 ? fr::Launch<2, 2, 2>(groups, numGroups, in, out, inStride, outStride, n, stream)
-									   : fr::Launch<2, 2, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
-			if (spb >= 2) return fr::Launch<2, 1, 2>(groups, numGroups, in, out, inStride, outStride, n, stream);
+			if (spb >= 4 && FrameLaunchFits(maxA4, 2, 4, 1)) return fr::Launch<2, 1, 4>(groups, numGroups, in, out, inStride, outStride, n, stream);
+			if (prefetch == 2)
+			{
+				if (spb >= 2 && FrameLaunchFits(maxA4, 2, 2, 2)) return fr::Launch<2, 2, 2>(groups, numGroups, in, out, inStride, outStride, n, stream);
+				if (FrameLaunchFits(maxA4, 2, 1, 2)) return fr::Launch<2, 2, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
+			}
+			if (spb >= 2 && FrameLaunchFits(maxA4, 2, 2, 1)) return fr::Launch<2, 1, 2>(groups, numGroups, in, out, inStride, outStride, n, stream);
 			return fr::Launch<2, 1, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
 		}
 		return fr::Launch<1, 0, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);

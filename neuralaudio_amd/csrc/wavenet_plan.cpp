@@ -5,6 +5,7 @@
 //   rechannel [out][in]; per layer (:420-425) conv [out][in][k] + bias, input mix-in [out][cond],
 //   1x1 [out][in] + bias; head conv [out][in][k] (+ bias); last float = head scale.
 #include "wavenet_plan.h"
+#include "frame_lds.h"
 
 #include <algorithm>
 #include <cmath>
@@ -843,7 +844,7 @@ namespace na
 								plan.wpk[(size_t)tail + 2 * CP + c] = W(b1 + c);
 							}
 						}
-						st.a4_floats = (K + 1) * 64 * st.G + 12 * st.G;
+						st.a4_floats = FrameLayerBlockFloats(K, st.G);
 						SetRing(st, layerRing[a][l]);
 						if (cfg.activation == ACT_LEAKYRELU) st.flags |= WN_FLAG_LEAKY;
 						else if (desc.mathMode == MATH_STD) st.flags |= WN_FLAG_STD_TANH;
@@ -943,7 +944,38 @@ namespace na
 	void CheckWaveNetRunnable(const WaveNetDesc& desc)
 	{
 		const WaveNetPlan plan = BuildWaveNetPlan(desc);
-		if (!plan.genericOnly) return;
+		if (!plan.genericOnly)
+		{
+			// Up to 16 channels the f32 frame kernel is the kernel of last resort (FamilyFor), and it stages a layer's whole weight block
+			// -- every conv tap -- in LDS: a block that does not fit beside one stream's 128-frame block images (frame_lds.h) could run
+			// no buffer longer than 64 frames.  Refused here, by name, instead of at the first long buffer on the audio thread.
+			for (size_t a = 0; a < desc.arrays.size(); a++)
+			{
+				const WnArrayCfg& cfg = desc.arrays[a];
+				const int G = (cfg.channels + 3) / 4;
+				for (size_t l = 0; l < cfg.kernelSizes.size(); l++)
+				{
+					const int K = cfg.kernelSizes[l];
+					if (FrameModelFits(FrameLayerBlockFloats(K, G))) continue;
+					std::stringstream str;
+					str << "WaveNet layer array " << a << ", layer " << l << ": kernel size " << K << " at " << cfg.channels
+					    << " channels needs " << FrameLaunchLdsBytes(FrameLayerBlockFloats(K, G), 2, 1, 1) << " bytes of LDS on the f32 frame kernel (limit "
+					    << FRAME_LDS_LIMIT << "); the largest kernel size at this width is " << FrameMaxKernelSize(G);
+					throw std::runtime_error(str.str());
+				}
+			}
+			// The loop above names the layer; what the launcher compares is the plan's largest staged block of ANY stage type.  Today
+			// that is always a layer's (the array link stages 512 floats), so this cannot fire -- it keeps "a model that loads can run
+			// every buffer" exact should another stage type ever stage a block of its own.
+			if (!FrameModelFits(plan.maxA4Floats))
+			{
+				std::stringstream str;
+				str << "WaveNet: the largest staged weight block (" << plan.maxA4Floats << " floats) needs " << FrameLaunchLdsBytes(plan.maxA4Floats, 2, 1, 1)
+				    << " bytes of LDS on the f32 frame kernel (limit " << FRAME_LDS_LIMIT << ")";
+				throw std::runtime_error(str.str());
+			}
+			return;
+		}
 		const std::string who = "WaveNet with layer arrays wider than 16 channels (f16-split arithmetic only): ";
 		if (!plan.splitWeightsOk)
 			throw std::runtime_error(who + "the weights do not fit the (hi, lo) f16 operand format (a weight beyond 32752, or a weight matrix whose largest entry is below 2^-12)");

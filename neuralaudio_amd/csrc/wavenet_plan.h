@@ -64,7 +64,9 @@ namespace na
 	WaveNetPlan BuildWaveNetPlan(const WaveNetDesc& desc, bool splitStateFormat = false);
 	// Layer arrays wider than 16 channels run on the runtime-shaped kernels only, whose operands are f16 (hi, lo) pairs and which have no
 	// f32 fallback: throws std::runtime_error at LOAD time for a model whose weights do not fit that format or whose range bound leaves
-	// an input limit below kSplitMinInputLimit.  Narrower models always have a kernel: nothing to check.
+	// an input limit below kSplitMinInputLimit.  Narrower models always have a kernel, the f32 frame kernel, as long as
+	// the weight block of every layer fits its LDS beside one stream's 128-frame block (frame_lds.h): a layer kernel size beyond that
+	// (70 at 13 .. 16 channels) is refused with a message naming the layer.
 	void CheckWaveNetRunnable(const WaveNetDesc& desc);
 	// Stream packing (wavenet_plan.cpp): how many streams of this model fit one virtual stream of the f16-split kernel (1: none),
 	// the virtual model, and its plan (WaveNetPlan::pack = P; arrays / rings / stages describe the VIRTUAL model).

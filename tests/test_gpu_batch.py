@@ -59,8 +59,10 @@ def test_config3_mixed_lite_feather_nano_batch(na, loader):
 
 
 def test_fused_launch_odd_group_sizes_two_streams_per_workgroup(na, loader):
-    """>= 512 streams: one fused launch over three architectures with two streams per workgroup; odd group sizes leave a
-    half-filled last workgroup per group (the shadow wave must not write), interleaved rows make the slot/row tables non-contiguous."""
+    """>= 512 streams of three architectures in one batch, odd group sizes, interleaved rows that make the slot / row tables
+    non-contiguous.  Written in round 1 for the f32 frame kernel's fused launch with two streams per workgroup and its shadow wave; by
+    default Standard now runs on the specialised split chain and Feather and Nano on the packed split chains (WaveNetSpecKernel), so
+    this test reaches THEIR fused launches and tables -- the frame kernel's are in tests/test_gpu_frame.py."""
     std = loader.CreateFromFile(_path("BossWN-standard.nam"), doPrewarm=False)
     feather = loader.CreateFromFile(_path("BossWN-feather.nam"), doPrewarm=False)
     nano = loader.CreateFromFile(_path("BossWN-nano.nam"), doPrewarm=False)
@@ -685,7 +687,7 @@ def test_ondemand_composite_load_mode(na):
     b.AddStreams(la, 2, quality=1.0)
     if os.environ.get("NA_WN_KERNEL") == "generic":
         return  # (every group of the runtime-shaped kernel is a launch of its own)
-    assert b.IsQualityChangeRealtimeSafe(0, 0.1)  # both submodels ride in one frame-kernel launch
+    assert b.IsQualityChangeRealtimeSafe(0, 0.1)  # both submodels ride in one WaveNet launch (by default the A2 chains of the f16-split kernels)
     b.AddStreams(na.NeuralModelLoader().CreateFromFile(_path("BossLSTM-1x16.nam")), 1)
     assert not b.IsQualityChangeRealtimeSafe(0, 0.1)  # WaveNet launch + recurrent launch: two units
 

@@ -76,6 +76,19 @@ def test_forced_recurrent_regime_passes_the_runtime_shaped_kernel_suite(env):
     forced_run(dict(env, NA_TEST_NO_WARM="1"), [os.path.join(T, "test_gpu_recurrent_rt.py")], 240)
 
 
+# the f32 frame kernel's instantiations that ship behind a tuning knob over its own file (the knobs do not skip it): ring history
+# prefetched into LDS (Launch<2, 2, 1> and <2, 2, 2>), no prefetch at all for long buffers too (<2, 0, 1>), and four streams per workgroup
+# (<2, 1, 4>) -- each takes the default shape where its LDS does not fit (frame_lds.h), which the file's large-kernel tests reach.
+FRAME = [{"NA_FR_PF": "2"}, {"NA_FR_PF": "0"}, {"NA_FR_SPB": "4"}]
+
+
+@pytest.mark.gpu
+@pytest.mark.watchdog(260)
+@pytest.mark.parametrize("env", FRAME, ids=ident)
+def test_forced_frame_kernel_regime_passes_the_frame_kernel_suite(env):
+    forced_run(dict(env, NA_TEST_NO_WARM="1"), [os.path.join(T, "test_gpu_frame.py")], 240)
+
+
 @pytest.mark.gpu_soak
 @pytest.mark.watchdog(330)
 @pytest.mark.parametrize("env", SOAK, ids=ident)

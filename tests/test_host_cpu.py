@@ -18,6 +18,7 @@ import pytest
 
 import na_oracle as O
 import ref_np
+import frame_cases as FC
 import recurrent_cases as RC
 import wide_cases as WC
 
@@ -998,3 +999,128 @@ def test_recurrent_oracle_keeps_its_headroom_under_the_gpu_bound(c):
         err = O.rms(got - want)
         print("%s amplitude %g: oracle-float64 rms %.3g, bound %.3g" % (RC.case_id(c), amp, err, RC.bound(want)))
         assert np.all(np.isfinite(got)) and err <= share * RC.bound(want), (RC.case_id(c), amp, err, RC.bound(want))
+
+
+# ---- the f32 frame kernel's test shapes (tests/frame_cases.py, run by tests/test_gpu_frame.py) -------------------------------------------
+
+def _frame_cases():
+    fuzz = [FC.fuzz_case(seed) for seed in range(FC.NUM_FUZZ_SEEDS)]
+    batch = [FC.small_k2_model()] + FC.table_models() + FC.fused_models() + [FC.lds_model(k) for k in (62, 63, 70)]
+    return FC.named_cases(), fuzz, batch
+
+
+def test_every_frame_case_loads_and_is_predicted_on_the_frame_kernel(na):
+    """tests/test_gpu_frame.py runs every case without a skip and asserts the kernel's name before it trusts a comparison, so every
+    generated shape must load and land on the f32 frame kernel by default -- at one stream and at 600, so neither packing nor padding
+    takes it away -- with no input limit, and with the receptive field its layers add up to."""
+    loader = na.NeuralModelLoader()
+    named, fuzz, batch = _frame_cases()
+    names = [c["name"] for c in named + [c for c, _ in fuzz] + batch]
+    assert len(set(names)) == len(names)
+    for case in named + [c for c, _ in fuzz] + batch:
+        arrays = case["arrays"]
+        assert max(max(a["channels"], a["head_size"], a["input_size"]) for a in arrays) <= 16 and 1 <= len(arrays) <= 2, case["name"]
+        assert all(1 <= len(a["kernel_sizes"]) <= (4 if case["family"] != "no range proof" else 13) for a in arrays), case["name"]
+        assert case["rule"] in (FC.RULE_F32, FC.RULE_F64) and (case["rule"] == FC.RULE_F64) == bool(case["scale"]), case["name"]
+        m = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, FC.weights(case)), ".nam", doPrewarm=False)
+        assert m is not None, case["name"]
+        for streams in (1, 600):
+            info = m.KernelInfo(1.0, streams)
+            assert info["kernel"] == "frame" and info["pack"] == 1 and info["input_limit"] == float("inf"), (case["name"], streams, info)
+        assert m.GetReceptiveFieldSize() == FC.receptive_field(arrays), case["name"]
+        assert FC.work(arrays, case["samples"]) <= FC.WORK_CAP, case["name"]
+    for case, sizes in fuzz:
+        assert sizes[:3] == [1, 1, 17] and sum(sizes) == FC.SAMPLES == case["samples"], case["name"]
+        assert set(sizes) & {31, 63, 64, 65, 127, 128} and max(sizes) > FC.BLOCK, (case["name"], sizes)
+    for case in named + [c for c, _ in fuzz]:  # every ring wraps at least twice
+        longest = max(FC.ring_frames((k - 1) * d) for a in case["arrays"] for k, d in zip(a["kernel_sizes"], a["dilations"]))
+        assert case["samples"] >= 2 * max(longest, FC.ring_frames(case["arrays"][-1]["head_kernel_size"] - 1)), (case["name"], longest)
+
+
+def test_frame_cases_reach_every_path_of_the_kernel_they_name():
+    """The named cases alone -- and the seeded draw once more -- reach: every channel-group count, partially filled groups, both
+    activations, one and two arrays with equal and with different G across the link, conv heads on both sides of the reach that picks
+    HeadConvLds or HeadConvPk (with and without a bias, every head G), staged blocks on both sides of the stager's 384 and 512 float4,
+    kernel sizes on both sides of the wide prefetch depth at G <= 2 and at G >= 3, tap shifts on both sides of 64 and of 128 frames, a
+    K = 1 layer, and a model without the range proof."""
+    named, fuzz, _ = _frame_cases()
+
+    def reach(cases):
+        r = dict(G=set(), partial=set(), acts=set(), arrays=set(), link=set(), head=set(), blocks=set(), taps=set(), shifts=set(), ks=set(), rules=set())
+        for c in cases:
+            arrays = c["arrays"]
+            r["arrays"].add(len(arrays))
+            r["rules"].add(c["rule"])
+            if len(arrays) == 2:
+                r["link"].add(FC.groups(arrays[0]["channels"]) == FC.groups(arrays[1]["channels"]))
+            last = arrays[-1]
+            if last["head_kernel_size"] > 1:
+                r["head"].add((last["head_kernel_size"] - 1 <= FC.HEAD_SHORT_REACH, FC.groups(last["channels"]), bool(last["has_head_bias"])))
+            maxk = max(k for a in arrays for k in a["kernel_sizes"])
+            for a in arrays:
+                g = FC.groups(a["channels"])
+                r["G"].add(g)
+                r["partial"].add((g, a["channels"] % 4 != 0))
+                r["acts"].add(a["activation"])
+                for k in a["kernel_sizes"]:
+                    r["ks"].add(k)
+                    f4 = FC.layer_block_f4(k, a["channels"])
+                    r["blocks"].add((f4 > FC.STAGER_F4, f4 > FC.STAGER_F4_SPB))
+                    if maxk > 3:  # (the kernel's `wide`: a model with a K > 3 requests five taps ahead in its G <= 2 runs)
+                        r["taps"].add((g <= 2, (k - 1 > FC.HPF_WIDE) - (k - 1 < FC.HPF_WIDE)))
+            r["shifts"].update(FC.layer_shifts(arrays))
+        return r
+
+    for what, r in (("named", reach(named)), ("fuzz", reach([c for c, _ in fuzz]))):
+        assert r["G"] == {1, 2, 3, 4} and r["acts"] == {O.ACT_TANH, O.ACT_LEAKYRELU} and r["arrays"] == {1, 2} and r["link"] == {True, False}, (what, r)
+        assert {p for p in r["partial"] if p[1]} == {(g, True) for g in (1, 2, 3, 4)}, (what, r["partial"])
+        assert {h[0] for h in r["head"]} == {True, False}, (what, r["head"])
+        assert {(False, False), (True, False), (True, True)} <= r["blocks"], (what, r["blocks"])
+        assert {(wide, side) for wide in (True, False) for side in (-1, 0, 1)} <= r["taps"], (what, r["taps"])
+        for edge in (64, 128):
+            assert any(s < edge for s in r["shifts"]) and edge in r["shifts"] and any(edge < s < edge + 64 for s in r["shifts"]), (what, edge, r["shifts"])
+        assert 1 in r["ks"], (what, r["ks"])
+    r = reach(named)
+    assert r["rules"] == {FC.RULE_F32, FC.RULE_F64}
+    assert {h[:2] for h in r["head"]} == {(s, g) for s in (True, False) for g in (1, 2, 3, 4)}, r["head"]  # both head kernels at every head G ...
+    assert {(h[0], h[2]) for h in r["head"]} == {(s, b) for s in (True, False) for b in (True, False)}, r["head"]  # ... with and without bias
+    assert {c["arrays"][0]["channels"] for c in named if c["family"] == "g sweep" and len(c["arrays"]) == 1} == set(FC.CHANNELS)
+    assert set(FC.layer_shifts([a for c in named if c["family"] == "tap shifts" for a in c["arrays"]])) >= {d * m for d in FC.SHIFT_DILATIONS for m in (1, 2, 3)}
+
+
+def test_frame_kernel_lds_limit_is_decided_at_load(na, tmp_path):
+    """frame_lds.h is the one place that sizes the LDS of a frame-kernel launch (block images + two staged weight blocks of the launch's
+    largest layer + the optional history buffers, against the 160 KB of a gfx950 workgroup).  16 channels: K = 62 fits two streams per
+    workgroup (162 176 bytes) and K = 63 does not (164 224) -- the launcher then takes one; K = 70 fits one stream with 128-frame blocks
+    (162 176) and K = 71 only 64-frame blocks (156 032 against 164 224): such a model could not run a buffer of more than 64 frames, and
+    is refused when it loads, with the layer and its kernel size in the message."""
+    exe = tmp_path / "frame_lds_cases"
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "neuralaudio_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "frame_lds_cases.cpp"), "-o", str(exe)], check=True)
+    rows = [(16, 62, 2, 2, 1), (16, 63, 2, 2, 1), (16, 63, 2, 1, 1), (16, 70, 2, 1, 1), (16, 71, 2, 1, 1), (16, 71, 1, 1, 0), (16, 70, 2, 1, 2),
+            (16, 3, 2, 4, 1), (16, 3, 1, 1, 0), (4, 23, 2, 1, 1)]
+    text = "".join(" ".join(map(str, r)) + "\n" for r in rows)
+    out = [tuple(int(v) for v in line.split()) for line in subprocess.run([str(exe)], input=text, capture_output=True, text=True, check=True).stdout.splitlines()]
+    assert len(out) == len(rows)
+    got = {r: o for r, o in zip(rows, out)}
+    for r, o in got.items():  # the formula of the issue, restated: images + two weight buffers (at least what the stager writes) + history buffers
+        c, k, wps, spb, pf = r
+        g = (c + 3) // 4
+        floats = (k + 1) * 64 * g + 12 * g
+        stride = max((floats + 3) // 4, 384 if wps * spb <= 2 else 512)
+        lds = spb * 2 * wps * 4 * 64 * 16 + 2 * stride * 16 + (wps * spb * 2 * 4 * 64 * 16 if pf == 2 else 0)
+        assert o[:4] == (floats, stride, lds, int(lds <= 160 * 1024)), (r, o)
+    assert got[(16, 62, 2, 2, 1)][2:4] == (162176, 1) and got[(16, 63, 2, 2, 1)][2:4] == (164224, 0) and got[(16, 63, 2, 1, 1)][3] == 1
+    assert got[(16, 70, 2, 1, 1)][2:5] == (162176, 1, 1) and got[(16, 71, 2, 1, 1)][2:5] == (164224, 0, 0) and got[(16, 71, 1, 1, 0)][2:4] == (156032, 1)
+    assert got[(16, 70, 2, 1, 2)][3] == 0  # (the LDS history buffers of NA_FR_PF=2 give way: the launcher falls back to registers)
+    assert got[(16, 70, 2, 1, 1)][5] == 70 and got[(16, 3, 2, 4, 1)][2:4] == (4 * 16384 + 2 * 512 * 16, 1) and got[(16, 3, 1, 1, 0)][2] == 8192 + 2 * 384 * 16
+    loader = na.NeuralModelLoader()
+    for k in (62, 63, 70):
+        case = FC.lds_model(k)
+        assert loader.CreateFromString(O.nam_json_wavenet_generic(case["arrays"], FC.weights(case)), ".nam", doPrewarm=False) is not None
+    case = FC.lds_model(71)
+    with pytest.raises(na.NeuralAudioError, match=r"layer array 0, layer 0: kernel size 71 at 16 channels needs 164224 bytes of LDS.*largest kernel size at this width is 70"):
+        loader.CreateFromString(O.nam_json_wavenet_generic(case["arrays"], FC.weights(case)), ".nam", doPrewarm=False)
+    # the limit follows the width: a second array of 4 channels may use a kernel size no 16-channel array may
+    arrays = FC.chain([16, 4], [([2], [1]), ([71], [1])], O.ACT_TANH)
+    assert loader.CreateFromString(O.nam_json_wavenet_generic(arrays, O.synth_wavenet_weights(arrays, seed=3)), ".nam", doPrewarm=False) is not None
