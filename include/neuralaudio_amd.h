@@ -137,6 +137,58 @@ NA_EXTERN int NA_BatchSetStreamGain(NA_Batch* batch, int stream, float gain, int
 NA_EXTERN float NA_BatchGetStreamGain(NA_Batch* batch, int stream); /* the target; 1 for a stream that never had one; < 0: bad id */
 NA_EXTERN int NA_BatchHandover(NA_Batch* batch, int from, int to, float quality, int fadeSamples);
 NA_EXTERN int NA_BatchHandoverRemaining(NA_Batch* batch, int stream); /* samples left of the fade `stream` is part of (either side); 0: none; < 0: stage not enabled / bad id */
+/* ---- the cabinet stage: per-stream impulse-response convolution ----
+ * Almost every capture this library runs is an amp without its cabinet; a session becomes listenable once the model output has been
+ * convolved with a cabinet impulse response (IR).  A host of the reference does that itself, with the samples in its hands; here the
+ * rows stay on the device, so this is the place for it: a second per-stream stage behind the model launches (behind the down kernel of
+ * a resampling batch) and in front of the output stage.  For every stream that has an IR the row's samples are replaced by their
+ * convolution with that IR.  A batch that enabled the stage and assigned no IR launches exactly what it launched before.
+ * Set-up side (not real-time safe: they allocate and may wait for what is in flight):
+ *   NA_BatchEnableCabinetStage(maxTaps in [1, 8192]) allocates one history ring per row of the batch's capacity -- ringSamples floats,
+ *     a power of two >= maxTaps - 1 + pieceSamples; pieceSamples is the longest run the stage processes at once, longer calls run in
+ *     pieces -- and the stage's tables; later NA_BatchAddStreams / NA_BatchReserveStreams grow both.  Idempotent for an equal or
+ *     smaller maxTaps; a larger maxTaps is refused while any stream has an IR.  Every call below fails ("cabinet stage not enabled")
+ *     before it.  NA_BatchGetCabinetInfo reports the sizes in effect and the device memory the stage holds.
+ *   NA_BatchLoadIR copies numTaps in [1, maxTaps] finite taps to the device and returns an IR id >= 0 (-1: failure); many streams may
+ *     share one IR; ids of unloaded IRs are recycled.  Taps are given at the rate of the rows the caller sees (in a resampling batch:
+ *     the external rate); the library does not resample IRs and reads no files.  NA_BatchUnloadIR fails while a stream uses the IR or
+ *     fades from it.
+ * Arithmetic -- all of it f32; positions count the samples the caller sees:
+ *   y is the stream's row as the call would have produced it without this stage.  T0 is the position of the first sample after the
+ *     set call that gave a dry stream an IR: y[t] = 0 for t < T0 (the history starts empty).
+ *   For an IR h of K taps: c_h[t] = sum over k in [0, K) of h[k] * y[t - k].  The dry path is the one-tap IR {1}: c_dry[t] = y[t],
+ *     bit for bit as a value.
+ *   Fade.  NA_BatchSetStreamIR from A to B with length N gives the k-th sample after the call (1 - w) * c_A[t] + w * c_B[t], with
+ *     w = (min(k, N-1) + 1) / N.  N = 0 means B from k = 0.  fadeSamples lies in [0, 1 << 20].  A switch between two IRs reads the same
+ *     history, so it is exact: after the fade the row is what it would be had the stream had B since T0.  A switch from dry starts the
+ *     history at T0; a stream that has faded to dry drops it.
+ *   Summation order.  Products and sums are f32 FMAs; the order in which one output's K products are summed is a function of the tap
+ *     index k and of K only (csrc/cabinet_stage.h): a sample's value does not depend on how the signal is cut into calls, on the
+ *     sample's index in a call, on row alignment or stride, on how many entries the launch has, or on maxTaps.  Any order is within
+ *     (K + 4) * 2^-24 * sum |h[k]| |y[t - k]| of the exact sum; integer taps and samples whose partial sums stay below 2^24 are exact.
+ *   With the output stage.  Its y_from / y_to are this stage's outputs: every row is convolved with its own IR first, then scaled and
+ *     cross-faded.  A preset change that keeps its cabinet: NA_BatchHandover(from, to, ...), then NA_BatchSetStreamIR(to, ir, 0).
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); the IR id must be loaded (or -1: dry); a set call while an IR fade of that stream is running is refused;
+ * a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a hand-over, make the stream
+ * dry at once and drop its history: a parked stream carries nothing over, and an activated stream is dry.  IR assignment and history
+ * are not part of a NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves them alone.
+ * NA_BatchSetStreamIR, NA_BatchGetStreamIR and NA_BatchStreamIRFadeRemaining are REAL-TIME SAFE: host arithmetic on tables that exist.
+ * While an entry exists -- a stream with an IR, or a fade towards dry -- a processing call behaves as it does with output-stage
+ * entries: its launches run in order on one stream (no half-batch chains, no resident launch), host buffers go through the library's
+ * device staging block, and it enqueues one table upload from a ring of pinned tables plus two launches (append to the rings,
+ * convolve) per piece of the call, over the streams with an entry only: no device or pinned allocation, no stream or event creation,
+ * no unbounded wait.  The cost follows each IR's own length, not maxTaps.  When the last entry retires -- its fade to dry has
+ * finished -- the free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; IR file reading; IR rate conversion; stereo IRs. */
+typedef struct NA_CabinetInfo { int maxTaps, ringSamples, pieceSamples, numIRs; long long deviceBytes; } NA_CabinetInfo;
+NA_EXTERN int NA_BatchEnableCabinetStage(NA_Batch* batch, int maxTaps);
+NA_EXTERN int NA_BatchGetCabinetInfo(NA_Batch* batch, NA_CabinetInfo* info);
+NA_EXTERN int NA_BatchLoadIR(NA_Batch* batch, const float* taps, int numTaps); /* an IR id >= 0; -1: failure */
+NA_EXTERN int NA_BatchUnloadIR(NA_Batch* batch, int ir);
+NA_EXTERN int NA_BatchSetStreamIR(NA_Batch* batch, int stream, int ir, int fadeSamples); /* ir = -1: none (dry) */
+NA_EXTERN int NA_BatchGetStreamIR(NA_Batch* batch, int stream); /* the target: id, -1 dry, <= -2 bad id / not enabled */
+NA_EXTERN int NA_BatchStreamIRFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's IR fade; 0: none; < 0: stage not enabled / bad id */
 NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);
@@ -488,6 +540,11 @@ NA_EXTERN int NA_DebugResampleTap(NA_Batch* batch, float* modelIn, float* modelO
 NA_EXTERN void NA_DebugSetRenderTap(float* modelIn, float* modelOut, long long capacity);
 /* tuning aid: device buffer (long long[stages*4*waves]) that workgroup 0 of the WaveNet kernel stamps with the shader clock; NULL = off */
 NA_EXTERN void NA_DebugSetTraceBuffer(void* deviceBuffer);
+/* Tests: runs on [NA_BatchNumStreams][n] host rows (`stride` floats apart), in place of model outputs, exactly what a processing call
+ * of n samples runs for the cabinet stage: table, launches, book advance.  Synchronous; set-up side (it allocates a device block). */
+NA_EXTERN int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
+/* Tests: launches of the cabinet stage's kernels so far (two per piece of a call with entries) */
+NA_EXTERN long long NA_DebugCabinetLaunches(void);
 #endif /* NA_RELEASE */
 
 #ifdef __cplusplus

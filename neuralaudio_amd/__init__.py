@@ -352,6 +352,54 @@ class Batch:
             raise NeuralAudioError(capi.last_error())
         return left
 
+    # -- the cabinet stage: EnableCabinetStage / LoadIR / UnloadIR are set-up side; SetStreamIR is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableCabinetStage(self, maxTaps):
+        if self._lib.NA_BatchEnableCabinetStage(self._h, int(maxTaps)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def CabinetInfo(self):
+        info = capi.NA_CabinetInfo()
+        if self._lib.NA_BatchGetCabinetInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_CabinetInfo._fields_}
+
+    def LoadIR(self, taps):
+        """Copies an impulse response (1-D, at the rate of the rows the caller sees) to the device; returns its id."""
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        ir = int(self._lib.NA_BatchLoadIR(self._h, _fptr(taps), int(taps.size)))
+        if ir < 0:
+            raise NeuralAudioError(capi.last_error())
+        return ir
+
+    def UnloadIR(self, ir):
+        if self._lib.NA_BatchUnloadIR(self._h, int(ir)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def SetStreamIR(self, stream, ir, fadeSamples=0):
+        """The stream's row is convolved with IR `ir` from the next sample on (-1: dry), cross-faded over `fadeSamples` samples."""
+        if self._lib.NA_BatchSetStreamIR(self._h, int(stream), int(ir), int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamIR(self, stream):
+        ir = int(self._lib.NA_BatchGetStreamIR(self._h, int(stream)))
+        if ir <= -2:
+            raise NeuralAudioError(capi.last_error())
+        return ir
+
+    def IRFadeRemaining(self, stream):
+        left = int(self._lib.NA_BatchStreamIRFadeRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
+
+    def DebugRunCabinetStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunCabinetStage)."""
+        assert rows.dtype == np.float32 and rows.flags["C_CONTIGUOUS"] and rows.ndim == 2 and rows.shape[0] == self.NumStreams()
+        n = rows.shape[1] if n is None else int(n)
+        if self._lib.NA_DebugRunCabinetStage(self._h, _fptr(rows), int(rows.shape[1]), n) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return rows
+
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:
             raise NeuralAudioError(capi.last_error())

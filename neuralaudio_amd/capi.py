@@ -40,6 +40,8 @@ NA_SYMBOLS = [
     "NA_BatchReserveStreams", "NA_BatchActivateStream", "NA_BatchParkStream", "NA_BatchIsParked", "NA_BatchFindParked", "NA_BatchNumParked",
     "NA_DebugDeviceResourceCalls", "NA_DebugRecurrentPlan", "NA_DebugRecurrentShapePlan",
     "NA_BatchEnableOutputStage", "NA_BatchSetStreamGain", "NA_BatchGetStreamGain", "NA_BatchHandover", "NA_BatchHandoverRemaining",
+    "NA_BatchEnableCabinetStage", "NA_BatchGetCabinetInfo", "NA_BatchLoadIR", "NA_BatchUnloadIR", "NA_BatchSetStreamIR", "NA_BatchGetStreamIR",
+    "NA_BatchStreamIRFadeRemaining", "NA_DebugRunCabinetStage", "NA_DebugCabinetLaunches",
 ]
 
 
@@ -61,6 +63,11 @@ class NA_ResampleInfo(C.Structure):
     _fields_ = [("externalRate", C.c_int), ("modelRate", C.c_int), ("ticksExternal", C.c_int), ("ticksModel", C.c_int),
                 ("tapsUp", C.c_int), ("tapsDown", C.c_int), ("quantum", C.c_int), ("latencySamples", C.c_int),
                 ("prototypeLength", C.c_int)]
+
+
+class NA_CabinetInfo(C.Structure):
+    _fields_ = [("maxTaps", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numIRs", C.c_int), ("deviceBytes", C.c_longlong)]
+
 
 _lib = None
 
@@ -155,6 +162,15 @@ def load_library():
         "NA_BatchGetStreamGain": (C.c_float, [vp, C.c_int]),
         "NA_BatchHandover": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_int]),
         "NA_BatchHandoverRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_BatchEnableCabinetStage": (C.c_int, [vp, C.c_int]),
+        "NA_BatchGetCabinetInfo": (C.c_int, [vp, C.POINTER(NA_CabinetInfo)]),
+        "NA_BatchLoadIR": (C.c_int, [vp, fp, C.c_int]),
+        "NA_BatchUnloadIR": (C.c_int, [vp, C.c_int]),
+        "NA_BatchSetStreamIR": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+        "NA_BatchGetStreamIR": (C.c_int, [vp, C.c_int]),
+        "NA_BatchStreamIRFadeRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_DebugRunCabinetStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
+        "NA_DebugCabinetLaunches": (C.c_longlong, []),
         "NA_DebugRecurrentPlan": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "NA_DebugRecurrentShapePlan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
         "NA_MultiCreate": (vp, [C.POINTER(C.c_int), C.c_int]),

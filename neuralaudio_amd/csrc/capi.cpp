@@ -533,6 +533,86 @@ int NA_BatchHandoverRemaining(NA_Batch* batch, int stream)
 	return rc == 0 ? left : -1;
 }
 
+// ---- the cabinet stage (gpu_batch.h EnableCabinetStage / LoadIR / SetStreamIR) ----
+int NA_BatchEnableCabinetStage(NA_Batch* batch, int maxTaps)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchEnableCabinetStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->EnableCabinetStage(maxTaps);
+	});
+}
+
+int NA_BatchGetCabinetInfo(NA_Batch* batch, NA_CabinetInfo* info)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchGetCabinetInfo: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		if (!info) throw std::runtime_error("NA_BatchGetCabinetInfo: bad argument");
+		const na::CabinetStageInfo i = batch->batch->GetCabinetInfo();
+		info->maxTaps = i.maxTaps;
+		info->ringSamples = i.ringSamples;
+		info->pieceSamples = i.pieceSamples;
+		info->numIRs = i.numIRs;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchLoadIR(NA_Batch* batch, const float* taps, int numTaps)
+{
+	int id = -1;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchLoadIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		id = batch->batch->LoadIR(taps, numTaps);
+	});
+	return rc == 0 ? id : -1;
+}
+
+int NA_BatchUnloadIR(NA_Batch* batch, int ir)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchUnloadIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->UnloadIR(ir);
+	});
+}
+
+int NA_BatchSetStreamIR(NA_Batch* batch, int stream, int ir, int fadeSamples)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchSetStreamIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->SetStreamIR(stream, ir, fadeSamples);
+	});
+}
+
+int NA_BatchGetStreamIR(NA_Batch* batch, int stream)
+{
+	int ir = -2;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchGetStreamIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		ir = batch->batch->GetStreamIR(stream);
+	});
+	return rc == 0 ? ir : -2;
+}
+
+int NA_BatchStreamIRFadeRemaining(NA_Batch* batch, int stream)
+{
+	int left = 0;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchStreamIRFadeRemaining: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		left = batch->batch->StreamIRFadeRemaining(stream);
+	});
+	return rc == 0 ? left : -1;
+}
+
+#ifndef NA_RELEASE
+int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunCabinetStage: null batch");
+		batch->batch->DebugRunCabinetStage(hostRows, stride, n);
+	});
+}
+long long NA_DebugCabinetLaunches(void) { return (long long)na::CabinetStageLaunches(); }
+#endif
+
 #ifndef NA_RELEASE
 long long NA_DebugDeviceResourceCalls(void) { return na::DeviceResourceCalls(); }
 #endif

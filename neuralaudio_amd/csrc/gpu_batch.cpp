@@ -144,6 +144,7 @@ namespace na
 			for (auto& g : groups) (void)g.release();
 			(void)residentState.release();
 			(void)resample.release();
+			(void)cabStage.release();
 			for (WnLaunchTable& t : wnTable) t.entries.clear();
 			return;
 		}
@@ -333,6 +334,7 @@ namespace na
 			pendingHistoryZero.reserve(streams.size());
 		}
 		if (outStage) EnsureStageRows((int)streams.size());
+		if (cabStage) EnsureCabinetRows((int)streams.size());
 		return first;
 	}
 
@@ -620,10 +622,12 @@ namespace na
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{
-		if (outStage && !outStage->inside && outStage->book.HasEntries())
+		const bool cabEntries = cabStage && cabStage->book.HasEntries(), outEntries = outStage && outStage->book.HasEntries();
+		if (!stagesInside && (cabEntries || outEntries))
 		{
-			// the output stage: behind everything this call launches -- the join of the units, the graph replay, the down
-			// kernel of a resampling batch -- on the same stream, outside any capture
+			// the per-stream stages: behind everything this call launches -- the join of the units, the graph replay,
+			// the down kernel of a resampling batch -- on the same stream, outside any capture: every row is convolved with its own IR
+			// first, then scaled and cross-faded
 			struct Inside
 			{
 				bool& flag;
@@ -631,10 +635,11 @@ namespace na
 				~Inside() { flag = false; }
 			};
 			{
-				Inside inside(outStage->inside);
+				Inside inside(stagesInside);
 				ProcessDeviceOn(launch, dIn, dOut, n, inStride, outStride);
 			}
-			RunOutputStage(launch, dOut, n, outStride);
+			if (cabEntries) RunCabinetStage(launch, dOut, n, outStride);
+			if (outEntries) RunOutputStage(launch, dOut, n, outStride);
 			return;
 		}
 		if (resample && !resample->plan.identity && !resample->inside)

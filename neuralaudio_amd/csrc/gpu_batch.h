@@ -17,6 +17,7 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "cabinet_stage.h"
 #include "device_resources.h"
 #include "launch_plan.h"
 #include "model_loader.h"
@@ -60,6 +61,12 @@ namespace na
 		bool rangeProven = true, weightsOk = true;
 	};
 	ModelKernelInfo PredictModelKernel(const LoadedModel& model, float quality, int streams);
+
+	struct CabinetStageInfo
+	{
+		int maxTaps = 0, ringSamples = 0, pieceSamples = 0, numIRs = 0;
+		long long deviceBytes = 0;
+	};
 
 	class ModelGroup; // one per distinct ModelDesc: packed weights + state of all its streams
 
@@ -120,6 +127,23 @@ namespace na
 		float GetStreamGain(int stream) const; // the target; < 0: not a live or parked stream of the batch
 		void Handover(int from, int to, float quality, int fadeSamples);
 		int HandoverRemaining(int stream) const;
+
+		// The cabinet stage (cabinet_stage.h): per-stream convolution of the row with an impulse response, behind the
+		// model launches (and the down kernel of a resampling batch) and in front of the output stage.  EnableCabinetStage, LoadIR and
+		// UnloadIR are the set-up side: a history ring per row (CreateStreams grows them), the tables, the IRs' taps on the device.
+		// SetStreamIR is host arithmetic on those tables; while an entry exists -- a stream with an IR, or a fade towards dry -- every
+		// processing call runs on the ordered path and enqueues ONE table upload and two launches per piece of kCabPieceSamples samples.
+		// Without an entry the batch launches exactly what it launches without the stage.
+		void EnableCabinetStage(int maxTaps);
+		bool HasCabinetStage() const { return cabStage != nullptr; }
+		CabinetStageInfo GetCabinetInfo() const;
+		int LoadIR(const float* taps, int numTaps);
+		void UnloadIR(int ir);
+		void SetStreamIR(int stream, int ir, int fadeSamples); // ir = -1: dry
+		int GetStreamIR(int stream) const;                     // the target
+		int StreamIRFadeRemaining(int stream) const;
+		// test hook (NA_DebugRunCabinetStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
+		void DebugRunCabinetStage(float* hostRows, long stride, size_t n);
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -273,11 +297,17 @@ namespace na
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
 		struct OutputStage; // (gpu_batch_internal.h)
 		std::unique_ptr<OutputStage> outStage;
-		bool StageHasEntries() const;
+		bool StageHasEntries() const; // of either stage
 		void EnsureStageRows(int rows);  // set-up side: tables for `rows` rows
 		void StageParkFinished();        // top of every processing call: the `from` streams of the fades that ended in the last one are parked
 		void StageLeave(int stream);     // park / removal: its fade ends, its gain is 1 again
 		void RunOutputStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + launch + the host mirror's advance
+		bool stagesInside = false;       // the model launches of a call with stage entries are under way (ProcessDeviceOn)
+		struct CabinetStage; // (gpu_batch_internal.h)
+		std::unique_ptr<CabinetStage> cabStage;
+		void EnsureCabinetRows(int rows); // set-up side: rings and tables for `rows` rows
+		void CabinetLeave(int stream);    // park / removal: dry at once, the history dropped
+		void RunCabinetStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + two launches per piece + the host mirror's advance
 		int AllocateIds(int count);
 		void DropTrailingRetiredRows();
 		// the kinds of the groups that have active streams once `leaving` has lost / `entering` has gained one, in group order (`active`:

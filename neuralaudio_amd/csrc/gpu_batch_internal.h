@@ -93,7 +93,6 @@ namespace na
 		bool used[kTables] = {};
 		int next = 0;
 		int capacity = 0;             // entries per table
-		bool inside = false;          // the model launches of a call with entries are under way (ProcessDeviceOn)
 		~OutputStage()
 		{
 			for (int i = 0; i < kTables; i++)
@@ -105,6 +104,25 @@ namespace na
 		}
 	};
 	hipError_t LaunchOutputStage(const OutStageLaunch& L, hipStream_t stream); // (output_stage_kernels.hip)
+
+	// the cabinet stage of a batch (cabinet_stage.h): the host mirror, the rows' history rings, the IRs' taps (owned
+	// through the book's ids) and the ring of entry tables
+	struct GpuBatch::CabinetStage
+	{
+		static constexpr int kTables = GpuBatch::kPipelineSlots + 1; // (as the output stage's)
+		CabinetBook book;
+		float* rings = nullptr;           // [ringRows][book.RingSamples()]
+		int ringRows = 0;
+		long long tapBytes = 0;           // device bytes of the loaded IRs
+		CabEntry* host[kTables] = {};     // pinned
+		CabEntry* dev[kTables] = {};
+		hipEvent_t done[kTables] = {};    // the launches that read dev[i] (and the upload that read host[i]) are over
+		bool used[kTables] = {};
+		int next = 0;
+		int capacity = 0;                 // entries per table
+		~CabinetStage();
+	};
+	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece
 
 	bool HostDirect(); // (gpu_batch_host.cpp) the kernels read / write pinned host blocks themselves instead of the copy engines
 }

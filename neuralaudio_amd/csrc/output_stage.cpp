@@ -46,7 +46,7 @@ namespace na
 		st.capacity = want;
 	}
 
-	bool GpuBatch::StageHasEntries() const { return outStage && outStage->book.HasEntries(); }
+	bool GpuBatch::StageHasEntries() const { return (outStage && outStage->book.HasEntries()) || (cabStage && cabStage->book.HasEntries()); }
 
 	void GpuBatch::SetStreamGain(int s, float gain, int rampSamples)
 	{
@@ -102,6 +102,7 @@ namespace na
 	// at its own gain -- and its own gain is 1 again: a parked stream carries nothing over.
 	void GpuBatch::StageLeave(int s)
 	{
+		CabinetLeave(s);
 		if (!outStage || s >= outStage->book.Rows()) return;
 		OutputStageBook& book = outStage->book;
 		(void)book.EndFadeOf(s);

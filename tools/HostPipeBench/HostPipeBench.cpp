@@ -14,6 +14,8 @@
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --handover K [--mix <model 2>] [--fade N=256]
 //       the click-free model switch on a batch that never stops (RunHandover below): every K-th buffer one of 16 sessions is handed over
 //       (NA_BatchHandover) to a parked stream of the other model (--mix), with one model to a second stream of it.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --cab TAPS [--cab-irs M=1]
+//       the cabinet stage on a batch that never stops (RunCabinet below): M impulse responses of TAPS taps spread over the streams.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -443,15 +445,133 @@ static int RunHandover(NeuralModel* model, NeuralModel* other, int streams, int 
 	return identical ? 0 : 3;
 }
 
+// --cab TAPS [--cab-irs M]: `streams` streams run through the pipelined host interface (two tickets in flight) in three phases of
+// `buffers`, `buffers` and buffers / 4 buffers: (1) the stage enabled and no IR; (2) M synthetic IRs of TAPS taps (decaying noise) spread
+// over all streams but the last, IR s % M on stream s; (3) all dry again but sixteen streams, each in a fade between two IRs that outlasts
+// the phase.  Prints the mean buffer period (Collect to Collect) of every phase beside the same phases of a batch without the stage, and
+// the cost of the set calls (host wall time).  The final buffer of the last stream, which stayed dry throughout, must equal the run
+// without the stage bit for bit (exit code 3 otherwise).
+struct CabinetRun
+{
+	double phaseUs[3] = { 0.0, 0.0, 0.0 }, phaseMaxUs[3] = { 0.0, 0.0, 0.0 }, setUs = 0.0, setMaxUs = 0.0, loadMs = 0.0;
+	long long deviceBytes = 0;
+	std::vector<float> lastRow;
+};
+
+static int RunCabinetVariant(NeuralModel* model, int streams, int frames, int buffers, int taps, int M, bool stage, CabinetRun& result)
+{
+	NA_Batch* batch = NA_BatchCreate(0, nullptr);
+	CHECK(batch != nullptr);
+	CHECK(NA_BatchAddStreams(batch, model, 1.0f, streams, 1) == 0);
+	const size_t count = (size_t)streams * frames;
+	std::vector<std::vector<float>> in(8, std::vector<float>(count));
+	for (size_t b = 0; b < in.size(); b++)
+		for (size_t i = 0; i < count; i++) in[b][i] = 0.5f * (float)((((i + b * 7919u) * 2654435761u) >> 8) & 0xffff) / 65536.0f - 0.25f;
+	std::vector<float> out(count);
+	std::vector<int> irs;
+	std::vector<double> tSet;
+	if (stage)
+	{
+		CHECK(NA_BatchEnableCabinetStage(batch, taps) == 0);
+		const double t0 = Now();
+		std::vector<float> h((size_t)taps);
+		for (int m = 0; m < M; m++)
+		{
+			unsigned seed = 12345u + 977u * (unsigned)m;
+			for (int k = 0; k < taps; k++)
+			{
+				seed = seed * 1664525u + 1013904223u;
+				h[(size_t)k] = ((float)(seed >> 8 & 0xffff) / 32768.0f - 1.0f) * std::exp(-6.0f * (float)k / (float)taps) * 0.1f;
+			}
+			const int id = NA_BatchLoadIR(batch, h.data(), taps);
+			CHECK(id >= 0);
+			irs.push_back(id);
+		}
+		result.loadMs = (Now() - t0) * 1e3;
+		NA_CabinetInfo info;
+		CHECK(NA_BatchGetCabinetInfo(batch, &info) == 0);
+		result.deviceBytes = info.deviceBytes;
+	}
+	auto setIR = [&](int s, int ir, int fade) -> int {
+		const double t0 = Now();
+		CHECK(NA_BatchSetStreamIR(batch, s, ir, fade) == 0);
+		tSet.push_back((Now() - t0) * 1e6);
+		return 0;
+	};
+	auto loop = [&](int n, double& meanUs, double& maxUs) -> int {
+		int pending = NA_BatchSubmit(batch, in[0].data(), (size_t)frames);
+		CHECK(pending >= 0);
+		double last = Now(), sum = 0.0;
+		maxUs = 0.0;
+		for (int i = 1; i <= n; i++)
+		{
+			int next = -1;
+			if (i < n)
+			{
+				next = NA_BatchSubmit(batch, in[(size_t)i % in.size()].data(), (size_t)frames);
+				CHECK(next >= 0);
+			}
+			CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
+			const double now = Now();
+			if (i > 20) // (the first buffers: first-use set-up of the pipelined interface, the change of steady state)
+			{
+				sum += (now - last) * 1e6;
+				maxUs = std::max(maxUs, (now - last) * 1e6);
+			}
+			last = now;
+			pending = next;
+		}
+		meanUs = sum / std::max(1, n - 20);
+		return 0;
+	};
+	if (loop(buffers, result.phaseUs[0], result.phaseMaxUs[0]) != 0) return 1;
+	if (stage)
+		for (int s = 0; s < streams - 1; s++)
+			if (setIR(s, irs[(size_t)(s % M)], 0) != 0) return 1;
+	if (loop(buffers, result.phaseUs[1], result.phaseMaxUs[1]) != 0) return 1;
+	if (stage)
+	{
+		for (int s = 0; s < streams - 1; s++)
+			if (setIR(s, s < 16 ? irs[(size_t)(s % M)] : -1, 0) != 0) return 1;
+		for (int s = 0; s < 16; s++)
+			if (setIR(s, irs[(size_t)((s + 1) % M)], 1 << 20) != 0) return 1; // (longer than the phase: sixteen fades throughout)
+	}
+	if (loop(std::max(buffers / 4, 60), result.phaseUs[2], result.phaseMaxUs[2]) != 0) return 1;
+	CHECK(NA_BatchProcess(batch, in[1].data(), out.data(), (size_t)frames) == 0);
+	result.lastRow.assign(out.begin() + (long)((size_t)(streams - 1) * frames), out.end());
+	result.setUs = Median(tSet);
+	result.setMaxUs = tSet.empty() ? 0.0 : *std::max_element(tSet.begin(), tSet.end());
+	NA_BatchDestroy(batch);
+	return 0;
+}
+
+static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, int taps, int M)
+{
+	CHECK(taps >= 1 && taps <= 8192 && M >= 1 && streams >= 18 && buffers > 60);
+	CabinetRun plain, cab;
+	if (RunCabinetVariant(model, streams, frames, buffers, taps, M, false, plain) != 0) return 1;
+	if (RunCabinetVariant(model, streams, frames, buffers, taps, M, true, cab) != 0) return 1;
+	const bool identical = plain.lastRow.size() == cab.lastRow.size() && std::memcmp(plain.lastRow.data(), cab.lastRow.data(), plain.lastRow.size() * sizeof(float)) == 0;
+	const double gmac = (double)(streams - 1) * frames * taps * 1e-9;
+	std::printf("{\"cab\": %d, \"irs\": %d, \"streams\": %d, \"frames\": %d, \"buffers\": %d, \"stage_device_bytes\": %lld, \"load_irs_ms\": %.3f, "
+		"\"set_ir_call_us\": {\"p50\": %.2f, \"max\": %.1f}, "
+		"\"buffer_period_us\": {\"no_ir\": %.1f, \"irs_on\": %.1f, \"fades_16\": %.1f, \"irs_on_max\": %.1f}, "
+		"\"no_stage_buffer_period_us\": {\"phase_1\": %.1f, \"phase_2\": %.1f, \"phase_3\": %.1f}, \"irs_on_gmac_per_buffer\": %.4f, "
+		"\"dry_stream_identical\": %s}\n",
+		taps, M, streams, frames, buffers, cab.deviceBytes, cab.loadMs, cab.setUs, cab.setMaxUs, cab.phaseUs[0], cab.phaseUs[1], cab.phaseUs[2], cab.phaseMaxUs[1],
+		plain.phaseUs[0], plain.phaseUs[1], plain.phaseUs[2], gmac, identical ? "true" : "false");
+	return identical ? 0 : 3;
+}
+
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
-	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256;
+	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1;
 	bool churnLegacy = false;
 	for (int i = 1; i < argc; i++)
 	{
@@ -464,6 +584,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--churn-legacy")) churnLegacy = true;
 		else if (!std::strcmp(argv[i], "--handover") && i + 1 < argc) handover = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--fade") && i + 1 < argc) fade = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--cab") && i + 1 < argc) cab = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--cab-irs") && i + 1 < argc) cabIRs = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
 			// rehearsal on a one-GPU box: the multi-GPU host bound to the library's loopback RCCL table (test build only), so that
@@ -496,6 +618,13 @@ int main(int argc, char** argv)
 	if (churn > 0)
 	{
 		const int rc = RunChurn(model, streams, frames, buffers, churn, churnEvery, churnLegacy);
+		DeleteModel(model);
+		DeleteLoader(loader);
+		return rc;
+	}
+	if (cab > 0)
+	{
+		const int rc = RunCabinet(model, streams, frames, buffers, cab, cabIRs);
 		DeleteModel(model);
 		DeleteLoader(loader);
 		return rc;
