@@ -7,19 +7,8 @@
 
 namespace na
 {
-	namespace
-	{
-		std::string Id(int s) { return "stream " + std::to_string(s); }
-	}
-
 	GpuBatch::CabinetStage::~CabinetStage()
 	{
-		for (int i = 0; i < kTables; i++)
-		{
-			if (host[i]) (void)CountedHipHostFree(host[i]);
-			if (dev[i]) (void)CountedHipFree(dev[i]);
-			if (done[i]) (void)hipEventDestroy(done[i]);
-		}
 		if (rings) (void)CountedHipFree(rings);
 		for (int ir = 0; ir < book.IRSlots(); ir++)
 			if (book.IsLoaded(ir)) (void)CountedHipFree(const_cast<float*>(book.TapsOf(ir)));
@@ -54,77 +43,33 @@ namespace na
 	{
 		CabinetStage& st = *cabStage;
 		st.book.Resize(rows);
-		for (int i = 0; i < CabinetStage::kTables; i++)
-			if (!st.done[i]) CheckHip(CountedHipEventCreateWithFlags(&st.done[i], hipEventDisableTiming), "hipEventCreate");
 		const int want = std::max(rows, 16);
+		st.tables.Ensure(*this, want);
 		if (want > st.ringRows)
 		{
 			// the rows that exist keep their histories: whatever reads or writes the old rings is over before they are copied
-			float* fresh = nullptr;
-			const size_t ring = (size_t)st.book.RingSamples();
-			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&fresh), (size_t)want * ring * sizeof(float)), "hipMalloc (cabinet rings)");
-			hipError_t e = hipMemset(fresh, 0, (size_t)want * ring * sizeof(float));
-			if (e == hipSuccess && st.rings)
-			{
-				try
-				{
-					Quiesce();
-				}
-				catch (...)
-				{
-					(void)CountedHipFree(fresh);
-					throw;
-				}
-				e = hipMemcpy(fresh, st.rings, (size_t)st.ringRows * ring * sizeof(float), hipMemcpyDeviceToDevice);
-			}
-			if (e == hipSuccess) e = hipDeviceSynchronize();
-			if (e != hipSuccess)
-			{
-				(void)CountedHipFree(fresh);
-				CheckHip(e, "cabinet rings");
-			}
-			if (st.rings) (void)CountedHipFree(st.rings);
-			st.rings = fresh;
+			if (st.rings) Quiesce();
+			GrowRowBlock(st.rings, (size_t)st.book.RingSamples(), st.ringRows, want, "hipMalloc (cabinet rings)", "cabinet rings");
 			st.ringRows = want;
 		}
-		if (want <= st.capacity) return;
-		for (int i = 0; i < CabinetStage::kTables; i++)
-		{
-			// (the launch that reads the old table is over before it goes)
-			if (st.used[i]) WaitEventBounded(st.done[i], "cabinet stage: table in flight");
-			st.used[i] = false;
-			if (st.host[i]) (void)CountedHipHostFree(st.host[i]);
-			if (st.dev[i]) (void)CountedHipFree(st.dev[i]);
-			st.host[i] = st.dev[i] = nullptr;
-		}
-		st.capacity = 0;
-		for (int i = 0; i < CabinetStage::kTables; i++)
-		{
-			CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&st.host[i]), (size_t)want * sizeof(CabEntry), hipHostMallocDefault), "hipHostMalloc");
-			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&st.dev[i]), (size_t)want * sizeof(CabEntry)), "hipMalloc");
-		}
-		st.capacity = want;
 	}
 
 	CabinetStageInfo GpuBatch::GetCabinetInfo() const
 	{
-		if (!cabStage) throw std::runtime_error("neuralaudio_amd: GetCabinetInfo: cabinet stage not enabled (NA_BatchEnableCabinetStage)");
-		const CabinetStage& st = *cabStage;
+		const CabinetStage& st = RequireStage(cabStage, "GetCabinetInfo");
 		CabinetStageInfo info;
 		info.maxTaps = st.book.MaxTaps();
 		info.ringSamples = st.book.RingSamples();
 		info.pieceSamples = kCabPieceSamples;
 		info.numIRs = st.book.NumIRs();
-		info.deviceBytes = (long long)st.ringRows * st.book.RingSamples() * (long long)sizeof(float) + (long long)CabinetStage::kTables * st.capacity * (long long)sizeof(CabEntry) +
-			st.tapBytes;
+		info.deviceBytes = (long long)st.ringRows * st.book.RingSamples() * (long long)sizeof(float) + st.tables.Bytes() + st.tapBytes;
 		return info;
 	}
 
 	int GpuBatch::LoadIR(const float* taps, int numTaps)
 	{
 		CheckUsable();
-		if (!cabStage) throw std::runtime_error("neuralaudio_amd: LoadIR: cabinet stage not enabled (NA_BatchEnableCabinetStage)");
-		CabinetStage& st = *cabStage;
+		CabinetStage& st = RequireStage(cabStage, "LoadIR");
 		if (!taps || numTaps < 1 || numTaps > st.book.MaxTaps())
 			throw std::runtime_error("neuralaudio_amd: LoadIR: numTaps must lie in [1, maxTaps] (maxTaps = " + std::to_string(st.book.MaxTaps()) + ")");
 		for (int k = 0; k < numTaps; k++)
@@ -148,8 +93,7 @@ namespace na
 	void GpuBatch::UnloadIR(int ir)
 	{
 		CheckUsable();
-		if (!cabStage) throw std::runtime_error("neuralaudio_amd: UnloadIR: cabinet stage not enabled (NA_BatchEnableCabinetStage)");
-		CabinetStage& st = *cabStage;
+		CabinetStage& st = RequireStage(cabStage, "UnloadIR");
 		if (!st.book.IsLoaded(ir)) throw std::runtime_error("neuralaudio_amd: UnloadIR: IR " + std::to_string(ir) + " is not loaded");
 		if (st.book.Users(ir) > 0) throw std::runtime_error("neuralaudio_amd: UnloadIR: IR " + std::to_string(ir) + " is in use (a stream has it or fades from it)");
 		Quiesce(); // (the last launch that read it may still run)
@@ -160,29 +104,27 @@ namespace na
 	void GpuBatch::SetStreamIR(int s, int ir, int fadeSamples)
 	{
 		CheckUsable();
-		if (!cabStage) throw std::runtime_error("neuralaudio_amd: SetStreamIR: cabinet stage not enabled (NA_BatchEnableCabinetStage)");
-		if (IsParked(s)) throw std::runtime_error("neuralaudio_amd: SetStreamIR: " + Id(s) + " is parked");
-		if (!IsLive(s)) throw std::runtime_error("neuralaudio_amd: SetStreamIR: " + Id(s) + " is not a live stream of the batch");
-		CabinetBook& book = cabStage->book;
+		CabinetBook& book = RequireStage(cabStage, "SetStreamIR").book;
+		if (IsParked(s)) throw std::runtime_error("neuralaudio_amd: SetStreamIR: " + StreamId(s) + " is parked");
+		if (!IsLive(s)) throw std::runtime_error("neuralaudio_amd: SetStreamIR: " + StreamId(s) + " is not a live stream of the batch");
 		if (ir != kCabDry && !book.IsLoaded(ir)) throw std::runtime_error("neuralaudio_amd: SetStreamIR: IR " + std::to_string(ir) + " is not loaded");
 		if (fadeSamples < 0 || fadeSamples > kOutStageMaxRamp) throw std::runtime_error("neuralaudio_amd: SetStreamIR: fadeSamples must lie in [0, 1 << 20]");
-		if (book.Fading(s)) throw std::runtime_error("neuralaudio_amd: SetStreamIR: an IR fade of " + Id(s) + " is running");
+		if (book.Fading(s)) throw std::runtime_error("neuralaudio_amd: SetStreamIR: an IR fade of " + StreamId(s) + " is running");
 		book.SetIR(s, ir, fadeSamples);
 	}
 
 	int GpuBatch::GetStreamIR(int s) const
 	{
-		if (!cabStage) throw std::runtime_error("neuralaudio_amd: GetStreamIR: cabinet stage not enabled (NA_BatchEnableCabinetStage)");
-		if (s < 0 || s >= (int)streams.size() || !streams[(size_t)s].live) throw std::runtime_error("neuralaudio_amd: GetStreamIR: " + Id(s) + " is not a stream of the batch");
-		return cabStage->book.Target(s);
+		const CabinetStage& st = RequireStage(cabStage, "GetStreamIR");
+		RequireRow(s, "GetStreamIR");
+		return st.book.Target(s);
 	}
 
 	int GpuBatch::StreamIRFadeRemaining(int s) const
 	{
-		if (!cabStage) throw std::runtime_error("neuralaudio_amd: StreamIRFadeRemaining: cabinet stage not enabled (NA_BatchEnableCabinetStage)");
-		if (s < 0 || s >= (int)streams.size() || !streams[(size_t)s].live)
-			throw std::runtime_error("neuralaudio_amd: StreamIRFadeRemaining: " + Id(s) + " is not a stream of the batch");
-		return cabStage->book.FadeRemaining(s);
+		const CabinetStage& st = RequireStage(cabStage, "StreamIRFadeRemaining");
+		RequireRow(s, "StreamIRFadeRemaining");
+		return st.book.FadeRemaining(s);
 	}
 
 	// The stream leaves (ParkStream, RemoveStreams): dry at once, its history dropped -- a parked stream carries nothing over
@@ -198,22 +140,19 @@ namespace na
 	void GpuBatch::RunCabinetStage(hipStream_t launch, float* dOut, size_t n, long outStride)
 	{
 		CabinetStage& st = *cabStage;
-		if (st.book.NumEntries() > st.capacity || st.book.Rows() > st.ringRows) throw std::runtime_error("neuralaudio_amd: cabinet stage: more entries than the tables hold");
-		const int b = st.next;
-		if (st.used[b]) WaitEventBounded(st.done[b], "cabinet stage: table in flight");
-		const int count = st.book.BuildTable(st.host[b]);
+		if (st.book.NumEntries() > st.tables.capacity || st.book.Rows() > st.ringRows) throw std::runtime_error("neuralaudio_amd: cabinet stage: more entries than the tables hold");
+		const auto table = st.tables.Take(*this);
+		const int count = st.book.BuildTable(table.host);
 		if (count > 0)
 		{
-			CheckHip(hipMemcpyAsync(st.dev[b], st.host[b], (size_t)count * sizeof(CabEntry), hipMemcpyHostToDevice, launch), "hipMemcpyAsync (cabinet stage table)");
+			CheckHip(hipMemcpyAsync(table.dev, table.host, (size_t)count * sizeof(CabEntry), hipMemcpyHostToDevice, launch), "hipMemcpyAsync (cabinet stage table)");
 			for (size_t done = 0; done < n; done += (size_t)kCabPieceSamples)
 			{
 				const int piece = (int)std::min<size_t>((size_t)kCabPieceSamples, n - done);
-				CheckHip(LaunchCabinetStage(CabLaunch{ st.dev[b], count, dOut, outStride, (unsigned long long)done, piece, st.rings, st.book.RingSamples() }, launch),
+				CheckHip(LaunchCabinetStage(CabLaunch{ table.dev, count, dOut, outStride, (unsigned long long)done, piece, st.rings, st.book.RingSamples() }, launch),
 					"CabinetStageKernel");
 			}
-			CheckHip(hipEventRecord(st.done[b], launch), "hipEventRecord");
-			st.used[b] = true;
-			st.next = (b + 1) % CabinetStage::kTables;
+			st.tables.Commit(launch);
 		}
 		st.book.Advance(n);
 	}
@@ -222,10 +161,10 @@ namespace na
 	void GpuBatch::DebugRunCabinetStage(float* hostRows, long stride, size_t n)
 	{
 		CheckUsable();
-		if (!cabStage) throw std::runtime_error("neuralaudio_amd: DebugRunCabinetStage: cabinet stage not enabled (NA_BatchEnableCabinetStage)");
+		const CabinetStage& st = RequireStage(cabStage, "DebugRunCabinetStage");
 		if (!hostRows || n == 0 || stride < (long)n || streams.empty()) throw std::runtime_error("neuralaudio_amd: DebugRunCabinetStage: bad argument");
 		Quiesce();
-		if (!cabStage->book.HasEntries()) return;
+		if (!st.book.HasEntries()) return;
 		const size_t floats = (size_t)streams.size() * (size_t)stride;
 		float* dRows = nullptr;
 		CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&dRows), floats * sizeof(float)), "hipMalloc");

@@ -583,8 +583,8 @@ namespace na
 		// A batch on its own stream that nobody has seen: a buffer of one contiguous WaveNet group runs as two free-running half-batch
 		// launches (the order of work on the internal streams is not observable from outside; Synchronize() and the host-buffer entry
 		// points wait for all of them).  1024 x A1 Standard x 128 frames: 40.1 -> 37.4 us per step.
-		// (a resampling batch orders up kernel -> model -> down kernel on the batch stream; so does a batch whose output stage has entries)
-		if (ownsStream && !streamObserved && !Resamples() && !StageHasEntries())
+		// (not for a call that runs ordered on the batch stream: a resampling batch, a batch whose stages have entries)
+		if (ownsStream && !streamObserved && !RunsOrdered())
 		{
 			if (TryResident(dIn, dOut, n, inStride, outStride)) return;
 			if (PrepareHalves(n))
@@ -619,181 +619,129 @@ namespace na
 		}
 	}
 
+	// One processing call on `launch`, and the one place that states its order: the up kernel, the model launches and the down kernel
+	// of a resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages once
+	// per call: behind everything the call has launched -- the join of the units, the graph replay, the down kernel -- on the same
+	// stream, outside any capture; every row is convolved with its own IR first, then scaled and cross-faded.
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{
-		const bool cabEntries = cabStage && cabStage->book.HasEntries(), outEntries = outStage && outStage->book.HasEntries();
-		if (!stagesInside && (cabEntries || outEntries))
+		if (Resamples()) ProcessResampledOn(launch, dIn, dOut, n, inStride, outStride);
+		else LaunchModelsOn(launch, dIn, dOut, n, inStride, outStride);
+		RunStages(launch, dOut, n, outStride);
+	}
+
+	void GpuBatch::RunStages(hipStream_t launch, float* dOut, size_t n, long outStride)
+	{
+		if (cabStage && cabStage->book.HasEntries()) RunCabinetStage(launch, dOut, n, outStride);
+		if (outStage && outStage->book.HasEntries()) RunOutputStage(launch, dOut, n, outStride);
+	}
+
+	// prepareOnly: upload the group tables the list's launches will look up and launch nothing (the pass in front of a stream capture)
+	void GpuBatch::LaunchWaveNetList(const ModelCall& c, LaunchKind which, const std::vector<WnFrameGroup>& list, hipStream_t s, bool prepareOnly)
+	{
+		WnLaunchTable& table = wnTable[(int)which];
+		bool compact = false;
+		for (const WnFrameGroup& g : list) compact = compact || g.model->compact_rings != 0;
+		size_t offset = 0, left = c.n;
+		while (left > 0)
 		{
-			// the per-stream stages: behind everything this call launches -- the join of the units, the graph replay,
-			// the down kernel of a resampling batch -- on the same stream, outside any capture: every row is convolved with its own IR
-			// first, then scaled and cross-faded
-			struct Inside
+			const int chunk = NextWaveNetChunk(left, compact);
+			// more groups than one launch's kernarg table holds (a batch of many different models): ONE launch with the table in device
+			// memory where the chains have one (128-frame blocks of the A1 families), else launches of eight groups each
+			if (which != LaunchKind::Frame && list.size() > (size_t)WN_FRAME_MAX_GROUPS)
 			{
-				bool& flag;
-				explicit Inside(bool& f) : flag(f) { flag = true; }
-				~Inside() { flag = false; }
-			};
-			{
-				Inside inside(stagesInside);
-				ProcessDeviceOn(launch, dIn, dOut, n, inStride, outStride);
-			}
-			if (cabEntries) RunCabinetStage(launch, dOut, n, outStride);
-			if (outEntries) RunOutputStage(launch, dOut, n, outStride);
-			return;
-		}
-		if (resample && !resample->plan.identity && !resample->inside)
-		{
-			ProcessResampledOn(launch, dIn, dOut, n, inStride, outStride);
-			return;
-		}
-		int activeGroups = 0;
-		for (auto& g : groups) activeGroups += (g->NumActive() > 0);
-		if (activeGroups <= 1)
-		{
-			for (auto& g : groups) g->Process(dIn, dOut, inStride, outStride, n, launch);
-			return;
-		}
-		// Mixed batch: the launch units of launch_plan.h.  Their arguments are gathered first (changed index lists are uploaded now,
-		// asynchronously on the batch stream: never inside a graph capture).
-		UpdatePlan();
-		const std::vector<LaunchUnit>& units = plan.units;
-		std::vector<std::vector<WnFrameGroup>> wnArgs(units.size());
-		std::vector<RecurrentGroup> recArgs;
-		for (size_t u = 0; u < units.size(); u++)
-		{
-			if (units[u].kind == LaunchKind::Recurrent)
-				for (int i : units[u].groups) recArgs.push_back(static_cast<LstmGroup*>(plan.groups[(size_t)i])->LaunchArgs());
-			else if (units[u].kind == LaunchKind::Own) plan.groups[(size_t)units[u].groups[0]]->SyncActiveLists();
-			else wnArgs[u] = WaveNetArgs(units[u], false);
-		}
-		// prepareOnly: upload the group tables the list's launches will look up and launch nothing (the pass in front of a stream capture)
-		auto launchWnList = [&](LaunchKind which, const std::vector<WnFrameGroup>& list, hipStream_t s, bool prepareOnly) {
-			WnLaunchTable& table = wnTable[(int)which];
-			bool compact = false;
-			for (const WnFrameGroup& g : list) compact = compact || g.model->compact_rings != 0;
-			size_t offset = 0, left = n;
-			while (left > 0)
-			{
-				const int chunk = NextWaveNetChunk(left, compact);
-				// more groups than one launch's kernarg table holds (a batch of many different models): ONE launch with the table in device
-				// memory where the chains have one (128-frame blocks of the A1 families), else launches of eight groups each
-				if (which != LaunchKind::Frame && list.size() > (size_t)WN_FRAME_MAX_GROUPS)
-				{
-					table.prepareOnly = prepareOnly;
-					const hipError_t te = LaunchWaveNetSpecTable(list.data(), (int)list.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, s, table);
-					table.prepareOnly = false;
-					if (te == hipSuccess)
-					{
-						offset += (size_t)chunk;
-						left -= (size_t)chunk;
-						continue;
-					}
-					if (te != hipErrorNotSupported) CheckHip(te, "WaveNet kernel (table launch)");
-					(void)hipGetLastError();
-				}
-				if (prepareOnly)
+				table.prepareOnly = prepareOnly;
+				const hipError_t te = LaunchWaveNetSpecTable(list.data(), (int)list.size(), c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s, table);
+				table.prepareOnly = false;
+				if (te == hipSuccess)
 				{
 					offset += (size_t)chunk;
 					left -= (size_t)chunk;
 					continue;
 				}
-				for (size_t first = 0; first < list.size(); first += WN_FRAME_MAX_GROUPS)
-				{
-					const int count = (int)std::min<size_t>(list.size() - first, (size_t)WN_FRAME_MAX_GROUPS);
-					CheckHip(which == LaunchKind::Frame ? LaunchWaveNetFrameFused(list.data() + first, count, dIn + offset, dOut + offset, inStride, outStride, chunk, s)
-														: LaunchWaveNetSplitFused(list.data() + first, count, dIn + offset, dOut + offset, inStride, outStride, chunk, s,
-															1 | WnBeyondCacheBit(StateBytes())),
-						"WaveNet kernel (fused)");
-				}
+				if (te != hipErrorNotSupported) CheckHip(te, "WaveNet kernel (table launch)");
+				(void)hipGetLastError();
+			}
+			if (prepareOnly)
+			{
 				offset += (size_t)chunk;
 				left -= (size_t)chunk;
+				continue;
 			}
-		};
-		auto launchRec = [&](hipStream_t s, bool prepareOnly) {
-			size_t offset = 0, left = n;
-			while (left > 0)
+			for (size_t first = 0; first < list.size(); first += WN_FRAME_MAX_GROUPS)
 			{
-				const int chunk = (int)std::min<size_t>(left, (size_t)LSTM_MAX_FRAMES);
-				if (recArgs.size() > (size_t)RECURRENT_MAX_GROUPS)
-				{
-					// (many different recurrent models: one launch, the group table in device memory)
-					WnLaunchTable& table = wnTable[(int)LaunchKind::Recurrent];
-					table.prepareOnly = prepareOnly;
-					const hipError_t te = LaunchRecurrentDppTable(recArgs.data(), (int)recArgs.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, s, table);
-					table.prepareOnly = false;
-					CheckHip(te, "RecurrentDppKernel (table launch)");
-					offset += (size_t)chunk;
-					left -= (size_t)chunk;
-					continue;
-				}
-				if (prepareOnly) break;
-				for (size_t first = 0; first < recArgs.size(); first += RECURRENT_MAX_GROUPS)
-					CheckHip(LaunchRecurrentDpp(recArgs.data() + first, (int)std::min<size_t>(recArgs.size() - first, (size_t)RECURRENT_MAX_GROUPS),
-						dIn + offset, dOut + offset, inStride, outStride, chunk, s), "RecurrentDppKernel (fused)");
+				const int count = (int)std::min<size_t>(list.size() - first, (size_t)WN_FRAME_MAX_GROUPS);
+				CheckHip(which == LaunchKind::Frame ? LaunchWaveNetFrameFused(list.data() + first, count, c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s)
+													: LaunchWaveNetSplitFused(list.data() + first, count, c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s,
+														1 | WnBeyondCacheBit(StateBytes())),
+					"WaveNet kernel (fused)");
+			}
+			offset += (size_t)chunk;
+			left -= (size_t)chunk;
+		}
+	}
+
+	void GpuBatch::LaunchRecurrentUnit(const ModelCall& c, hipStream_t s, bool prepareOnly)
+	{
+		const std::vector<RecurrentGroup>& recArgs = c.recArgs;
+		size_t offset = 0, left = c.n;
+		while (left > 0)
+		{
+			const int chunk = (int)std::min<size_t>(left, (size_t)LSTM_MAX_FRAMES);
+			if (recArgs.size() > (size_t)RECURRENT_MAX_GROUPS)
+			{
+				// (many different recurrent models: one launch, the group table in device memory)
+				WnLaunchTable& table = wnTable[(int)LaunchKind::Recurrent];
+				table.prepareOnly = prepareOnly;
+				const hipError_t te = LaunchRecurrentDppTable(recArgs.data(), (int)recArgs.size(), c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s, table);
+				table.prepareOnly = false;
+				CheckHip(te, "RecurrentDppKernel (table launch)");
 				offset += (size_t)chunk;
 				left -= (size_t)chunk;
+				continue;
 			}
-		};
-		auto run = [&](size_t u, hipStream_t s, bool prepareOnly) {
-			const LaunchUnit& unit = units[u];
-			if (unit.kind == LaunchKind::Recurrent) launchRec(s, prepareOnly);
-			else if (unit.kind != LaunchKind::Own) launchWnList(unit.kind, wnArgs[u], s, prepareOnly);
-			else if (!prepareOnly) plan.groups[(size_t)unit.groups[0]]->Process(dIn, dOut, inStride, outStride, n, s);
-		};
-		// group tables of an earlier topology go (their graphs first)
-		if (!graphCache.empty() && graphCache.front().key.version != topologyVersion)
-		{
-			for (auto& e : graphCache) (void)hipGraphExecDestroy(e.exec);
-			graphCache.clear();
+			if (prepareOnly) break;
+			for (size_t first = 0; first < recArgs.size(); first += RECURRENT_MAX_GROUPS)
+				CheckHip(LaunchRecurrentDpp(recArgs.data() + first, (int)std::min<size_t>(recArgs.size() - first, (size_t)RECURRENT_MAX_GROUPS),
+					c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s), "RecurrentDppKernel (fused)");
+			offset += (size_t)chunk;
+			left -= (size_t)chunk;
 		}
-		for (WnLaunchTable& t : wnTable) t.NewGeneration(topologyVersion);
-		if (units.size() == 1)
+	}
+
+	void GpuBatch::RunUnit(const ModelCall& c, size_t u, hipStream_t s, bool prepareOnly)
+	{
+		const LaunchUnit& unit = plan.units[u];
+		if (unit.kind == LaunchKind::Recurrent) LaunchRecurrentUnit(c, s, prepareOnly);
+		else if (unit.kind != LaunchKind::Own) LaunchWaveNetList(c, unit.kind, c.wnArgs[u], s, prepareOnly);
+		else if (!prepareOnly) plan.groups[(size_t)unit.groups[0]]->Process(c.dIn, c.dOut, c.inStride, c.outStride, c.n, s);
+	}
+
+	// Several units: fork onto side streams so their kernels share the GPU, then join back into the batch stream.
+	void GpuBatch::ForkJoinUnits(const ModelCall& c)
+	{
+		if (!forkEvent) CheckHip(CountedHipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
+		CheckHip(hipEventRecord(forkEvent, stream), "hipEventRecord");
+		for (size_t u = 0; u < plan.units.size(); u++)
 		{
-			run(0, launch, false);
-			return;
+			ModelGroup* owner = plan.groups[(size_t)plan.units[u].groups[0]];
+			hipStream_t side = owner->SideStream();
+			CheckHip(hipStreamWaitEvent(side, forkEvent, 0), "hipStreamWaitEvent");
+			RunUnit(c, u, side, false);
+			CheckHip(hipEventRecord(owner->DoneEvent(), side), "hipEventRecord");
+			CheckHip(hipStreamWaitEvent(stream, owner->DoneEvent(), 0), "hipStreamWaitEvent");
 		}
-		// tuning knob: the units one after the other on the batch stream instead of concurrently on side streams
-		if (Tuning::Get().batchSerial)
-		{
-			for (size_t u = 0; u < units.size(); u++) run(u, stream, false);
-			return;
-		}
-		// Several units: fork onto side streams so their kernels share the GPU, then join back into the batch stream.  The fork/join
-		// costs ~5 HIP calls per unit, which would make a buffer host-bound, so the sequence is captured once into a hipGraph and
-		// replayed while the call signature (pointers, n, strides) and the active-stream lists stay the same -- the steady state of a
-		// real-time host.
-		auto forkJoin = [&] {
-			if (!forkEvent) CheckHip(CountedHipEventCreateWithFlags(&forkEvent, hipEventDisableTiming), "hipEventCreate");
-			CheckHip(hipEventRecord(forkEvent, stream), "hipEventRecord");
-			for (size_t u = 0; u < units.size(); u++)
-			{
-				ModelGroup* owner = plan.groups[(size_t)units[u].groups[0]];
-				hipStream_t side = owner->SideStream();
-				CheckHip(hipStreamWaitEvent(side, forkEvent, 0), "hipStreamWaitEvent");
-				run(u, side, false);
-				CheckHip(hipEventRecord(owner->DoneEvent(), side), "hipEventRecord");
-				CheckHip(hipStreamWaitEvent(stream, owner->DoneEvent(), 0), "hipStreamWaitEvent");
-			}
-		};
-		// The runtime this process actually runs on may be OLDER than the ROCm 7.2 this library is built against: a host that loads
-		// PyTorch first gets PyTorch's bundled libamdhip64 (HIP 7.0.51831 with torch 2.10+rocm7.0) for the whole process, and that
-		// runtime's graph replay crashes after other graphs of the process were destroyed (hip::Graph::UpdateStreams under
-		// hipGraphLaunch; seen in tests/test_gpu_multi.py behind any other test file, never on 7.2: profiles/r06_gputest_timing.txt).  On a
-		// runtime older than the one it was built for the sequence is therefore issued directly, every buffer: ~5 HIP calls per launch
-		// unit of host time, the same streams, events and results.
-		static const bool graphsTrusted = [] {
-			int v = 0;
-			return hipRuntimeGetVersion(&v) == hipSuccess && v >= 70200000 && !Tuning::Get().batchNoGraph;
-		}();
-		if (!graphsTrusted)
-		{
-			forkJoin();
-			return;
-		}
+	}
+
+	// The fork/join costs ~5 HIP calls per unit, which would make a buffer host-bound, so the sequence is captured once into a hipGraph
+	// and replayed while the call signature (pointers, n, strides) and the active-stream lists stay the same -- the steady state of a
+	// real-time host.
+	void GpuBatch::ReplayUnitsGraph(const ModelCall& c)
+	{
 		hipGraphExec_t graphExec = nullptr;
 		for (auto& e : graphCache)
-			if (e.key.dIn == dIn && e.key.dOut == dOut && e.key.n == n && e.key.inStride == inStride && e.key.outStride == outStride) graphExec = e.exec;
+			if (e.key.dIn == c.dIn && e.key.dOut == c.dOut && e.key.n == c.n && e.key.inStride == c.inStride && e.key.outStride == c.outStride) graphExec = e.exec;
 		if (!graphExec)
 		{
 			if (graphCache.size() >= 16)
@@ -802,12 +750,12 @@ namespace na
 				graphCache.erase(graphCache.begin());
 			}
 			// the group tables of the table launches are uploaded here, in front of the capture (WnLaunchTable)
-			for (size_t u = 0; u < units.size(); u++) run(u, stream, true);
+			for (size_t u = 0; u < plan.units.size(); u++) RunUnit(c, u, stream, true);
 			hipGraph_t graph = nullptr;
 			CheckHip(hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed), "hipStreamBeginCapture");
 			try
 			{
-				forkJoin();
+				ForkJoinUnits(c);
 			}
 			catch (...)
 			{
@@ -819,9 +767,63 @@ namespace na
 			const hipError_t e = hipGraphInstantiate(&graphExec, graph, nullptr, nullptr, 0);
 			(void)hipGraphDestroy(graph);
 			CheckHip(e, "hipGraphInstantiate");
-			graphCache.push_back({ { dIn, dOut, n, inStride, outStride, topologyVersion }, graphExec });
+			graphCache.push_back({ { c.dIn, c.dOut, c.n, c.inStride, c.outStride, topologyVersion }, graphExec });
 		}
 		CheckHip(hipGraphLaunch(graphExec, stream), "hipGraphLaunch");
+	}
+
+	// The model launches of a call, over n frames of device rows: one group's own launches, or the launch units of a mixed batch
+	void GpuBatch::LaunchModelsOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
+	{
+		int activeGroups = 0;
+		for (auto& g : groups) activeGroups += (g->NumActive() > 0);
+		if (activeGroups <= 1)
+		{
+			for (auto& g : groups) g->Process(dIn, dOut, inStride, outStride, n, launch);
+			return;
+		}
+		// Mixed batch: the launch units of launch_plan.h.  Their arguments are gathered first (changed index lists are uploaded now,
+		// asynchronously on the batch stream: never inside a graph capture).
+		UpdatePlan();
+		const std::vector<LaunchUnit>& units = plan.units;
+		ModelCall c{ dIn, dOut, n, inStride, outStride, std::vector<std::vector<WnFrameGroup>>(units.size()), {} };
+		for (size_t u = 0; u < units.size(); u++)
+		{
+			if (units[u].kind == LaunchKind::Recurrent)
+				for (int i : units[u].groups) c.recArgs.push_back(static_cast<LstmGroup*>(plan.groups[(size_t)i])->LaunchArgs());
+			else if (units[u].kind == LaunchKind::Own) plan.groups[(size_t)units[u].groups[0]]->SyncActiveLists();
+			else c.wnArgs[u] = WaveNetArgs(units[u], false);
+		}
+		// group tables of an earlier topology go (their graphs first)
+		if (!graphCache.empty() && graphCache.front().key.version != topologyVersion)
+		{
+			for (auto& e : graphCache) (void)hipGraphExecDestroy(e.exec);
+			graphCache.clear();
+		}
+		for (WnLaunchTable& t : wnTable) t.NewGeneration(topologyVersion);
+		if (units.size() == 1)
+		{
+			RunUnit(c, 0, launch, false);
+			return;
+		}
+		// tuning knob: the units one after the other on the batch stream instead of concurrently on side streams
+		if (Tuning::Get().batchSerial)
+		{
+			for (size_t u = 0; u < units.size(); u++) RunUnit(c, u, stream, false);
+			return;
+		}
+		// The runtime this process actually runs on may be OLDER than the ROCm 7.2 this library is built against: a host that loads
+		// PyTorch first gets PyTorch's bundled libamdhip64 (HIP 7.0.51831 with torch 2.10+rocm7.0) for the whole process, and that
+		// runtime's graph replay crashes after other graphs of the process were destroyed (hip::Graph::UpdateStreams under
+		// hipGraphLaunch; seen in tests/test_gpu_multi.py behind any other test file, never on 7.2: profiles/r06_gputest_timing.txt).  On a
+		// runtime older than the one it was built for the fork/join is therefore issued directly, every buffer: ~5 HIP calls per launch
+		// unit of host time, the same streams, events and results.
+		static const bool graphsTrusted = [] {
+			int v = 0;
+			return hipRuntimeGetVersion(&v) == hipSuccess && v >= 70200000 && !Tuning::Get().batchNoGraph;
+		}();
+		if (graphsTrusted) ReplayUnitsGraph(c);
+		else ForkJoinUnits(c);
 	}
 
 	void GpuBatch::WeightImages(const LoadedModel& model, std::vector<std::pair<void*, size_t>>& out) const

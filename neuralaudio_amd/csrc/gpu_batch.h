@@ -298,11 +298,14 @@ namespace na
 		struct OutputStage; // (gpu_batch_internal.h)
 		std::unique_ptr<OutputStage> outStage;
 		bool StageHasEntries() const; // of either stage
+		// the call runs ordered on ONE stream: up kernel -> model launches -> down kernel of a resampling batch, the stages behind the
+		// model launches (no half-batch chains, no resident launch)
+		bool RunsOrdered() const { return Resamples() || StageHasEntries(); }
+		void RequireRow(int stream, const char* who) const; // throws "<who>: stream <s> is not a stream of the batch" (a parked one is)
 		void EnsureStageRows(int rows);  // set-up side: tables for `rows` rows
 		void StageParkFinished();        // top of every processing call: the `from` streams of the fades that ended in the last one are parked
 		void StageLeave(int stream);     // park / removal: its fade ends, its gain is 1 again
 		void RunOutputStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + launch + the host mirror's advance
-		bool stagesInside = false;       // the model launches of a call with stage entries are under way (ProcessDeviceOn)
 		struct CabinetStage; // (gpu_batch_internal.h)
 		std::unique_ptr<CabinetStage> cabStage;
 		void EnsureCabinetRows(int rows); // set-up side: rings and tables for `rows` rows
@@ -337,7 +340,7 @@ namespace na
 		};
 		hipEvent_t forkEvent = nullptr;
 
-		// cached hipGraph of the multi-group fork/launch/join sequence (see ProcessDevice)
+		// cached hipGraph of the multi-group fork/launch/join sequence (gpu_batch.cpp ReplayUnitsGraph)
 		struct GraphKey
 		{
 			const float* dIn;
@@ -415,7 +418,7 @@ namespace na
 		// ring in pinned host memory -- for the batches the chains serve whose buffer is one launch of 128-frame A1 Standard blocks
 		struct ResidentState;
 		std::unique_ptr<ResidentState> residentState;
-		WnLaunchTable wnTable[4]; // device tables of launch lists with more groups than a launch's kernarg segment holds (gpu_batch.cpp launchWnList), by LaunchKind
+		WnLaunchTable wnTable[4]; // device tables of launch lists with more groups than a launch's kernarg segment holds (gpu_batch.cpp LaunchWaveNetList), by LaunchKind
 		bool lastStepResident = false;
 		bool residentWanted = Tuning::Get().residentOn;
 		bool TryResident(const float* dIn, float* dOut, size_t n, long inStride, long outStride);
@@ -435,14 +438,26 @@ namespace na
 		void LaunchHalves(const float* dIn, float* dOut, size_t n, long inStride, long outStride, hipEvent_t* done, bool hostRows);
 		void JoinHalves(); // the half-batch chains are done (host-side wait); the next launches go to the batch stream again
 		hipEvent_t marks[1 + kMaxChains][2] = {};
+		// One processing call on `launch`, the one place that states its order (gpu_batch.cpp): ProcessResampledOn or LaunchModelsOn,
+		// then RunStages
 		void ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
+		void RunStages(hipStream_t launch, float* dOut, size_t n, long outStride); // the stages with entries: cabinet, then output
+		// the model launches of a call, and their parts (gpu_batch.cpp)
+		struct ModelCall; // (gpu_batch_internal.h)
+		void LaunchModelsOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
+		void LaunchWaveNetList(const ModelCall& c, LaunchKind which, const std::vector<WnFrameGroup>& list, hipStream_t s, bool prepareOnly);
+		void LaunchRecurrentUnit(const ModelCall& c, hipStream_t s, bool prepareOnly);
+		void RunUnit(const ModelCall& c, size_t u, hipStream_t s, bool prepareOnly);
+		void ForkJoinUnits(const ModelCall& c);
+		void ReplayUnitsGraph(const ModelCall& c);
 		struct ResampleState; // (gpu_batch_internal.h)
 		std::unique_ptr<ResampleState> resample;
 		void ProcessResampledOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
 		void EnsureResampleRows(int rows);           // set-up side only (AddStreams): histories and model-side rows for `rows` rows
 		void EnsureResampleFrames(size_t n);         // model-side buffers for pieces of n external samples
 		void ZeroResampleHistories(int first, int count);
-		void WaitFresh(float* fresh);                // bounded wait for the set-up of a new block; frees it if the wait fails
+		// set-up side: a zeroed [rows][rowFloats] block in place of `block`, the first `keepRows` rows copied over (resample.cpp)
+		void GrowRowBlock(float*& block, size_t rowFloats, int keepRows, int rows, const char* mallocWhat, const char* what);
 		// ordering between the batch stream and the slot streams: the stream state makes every kernel launch depend on the previous one
 		bool pipelineUsed = false;
 		hipEvent_t lastKernelEvent = nullptr, mainDone = nullptr;

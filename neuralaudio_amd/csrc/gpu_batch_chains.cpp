@@ -358,7 +358,7 @@ namespace na
 	// The buffer as two launch lists of half of every group's streams each (see halfStream); false: it runs as ordered launches.
 	bool GpuBatch::PrepareHalves(size_t n)
 	{
-		if (Tuning::Get().hostHalvesOff || Resamples()) return false;
+		if (Tuning::Get().hostHalvesOff || RunsOrdered()) return false;
 		UpdatePlan();
 		if (!IsOneSplitLaunch(plan.units, true, WN_FRAME_MAX_GROUPS)) return false;
 		const LaunchUnit& unit = plan.units[0];

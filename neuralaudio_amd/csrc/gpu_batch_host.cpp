@@ -107,8 +107,8 @@ namespace na
 			// blocks the caller registered: the kernels run on them as they are (no staging copies: 81 -> ~62 us for 1024 x 128)
 			float* dIn = static_cast<float*>(RegisteredDevicePointer(in, total * sizeof(float)));
 			float* dOut = static_cast<float*>(RegisteredDevicePointer(out, total * sizeof(float)));
-			// (while the output stage has entries the rows go through the staging block below: the stage works in place on device memory,
-			// not as a read-modify-write over the bus)
+			// (while a stage has entries the rows go through the staging block below: the stages work in place on device memory, not as
+			// a read-modify-write over the bus -- that, not the order of the call, is what !StageHasEntries() means here and in `direct`)
 			if (dIn && dOut && !StageHasEntries())
 			{
 				ProcessDeviceOrdered(dIn, dOut, n, (long)n, (long)n);
@@ -119,7 +119,7 @@ namespace na
 		}
 		EnsureStaging(total);
 		float* dStage = nullptr;
-		// (output stage entries: the copy engines and the device block, for the same reason)
+		// (stage entries: the copy engines and the device block, for the same reason)
 		const bool direct = HostDirect() && !StageHasEntries() && hipHostGetDevicePointer(reinterpret_cast<void**>(&dStage), hostStage, 0) == hipSuccess && dStage != nullptr;
 		if (direct && PrepareHalves(n) && halfLists->RowRangesOnly())
 		{
@@ -245,7 +245,7 @@ namespace na
 			for (size_t r = 0; r < streams.size(); r++)
 				if (streams[r].parked) p.parkedRows.push_back((int)r);
 		if (in) memcpy(p.hostIn, in, total * sizeof(float)); // nullptr: the caller filled NextInput() in place
-		const bool direct = HostDirect() && !StageHasEntries(); // (see ProcessHost)
+		const bool direct = HostDirect() && !StageHasEntries(); // (no read-modify-write over the bus: see ProcessHost)
 		float *dIn = nullptr, *dOut = nullptr;
 		if (direct && hipHostGetDevicePointer(reinterpret_cast<void**>(&dIn), p.hostIn, 0) == hipSuccess && dIn != nullptr &&
 			hipHostGetDevicePointer(reinterpret_cast<void**>(&dOut), p.hostOut, 0) == hipSuccess && dOut != nullptr)

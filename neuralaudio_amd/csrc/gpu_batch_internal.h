@@ -56,6 +56,17 @@ namespace na
 		}
 	};
 
+	// the model launches of one call (GpuBatch::LaunchModelsOn): its signature and the arguments gathered for the plan's launch units
+	struct GpuBatch::ModelCall
+	{
+		const float* dIn;
+		float* dOut;
+		size_t n;
+		long inStride, outStride;
+		std::vector<std::vector<WnFrameGroup>> wnArgs; // per unit: the groups of a frame / split / packed unit
+		std::vector<RecurrentGroup> recArgs;           // the groups of the recurrent unit
+	};
+
 	// a resampling batch (resample.cpp): the plan, the batch's counters, the coefficient tables, the per-row histories
 	// and the fixed model-side buffers
 	struct GpuBatch::ResampleState
@@ -72,7 +83,6 @@ namespace na
 		int pieceFrames = 0;        // a longer call runs in pieces of this many external samples (the LDS window of the stages)
 		int sizedFrames = 0;        // external samples per piece the model-side buffers hold
 		int modelStride = 0;
-		bool inside = false;        // the model launches of a resampled call are under way (ProcessDeviceOn)
 		int lastFrames = 0, lastRows = 0; // NA_DebugResampleTap: model frames and rows of the last piece
 		~ResampleState()
 		{
@@ -81,19 +91,22 @@ namespace na
 		}
 	};
 
-	// the output stage of a batch (output_stage.h, DESIGN.md 2.9): the host mirror and the ring of entry tables
-	struct GpuBatch::OutputStage
+	// The ring of entry tables of a per-stream stage (output_stage.cpp, cabinet_stage.cpp): pinned and device blocks of `capacity` entries
+	// and an event each.  One table more than buffers can be in flight (Submit): the table a call takes was read by a launch whose
+	// ticket has been collected.  `inFlight` names the stage in the message of a wait that ran into the limit.
+	template <class Entry>
+	struct StageTables
 	{
-		// one table more than buffers can be in flight (Submit): the table a call takes was read by a launch whose ticket has been collected
 		static constexpr int kTables = GpuBatch::kPipelineSlots + 1;
-		OutputStageBook book;
-		OutStageEntry* host[kTables] = {}; // pinned
-		OutStageEntry* dev[kTables] = {};
-		hipEvent_t done[kTables] = {};     // the launch that read dev[i] (and the upload that read host[i]) is over
+		const char* inFlight;
+		Entry* host[kTables] = {};     // pinned
+		Entry* dev[kTables] = {};
+		hipEvent_t done[kTables] = {}; // the launches that read dev[i] (and the upload that read host[i]) are over
 		bool used[kTables] = {};
 		int next = 0;
-		int capacity = 0;             // entries per table
-		~OutputStage()
+		int capacity = 0;              // entries per table
+		explicit StageTables(const char* what) : inFlight(what) {}
+		~StageTables()
 		{
 			for (int i = 0; i < kTables; i++)
 			{
@@ -102,6 +115,63 @@ namespace na
 				if (done[i]) (void)hipEventDestroy(done[i]);
 			}
 		}
+		// set-up side: the events, and tables of at least `want` entries (the launches that read the old ones are over before they go)
+		void Ensure(GpuBatch& batch, int want)
+		{
+			for (hipEvent_t& e : done)
+				if (!e) CheckHip(CountedHipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+			if (want <= capacity) return;
+			for (int i = 0; i < kTables; i++)
+			{
+				if (used[i]) batch.WaitEventBounded(done[i], inFlight);
+				used[i] = false;
+				if (host[i]) (void)CountedHipHostFree(host[i]);
+				if (dev[i]) (void)CountedHipFree(dev[i]);
+				host[i] = dev[i] = nullptr;
+			}
+			capacity = 0;
+			for (int i = 0; i < kTables; i++)
+			{
+				CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&host[i]), (size_t)want * sizeof(Entry), hipHostMallocDefault), "hipHostMalloc");
+				CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&dev[i]), (size_t)want * sizeof(Entry)), "hipMalloc");
+			}
+			capacity = want;
+		}
+		// the next table, pinned block and device twin, once the launch that last read it is over (a bounded wait)
+		struct Table
+		{
+			Entry *host, *dev;
+		};
+		Table Take(GpuBatch& batch)
+		{
+			if (used[next]) batch.WaitEventBounded(done[next], inFlight);
+			return { host[next], dev[next] };
+		}
+		// behind the upload and the launches that read the table taken: the ring moves on
+		void Commit(hipStream_t stream)
+		{
+			CheckHip(hipEventRecord(done[next], stream), "hipEventRecord");
+			used[next] = true;
+			next = (next + 1) % kTables;
+		}
+		long long Bytes() const { return (long long)kTables * capacity * (long long)sizeof(Entry); }
+	};
+
+	// the argument checks the stages' calls share: the texts are part of the interface (the tests match on them)
+	inline std::string StreamId(int s) { return "stream " + std::to_string(s); }
+	template <class Stage>
+	Stage& RequireStage(const std::unique_ptr<Stage>& stage, const char* who)
+	{
+		if (!stage) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + Stage::kNotEnabled);
+		return *stage;
+	}
+
+	// the output stage of a batch (output_stage.h, DESIGN.md 2.9): the host mirror and the ring of entry tables
+	struct GpuBatch::OutputStage
+	{
+		static constexpr const char* kNotEnabled = "output stage not enabled (NA_BatchEnableOutputStage)";
+		OutputStageBook book;
+		StageTables<OutStageEntry> tables{ "output stage: table in flight" };
 	};
 	hipError_t LaunchOutputStage(const OutStageLaunch& L, hipStream_t stream); // (output_stage_kernels.hip)
 
@@ -109,17 +179,12 @@ namespace na
 	// through the book's ids) and the ring of entry tables
 	struct GpuBatch::CabinetStage
 	{
-		static constexpr int kTables = GpuBatch::kPipelineSlots + 1; // (as the output stage's)
+		static constexpr const char* kNotEnabled = "cabinet stage not enabled (NA_BatchEnableCabinetStage)";
 		CabinetBook book;
 		float* rings = nullptr;           // [ringRows][book.RingSamples()]
 		int ringRows = 0;
 		long long tapBytes = 0;           // device bytes of the loaded IRs
-		CabEntry* host[kTables] = {};     // pinned
-		CabEntry* dev[kTables] = {};
-		hipEvent_t done[kTables] = {};    // the launches that read dev[i] (and the upload that read host[i]) are over
-		bool used[kTables] = {};
-		int next = 0;
-		int capacity = 0;                 // entries per table
+		StageTables<CabEntry> tables{ "cabinet stage: table in flight" };
 		~CabinetStage();
 	};
 	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece

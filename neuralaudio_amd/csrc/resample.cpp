@@ -157,10 +157,24 @@ namespace na
 		resample = std::move(rs);
 	}
 
-	// waits for the clear / copy into a block that no member owns yet; a wait that fails gives the block back -- unless the batch broke:
-	// the clear may then still be pending, and the block is left alone like everything else of a broken batch (GpuBatch::IsBroken)
-	void GpuBatch::WaitFresh(float* fresh)
+	// Set-up side, shared by the resampling histories and the cabinet stage's rings: `block` becomes a zeroed [rows][rowFloats] block
+	// whose first `keepRows` rows are the old block's.  The caller has waited for whatever reads or writes the old block.  Clear and
+	// copy run on the batch stream, not the legacy stream: another shard of a multi batch may be capturing a graph on its own stream,
+	// and a legacy-stream operation would have to wait for that stream.  The wait for them is bounded; if it fails the fresh block,
+	// which no member owns yet, is given back -- unless the batch broke: the clear may then still be pending, and the block is left
+	// alone like everything else of a broken batch (GpuBatch::IsBroken).
+	void GpuBatch::GrowRowBlock(float*& block, size_t rowFloats, int keepRows, int rows, const char* mallocWhat, const char* what)
 	{
+		float* fresh = nullptr;
+		CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&fresh), (size_t)rows * rowFloats * sizeof(float)), mallocWhat);
+		hipError_t e = hipMemsetAsync(fresh, 0, (size_t)rows * rowFloats * sizeof(float), stream);
+		if (e == hipSuccess && block && keepRows > 0)
+			e = hipMemcpyAsync(fresh, block, (size_t)keepRows * rowFloats * sizeof(float), hipMemcpyDeviceToDevice, stream);
+		if (e != hipSuccess)
+		{
+			(void)CountedHipFree(fresh);
+			CheckHip(e, what);
+		}
 		try
 		{
 			WaitStreamBounded(stream, "hipStreamSynchronize");
@@ -170,6 +184,8 @@ namespace na
 			if (!IsBroken()) (void)CountedHipFree(fresh);
 			throw;
 		}
+		if (block) (void)CountedHipFree(block);
+		block = fresh;
 	}
 
 	// set-up side (AddStreams): rows only ever grow; the histories of the rows that exist move to the new block
@@ -177,30 +193,13 @@ namespace na
 	{
 		ResampleState& r = *resample;
 		if (rows <= r.rowCapacity) return;
-		const ResamplePlan& p = r.plan;
 		const int cap = std::max(rows, r.rowCapacity * 2);
+		const char* what = "resampling: growing the row blocks";
 		WaitStreamBounded(stream, "hipStreamSynchronize");
-		auto grow = [&](float*& block, size_t rowFloats, bool keep) {
-			float* fresh = nullptr;
-			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&fresh), (size_t)cap * rowFloats * sizeof(float)), "hipMalloc");
-			// (on the batch stream, not the legacy stream: another shard of a multi batch may be capturing a graph on its own stream, and
-			// a legacy-stream operation would have to wait for that stream)
-			hipError_t e = hipMemsetAsync(fresh, 0, (size_t)cap * rowFloats * sizeof(float), stream);
-			if (e == hipSuccess && keep && block && r.rowCapacity > 0)
-				e = hipMemcpyAsync(fresh, block, (size_t)r.rowCapacity * rowFloats * sizeof(float), hipMemcpyDeviceToDevice, stream);
-			if (e != hipSuccess)
-			{
-				(void)CountedHipFree(fresh);
-				CheckHip(e, "resampling: growing the row blocks");
-			}
-			WaitFresh(fresh);
-			if (block) (void)CountedHipFree(block);
-			block = fresh;
-		};
-		grow(r.histUp, (size_t)p.histUp, true);
-		grow(r.histDown, (size_t)p.histDown, true);
-		grow(r.modelIn, (size_t)r.modelStride, false);
-		grow(r.modelOut, (size_t)r.modelStride, false);
+		GrowRowBlock(r.histUp, (size_t)r.plan.histUp, r.rowCapacity, cap, "hipMalloc", what);
+		GrowRowBlock(r.histDown, (size_t)r.plan.histDown, r.rowCapacity, cap, "hipMalloc", what);
+		GrowRowBlock(r.modelIn, (size_t)r.modelStride, 0, cap, "hipMalloc", what);
+		GrowRowBlock(r.modelOut, (size_t)r.modelStride, 0, cap, "hipMalloc", what);
 		r.rowCapacity = cap;
 	}
 
@@ -213,19 +212,7 @@ namespace na
 		WaitStreamBounded(stream, "hipStreamSynchronize");
 		const int stride = (int)(((long long)n * p.te) / p.tm) + p.quantum + 1;
 		for (float** block : { &r.modelIn, &r.modelOut })
-		{
-			float* fresh = nullptr;
-			CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&fresh), (size_t)r.rowCapacity * (size_t)stride * sizeof(float)), "hipMalloc");
-			const hipError_t e = hipMemsetAsync(fresh, 0, (size_t)r.rowCapacity * (size_t)stride * sizeof(float), stream); // (see EnsureResampleRows)
-			if (e != hipSuccess)
-			{
-				(void)CountedHipFree(fresh);
-				CheckHip(e, "hipMemsetAsync");
-			}
-			WaitFresh(fresh);
-			if (*block) (void)CountedHipFree(*block);
-			*block = fresh;
-		}
+			GrowRowBlock(*block, (size_t)stride, 0, r.rowCapacity, "hipMalloc", "hipMemsetAsync");
 		r.sizedFrames = (int)n;
 		r.modelStride = stride;
 	}
@@ -274,20 +261,7 @@ namespace na
 			up.gain = (float)p.te;
 			up.cleanNaN = 1;
 			CheckHip(LaunchResampleUp(up, launch), "ResampleUpKernel");
-			if (frames > 0)
-			{
-				r.inside = true;
-				try
-				{
-					ProcessDeviceOn(launch, r.modelIn, r.modelOut, (size_t)frames, r.modelStride, r.modelStride);
-				}
-				catch (...)
-				{
-					r.inside = false;
-					throw;
-				}
-				r.inside = false;
-			}
+			if (frames > 0) LaunchModelsOn(launch, r.modelIn, r.modelOut, (size_t)frames, r.modelStride, r.modelStride);
 			ResampleStageArgs down;
 			down.in = r.modelOut;
 			down.inStride = r.modelStride;

@@ -61,7 +61,7 @@ namespace na
 	// An entry is IMMUTABLE once uploaded -- a table with other contents (another block length, other members) gets its own device
 	// buffer -- so a captured graph that replays a table launch keeps reading what it was captured with, and nothing is allocated,
 	// freed or copied inside a stream capture: the batch runs the launch list once with `prepareOnly` set before it begins the capture
-	// (gpu_batch.cpp ProcessDeviceOn), which uploads every table the captured launches will look up.  The upload is a blocking copy
+	// (gpu_batch.cpp ReplayUnitsGraph), which uploads every table the captured launches will look up.  The upload is a blocking copy
 	// into a buffer no launch has seen yet.  Entries are dropped when the batch's topology changes (NewGeneration, after the graphs
 	// that point at them are gone; hipFree waits for the device).
 	struct WnLaunchTable

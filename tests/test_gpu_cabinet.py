@@ -371,6 +371,65 @@ def test_resampling_batch(na, models):
     assert worst > 0.0 and np.array_equal(y[5, -300:], yt[5, -300:])
 
 
+def test_both_stages_on_a_resampling_batch(na, models):
+    """A 44.1 kHz resampling batch with both stages at work: an IR and a gain ramp on row 8, a hand-over from row 4 to row 2 whose fade
+    ends on a call boundary of both cuts (the call behind it parks row 4 in both).  Once as calls of 128, 441, 100 and 300, once with
+    each of those cut into RAGGED lengths: both within the helpers' bounds, and the same bits in every row."""
+    segments = [128, 441, 100, 300]
+    f, t = 4, 2  # Standard -> packed nano
+    x = H.signal(sum(segments), 28, same=[(f, t)])
+    at = {1: [("ir", 8, "cabB", 0), ("gain", 8, 0.3, 300), ("handover", f, t, segments[1])], 3: [("gain", 8, 1.0, 64), ("ir", 8, "cabA", 100)]}
+    outs = []
+    for cut in (lambda n: [n], H.ragged):
+        calls, ops = [], {}
+        for i, n in enumerate(segments):
+            if i in at:
+                ops[len(calls)] = at[i]
+            calls += cut(n)
+        state = {}
+
+        def hook(b, cab, outc, i):
+            if b.IsParked(f):
+                state.setdefault("parked by the call at", sum(calls[:i]))
+
+        y, yt, worst = K.run_scenario(na, models, x, calls, ops, _irs(), resample=44100, out_stage=True, hook=hook)
+        print("both stages, resampling, %d calls: largest error %.4f of the limit" % (len(calls), worst))
+        assert worst > 0.0 and np.any(y[t, -100:])
+        assert state["parked by the call at"] == sum(segments[:2])
+        outs.append(y)
+    assert len(outs) == 2 and np.array_equal(outs[0], outs[1]), np.flatnonzero(np.any(outs[0] != outs[1], axis=1))
+
+
+def test_ring_growth_keeps_the_histories(na, models):
+    """Four Standard streams, an IR on row 1, two calls of 128; sixteen more streams take the rows past the rings' first capacity of 16,
+    so the rings move to a larger block; two more calls.  Row 1 is, bit for bit, the row of a batch that had twenty streams all along,
+    and (row 0 runs the same input dry) the convolution of its whole history, the samples from before the move included."""
+    n, taps = 128, _irs()["cabA"]
+    x = np.stack([H.noise(4 * n, 2900 + r) for r in range(20)])
+    x[1] = x[0]
+    rows = {}
+    for grown in (True, False):
+        b = na.Batch(0)
+        assert b.AddStreams(models[H.STD], 4) == 0
+        if not grown:
+            assert b.AddStreams(models[H.STD], 16) == 4
+        b.EnableCabinetStage(256)
+        b.SetStreamIR(1, b.LoadIR(taps), 0)
+        before = b.CabinetInfo()["deviceBytes"]
+        out = []
+        for k in range(4):
+            if grown and k == 2:
+                assert b.AddStreams(models[H.STD], 16) == 4
+                info = b.CabinetInfo()
+                assert info["deviceBytes"] > before and info["deviceBytes"] >= 20 * info["ringSamples"] * 4
+            out.append(b.Process(x[:b.NumStreams(), k * n:(k + 1) * n])[:4])
+        rows[grown] = np.concatenate(out, axis=1)
+        b.close()
+    assert np.array_equal(rows[True][0], rows[False][0]), "a dry row does not depend on the number of rows"
+    assert np.array_equal(rows[True][1], rows[False][1])
+    assert np.all(np.abs(rows[True][1] - K.conv64(taps, rows[True][0])) <= K.conv_bound(taps, rows[True][0]))
+
+
 def test_park_and_reactivate(na, models):
     """A parked stream comes back dry; an IR set again starts from an empty history (the contract's T0 is the new set call)."""
     calls = [128, 128, 64, 128, 200, 128]
