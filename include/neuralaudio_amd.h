@@ -517,6 +517,14 @@ NA_EXTERN int NA_DebugRecurrentPlan(NeuralModel* model, int out[6]);
  * the classic head), with rpl > 0 / forceL2w >= 0 in place of the tuning knobs NA_REC_RPL / NA_REC_L2W (0 / -1: the knobs).  Returns 1 if
  * the loader's shape predicate of this kernel admits the shape, 0 if not, -1 on a bad argument. */
 NA_EXTERN int NA_DebugRecurrentShapePlan(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, int rpl, int forceL2w, int out[6]);
+/* Tests: which kernel runs a recurrent model of this shape, host side only -- the decision a model group takes once and
+ * NA_BatchStreamKernelName reports.  haveWT: the transposed weight image exists (every model with a recurrent layer).  knobMask: bit 0
+ * NA_LSTM_NO_DPP, 1 NA_GRU_NO_DPP, 2 NA_LSTM_LANE_KERNEL, 3 NA_LSTM_NO_WAVE_RT, 4 NA_REC_NO_DPP32, 5 NA_REC_L2W, and rpl for NA_REC_RPL (0: the
+ * default) -- the environment is not read; knobMask -1: the process's own tuning knobs.  Returns 0 when no kernel takes the shape, else 1
+ * RecurrentDppKernel, 2 LstmWaveKernel, 3 GruWaveKernel, 4 RecurrentWaveRtKernel, 5 LstmBlockKernel, 6 LstmGenericKernel, 7 GruGenericKernel
+ * (the name goes to outName[cap]); -1 on a bad argument. */
+NA_EXTERN int NA_DebugRecurrentKernel(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, int haveWT, int knobMask, int rpl,
+	char* outName, int cap);
 /* Tests: export / import kernel launches of the stream snapshots so far (one per model group and call, whatever the stream count) */
 NA_EXTERN long long NA_DebugSnapshotLaunches(void);
 /* Tests: which implementation of the NCCL entry points the multi-GPU host binds.  0 = librccl.so (the product).  1 = a loopback table

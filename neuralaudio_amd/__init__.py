@@ -74,6 +74,21 @@ def recurrent_shape_plan(kind, hidden, layers=1, tail_layers=0, tail_width=0, ta
     return dict(_recurrent_plan_dict(out), admitted=bool(r))
 
 
+RECURRENT_KNOB_BITS = {"NA_LSTM_NO_DPP": 1, "NA_GRU_NO_DPP": 2, "NA_LSTM_LANE_KERNEL": 4, "NA_LSTM_NO_WAVE_RT": 8, "NA_REC_NO_DPP32": 16, "NA_REC_L2W": 32}
+
+
+def recurrent_kernel(kind, hidden, layers=1, tail_layers=0, tail_width=0, tail_history=0, have_wt=True, knobs=(), rpl=0):
+    """Test hook, host side only (NA_DebugRecurrentKernel): the name of the kernel that runs an "lstm" / "gru" of this shape ("": none).
+    knobs: names from RECURRENT_KNOB_BITS (the environment is not read), or None for the process's own tuning knobs; rpl: NA_REC_RPL."""
+    mask = -1 if knobs is None else sum(RECURRENT_KNOB_BITS[k] for k in knobs)
+    name = C.create_string_buffer(64)
+    r = capi.load_library().NA_DebugRecurrentKernel(1 if kind == "gru" else 0, int(hidden), int(layers), int(tail_layers), int(tail_width),
+                                                    int(tail_history), int(bool(have_wt)), mask, int(rpl), name, 64)
+    if r < 0:
+        raise NeuralAudioError("NA_DebugRecurrentKernel: bad argument")
+    return name.value.decode()
+
+
 def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 

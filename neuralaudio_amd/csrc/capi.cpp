@@ -350,7 +350,25 @@ int NA_DebugRecurrentShapePlan(int cell, int hidden, int numLayers, int tailLaye
 }
 #endif
 
-// The runtime-shaped recurrent kernel's plan for a recurrent model (lstm_dev.h RecurrentWavePlan -- what the launcher reads), host side
+// Which kernel runs a recurrent model of this shape (lstm_dev.h RecurrentKernelFor -- what a model group asks once and its launches obey),
+// host side only.  knobMask: bit 0 NA_LSTM_NO_DPP, 1 NA_GRU_NO_DPP, 2 NA_LSTM_LANE_KERNEL, 3 NA_LSTM_NO_WAVE_RT, 4 NA_REC_NO_DPP32, 5 NA_REC_L2W; rpl:
+// NA_REC_RPL (0: one row per lane) -- the environment is not read.  knobMask -1: the process's own tuning knobs (rpl is ignored).  Returns
+// the RecurrentKernel value (0: no kernel takes the shape) and writes the kernel's name, -1 on a bad argument.
+#ifndef NA_RELEASE
+int NA_DebugRecurrentKernel(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, int haveWT, int knobMask, int rpl, char* outName, int cap)
+{
+	if ((cell != 0 && cell != 1) || hidden < 1 || numLayers < 0 || tailLayers < 0 || knobMask < -1 || knobMask > 63) return -1;
+	const int b = knobMask;
+	const na::RecurrentKnobs k = b < 0 ? na::RecurrentKnobs::FromTuning()
+		: na::RecurrentKnobs{ (b & 1) != 0, (b & 2) != 0, (b & 4) != 0, (b & 8) != 0, (b & 16) != 0, rpl > 0 ? rpl : 1, (b & 32) != 0 };
+	const na::RecurrentKernel kernel = na::RecurrentKernelFor(cell == 1 ? na::LSTM_CELL_GRU : na::LSTM_CELL_LSTM, hidden, numLayers, tailLayers, tailWidth, tailHistory,
+		haveWT != 0, k).kernel;
+	if (outName && cap > 0) snprintf(outName, (size_t)cap, "%s", na::RecurrentKernelName(kernel));
+	return (int)kernel;
+}
+#endif
+
+// The runtime-shaped recurrent kernel's plan for a recurrent model (lstm_dev.h RecurrentPlan -- what the launcher reads), host side
 // only: out = { runs on RecurrentWaveRtKernel, waves per stream, gate rows per lane, weights streamed from L2, head inside the sample
 // loop, dynamic LDS bytes }; 0, or -1 when the model is not a single recurrent one.
 #ifndef NA_RELEASE

@@ -886,10 +886,13 @@ namespace na
 				dW.UploadUnless(peerWeights, w, stream); // (weight images: may be left for a peer device to fill)
 				dInit.Upload(init, stream);
 				dev.w = dW.Get();
+				dev.cell = (lstm.cell == CELL_GRU) ? LSTM_CELL_GRU : LSTM_CELL_LSTM;
+				// which kernel runs the model, decided once (lstm_dev.h; the transposed image below exists whenever there is a gate matrix)
+				choice = RecurrentKernelFor(dev.cell, lstm.hiddenSize, lstm.numLayers, dev.tailLayers, dev.tailWidth, dev.tailHistMax, lstm.numLayers > 0, RecurrentKnobs::FromTuning());
 				{
 					// the gate matrices once more, transposed into [quad of inputs][row][4] (lstm_dev.h: LstmModelDev::wT)
 					const int H = lstm.hiddenSize, gateRows = ((lstm.cell == CELL_GRU) ? 3 : 4) * H;
-					dev.waves = RecurrentWavePlan(lstm.cell == CELL_GRU ? LSTM_CELL_GRU : LSTM_CELL_LSTM, H, lstm.numLayers, dev.tailLayers, dev.tailWidth, dev.tailHistMax).waves;
+					dev.waves = choice.plan.waves;
 					dev.rowsPad = (gateRows + 64 * dev.waves - 1) / (64 * dev.waves) * (64 * dev.waves);
 					std::vector<float> wt;
 					for (int l = 0; l < lstm.numLayers; l++)
@@ -908,14 +911,13 @@ namespace na
 					dWT.UploadUnless(peerWeights, wt, stream);
 					dev.wT = dWT.Get();
 				}
-				dev.cell = (lstm.cell == CELL_GRU) ? LSTM_CELL_GRU : LSTM_CELL_LSTM;
 				dev.numLayers = lstm.numLayers;
 				dev.hidden = lstm.hiddenSize;
 				dev.math = (lstm.mathMode == MATH_STD) ? LSTM_MATH_STD : LSTM_MATH_FAST;
 				numElems = lstm.numLayers * 2 * lstm.hiddenSize + convRows;
 				dZeros.Alloc(LSTM_MAX_FRAMES);
 				CheckHip(hipMemsetAsync(dZeros.Get(), 0, LSTM_MAX_FRAMES * sizeof(float), stream), "hipMemsetAsync");
-				dpp = !(Tuning::Get().lstmNoDpp || Tuning::Get().gruNoDpp || Tuning::Get().lstmLaneKernel) && RecurrentDppSupported(dev);
+				dpp = choice.kernel == RecurrentKernel::Dpp;
 				kind = dpp ? LaunchKind::Recurrent : LaunchKind::Own;
 			}
 
@@ -994,8 +996,7 @@ namespace na
 
 			hipError_t Launch(const int* slots, const int* rows, int count, const float* dIn, float* dOut, long inStride, long outStride, int n, hipStream_t s)
 			{
-				if (dev.cell == LSTM_CELL_GRU) return LaunchGruBlock(dev, state.Get(), (int)capacity, slots, rows, count, dIn, dOut, inStride, outStride, n, s);
-				return LaunchLstmBlock(dev, state.Get(), (int)capacity, slots, rows, count, dIn, dOut, inStride, outStride, n, s);
+				return LaunchRecurrentBlock(choice, { dev, state.Get(), (int)capacity, slots, rows, count, dIn, dOut, inStride, outStride, n, s });
 			}
 
 			// 8 + 2*4*(state floats)/N bytes per sample (a GRU has no cell state: half of it)
@@ -1029,10 +1030,8 @@ namespace na
 			{
 				// (four streams per wave from RecurrentQuadMinStreams() streams in ONE launch: a batch of several recurrent models decides on
 				// their total, this name on the group's own count)
-				if (RecurrentDppSupported(dev))
-					return (RecurrentQuadSupported(dev) && RecurrentQuadMinStreams() > 0 &&
-						NumActive() >= RecurrentQuadMinStreams()) ? "RecurrentQuadKernel" : "RecurrentDppKernel";
-				return dev.cell == LSTM_CELL_GRU ? "GruWaveKernel / RecurrentWaveRtKernel / GruGenericKernel" : "LstmWaveKernel / RecurrentWaveRtKernel / LstmBlockKernel / LstmGenericKernel";
+				if (dpp && RecurrentQuadSupported(dev) && RecurrentQuadMinStreams() > 0 && NumActive() >= RecurrentQuadMinStreams()) return "RecurrentQuadKernel";
+				return RecurrentKernelName(choice.kernel);
 			}
 
 		protected:
@@ -1072,7 +1071,8 @@ namespace na
 			}
 
 			DevArray<int> dSnapLists;
-			bool dpp = false; // the LDS-free kernel runs this model (a launch of kind Recurrent)
+			RecurrentChoice choice = {}; // the kernel that runs this model, decided at construction
+			bool dpp = false; // ... is the LDS-free one (a launch of kind Recurrent)
 			LstmModelDev dev = {};
 			DevArray<float> dW, dWT, dInit, dZeros;
 			DevArray<float> dArmed; // the pool's template: [numElems], the state a one-stream prewarm leaves (empty until a prewarmed reserve)

@@ -12,7 +12,6 @@
 // the whole block, [x; h] broadcast from LDS, the z / r gates meet the c rows through LDS, the dense head is computed for
 // the whole block after the sample loop (same structure as LstmWaveKernel).
 #include "device_once.h"
-#include "tuning.h"
 #include <cstdlib>
 
 #include <hip/hip_runtime.h>
@@ -211,59 +210,38 @@ namespace na
 			}
 		}
 
-		hipError_t LaunchGruGeneric(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams, const float* in,
-			float* out, long inStride, long outStride, int n, hipStream_t stream)
-		{
-			const size_t ldsBytes = ((size_t)64 * (n + 1) + (size_t)m.numLayers * m.hidden * 64 + (size_t)6 * m.hidden * 64 + (size_t)2 * (m.tailLayers > 0 ? m.tailWidth : 0) * 64) * sizeof(float);
-			if (ldsBytes > 160 * 1024) return hipErrorInvalidValue;
-			static PerDeviceOnce attr; // (hipFuncSetAttribute applies to the current device's copy of the kernel)
-			(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&GruGenericKernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-			hipLaunchKernelGGL(GruGenericKernel, dim3((unsigned)((numStreams + 63) / 64)), dim3(64), ldsBytes, stream, m, state, capacity, slots, rows,
-				numStreams, in, out, inStride, outStride, n);
-			return hipGetLastError();
-		}
-
 		template <int H, int L>
-		hipError_t LaunchHL(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams, const float* in,
-			float* out, long inStride, long outStride, int n, hipStream_t stream)
+		hipError_t LaunchHL(const RecurrentBlock& b)
 		{
-			hipLaunchKernelGGL((GruWaveKernel<H, L>), dim3((unsigned)numStreams), dim3(64), 0, stream, m, state, capacity, slots, rows, in, out, inStride,
-				outStride, n);
+			hipLaunchKernelGGL((GruWaveKernel<H, L>), dim3((unsigned)b.numStreams), dim3(64), 0, b.stream, b.m, b.state, b.capacity, b.slots, b.rows, b.in, b.out, b.inStride,
+				b.outStride, b.n);
 			return hipGetLastError();
 		}
 	}
 
-	hipError_t LaunchGruBlock(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams, const float* in,
-		float* out, long inStride, long outStride, int n, hipStream_t stream)
+	hipError_t LaunchGruGeneric(const RecurrentBlock& b)
 	{
-		if (numStreams <= 0 || n <= 0) return hipSuccess;
-		if (n > LSTM_MAX_FRAMES || !GruShapeSupported(m.hidden, m.numLayers, m.tailLayers > 0 ? m.tailWidth : 0, m.tailLayers > 0 ? m.tailHistMax : 0)) return hipErrorInvalidValue;
-		if (m.tailLayers > 0)
+		const size_t ldsBytes = (size_t)GruGenericLdsBytes(b.m.hidden, b.m.numLayers, b.n, b.m.tailLayers > 0 ? b.m.tailWidth : 0);
+		if (ldsBytes > 160 * 1024) return hipErrorInvalidValue;
+		static PerDeviceOnce attr; // (hipFuncSetAttribute applies to the current device's copy of the kernel)
+		(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&GruGenericKernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+		hipLaunchKernelGGL(GruGenericKernel, dim3((unsigned)((b.numStreams + 63) / 64)), dim3(64), ldsBytes, b.stream, b.m, b.state, b.capacity, b.slots, b.rows,
+			b.numStreams, b.in, b.out, b.inStride, b.outStride, b.n);
+		return hipGetLastError();
+	}
+
+	hipError_t LaunchGruWave(const RecurrentBlock& b)
+	{
+		if (!GruWaveShape(b.m.hidden, b.m.numLayers)) return hipErrorInvalidValue;
+#define NA_GRU_CASE(HH) case HH: return b.m.numLayers == 1 ? LaunchHL<HH, 1>(b) : LaunchHL<HH, 2>(b)
+		switch (b.m.hidden)
 		{
-			// generic keras stack: the runtime-shaped wave kernel if the weights fit the LDS, else the lane = stream kernel
-			hipError_t err = hipSuccess;
-			if (LaunchRecurrentWaveRt(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream, err)) return err;
-			if (m.tailHistMax > 0) return hipErrorNotSupported; // (conv1d tails: the runtime-shaped wave kernel only)
-			return LaunchGruGeneric(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream);
+			NA_GRU_CASE(8);
+			NA_GRU_CASE(12);
+			NA_GRU_CASE(16);
+			NA_GRU_CASE(20);
+		default: return hipErrorInvalidValue; // (a shape the predicate admits without an instance)
 		}
-		const bool noDpp = Tuning::Get().gruNoDpp; // tuning knob: the LDS-broadcast kernel for every shape
-		if (!noDpp && RecurrentDppSupported(m))
-		{
-			const RecurrentGroup g = { m, state, capacity, slots, rows, numStreams };
-			return LaunchRecurrentDpp(&g, 1, in, out, inStride, outStride, n, stream);
-		}
-#define NA_GRU_CASE(HH) \
-	if (m.hidden == HH && m.numLayers <= 2) return m.numLayers == 1 ? LaunchHL<HH, 1>(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream) \
-												: LaunchHL<HH, 2>(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream);
-		NA_GRU_CASE(8)
-		NA_GRU_CASE(12)
-		NA_GRU_CASE(16)
-		NA_GRU_CASE(20)
 #undef NA_GRU_CASE
-		{
-			hipError_t err = hipSuccess;
-			if (LaunchRecurrentWaveRt(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream, err)) return err;
-		}
-		return LaunchGruGeneric(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream);
 	}
 }

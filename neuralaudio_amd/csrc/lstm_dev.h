@@ -85,74 +85,40 @@ namespace na
 	}
 	// shapes of the LDS-free kernels (recurrent_dpp_kernels.hip RecurrentDppSupported): hidden sizes below a layout (8 or 16 units per gate
 	// block) are padded into it: 12 (the reference's static 1x12 / 2x12) runs as 16 ... and one-layer LSTMs (the reference's static 1x24) /
-	// keras GRUs of 17 .. 32 units on the 32-unit layout
-	inline bool RecurrentDppShape(int cell, int hidden, int numLayers, int tailLayers)
+	// keras GRUs of 17 .. 32 units on the 32-unit layout (noDpp32: the tuning knob NA_REC_NO_DPP32 takes that layout away)
+	inline bool RecurrentDppShape(int cell, int hidden, int numLayers, int tailLayers, bool noDpp32)
 	{
 		if (tailLayers != 0) return false; // generic keras stacks run on the runtime-shaped kernels
 		if (cell != LSTM_CELL_LSTM && cell != LSTM_CELL_GRU) return false;
-		if (numLayers == 1 && hidden > 16 && hidden <= 32) return !Tuning::Get().recNoDpp32;
+		if (numLayers == 1 && hidden > 16 && hidden <= 32) return !noDpp32;
 		return hidden >= 1 && hidden <= 16 && (numLayers == 1 || numLayers == 2);
 	}
-
-	// THE decision of how a recurrent model runs on the runtime-shaped kernel (RecurrentWaveRtKernel), in one place: the launcher, the
-	// group that lays the weights out and the test hook (NA_DebugRecurrentPlan) all read it; the kernel shares RecurrentHeadInLoop /
-	// RecurrentRowsPerLane / RecurrentWaveLdsFloats' layout.  No HIP types: it works without a device.
-	struct RecurrentPlan
+	// the shaped one-wave instances (LstmWaveKernel<H, L> / GruWaveKernel<H, L>) and the shaped lane = stream ones (LstmBlockKernel<H>): the
+	// decision below and the instantiation switches of the kernel files both read these
+	inline bool LstmWaveShape(int hidden, int numLayers)
 	{
-		int runs;        // 1: the model runs on this kernel (0: a shaped / LDS-free kernel or a lane = stream kernel takes it; the rest is then what this kernel WOULD do)
-		int waves;       // waves per stream: 1 = RecurrentWaveRtKernel<64> (wave fences), 2 .. 16 = <1024> (barriers)
-		int rowsPerLane; // gate rows per lane, 1 .. 8
-		int l2w;         // 1: the gate weights are streamed transposed from L2, 0: they sit in LDS
-		int headInLoop;  // 1: the 1-unit head is evaluated inside the sample loop by the first wave
-		long ldsBytes;   // dynamic LDS of the launch
-	};
-	// haveWT: the transposed weight image exists (LstmModelDev::wT).  rpl > 0 / forceL2w >= 0: these instead of the tuning knobs NA_REC_RPL /
-	// NA_REC_L2W (tests ask for the default plan of a shape whatever the environment says)
-	inline RecurrentPlan RecurrentWavePlan(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, bool haveWT = true,
-		int rpl = 0, int forceL2w = -1)
-	{
-		const Tuning& t = Tuning::Get();
-		if (rpl <= 0) rpl = t.recRpl > 0 ? t.recRpl : 1; // tuning knob: gate rows per lane
-		const bool forceL2 = forceL2w >= 0 ? forceL2w != 0 : t.recL2w;
-		const bool gru = cell == LSTM_CELL_GRU, hasTail = tailLayers > 0, convTail = hasTail && tailHistory > 0;
-		const int gateRows = (gru ? 3 : 4) * hidden;
-		RecurrentPlan p = {};
-		p.waves = RecurrentWaveWaves(gateRows, rpl);
-		p.rowsPerLane = RecurrentRowsPerLane(gateRows, 64 * p.waves);
-		p.headInLoop = RecurrentHeadInLoop(hidden, hasTail) ? 1 : 0;
-		const int tw = hasTail ? tailWidth : 0, th = hasTail ? tailHistory : 0;
-		p.ldsBytes = RecurrentWaveLdsFloats(cell, hidden, numLayers, tw, th, hasTail, true) * 4;
-		// weights larger than the LDS (LSTM 2x64: 197 KB): streamed from L2, transposed for coalesced reads (NA_REC_L2W=1 forces the mode)
-		p.l2w = (p.ldsBytes > RECURRENT_LDS_BYTES || (forceL2 && numLayers > 0)) ? 1 : 0;
-		if (p.l2w) p.ldsBytes = RecurrentWaveLdsFloats(cell, hidden, numLayers, tw, th, hasTail, false) * 4;
-		// who runs first: without a tail the LDS-free kernels and the shaped one-wave instances (LstmWaveKernel: 8 .. 32 units, GruWaveKernel:
-		// 8 .. 20, one or two layers) take their shapes; tuning knobs send LSTMs to the lane = stream kernels -- except tails with conv1d
-		// layers, which only this kernel evaluates
-		bool shapedFirst = false;
-		if (!hasTail)
-		{
-			const bool listed = hidden == 8 || hidden == 12 || hidden == 16 || hidden == 20 || (!gru && (hidden == 24 || hidden == 32));
-			shapedFirst = (!(gru ? t.gruNoDpp : t.lstmNoDpp) && RecurrentDppShape(cell, hidden, numLayers, tailLayers)) || (listed && (numLayers == 1 || numLayers == 2));
-		}
-		const bool off = (t.lstmNoWaveRt || (!gru && t.lstmLaneKernel)) && !convTail;
-		p.runs = (!shapedFirst && !off && hidden >= 1 && hidden <= RECURRENT_WAVE_MAX_HIDDEN && numLayers >= 0 && !(numLayers == 0 && !hasTail) &&
-			(!p.l2w || haveWT) && p.ldsBytes <= RECURRENT_LDS_BYTES) ? 1 : 0;
-		return p;
+		return (hidden == 8 || hidden == 12 || hidden == 16 || hidden == 20 || hidden == 24 || hidden == 32) && (numLayers == 1 || numLayers == 2);
 	}
-	// the lane = stream kernels' bound (LstmGenericKernel / GruGenericKernel: state of 64 streams in LDS)
+	inline bool GruWaveShape(int hidden, int numLayers) { return (hidden == 8 || hidden == 12 || hidden == 16 || hidden == 20) && (numLayers == 1 || numLayers == 2); }
+	inline bool LstmBlockShape(int hidden) { return hidden == 4 || hidden == 40 || LstmWaveShape(hidden, 1); }
+	// dynamic LDS of the lane = stream kernels for a block of n samples (state of 64 streams in LDS; tailWidth: 0 without a dense tail).
+	// RecurrentKernelFor chooses these kernels only where the longest block (n = LSTM_MAX_FRAMES) fits, so the launchers' own checks of
+	// the block at hand (the kernels' bound, kept beside them) cannot fail behind a choice
+	inline long LstmBlockLdsBytes(int hidden, int numLayers, int n) { return (64L * (n + 1) + (long)numLayers * 2 * hidden * 64) * 4; }
+	inline long LstmGenericLdsBytes(int hidden, int numLayers, int n, int tailWidth) { return LstmBlockLdsBytes(hidden, numLayers, n) + ((long)hidden * 64 + 2L * tailWidth * 64) * 4; }
+	inline long GruGenericLdsBytes(int hidden, int numLayers, int n, int tailWidth) { return (64L * (n + 1) + (long)numLayers * hidden * 64 + 6L * hidden * 64 + 2L * tailWidth * 64) * 4; }
+	// the lane = stream kernels' bound (LstmGenericKernel / GruGenericKernel at the longest block)
 	inline bool LstmLaneKernelShape(int hidden, int numLayers, int tailWidth = 0)
 	{
 		if (hidden < 1 || numLayers < (tailWidth > 0 ? 0 : 1) || numLayers > LSTM_MAX_LAYERS || tailWidth > LSTM_MAX_TAIL_WIDTH) return false;
-		const long bytes = (64L * (LSTM_MAX_FRAMES + 1) + (long)numLayers * 2 * hidden * 64 + (long)hidden * 64 + 2L * tailWidth * 64) * 4;
-		return bytes <= 160L * 1024;
+		return LstmGenericLdsBytes(hidden, numLayers, LSTM_MAX_FRAMES, tailWidth) <= RECURRENT_LDS_BYTES;
 	}
 	inline bool GruLaneKernelShape(int hidden, int numLayers, int tailWidth = 0)
 	{
 		if (hidden < 1 || numLayers < 1 || numLayers > LSTM_MAX_LAYERS || tailWidth > LSTM_MAX_TAIL_WIDTH) return false;
-		const long bytes = (64L * (LSTM_MAX_FRAMES + 1) + (long)numLayers * hidden * 64 + 6L * hidden * 64 + 2L * tailWidth * 64) * 4; // GruGenericKernel's LDS
-		return bytes <= 160L * 1024;
+		return GruGenericLdsBytes(hidden, numLayers, LSTM_MAX_FRAMES, tailWidth) <= RECURRENT_LDS_BYTES;
 	}
-	// (a tail with conv1d layers -- tailHistory > 0 -- only runs on the runtime-shaped wave kernel)
+	// what the loader admits (knob-independent; a tail with conv1d layers -- tailHistory > 0 -- only runs on the runtime-shaped wave kernel)
 	inline bool LstmShapeSupported(int hidden, int numLayers, int tailWidth = 0, int tailHistory = 0)
 	{
 		return (tailHistory == 0 && LstmLaneKernelShape(hidden, numLayers, tailWidth)) || RecurrentWaveShape(hidden, numLayers, tailWidth, tailHistory);
@@ -160,6 +126,97 @@ namespace na
 	inline bool GruShapeSupported(int hidden, int numLayers, int tailWidth = 0, int tailHistory = 0)
 	{
 		return (tailHistory == 0 && GruLaneKernelShape(hidden, numLayers, tailWidth)) || (numLayers >= 1 && RecurrentWaveShape(hidden, numLayers, tailWidth, tailHistory));
+	}
+
+	// How the runtime-shaped kernel (RecurrentWaveRtKernel) runs a model: the kernel shares RecurrentHeadInLoop / RecurrentRowsPerLane /
+	// RecurrentWaveLdsFloats' layout.
+	struct RecurrentPlan
+	{
+		int runs;        // 1: RecurrentKernelFor chose this kernel (0: another kernel runs the model; the rest is then what this kernel WOULD do)
+		int waves;       // waves per stream: 1 = RecurrentWaveRtKernel<64> (wave fences), 2 .. 16 = <1024> (barriers)
+		int rowsPerLane; // gate rows per lane, 1 .. 8
+		int l2w;         // 1: the gate weights are streamed transposed from L2, 0: they sit in LDS
+		int headInLoop;  // 1: the 1-unit head is evaluated inside the sample loop by the first wave
+		long ldsBytes;   // dynamic LDS of the launch
+	};
+
+	// THE decision of which kernel runs a recurrent model, in one place: the group (gpu_groups.h LstmGroup) asks once and keeps the answer,
+	// the launcher (recurrent_launch.cpp) switches on it, NA_BatchStreamKernelName reports it, the test hooks (NA_DebugRecurrentKernel,
+	// NA_DebugRecurrentPlan) ask it about any shape and knob set.  No HIP types, no environment: a pure function that works without a device.
+	enum class RecurrentKernel { None, Dpp, LstmWave, GruWave, WaveRt, LstmBlock, LstmGeneric, GruGeneric };
+	inline const char* RecurrentKernelName(RecurrentKernel k)
+	{
+		static const char* const names[] = { "", "RecurrentDppKernel", "LstmWaveKernel", "GruWaveKernel", "RecurrentWaveRtKernel", "LstmBlockKernel", "LstmGenericKernel", "GruGenericKernel" };
+		return names[(int)k];
+	}
+	// the tuning knobs that bear on the choice (tuning.h: NA_LSTM_NO_DPP, NA_GRU_NO_DPP, NA_LSTM_LANE_KERNEL, NA_LSTM_NO_WAVE_RT, NA_REC_NO_DPP32, NA_REC_RPL, NA_REC_L2W)
+	struct RecurrentKnobs
+	{
+		bool lstmNoDpp = false, gruNoDpp = false, lstmLaneKernel = false, lstmNoWaveRt = false, recNoDpp32 = false;
+		int recRpl = 1;
+		bool recL2w = false;
+		static RecurrentKnobs FromTuning()
+		{
+			const Tuning& t = Tuning::Get();
+			return { t.lstmNoDpp, t.gruNoDpp, t.lstmLaneKernel, t.lstmNoWaveRt, t.recNoDpp32, t.recRpl, t.recL2w };
+		}
+	};
+	struct RecurrentChoice
+	{
+		RecurrentKernel kernel; // None: no kernel takes the shape under these knobs (the launch is an error)
+		RecurrentPlan plan;     // the runtime-shaped kernel's plan (plan.runs == (kernel == WaveRt))
+	};
+	// haveWT: the transposed weight image exists (LstmModelDev::wT)
+	inline RecurrentChoice RecurrentKernelFor(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, bool haveWT, const RecurrentKnobs& k)
+	{
+		const bool gru = cell == LSTM_CELL_GRU, hasTail = tailLayers > 0, convTail = hasTail && tailHistory > 0;
+		const int tw = hasTail ? tailWidth : 0, th = hasTail ? tailHistory : 0;
+		const int gateRows = (gru ? 3 : 4) * hidden;
+		RecurrentPlan p = {};
+		p.waves = RecurrentWaveWaves(gateRows, k.recRpl > 0 ? k.recRpl : 1);
+		p.rowsPerLane = RecurrentRowsPerLane(gateRows, 64 * p.waves);
+		p.headInLoop = RecurrentHeadInLoop(hidden, hasTail) ? 1 : 0;
+		p.ldsBytes = RecurrentWaveLdsFloats(cell, hidden, numLayers, tw, th, hasTail, true) * 4;
+		// weights larger than the LDS (LSTM 2x64: 197 KB): streamed from L2, transposed for coalesced reads (NA_REC_L2W=1 forces the mode)
+		p.l2w = (p.ldsBytes > RECURRENT_LDS_BYTES || (k.recL2w && numLayers > 0)) ? 1 : 0;
+		if (p.l2w) p.ldsBytes = RecurrentWaveLdsFloats(cell, hidden, numLayers, tw, th, hasTail, false) * 4;
+		// the runtime-shaped kernel takes the model: tuning knobs send models to the lane = stream kernels -- except tails with conv1d layers,
+		// which only this kernel evaluates
+		const bool rtFits = !((k.lstmNoWaveRt || (!gru && k.lstmLaneKernel)) && !convTail) && hidden >= 1 && hidden <= RECURRENT_WAVE_MAX_HIDDEN && numLayers >= 0 &&
+			!(numLayers == 0 && !hasTail) && (!p.l2w || haveWT) && p.ldsBytes <= RECURRENT_LDS_BYTES;
+		// the LDS-free kernels and the shaped one-wave instances come first (models without a tail); the lane = stream kernels last
+		const bool dpp = !(gru ? k.gruNoDpp : k.lstmNoDpp) && RecurrentDppShape(cell, hidden, numLayers, tailLayers, k.recNoDpp32);
+		RecurrentKernel kernel = RecurrentKernel::None;
+		if (gru)
+		{
+			if (!GruShapeSupported(hidden, numLayers, tw, th)) kernel = RecurrentKernel::None;
+			else if (dpp) kernel = RecurrentKernel::Dpp;
+			else if (!hasTail && GruWaveShape(hidden, numLayers)) kernel = RecurrentKernel::GruWave;
+			else if (rtFits) kernel = RecurrentKernel::WaveRt;
+			else if (!convTail && GruGenericLdsBytes(hidden, numLayers, LSTM_MAX_FRAMES, tw) <= RECURRENT_LDS_BYTES) kernel = RecurrentKernel::GruGeneric;
+		}
+		else
+		{
+			const bool lane = k.lstmLaneKernel && !convTail; // NA_LSTM_LANE_KERNEL: the lane = stream kernels for everything they evaluate
+			if (!lane && dpp) kernel = RecurrentKernel::Dpp;
+			else if (!lane && !hasTail && LstmWaveShape(hidden, numLayers)) kernel = RecurrentKernel::LstmWave;
+			else if (rtFits) kernel = RecurrentKernel::WaveRt;
+			else if (convTail) kernel = RecurrentKernel::None;
+			else if (!hasTail && LstmBlockShape(hidden)) kernel = LstmBlockLdsBytes(hidden, numLayers, LSTM_MAX_FRAMES) <= RECURRENT_LDS_BYTES ? RecurrentKernel::LstmBlock : RecurrentKernel::None;
+			else if (LstmGenericLdsBytes(hidden, numLayers, LSTM_MAX_FRAMES, tw) <= RECURRENT_LDS_BYTES) kernel = RecurrentKernel::LstmGeneric;
+		}
+		p.runs = kernel == RecurrentKernel::WaveRt ? 1 : 0;
+		return { kernel, p };
+	}
+	// The runtime-shaped kernel's plan alone, under the process's tuning knobs.  rpl > 0 / forceL2w >= 0: these instead of NA_REC_RPL /
+	// NA_REC_L2W (tests ask for the default plan of a shape whatever the environment says)
+	inline RecurrentPlan RecurrentWavePlan(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, bool haveWT = true,
+		int rpl = 0, int forceL2w = -1)
+	{
+		RecurrentKnobs k = RecurrentKnobs::FromTuning();
+		if (rpl > 0) k.recRpl = rpl;
+		if (forceL2w >= 0) k.recL2w = forceL2w != 0;
+		return RecurrentKernelFor(cell, hidden, numLayers, tailLayers, tailWidth, tailHistory, haveWT, k).plan;
 	}
 
 	struct LstmModelDev
@@ -190,6 +247,6 @@ namespace na
 		const float* wT;
 		int layerOffT[LSTM_MAX_LAYERS]; // float offsets into wT
 		int rowsPad; // (a multiple of 64 x waves)
-		int waves;   // waves per stream of the runtime-shaped kernel (RecurrentWavePlan)
+		int waves;   // waves per stream of the runtime-shaped kernel (RecurrentPlan::waves)
 	};
 }

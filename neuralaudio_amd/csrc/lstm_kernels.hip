@@ -6,7 +6,6 @@
 //   LSTMLayer::Process    NeuralAudio/LSTMDynamic.h:95-108 (same arithmetic, runtime shaped)
 //   FastMath Tanh/Sigmoid NeuralAudio/Activation.h:83-96
 #include "device_once.h"
-#include "tuning.h"
 #include <cstdlib>
 
 #include <hip/hip_runtime.h>
@@ -297,36 +296,28 @@ namespace na
 	}
 
 	template <int H, int L>
-	static hipError_t LaunchWaveHL(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
+	static hipError_t LaunchWaveHL(const RecurrentBlock& b)
 	{
-		hipLaunchKernelGGL((LstmWaveKernel<H, L>), dim3((unsigned)numStreams), dim3(64), 0, stream, m, state, capacity, slots, rows, in, out,
-			inStride, outStride, n);
+		hipLaunchKernelGGL((LstmWaveKernel<H, L>), dim3((unsigned)b.numStreams), dim3(64), 0, b.stream, b.m, b.state, b.capacity, b.slots, b.rows, b.in, b.out,
+			b.inStride, b.outStride, b.n);
 		return hipGetLastError();
 	}
 
-	// returns false when (H, layers) has no wave-per-stream instance (the lane-per-stream kernel is used instead)
-	static bool LaunchLstmWave(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream, hipError_t& err)
+	hipError_t LaunchLstmWave(const RecurrentBlock& b)
 	{
-		const bool noDpp = Tuning::Get().lstmNoDpp; // tuning knob: fall back to the LDS-broadcast wave kernel
-		if (!noDpp && RecurrentDppSupported(m))
+		if (!LstmWaveShape(b.m.hidden, b.m.numLayers)) return hipErrorInvalidValue;
+#define NA_LSTM_WAVE(HH) case HH: return b.m.numLayers == 1 ? LaunchWaveHL<HH, 1>(b) : LaunchWaveHL<HH, 2>(b)
+		switch (b.m.hidden)
 		{
-			const RecurrentGroup g = { m, state, capacity, slots, rows, numStreams };
-			err = LaunchRecurrentDpp(&g, 1, in, out, inStride, outStride, n, stream);
-			return true;
+			NA_LSTM_WAVE(8);
+			NA_LSTM_WAVE(12);
+			NA_LSTM_WAVE(16);
+			NA_LSTM_WAVE(20);
+			NA_LSTM_WAVE(24);
+			NA_LSTM_WAVE(32);
+		default: return hipErrorInvalidValue; // (a shape the predicate admits without an instance)
 		}
-#define NA_LSTM_WAVE(HH) \
-	if (m.hidden == HH && m.numLayers == 1) { err = LaunchWaveHL<HH, 1>(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream); return true; } \
-	if (m.hidden == HH && m.numLayers == 2) { err = LaunchWaveHL<HH, 2>(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream); return true; }
-		NA_LSTM_WAVE(8)
-		NA_LSTM_WAVE(12)
-		NA_LSTM_WAVE(16)
-		NA_LSTM_WAVE(20)
-		NA_LSTM_WAVE(24)
-		NA_LSTM_WAVE(32)
 #undef NA_LSTM_WAVE
-		return false;
 	}
 
 	// ------------------------------------------------------------------------------------------------------------
@@ -612,31 +603,19 @@ namespace na
 		}
 	}
 
-	// false: the shape does not fit (hidden > 64 or the weights exceed the LDS): the lane = stream kernels take it
-	bool LaunchRecurrentWaveRt(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream, hipError_t& err)
+	template <int MAXT>
+	static hipError_t LaunchWaveRt(const RecurrentPlan& plan, const RecurrentBlock& b, int waves)
 	{
-		// (lstm_dev.h RecurrentWavePlan: tuning knobs, LDS or L2-streamed weights, the LDS size)
-		const RecurrentPlan plan = RecurrentWavePlan(m.cell, m.hidden, m.numLayers, m.tailLayers, m.tailWidth, m.tailHistMax, m.wT != nullptr);
-		if (!plan.runs) return false;
-		const size_t ldsBytes = (size_t)plan.ldsBytes;
-		const int l2w = plan.l2w;
-		static PerDeviceOnce attr, attrBlock; // (hipFuncSetAttribute applies to the current device's copy of the kernel)
-		const int waves = m.waves > 1 ? m.waves : 1;
-		if (waves == 1)
-		{
-			(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&RecurrentWaveRtKernel<64>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-			hipLaunchKernelGGL(RecurrentWaveRtKernel<64>, dim3((unsigned)numStreams), dim3(64), ldsBytes, stream, m, state, capacity, slots, rows, in, out, inStride,
-				outStride, n, l2w);
-		}
-		else
-		{
-			(void)attrBlock.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&RecurrentWaveRtKernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-			hipLaunchKernelGGL(RecurrentWaveRtKernel<1024>, dim3((unsigned)numStreams), dim3(64u * (unsigned)waves), ldsBytes, stream, m, state, capacity, slots, rows, in,
-				out, inStride, outStride, n, l2w);
-		}
-		err = hipGetLastError();
-		return true;
+		static PerDeviceOnce attr; // per instantiation and device (hipFuncSetAttribute applies to the current device's copy of the kernel)
+		(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&RecurrentWaveRtKernel<MAXT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+		hipLaunchKernelGGL(RecurrentWaveRtKernel<MAXT>, dim3((unsigned)b.numStreams), dim3(64u * (unsigned)waves), (size_t)plan.ldsBytes, b.stream, b.m, b.state, b.capacity,
+			b.slots, b.rows, b.in, b.out, b.inStride, b.outStride, b.n, plan.l2w);
+		return hipGetLastError();
+	}
+
+	hipError_t LaunchRecurrentWaveRt(const RecurrentPlan& plan, const RecurrentBlock& b)
+	{
+		return b.m.waves > 1 ? LaunchWaveRt<1024>(plan, b, b.m.waves) : LaunchWaveRt<64>(plan, b, 1);
 	}
 
 	// initial hidden / cell state of the listed slots (NAM: stored in the weights, LSTM.h:51-55; keras: zeros)
@@ -661,18 +640,35 @@ namespace na
 	}
 
 	template <int H>
-	static hipError_t LaunchH(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
+	static hipError_t LaunchH(const RecurrentBlock& b)
 	{
-		const size_t ldsBytes = ((size_t)64 * (n + 1) + (size_t)m.numLayers * 2 * H * 64) * sizeof(float);
+		const size_t ldsBytes = (size_t)LstmBlockLdsBytes(H, b.m.numLayers, b.n);
 		if (ldsBytes > 160 * 1024) return hipErrorInvalidValue;
 		static PerDeviceOnce attr; // per instantiation and device
 		(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&LstmBlockKernel<H>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-		hipLaunchKernelGGL(LstmBlockKernel<H>, dim3((unsigned)((numStreams + 63) / 64)), dim3(64), ldsBytes, stream, m, state, capacity,
-			slots, rows, numStreams, in, out, inStride, outStride, n);
+		hipLaunchKernelGGL(LstmBlockKernel<H>, dim3((unsigned)((b.numStreams + 63) / 64)), dim3(64), ldsBytes, b.stream, b.m, b.state, b.capacity,
+			b.slots, b.rows, b.numStreams, b.in, b.out, b.inStride, b.outStride, b.n);
 		return hipGetLastError();
 	}
 
+	hipError_t LaunchLstmBlockH(const RecurrentBlock& b)
+	{
+		if (!LstmBlockShape(b.m.hidden)) return hipErrorInvalidValue;
+#define NA_LSTM_CASE(HH) case HH: return LaunchH<HH>(b)
+		switch (b.m.hidden)
+		{
+			NA_LSTM_CASE(4);
+			NA_LSTM_CASE(8);
+			NA_LSTM_CASE(12);
+			NA_LSTM_CASE(16);
+			NA_LSTM_CASE(20);
+			NA_LSTM_CASE(24);
+			NA_LSTM_CASE(32);
+			NA_LSTM_CASE(40);
+		default: return hipErrorInvalidValue; // (a size the predicate admits without an instance)
+		}
+#undef NA_LSTM_CASE
+	}
 
 	// ------------------------------------------------------------------------------------------------------------
 	// Any hidden size / layer count (the reference's runtime-shaped path, LSTMDynamic.h:95-108,175-215): lane = stream, runtime loops,
@@ -764,50 +760,15 @@ namespace na
 		}
 	}
 
-	static size_t LstmGenericLdsBytes(int hidden, int numLayers, int n, int tailWidth)
+	hipError_t LaunchLstmGeneric(const RecurrentBlock& b)
 	{
-		return ((size_t)64 * (n + 1) + (size_t)numLayers * 2 * hidden * 64 + (size_t)hidden * 64 + (size_t)2 * tailWidth * 64) * sizeof(float);
-	}
-
-	static hipError_t LaunchGeneric(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams, const float* in,
-		float* out, long inStride, long outStride, int n, hipStream_t stream)
-	{
-		const size_t ldsBytes = LstmGenericLdsBytes(m.hidden, m.numLayers, n, m.tailLayers > 0 ? m.tailWidth : 0);
+		const size_t ldsBytes = (size_t)LstmGenericLdsBytes(b.m.hidden, b.m.numLayers, b.n, b.m.tailLayers > 0 ? b.m.tailWidth : 0);
 		if (ldsBytes > 160 * 1024) return hipErrorInvalidValue;
 		static PerDeviceOnce attr;
 		(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&LstmGenericKernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-		hipLaunchKernelGGL(LstmGenericKernel, dim3((unsigned)((numStreams + 63) / 64)), dim3(64), ldsBytes, stream, m, state, capacity, slots, rows,
-			numStreams, in, out, inStride, outStride, n);
+		hipLaunchKernelGGL(LstmGenericKernel, dim3((unsigned)((b.numStreams + 63) / 64)), dim3(64), ldsBytes, b.stream, b.m, b.state, b.capacity, b.slots, b.rows,
+			b.numStreams, b.in, b.out, b.inStride, b.outStride, b.n);
 		return hipGetLastError();
-	}
-
-	hipError_t LaunchLstmBlock(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
-	{
-		if (numStreams <= 0 || n <= 0) return hipSuccess;
-		if (n > LSTM_MAX_FRAMES) return hipErrorInvalidValue;
-		{
-			const bool forceLaneKernel = Tuning::Get().lstmLaneKernel && !(m.tailLayers > 0 && m.tailHistMax > 0); // tuning knob (conv1d tails: the wave kernel only)
-			hipError_t err = hipSuccess;
-			if (!forceLaneKernel && m.tailLayers == 0 && LaunchLstmWave(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream, err)) return err;
-			if (!forceLaneKernel && LaunchRecurrentWaveRt(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream, err)) return err;
-		}
-		if (m.tailLayers > 0 && m.tailHistMax > 0) return hipErrorNotSupported; // (conv1d tails: the runtime-shaped wave kernel only)
-		if (m.tailLayers > 0) return LaunchGeneric(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream); // generic keras stack
-#define NA_LSTM_CASE(HH) case HH: return LaunchH<HH>(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream)
-		switch (m.hidden)
-		{
-			NA_LSTM_CASE(4);
-			NA_LSTM_CASE(8);
-			NA_LSTM_CASE(12);
-			NA_LSTM_CASE(16);
-			NA_LSTM_CASE(20);
-			NA_LSTM_CASE(24);
-			NA_LSTM_CASE(32);
-			NA_LSTM_CASE(40);
-		default: return LaunchGeneric(m, state, capacity, slots, rows, numStreams, in, out, inStride, outStride, n, stream);
-		}
-#undef NA_LSTM_CASE
 	}
 
 	hipError_t LaunchLstmInitState(float* state, int capacity, const int* slots, int numStreams, const float* init, int numElems,

@@ -8,9 +8,30 @@
 namespace na
 {
 
-	// One block of n <= 128 samples for `numStreams` streams of one model (lane = stream).
-	hipError_t LaunchLstmBlock(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
+	// One block of n samples for `numStreams` streams of one model: what every recurrent launcher below takes
+	struct RecurrentBlock
+	{
+		const LstmModelDev& m;
+		float* state;
+		int capacity;
+		const int *slots, *rows;
+		int numStreams;
+		const float* in;
+		float* out;
+		long inStride, outStride;
+		int n;
+		hipStream_t stream;
+	};
+	// ... on the kernel that RecurrentKernelFor chose for the model (lstm_dev.h; recurrent_launch.cpp: a switch, the guards on n and the
+	// stream count).  The launchers behind it, one per kernel and without policy: lstm_kernels.hip, gru_kernels.hip
+	hipError_t LaunchRecurrentBlock(const RecurrentChoice& choice, const RecurrentBlock& b);
+	hipError_t LaunchLstmWave(const RecurrentBlock& b);    // LstmWaveKernel<H, L>: the shapes of LstmWaveShape
+	hipError_t LaunchLstmBlockH(const RecurrentBlock& b);  // LstmBlockKernel<H>: the sizes of LstmBlockShape
+	hipError_t LaunchLstmGeneric(const RecurrentBlock& b); // LstmGenericKernel
+	hipError_t LaunchGruWave(const RecurrentBlock& b);     // GruWaveKernel<H, L>: the shapes of GruWaveShape
+	hipError_t LaunchGruGeneric(const RecurrentBlock& b);  // GruGenericKernel
+	// RecurrentWaveRtKernel<64 | 1024>: LSTM or GRU cells, any layer count, classic head or dense / conv1d chain, as `plan` lays it out
+	hipError_t LaunchRecurrentWaveRt(const RecurrentPlan& plan, const RecurrentBlock& b);
 
 	// LDS-free kernels for hidden size 8 / 16, 1-2 layers, LSTM or GRU (recurrent_dpp_kernels.hip): one launch over several model groups
 	constexpr int RECURRENT_MAX_GROUPS = 8;
@@ -30,20 +51,12 @@ namespace na
 	int RecurrentQuadMinStreams();
 	int SetRecurrentQuadMinStreams(int streams); // returns the previous value
 	long RecurrentQuadLaunches();
-	// The runtime-shaped one-wave-per-stream kernel (lstm_kernels.hip): LSTM or GRU cells, hidden <= 64, any layer count, classic head or
-	// dense chain, as long as the weights of all layers fit the LDS.  false: not launched (the lane = stream kernels take the model).
-	bool LaunchRecurrentWaveRt(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream, hipError_t& err);
 	hipError_t LaunchRecurrentDpp(const RecurrentGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
 		hipStream_t stream);
 	// ... any number of groups in one launch, the group table in device memory (`table`: the batch's cache of it; wavenet_launch.h)
 	struct WnLaunchTable;
 	hipError_t LaunchRecurrentDppTable(const RecurrentGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
 		hipStream_t stream, WnLaunchTable& table);
-
-	// keras GRU (gru_kernels.hip): same state layout (only the h half of every layer is used), m.cell == LSTM_CELL_GRU
-	hipError_t LaunchGruBlock(const LstmModelDev& m, float* state, int capacity, const int* slots, const int* rows, int numStreams,
-		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
 
 	// state[k*capacity + slot] = init[k] for the listed slots
 	hipError_t LaunchLstmInitState(float* state, int capacity, const int* slots, int numStreams, const float* init, int numElems,

@@ -1448,7 +1448,7 @@ namespace na
 
 	bool RecurrentDppSupported(const LstmModelDev& m)
 	{
-		return RecurrentDppShape(m.cell, m.hidden, m.numLayers, m.tailLayers); // (lstm_dev.h)
+		return RecurrentDppShape(m.cell, m.hidden, m.numLayers, m.tailLayers, Tuning::Get().recNoDpp32); // (lstm_dev.h)
 	}
 
 	hipError_t LaunchRecurrentDppTable(const RecurrentGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,

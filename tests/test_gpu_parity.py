@@ -179,6 +179,63 @@ def test_recurrent_models_through_tiny_and_ragged_buffers(na, kind, layers, hidd
     assert O.rms(np.concatenate(out) - want) < 5e-6
 
 
+# one shape per recurrent kernel that some knob set can reach (lstm_dev.h RecurrentKernelFor): the LDS-free kernel, the shaped one-wave
+# instances, the runtime-shaped kernel on one wave and on a workgroup, and -- under NA_LSTM_LANE_KERNEL / NA_LSTM_NO_WAVE_RT, in the forced
+# runs of test_gpu_families.py -- LstmBlockKernel<40>, LstmGenericKernel (also with a dense tail) and GruGenericKernel
+DISPATCH_SHAPES = [[("lstm", 16)], [("lstm", 24), ("lstm", 24)], [("gru", 20), ("gru", 20)], [("lstm", 16), ("lstm", 16), ("lstm", 16)], [("gru", 86)],
+                   [("lstm", 40)], [("lstm", 5)], [("lstm", 8), ("dense", 4, "tanh"), ("dense", 1)]]
+
+
+@pytest.mark.parametrize("spec", DISPATCH_SHAPES, ids=lambda s: "-".join("%s%d" % (l[0], l[1]) for l in s))
+def test_the_kernel_the_decision_names_runs_and_is_right(na, loader, spec):
+    """Three streams (the lane = stream kernels mask 61 idle lanes), 72 samples as calls of 65 and 7: NA_BatchStreamKernelName is the
+    kernel that RecurrentKernelFor names for the process's own tuning knobs, and the output is the oracle's."""
+    import json
+    import recurrent_cases as RC
+    import ref_np as R
+    kind, hidden, layers, tail_layers, tail_width, tail_history = RC.stack_dims(spec)
+    want_name = na.recurrent_kernel(kind, hidden, layers, tail_layers, tail_width, tail_history, knobs=None)
+    x = np.stack([O.signal_noise(72, 20 + s) for s in range(3)])
+    if tail_layers:
+        mj = R.synth_keras_stack(spec, seed=77)
+        doc, ext, prewarm = json.dumps(mj), ".json", True
+        want = np.stack([R.keras_stack_forward(mj, x[s]) for s in range(3)])
+    elif kind == "lstm":
+        w = O.synth_lstm_weights(layers, hidden, seed=70 + hidden)
+        doc, ext, prewarm = O.nam_json_lstm(layers, hidden, w), ".nam", True
+        want = np.stack([O.OracleLSTM.from_nam(layers, hidden, w).process(x[s]) for s in range(3)])
+    else:
+        gj = O.synth_keras_gru(layers, hidden, seed=70 + hidden)
+        doc, ext, prewarm = json.dumps(gj), ".json", True
+        want = np.stack([O.OracleGRU(gj).process(x[s]) for s in range(3)])
+    if want_name == "":
+        # no kernel takes the shape under these knobs (GRU 1x86 without the runtime-shaped kernel: beyond GruGenericKernel's LDS): an error, no launch
+        m = loader.CreateFromString(doc, ext, doPrewarm=False)
+        assert m is not None
+        b = na.Batch(0)
+        b.AddStreams(m, 3, doPrewarm=False)
+        with pytest.raises(na.NeuralAudioError):
+            b.Process(x[:, :65])
+        return
+    m = loader.CreateFromString(doc, ext, doPrewarm=prewarm)
+    assert m is not None
+    b = na.Batch(0)
+    b.AddStreams(m, 3)
+    y = np.concatenate([b.Process(x[:, :65]), b.Process(x[:, 65:])], axis=1)
+    # the LDS-free kernel reports its four-streams-per-wave flavour where the library's threshold (NA_REC_QUAD_MIN; default 2049 streams)
+    # puts the three streams of a one-layer model of up to 16 units on it: the library says what its threshold is
+    lib = na.capi.load_library()
+    quad_min = lib.NA_DebugSetRecurrentQuadMin(0)
+    lib.NA_DebugSetRecurrentQuadMin(quad_min)
+    if want_name == "RecurrentDppKernel" and layers == 1 and hidden <= 16 and 0 < quad_min <= 3:
+        want_name = "RecurrentQuadKernel"
+    assert b.StreamKernelName(0) == want_name and b.StreamKernelName(2) == want_name, (b.StreamKernelName(0), b.StreamKernelName(2), want_name)
+    for s in range(3):
+        err = O.rms(y[s] - want[s])
+        print("%s stream %d: rms error %.3g, bound %.3g" % (want_name, s, err, RC.bound(want[s])))
+        assert err <= RC.bound(want[s]), (spec, s, err)
+
+
 @pytest.mark.parametrize("layers,hidden", [(1, 3), (1, 18), (3, 16), (2, 40), (2, 64), (1, 128), (2, 96), (3, 128)])
 def test_runtime_shaped_lstm_matches_oracle(na, loader, layers, hidden):
     """Hidden sizes / layer counts without a shaped kernel run on the runtime-shaped one (LSTMDynamic.h:95-108 accepts any); shapes
