@@ -189,6 +189,77 @@ NA_EXTERN int NA_BatchUnloadIR(NA_Batch* batch, int ir);
 NA_EXTERN int NA_BatchSetStreamIR(NA_Batch* batch, int stream, int ir, int fadeSamples); /* ir = -1: none (dry) */
 NA_EXTERN int NA_BatchGetStreamIR(NA_Batch* batch, int stream); /* the target: id, -1 dry, <= -2 bad id / not enabled */
 NA_EXTERN int NA_BatchStreamIRFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's IR fade; 0: none; < 0: stage not enabled / bad id */
+/* ---- the gate stage: a per-stream noise gate ----
+ * High-gain captures turn pickup hum into a loud hiss between notes.  A host of the reference gates that itself: it listens to the dry
+ * input and scales the amp's output, because it holds both buffers.  Here the rows stay on the device, and a gate needs both ends of a
+ * processing call -- the input rows before the models run and the output rows after them -- so it is a stage of the library: a third
+ * per-stream stage, off unless enabled.  A batch that enabled it and set no gate launches exactly what it launched before.
+ * Order of a processing call: the gate DETECTOR in front of everything -- it reads the input rows as the caller passed them (in a
+ * resampling batch: the external-rate rows; input and output rows may be the same memory) -- then the up kernel, the model launches
+ * and the down kernel as before, then the gate APPLY, the cabinet stage and the output stage.  The gate scales the amp's output in
+ * front of the cabinet, so the cabinet's tail rings out through a closing gate.  In a resampling batch the gain g[t] computed from
+ * input sample t multiplies output sample t of the caller's row: the audio lags the gain by latencySamples (NA_BatchGetResampleInfo),
+ * which acts as a small look-ahead; it is not compensated.
+ * Arithmetic.  All floating-point operations are separately rounded f32 operations in this order, with no FMA contraction (fl(.) is
+ * one rounding to f32, round to nearest even), so that a float32 restatement is bit-exact and the samples out do not depend on how
+ * the signal is cut into calls.
+ *   Constants of an entry: a = detectorCoeff in (0, 1]; Po = openPower >= Pc = closePower >= 0, thresholds as power; H = holdSamples;
+ *     A = attackSamples, R = releaseSamples; floor = floorGain in [0, 1], the gain of the closed gate.
+ *   Derived: span = fl(1 - floor), computed once on the host; U = 2^30; stepUp = ceil(U / A); stepDown = ceil(U / R).
+ *   State per stream: f32 p, integer hold, bit open, unsigned u in [0, U].
+ *   For each sample, in order, with x the input sample and y the row's sample after the models:
+ *     x' = (x is NaN) ? 0 : min(|x|, 1e18f)
+ *     s = fl(x' * x');  d = fl(s - p);  p = fl(p + fl(a * d))
+ *     if      p >= Po:  open = 1, hold = H
+ *     else if p <  Pc:  if hold > 0: hold -= 1  else: open = 0
+ *     (between the thresholds nothing changes)
+ *     u = open ? min(U, u + stepUp) : (u > stepDown ? u - stepDown : 0)
+ *     g = (u == U) ? 1.0f : fl(floor + fl(span * fl((float)u * 2^-30)))
+ *     y = fl(y * g)
+ *   (float)u is round-to-nearest-even.  u is an integer on purpose: a gate that has been open for A samples is at exactly g = 1 and
+ *   passes the row bit for bit, a closed gate with floor = 0 gives exact zeros, and the host can tell from sample counts alone when a
+ *   ramp has ended.
+ * NA_GateParamsFromDb is host arithmetic and needs no device: thresholds are dBFS of a sine's peak, so power = 10^(dB/10) / 2;
+ *   floorGain = 10^(floorDb/20), a floorDb of -inf gives 0; detectorCoeff = 1 - exp(-1 / (ms * rate / 1000)), computed in double and
+ *   rounded once; sample counts are max(1, round(ms * rate / 1000)), hold may be 0.  It refuses what the set call would refuse.
+ * NA_BatchEnableGateStage is the set-up side (allocates; idempotent): a state per row, a gain block of gainSamples floats per row
+ *   (a power of two >= 2048) and the stage's device + pinned tables; later NA_BatchAddStreams / NA_BatchReserveStreams grow them.  A
+ *   processing call longer than gainSamples grows the gain block first: that growth is not real-time safe -- the rule for the first
+ *   use of a longer buffer.  Every call below fails ("gate stage not enabled (NA_BatchEnableGateStage)") before it.
+ *   NA_BatchGetGateInfo reports gainSamples, the number of entries and the device memory the stage holds.
+ * NA_BatchSetStreamGate is REAL-TIME SAFE: host arithmetic on tables that exist.
+ *   The stream has no gate: the gate starts at the next sample, from p = 0, open = 1, hold = H, u = U (startOpen != 0) or from p = 0,
+ *     open = 0, hold = 0, u = 0 (startOpen == 0: for the `to` stream of a hand-over whose session is gated shut).
+ *   The stream has a gate: the new constants apply from the next sample; the state is kept, with hold = min(hold, H); startOpen is
+ *     ignored.
+ *   params == NULL takes the gate away, click-free: the entry stays with `open` forced to 1 (the follower and the hold counter go on)
+ *     and retires once attackSamples samples have been produced since the call; u == U by then, by construction.  A set call during
+ *     that tail re-arms the gate on the kept state.  On a stream without a gate it does nothing.
+ *   Every float must be finite; openPower >= closePower >= 0; floorGain in [0, 1]; detectorCoeff in (0, 1]; attackSamples and
+ *     releaseSamples in [1, 1 << 20]; holdSamples in [0, 1 << 24].  Each failure names the field.
+ * NA_BatchGetStreamGate returns 1 and fills *out with the constants in effect, 0 when the stream has no gate or one that is being taken
+ *   away, < 0 on a bad id or when the stage is not enabled.  NA_BatchStreamGateGain returns the g of the last sample produced (1 for a
+ *   stream without a gate, < 0 on a bad id); it reads the device state and synchronises the batch: a diagnostic like
+ *   NA_BatchStreamRangeEvents, not for the audio path.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a
+ * hand-over, drop the gate at once: a parked stream carries nothing over, and an activated stream has none.  Gates are not part of a
+ * NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves them alone.
+ * While an entry exists -- a stream with a gate, or one whose gate is being taken away -- a processing call behaves as it does with
+ * entries of the other stages: its launches run in order on one stream (no half-batch chains, no resident launch), host buffers go
+ * through the library's device staging block, and it enqueues one table upload from a ring of pinned tables plus two launches
+ * (detector, apply) over the gated streams only, whatever n: no device or pinned allocation, no stream or event creation, no unbounded
+ * wait.  With the last entry the free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; a side-chain input; gain-reduction meters that are
+ * safe to read from the audio thread. */
+typedef struct NA_GateParams { float openPower, closePower, floorGain, detectorCoeff; int attackSamples, holdSamples, releaseSamples; } NA_GateParams;
+typedef struct NA_GateInfo { int gainSamples, numGates; long long deviceBytes; } NA_GateInfo;
+NA_EXTERN int NA_GateParamsFromDb(int sampleRate, float openDb, float closeDb, float floorDb, float detectorMs, float attackMs, float holdMs, float releaseMs, NA_GateParams* out);
+NA_EXTERN int NA_BatchEnableGateStage(NA_Batch* batch);
+NA_EXTERN int NA_BatchGetGateInfo(NA_Batch* batch, NA_GateInfo* info);
+NA_EXTERN int NA_BatchSetStreamGate(NA_Batch* batch, int stream, const NA_GateParams* params, int startOpen); /* params = NULL: the gate goes, click-free */
+NA_EXTERN int NA_BatchGetStreamGate(NA_Batch* batch, int stream, NA_GateParams* out); /* 1: filled; 0: no gate; < 0: bad id / not enabled */
+NA_EXTERN float NA_BatchStreamGateGain(NA_Batch* batch, int stream); /* the g of the last sample produced; 1: no gate; < 0: bad id / not enabled */
 NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);
@@ -553,6 +624,8 @@ NA_EXTERN void NA_DebugSetTraceBuffer(void* deviceBuffer);
 NA_EXTERN int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
 /* Tests: launches of the cabinet stage's kernels so far (two per piece of a call with entries) */
 NA_EXTERN long long NA_DebugCabinetLaunches(void);
+/* Tests: launches of the gate stage's two kernels so far (two per processing call with entries) */
+NA_EXTERN long long NA_DebugGateLaunches(void);
 #endif /* NA_RELEASE */
 
 #ifdef __cplusplus

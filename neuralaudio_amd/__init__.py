@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -46,6 +46,32 @@ def db_to_gain(db):
     """Decibels as the linear gain Batch.SetStreamGain takes: 10 ** (db / 20), 0.0 at -inf (GetRecommendedOutputDBAdjustment is in dB)."""
     db = float(db)
     return 0.0 if db == float("-inf") else 10.0 ** (db / 20.0)
+
+
+GATE_FIELDS = ("openPower", "closePower", "floorGain", "detectorCoeff", "attackSamples", "holdSamples", "releaseSamples")
+
+
+def _gate_dict(p):
+    return {name: (float if name in GATE_FIELDS[:4] else int)(getattr(p, name)) for name in GATE_FIELDS}
+
+
+def _gate_params(d):
+    if isinstance(d, capi.NA_GateParams):
+        return d
+    p = capi.NA_GateParams()
+    for name in GATE_FIELDS:
+        setattr(p, name, d[name])
+    return p
+
+
+def gate_params_from_db(sample_rate, open_db, close_db, floor_db=float("-inf"), detector_ms=1.0, attack_ms=1.0, hold_ms=50.0, release_ms=100.0):
+    """The constants Batch.SetStreamGate takes, from decibels and milliseconds (NA_GateParamsFromDb): thresholds are dBFS of a sine's peak,
+    floor_db = -inf closes the gate to silence.  Host arithmetic: needs no device."""
+    out = capi.NA_GateParams()
+    if capi.load_library().NA_GateParamsFromDb(int(sample_rate), float(open_db), float(close_db), float(floor_db), float(detector_ms),
+                                               float(attack_ms), float(hold_ms), float(release_ms), C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _gate_dict(out)
 
 
 def rccl_available():
@@ -414,6 +440,39 @@ class Batch:
         if self._lib.NA_DebugRunCabinetStage(self._h, _fptr(rows), int(rows.shape[1]), n) != 0:
             raise NeuralAudioError(capi.last_error())
         return rows
+
+    # -- the gate stage: EnableGateStage is set-up side; SetStreamGate is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableGateStage(self):
+        if self._lib.NA_BatchEnableGateStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetGateInfo(self):
+        info = capi.NA_GateInfo()
+        if self._lib.NA_BatchGetGateInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_GateInfo._fields_}
+
+    def SetStreamGate(self, stream, params, startOpen=True):
+        """A noise gate on the stream from the next sample on: `params` a dict of the NA_GateParams fields (gate_params_from_db makes one
+        from decibels and milliseconds); None takes the gate away, click-free.  A stream that has a gate keeps its state."""
+        p = None if params is None else C.byref(_gate_params(params))
+        if self._lib.NA_BatchSetStreamGate(self._h, int(stream), p, 1 if startOpen else 0) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamGate(self, stream):
+        """The constants in effect as a dict; None: no gate (or one that is being taken away)."""
+        out = capi.NA_GateParams()
+        rc = int(self._lib.NA_BatchGetStreamGate(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _gate_dict(out) if rc else None
+
+    def StreamGateGain(self, stream):
+        """The gate's gain at the last sample produced (1 without a gate).  Synchronises the batch: a diagnostic."""
+        gain = float(self._lib.NA_BatchStreamGateGain(self._h, int(stream)))
+        if gain < 0:
+            raise NeuralAudioError(capi.last_error())
+        return gain
 
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:

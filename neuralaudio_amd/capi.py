@@ -42,6 +42,8 @@ NA_SYMBOLS = [
     "NA_BatchEnableOutputStage", "NA_BatchSetStreamGain", "NA_BatchGetStreamGain", "NA_BatchHandover", "NA_BatchHandoverRemaining",
     "NA_BatchEnableCabinetStage", "NA_BatchGetCabinetInfo", "NA_BatchLoadIR", "NA_BatchUnloadIR", "NA_BatchSetStreamIR", "NA_BatchGetStreamIR",
     "NA_BatchStreamIRFadeRemaining", "NA_DebugRunCabinetStage", "NA_DebugCabinetLaunches",
+    "NA_GateParamsFromDb", "NA_BatchEnableGateStage", "NA_BatchGetGateInfo", "NA_BatchSetStreamGate", "NA_BatchGetStreamGate",
+    "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
 ]
 
 
@@ -67,6 +69,15 @@ class NA_ResampleInfo(C.Structure):
 
 class NA_CabinetInfo(C.Structure):
     _fields_ = [("maxTaps", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numIRs", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+class NA_GateParams(C.Structure):
+    _fields_ = [("openPower", C.c_float), ("closePower", C.c_float), ("floorGain", C.c_float), ("detectorCoeff", C.c_float),
+                ("attackSamples", C.c_int), ("holdSamples", C.c_int), ("releaseSamples", C.c_int)]
+
+
+class NA_GateInfo(C.Structure):
+    _fields_ = [("gainSamples", C.c_int), ("numGates", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 _lib = None
@@ -171,6 +182,13 @@ def load_library():
         "NA_BatchStreamIRFadeRemaining": (C.c_int, [vp, C.c_int]),
         "NA_DebugRunCabinetStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
         "NA_DebugCabinetLaunches": (C.c_longlong, []),
+        "NA_GateParamsFromDb": (C.c_int, [C.c_int] + [C.c_float] * 7 + [C.POINTER(NA_GateParams)]),
+        "NA_BatchEnableGateStage": (C.c_int, [vp]),
+        "NA_BatchGetGateInfo": (C.c_int, [vp, C.POINTER(NA_GateInfo)]),
+        "NA_BatchSetStreamGate": (C.c_int, [vp, C.c_int, C.POINTER(NA_GateParams), C.c_int]),
+        "NA_BatchGetStreamGate": (C.c_int, [vp, C.c_int, C.POINTER(NA_GateParams)]),
+        "NA_BatchStreamGateGain": (C.c_float, [vp, C.c_int]),
+        "NA_DebugGateLaunches": (C.c_longlong, []),
         "NA_DebugRecurrentPlan": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "NA_DebugRecurrentShapePlan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
         "NA_DebugRecurrentKernel": (C.c_int, [C.c_int] * 9 + [C.c_char_p, C.c_int]),

@@ -631,6 +631,103 @@ int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long stride, size_
 long long NA_DebugCabinetLaunches(void) { return (long long)na::CabinetStageLaunches(); }
 #endif
 
+// ---- the gate stage (gpu_batch.h EnableGateStage / SetStreamGate) ----
+namespace
+{
+	void GateParamsIn(const NA_GateParams& p, na::GateParams& g)
+	{
+		g.openPower = p.openPower;
+		g.closePower = p.closePower;
+		g.floorGain = p.floorGain;
+		g.detectorCoeff = p.detectorCoeff;
+		g.attackSamples = p.attackSamples;
+		g.holdSamples = p.holdSamples;
+		g.releaseSamples = p.releaseSamples;
+	}
+	void GateParamsOut(const na::GateParams& g, NA_GateParams* p)
+	{
+		p->openPower = g.openPower;
+		p->closePower = g.closePower;
+		p->floorGain = g.floorGain;
+		p->detectorCoeff = g.detectorCoeff;
+		p->attackSamples = g.attackSamples;
+		p->holdSamples = g.holdSamples;
+		p->releaseSamples = g.releaseSamples;
+	}
+}
+
+int NA_GateParamsFromDb(int sampleRate, float openDb, float closeDb, float floorDb, float detectorMs, float attackMs, float holdMs, float releaseMs, NA_GateParams* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_GateParamsFromDb: bad argument");
+		na::GateParams g;
+		if (const char* why = na::GateParamsFromDb(sampleRate, openDb, closeDb, floorDb, detectorMs, attackMs, holdMs, releaseMs, g))
+			throw std::runtime_error(std::string("NA_GateParamsFromDb: ") + why);
+		GateParamsOut(g, out);
+	});
+}
+
+int NA_BatchEnableGateStage(NA_Batch* batch)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchEnableGateStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->EnableGateStage();
+	});
+}
+
+int NA_BatchGetGateInfo(NA_Batch* batch, NA_GateInfo* info)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchGetGateInfo: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		if (!info) throw std::runtime_error("NA_BatchGetGateInfo: bad argument");
+		const na::GateStageInfo i = batch->batch->GetGateInfo();
+		info->gainSamples = i.gainSamples;
+		info->numGates = i.numGates;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamGate(NA_Batch* batch, int stream, const NA_GateParams* params, int startOpen)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchSetStreamGate: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		if (!params)
+		{
+			batch->batch->SetStreamGate(stream, nullptr, false);
+			return;
+		}
+		na::GateParams g;
+		GateParamsIn(*params, g);
+		batch->batch->SetStreamGate(stream, &g, startOpen != 0);
+	});
+}
+
+int NA_BatchGetStreamGate(NA_Batch* batch, int stream, NA_GateParams* out)
+{
+	int has = 0;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchGetStreamGate: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		na::GateParams g;
+		has = batch->batch->GetStreamGate(stream, g) ? 1 : 0;
+		if (has && out) GateParamsOut(g, out);
+	});
+	return rc == 0 ? has : -1;
+}
+
+float NA_BatchStreamGateGain(NA_Batch* batch, int stream)
+{
+	float gain = -1.0f;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchStreamGateGain: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		gain = batch->batch->StreamGateGain(stream);
+	});
+	return rc == 0 ? gain : -1.0f;
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugGateLaunches(void) { return (long long)na::GateStageLaunches(); }
+#endif
+
 #ifndef NA_RELEASE
 long long NA_DebugDeviceResourceCalls(void) { return na::DeviceResourceCalls(); }
 #endif

@@ -145,6 +145,7 @@ namespace na
 			(void)residentState.release();
 			(void)resample.release();
 			(void)cabStage.release();
+			(void)gateStage.release();
 			for (WnLaunchTable& t : wnTable) t.entries.clear();
 			return;
 		}
@@ -335,6 +336,7 @@ namespace na
 		}
 		if (outStage) EnsureStageRows((int)streams.size());
 		if (cabStage) EnsureCabinetRows((int)streams.size());
+		if (gateStage) EnsureGateRows((int)streams.size());
 		return first;
 	}
 
@@ -619,13 +621,16 @@ namespace na
 		}
 	}
 
-	// One processing call on `launch`, and the one place that states its order: the up kernel, the model launches and the down kernel
-	// of a resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages once
-	// per call: behind everything the call has launched -- the join of the units, the graph replay, the down kernel -- on the same
-	// stream, outside any capture; every row is convolved with its own IR first, then scaled and cross-faded.
+	// One processing call on `launch`, and the one place that states its order: the gate detector in front of
+	// everything -- it reads the input rows as the caller passed them, which may be the output rows, so before any model writes --,
+	// the up kernel, the model launches and the down kernel of a resampling batch (ProcessResampledOn) or the model launches alone,
+	// then the per-stream stages once per call: behind everything the call has launched -- the join of the
+	// units, the graph replay, the down kernel -- on the same stream, outside any capture; every row is gated first, then convolved
+	// with its own IR (the cabinet's tail rings out through a closing gate), then scaled and cross-faded.
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{
+		if (gateStage && gateStage->book.HasEntries()) RunGateDetector(launch, dIn, n, inStride);
 		if (Resamples()) ProcessResampledOn(launch, dIn, dOut, n, inStride, outStride);
 		else LaunchModelsOn(launch, dIn, dOut, n, inStride, outStride);
 		RunStages(launch, dOut, n, outStride);
@@ -633,6 +638,7 @@ namespace na
 
 	void GpuBatch::RunStages(hipStream_t launch, float* dOut, size_t n, long outStride)
 	{
+		if (gateStage && gateStage->book.HasEntries()) RunGateApply(launch, dOut, n, outStride);
 		if (cabStage && cabStage->book.HasEntries()) RunCabinetStage(launch, dOut, n, outStride);
 		if (outStage && outStage->book.HasEntries()) RunOutputStage(launch, dOut, n, outStride);
 	}

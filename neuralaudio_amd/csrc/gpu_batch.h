@@ -19,6 +19,7 @@
 
 #include "cabinet_stage.h"
 #include "device_resources.h"
+#include "gate_stage.h"
 #include "launch_plan.h"
 #include "model_loader.h"
 #include "output_stage.h"
@@ -65,6 +66,12 @@ namespace na
 	struct CabinetStageInfo
 	{
 		int maxTaps = 0, ringSamples = 0, pieceSamples = 0, numIRs = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct GateStageInfo
+	{
+		int gainSamples = 0, numGates = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -144,6 +151,20 @@ namespace na
 		int StreamIRFadeRemaining(int stream) const;
 		// test hook (NA_DebugRunCabinetStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
 		void DebugRunCabinetStage(float* hostRows, long stride, size_t n);
+
+		// The gate stage (gate_stage.h): a per-stream noise gate that listens to the stream's input row and scales the row
+		// the models produced for it -- the detector launch in front of everything of the call, the apply launch first of the stages, in
+		// front of the cabinet.  EnableGateStage is the set-up side: a state and a gain row per row (CreateStreams grows them; a call
+		// longer than the gain rows grows those first, like any first use of a longer buffer) and the tables.  SetStreamGate is host
+		// arithmetic on those tables; while an entry exists -- a stream with a gate, or one whose gate is being taken away -- every
+		// processing call runs on the ordered path and enqueues ONE table upload and two launches, whatever n.  Without an entry the
+		// batch launches exactly what it launches without the stage.
+		void EnableGateStage();
+		bool HasGateStage() const { return gateStage != nullptr; }
+		GateStageInfo GetGateInfo() const;
+		void SetStreamGate(int stream, const GateParams* params, bool startOpen); // params == nullptr: the gate goes, click-free
+		bool GetStreamGate(int stream, GateParams& out) const;                    // false: no gate (or one that is being taken away)
+		float StreamGateGain(int stream); // the g of the last sample produced; synchronises the batch: a diagnostic
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -297,7 +318,7 @@ namespace na
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
 		struct OutputStage; // (gpu_batch_internal.h)
 		std::unique_ptr<OutputStage> outStage;
-		bool StageHasEntries() const; // of either stage
+		bool StageHasEntries() const; // of any stage
 		// the call runs ordered on ONE stream: up kernel -> model launches -> down kernel of a resampling batch, the stages behind the
 		// model launches (no half-batch chains, no resident launch)
 		bool RunsOrdered() const { return Resamples() || StageHasEntries(); }
@@ -311,6 +332,13 @@ namespace na
 		void EnsureCabinetRows(int rows); // set-up side: rings and tables for `rows` rows
 		void CabinetLeave(int stream);    // park / removal: dry at once, the history dropped
 		void RunCabinetStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + two launches per piece + the host mirror's advance
+		struct GateStage; // (gpu_batch_internal.h)
+		std::unique_ptr<GateStage> gateStage;
+		void EnsureGateRows(int rows);    // set-up side: states, gain rows and tables for `rows` rows
+		void EnsureGateSamples(size_t n); // gain rows of at least n samples (grows them: not real-time safe)
+		void GateLeave(int stream);       // park / removal: the gate goes at once
+		void RunGateDetector(hipStream_t launch, const float* dIn, size_t n, long inStride); // table upload + the detector launch
+		void RunGateApply(hipStream_t launch, float* dOut, size_t n, long outStride);        // the apply launch + the host mirror's advance
 		int AllocateIds(int count);
 		void DropTrailingRetiredRows();
 		// the kinds of the groups that have active streams once `leaving` has lost / `entering` has gained one, in group order (`active`:
@@ -438,10 +466,10 @@ namespace na
 		void LaunchHalves(const float* dIn, float* dOut, size_t n, long inStride, long outStride, hipEvent_t* done, bool hostRows);
 		void JoinHalves(); // the half-batch chains are done (host-side wait); the next launches go to the batch stream again
 		hipEvent_t marks[1 + kMaxChains][2] = {};
-		// One processing call on `launch`, the one place that states its order (gpu_batch.cpp): ProcessResampledOn or LaunchModelsOn,
-		// then RunStages
+		// One processing call on `launch`, the one place that states its order (gpu_batch.cpp): the gate detector, ProcessResampledOn or
+		// LaunchModelsOn, then RunStages
 		void ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
-		void RunStages(hipStream_t launch, float* dOut, size_t n, long outStride); // the stages with entries: cabinet, then output
+		void RunStages(hipStream_t launch, float* dOut, size_t n, long outStride); // the stages with entries: gate apply, cabinet, then output
 		// the model launches of a call, and their parts (gpu_batch.cpp)
 		struct ModelCall; // (gpu_batch_internal.h)
 		void LaunchModelsOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);

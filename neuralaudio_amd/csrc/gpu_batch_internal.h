@@ -189,5 +189,23 @@ namespace na
 	};
 	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece
 
+	// the gate stage of a batch (gate_stage.h): the host mirror, the rows' states and gain rows on the device, the ring of
+	// entry tables, and -- between the detector and the apply launch of one call -- the table that call runs on
+	struct GpuBatch::GateStage
+	{
+		static constexpr const char* kNotEnabled = "gate stage not enabled (NA_BatchEnableGateStage)";
+		GateBook book;
+		float* state = nullptr;           // [rowCapacity] GateState
+		float* gains = nullptr;           // [rowCapacity][gainSamples]
+		int rowCapacity = 0;
+		int gainSamples = kGateMinGainSamples; // a power of two
+		StageTables<GateEntry> tables{ "gate stage: table in flight" };
+		const GateEntry* dev = nullptr;   // the device table the detector of this call read ...
+		int count = 0;                    // ... and its entries; 0: the call has none
+		~GateStage();
+	};
+	hipError_t LaunchGateDetect(const GateDetectLaunch& L, hipStream_t stream); // (gate_stage_kernels.hip)
+	hipError_t LaunchGateApply(const GateApplyLaunch& L, hipStream_t stream);
+
 	bool HostDirect(); // (gpu_batch_host.cpp) the kernels read / write pinned host blocks themselves instead of the copy engines
 }

@@ -21,7 +21,11 @@ namespace na
 		outStage->tables.Ensure(*this, std::max(rows, 16));
 	}
 
-	bool GpuBatch::StageHasEntries() const { return (outStage && outStage->book.HasEntries()) || (cabStage && cabStage->book.HasEntries()); }
+	bool GpuBatch::StageHasEntries() const
+	{
+		return (outStage && outStage->book.HasEntries()) || (cabStage && cabStage->book.HasEntries()) ||
+			(gateStage && gateStage->book.HasEntries());
+	}
 
 	void GpuBatch::RequireRow(int s, const char* who) const
 	{
@@ -82,6 +86,7 @@ namespace na
 	// at its own gain -- and its own gain is 1 again: a parked stream carries nothing over.
 	void GpuBatch::StageLeave(int s)
 	{
+		GateLeave(s);
 		CabinetLeave(s);
 		if (!outStage || s >= outStage->book.Rows()) return;
 		OutputStageBook& book = outStage->book;

@@ -15,6 +15,9 @@
 //       the click-free model switch on a batch that never stops (RunHandover below): every K-th buffer one of 16 sessions is handed over
 //       (NA_BatchHandover) to a parked stream of the other model (--mix), with one model to a second stream of it.
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --cab TAPS [--cab-irs M=1]
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --gate K
+//       the plain run below with the gate stage enabled and noise gates on the first K streams (K = 0: enabled, no gate set: must cost
+//       nothing); adds the device span per buffer of the pipelined loop between the library's event marks.
 //       the cabinet stage on a batch that never stops (RunCabinet below): M impulse responses of TAPS taps spread over the streams.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
@@ -565,13 +568,13 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
-	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1;
+	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1;
 	bool churnLegacy = false;
 	for (int i = 1; i < argc; i++)
 	{
@@ -586,6 +589,7 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--fade") && i + 1 < argc) fade = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--cab") && i + 1 < argc) cab = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--cab-irs") && i + 1 < argc) cabIRs = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) gate = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
 			// rehearsal on a one-GPU box: the multi-GPU host bound to the library's loopback RCCL table (test build only), so that
@@ -651,6 +655,14 @@ int main(int argc, char** argv)
 	NA_Batch* batch = NA_BatchCreate(0, nullptr);
 	CHECK(batch != nullptr);
 	CHECK(NA_BatchAddStreams(batch, model, 1.0f, streams, 1) >= 0);
+	if (gate >= 0)
+	{
+		// thresholds around the input's level (+-0.125, a power of ~5e-3), so that the gates open and close on the signal itself
+		CHECK(NA_BatchEnableGateStage(batch) == 0);
+		NA_GateParams gp;
+		CHECK(NA_GateParamsFromDb(48000, -20.0f, -26.0f, -60.0f, 1.0f, 1.0f, 5.0f, 20.0f, &gp) == 0);
+		for (int s = 0; s < std::min(gate, streams); s++) CHECK(NA_BatchSetStreamGate(batch, s, &gp, 1) == 0);
+	}
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -698,9 +710,10 @@ int main(int argc, char** argv)
 	}
 	std::sort(latInPlace.begin(), latInPlace.end());
 
-	// copying entry points, two buffers in flight
+	// copying entry points, two buffers in flight (between the library's event marks: the device's span of the same loop)
 	int pending = NA_BatchSubmit(batch, in.data(), (size_t)frames);
 	CHECK(pending >= 0);
+	if (gate >= 0) CHECK(NA_BatchMarkTime(batch, 0) == 0);
 	double t0 = Now();
 	for (int i = 0; i < buffers; i++)
 	{
@@ -711,6 +724,12 @@ int main(int argc, char** argv)
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
+	double usMarked = 0.0; // (--gate only: the plain run stays what it was)
+	if (gate >= 0)
+	{
+		CHECK(NA_BatchMarkTime(batch, 1) == 0);
+		usMarked = (double)NA_BatchElapsedMs(batch) * 1e3 / buffers;
+	}
 
 	// zero-copy entry points: the host writes the next input in place and reads the result in place (here: one pass over each);
 	// `depth` buffers in flight (the engine has 3 slots)
@@ -748,9 +767,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
