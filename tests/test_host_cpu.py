@@ -20,6 +20,7 @@ import na_oracle as O
 import ref_np
 import frame_cases as FC
 import recurrent_cases as RC
+import split_cases as SC
 import wide_cases as WC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1124,3 +1125,124 @@ def test_frame_kernel_lds_limit_is_decided_at_load(na, tmp_path):
     # the limit follows the width: a second array of 4 channels may use a kernel size no 16-channel array may
     arrays = FC.chain([16, 4], [([2], [1]), ([71], [1])], O.ACT_TANH)
     assert loader.CreateFromString(O.nam_json_wavenet_generic(arrays, O.synth_wavenet_weights(arrays, seed=3)), ".nam", doPrewarm=False) is not None
+
+
+# ---- the f16-split interpreter's test shapes (tests/split_cases.py, run by tests/test_gpu_split.py) --------------------------------------
+
+def _split_cases():
+    return SC.named_cases(), [SC.fuzz_case(seed) for seed in range(SC.NUM_FUZZ_SEEDS)], SC.batch_models()
+
+
+def test_every_split_case_loads_and_is_predicted_on_the_split_kernel_in_the_layout_it_claims(na):
+    """tests/test_gpu_split.py runs every case without a skip and asserts kernel name and pack factor before it trusts a comparison, so
+    every generated shape must load and land on the f16-split kernels by default, at one stream and at 600, with the pack factor it
+    claims, a proven range, weights that fit the operand format, a finite input limit above the +-1 the signals are clipped to, and the
+    receptive field its layers add up to.  NA_ModelKernelInfo does not name the layout: the claim is split_cases.layout_of, the Python
+    restatement of the plan's rule, and what the library adds is that such a model runs on the split kernels at all -- a model that
+    neither fills its lane modes nor is padded or packed has no fast plan and runs on the frame kernel.  The decision edges next to the
+    table land there."""
+    loader = na.NeuralModelLoader()
+    named, fuzz, batch = _split_cases()
+    every = named + [c for c, _ in fuzz] + batch
+    names = [c["name"] for c in every]
+    assert len(set(names)) == len(names)
+    for case in every:
+        arrays = case["arrays"]
+        assert max(max(a["channels"], a["head_size"], a["input_size"]) for a in arrays) <= 16 and 1 <= len(arrays) <= 3, case["name"]
+        assert all(1 <= len(a["kernel_sizes"]) <= (4 if case["name"] != "rings-63" else 63) for a in arrays), case["name"]
+        assert case["layout"] in ("plain", "padded", "packed") and (case["pack"] > 1) == (case["layout"] == "packed"), case["name"]
+        m = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, SC.weights(case)), ".nam", doPrewarm=False)
+        assert m is not None, case["name"]
+        for streams in (1, 600):
+            info = m.KernelInfo(1.0, streams)
+            assert info["kernel"] == "f16-split" and info["pack"] == case["pack"] and info["range_proven"] and info["weights_ok"], (case["name"], streams, info)
+            assert 1.0 < info["input_limit"] < float("inf"), (case["name"], info)
+        assert m.GetReceptiveFieldSize() == SC.receptive_field(arrays), case["name"]
+        assert SC.work(arrays, case["samples"]) <= SC.WORK_CAP, case["name"]
+        assert SC.num_rings(arrays) <= SC.MAX_SPLIT_RINGS, case["name"]
+        firsts = [(d, i == 0) for a in arrays for i, d in enumerate(a["dilations"])]
+        assert case["samples"] >= 2 * max(SC.ring_frames(d, f) for d, f in firsts), case["name"]  # every ring wraps at least twice
+    for case, sizes in fuzz:
+        assert sizes[:3] == [1, 1, 17] and sum(sizes) == SC.SAMPLES == case["samples"], case["name"]
+        assert set(sizes) & {31, 63, 64, 65, 127, 128} and max(sizes) > SC.BLOCK, (case["name"], sizes)
+    by_name = {c["name"]: c for c in named}
+    assert by_name["padded-13-8"]["layout"] == "padded" and by_name["packed4-4-2"]["dense"] and not by_name["packed4-4-4"]["dense"]
+    assert SC.num_rings(by_name["rings-63"]["arrays"]) == 63
+    edges = SC.decision_edges()
+    assert {n for n, _, _ in edges} >= {"16-4", "12-4", "rings-64", "k2", "padded-last-head-2", "packed-last-head-2"}
+    for name, arrays, seed in edges:
+        m = loader.CreateFromString(O.nam_json_wavenet_generic(arrays, O.synth_wavenet_weights(arrays, seed=seed)), ".nam", doPrewarm=False)
+        assert m is not None, name
+        for streams in (1, 600):
+            info = m.KernelInfo(1.0, streams)
+            assert info["kernel"] == "frame" and info["pack"] == 1 and info["input_limit"] == float("inf"), (name, streams, info)
+        assert m.KernelInfo(1.0, 1)["range_proven"] == (not name.startswith("leaky")), name
+
+
+def test_split_cases_reach_every_path_of_the_interpreter_they_name():
+    """The named cases alone -- and the seeded draw once more -- reach: every layout; pack factors 1, 2 and 4, dense and not; kernel-level
+    channel groups 2 and 4 and single-group real streams inside a pack; one, two and three arrays; models whose rings are all compact,
+    none compact, and mixed; exact and roomy long rings; tap shifts on both sides of 16, 32, 64 and 128 frames; both activations; a
+    first array with and without head bias."""
+    named, fuzz, _ = _split_cases()
+
+    def reach(cases):
+        r = dict(layouts=set(), packs=set(), G=set(), real_g=set(), arrays=set(), rings=set(), kinds=set(), shifts=set(), acts=set(), bias0=set())
+        for c in cases:
+            arrays = c["arrays"]
+            r["layouts"].add(c["layout"])
+            r["packs"].add((c["pack"], c["dense"]))
+            r["G"].update(SC.kernel_groups(arrays))
+            if c["pack"] > 1:
+                r["real_g"].update((a["channels"] + 3) // 4 for a in arrays)
+            r["arrays"].add(len(arrays))
+            kinds = {SC.ring_kind(d, i == 0) for a in arrays for i, d in enumerate(a["dilations"])}
+            r["kinds"].update(kinds)
+            r["rings"].add("compact" if kinds == {"compact"} else ("mixed" if "compact" in kinds else "long"))
+            r["shifts"].update(SC.shifts(arrays))
+            r["acts"].update(a["activation"] for a in arrays)
+            if len(arrays) > 1:
+                r["bias0"].add(bool(arrays[0]["has_head_bias"]))
+        return r
+
+    for what, r in (("named", reach(named)), ("fuzz", reach([c for c, _ in fuzz]))):
+        assert r["layouts"] == {"plain", "padded", "packed"} and r["packs"] == {(1, False), (2, False), (4, False), (4, True)}, (what, r)
+        assert r["G"] == {2, 4} and 1 in r["real_g"] and r["arrays"] == {1, 2, 3}, (what, r)
+        assert r["rings"] == {"compact", "mixed", "long"} and r["kinds"] == {"compact", "roomy", "exact"}, (what, r)
+        assert r["acts"] == {O.ACT_TANH, O.ACT_LEAKYRELU} and r["bias0"] == {True, False}, (what, r)
+        for edge in SC.EDGES:
+            assert any(edge // 2 <= s < edge for s in r["shifts"]) and edge in r["shifts"] and any(edge < s <= edge + edge // 2 for s in r["shifts"]), (what, edge, r["shifts"])
+    shift = [c for c in named if c["family"] == "tap shifts"]
+    for pick in ({"plain"}, {"packed"}):  # every dilation of the list at kernel G = 4 and 2 (plain 16 / 8, P = 2) and at one real group (P = 4)
+        for p in (1, 2, 4):
+            got = {d for c in shift if c["layout"] in pick and c["pack"] == p for a in c["arrays"] for d in a["dilations"]}
+            assert not got or got == set(SC.DILATIONS), (pick, p, got)
+    assert {(c["layout"], c["pack"]) for c in shift} == {("plain", 1), ("packed", 2), ("packed", 4)}
+    # the layouts and widths the issue names
+    widths = {tuple(a["channels"] for a in c["arrays"]): c["layout"] for c in named if c["family"] == "widths"}
+    for cs in [(16, 8), (16, 16), (16,), (16, 8, 8)]:
+        assert widths[cs] == "plain", cs
+    for cs in [(13, 8), (12, 6), (13, 5), (9, 7), (16, 5), (10,), (6, 16)]:
+        assert widths[cs] == "padded", cs
+    for cs in [(8, 4), (7, 3), (5, 5), (8,), (6, 8), (8, 1), (8, 4, 2), (4, 2), (4, 4), (4, 3), (3, 1), (2, 2), (2, 4), (1,)]:
+        assert widths[cs] == "packed", cs
+    assert {c["layout"] for c in named if c["family"] == "activation"} == {"plain", "padded", "packed"}
+
+
+@pytest.mark.parametrize("part", range(4))
+def test_split_cases_are_well_conditioned(part):
+    """Keeps the GPU parity rule honest without a GPU: for every case the f32 oracle's worst 32-frame window stays within 1 / 16 of
+    the GPU bound -- 1.25e-7 RMS relative to the level above 1 -- of a float64 evaluation.  The project states the split arithmetic at
+    no more than 8 times the f32 oracle's error, so a correct kernel stays under the bound on every case here.  A case that fails gets
+    another seed, never a looser bound."""
+    named, fuzz, batch = _split_cases()
+    every = named + [c for c, _ in fuzz] + batch
+    for case in every[part::4]:
+        w = SC.weights(case)
+        x = O.signal_noise(case["samples"], seed=case["seed"])
+        yo = O.OracleWaveNet(case["arrays"], w).process(x)
+        y64, _ = ref_np.wavenet_forward(case["arrays"], w, x)
+        assert O.rms(y64) > 1e-5, (case["name"], O.rms(y64))
+        for a in range(0, x.size, 32):
+            err, level = O.rms(yo[a:a + 32] - y64[a:a + 32]), O.rms(y64[a:a + 32])
+            assert err <= 1.25e-7 * max(1.0, level), (case["name"], a, err, level)
