@@ -260,6 +260,67 @@ NA_EXTERN int NA_BatchGetGateInfo(NA_Batch* batch, NA_GateInfo* info);
 NA_EXTERN int NA_BatchSetStreamGate(NA_Batch* batch, int stream, const NA_GateParams* params, int startOpen); /* params = NULL: the gate goes, click-free */
 NA_EXTERN int NA_BatchGetStreamGate(NA_Batch* batch, int stream, NA_GateParams* out); /* 1: filled; 0: no gate; < 0: bad id / not enabled */
 NA_EXTERN float NA_BatchStreamGateGain(NA_Batch* batch, int stream); /* the g of the last sample produced; 1: no gate; < 0: bad id / not enabled */
+/* ---- the EQ stage: a per-stream tone stack ----
+ * Between the amp and the cabinet a session has its tone stack: bass, mid and treble shelves and peaks, usually with a high-pass and a
+ * low-pass around them.  A host of the reference runs a few biquads on the buffer it holds.  Here the rows stay on the device between
+ * the model launches and the cabinet stage, so the EQ is a stage of the library: a fourth per-stream stage, off unless enabled -- a
+ * cascade of up to NA_EQ_MAX_SECTIONS biquad sections per stream, applied to the row the models produced BEHIND the gate's apply and IN
+ * FRONT OF the cabinet stage.  A session's chain is model -> gate -> EQ -> cabinet -> output gain.  In a resampling batch the stage
+ * acts on the external-rate rows, behind the down kernel, as the cabinet does: coefficients are designed at the rate the caller sees.
+ * A batch that enabled the stage and gave no stream an EQ launches exactly what it launched before.
+ * Arithmetic.  Every floating-point operation below is one separately rounded IEEE operation (fl(.): f64, fl32(.): f32, round to
+ * nearest even) with no FMA contraction; f64 and f32 subnormals are kept.  A restatement in double is therefore bit-exact, and the
+ * samples out do not depend on how the signal is cut into calls, on alignment, on stride, on the other streams or on the sample's
+ * index in a call.
+ *   Input: the sample is sanitised in f32, then widened exactly:
+ *     x' = isnan(x) ? 0 : clamp(x, +-1e18f);  v0 = (double)x'
+ *   Section i of a cascade keeps four doubles x1, x2, y1, y2 (direct form I).  Per sample, for sections 0 .. S-1 in order:
+ *     acc = fl(b0*v); acc = fl(acc + fl(b1*x1)); acc = fl(acc + fl(b2*x2));
+ *     acc = fl(acc - fl(a1*y1)); acc = fl(acc - fl(a2*y2));
+ *     x2 = x1; x1 = v; y2 = y1; y1 = acc; v = acc
+ *   Output: o = (float)v, rounded to nearest even once.  A cascade of 0 sections is the identity on x'.
+ * NA_EqSectionFromDesign is host arithmetic and needs no device: the RBJ cookbook in double, Q form -- w0 = 2 pi f / Fs,
+ *   alpha = sin(w0) / (2 Q), A = 10^(dB / 40), divided through by a0.  kind: 0 low-pass, 1 high-pass, 2 low shelf, 3 high shelf,
+ *   4 peaking; gainDb matters for the shelves and the peak only.  It refuses a non-finite argument, freqHz outside (0, Fs / 2), q <= 0,
+ *   an unknown kind, and anything the set call would refuse.
+ * NA_BatchEnableEqStage is the set-up side (allocates; idempotent): two slots of coefficients and section states per row and the
+ *   stage's device + pinned tables; later NA_BatchAddStreams / NA_BatchReserveStreams grow them.  Every call below fails ("eq stage not
+ *   enabled (NA_BatchEnableEqStage)") before it.  NA_BatchGetEqInfo reports NA_EQ_MAX_SECTIONS, the number of entries and the device
+ *   memory the stage holds.
+ * NA_BatchSetStreamEq is REAL-TIME SAFE: host arithmetic on tables that exist.  At a moment when the stream runs cascade A (flat if it
+ *   has none) it switches to a new cascade B over N = fadeSamples samples.  B starts from A's state: for i < min(S_A, S_B) section i
+ *   of B copies the four values of section i of A; the other sections start at zero; a stream with no entry has an all-zero history.
+ *   The k-th sample after the call is fl32(fl32(fl32(1 - w) * o_A) + fl32(w * o_B)) with w = (min(k, N-1) + 1) / N, the weight the
+ *   other stages use; for w == 1 the sample is o_B itself.  N = 0 means B from k = 0: the classic coefficient change on kept state,
+ *   with no doubled work.  During a fade both cascades run on the same input; after it A is dropped.  numSections = 0 (sections may
+ *   be NULL) is the flat cascade: once it is the stream's only cascade the entry retires with its state.  The coefficients travel to
+ *   the device once, with the first processing call after the set call; there is no coefficient interpolation.
+ * NA_BatchGetStreamEq returns the section count of the target cascade and fills out[0 .. min(count, capacity)); < 0 on a bad id or when
+ *   the stage is not enabled.  NA_BatchStreamEqFadeRemaining returns the samples left of the stream's EQ fade, 0 without one.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ *   fails with "... is parked"); numSections must lie in [0, 8]; every coefficient must be finite; every section must be stable,
+ *   |a2| < 1 and |a1| < 1 + a2 (the message names the section index); fadeSamples must lie in [0, 1 << 20]; a set call while an EQ
+ *   fade of that stream is running is refused; a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the
+ *   park that ends a hand-over, make the stream flat at once and drop its state: an activated stream is flat.  The EQ is not part of a
+ *   NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves it alone.
+ * The position k is kept per entry and advanced by whole calls.  While an entry exists -- a stream with a cascade, or one that fades
+ * to flat -- a processing call behaves as it does with entries of the other stages: its launches run in order on one stream (no
+ * half-batch chains, no resident launch), host buffers go through the library's device staging block, and it enqueues one table upload
+ * from a ring of pinned tables plus ONE launch over the streams with an entry only, whatever n: no device or pinned allocation, no
+ * stream or event creation, no unbounded wait.  The upload holds one small entry per stream with an entry and the coefficients of
+ * the set calls since the last processing call -- not entries x sections.  With the last entry the free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches; the stage on the one-stream NeuralModel; more than 8 sections; coefficient
+ * interpolation. */
+#define NA_EQ_MAX_SECTIONS 8
+typedef struct NA_EqSection { double b0, b1, b2, a1, a2; } NA_EqSection;   /* normalised, a0 == 1 */
+typedef struct NA_EqInfo { int maxSections, numEntries; long long deviceBytes; } NA_EqInfo;
+/* host arithmetic, no device.  kind: 0 low-pass, 1 high-pass, 2 low shelf, 3 high shelf, 4 peaking (RBJ cookbook, Q form) */
+NA_EXTERN int NA_EqSectionFromDesign(int kind, double sampleRate, double freqHz, double q, double gainDb, NA_EqSection* out);
+NA_EXTERN int NA_BatchEnableEqStage(NA_Batch* batch);                       /* set-up side, allocates, idempotent */
+NA_EXTERN int NA_BatchGetEqInfo(NA_Batch* batch, NA_EqInfo* info);
+NA_EXTERN int NA_BatchSetStreamEq(NA_Batch* batch, int stream, const NA_EqSection* sections, int numSections, int fadeSamples); /* 0 sections / NULL: flat */
+NA_EXTERN int NA_BatchGetStreamEq(NA_Batch* batch, int stream, NA_EqSection* out, int capacity);   /* section count of the target; <0 bad id / not enabled */
+NA_EXTERN int NA_BatchStreamEqFadeRemaining(NA_Batch* batch, int stream);
 NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);
@@ -626,6 +687,10 @@ NA_EXTERN int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long str
 NA_EXTERN long long NA_DebugCabinetLaunches(void);
 /* Tests: launches of the gate stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugGateLaunches(void);
+/* Tests: launches of the EQ stage's kernel so far (one per processing call with entries) */
+NA_EXTERN long long NA_DebugEqLaunches(void);
+/* Tests: as NA_DebugRunCabinetStage, for the EQ stage: the stage alone on given rows -- table, launch, book advance */
+NA_EXTERN int NA_DebugRunEqStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
 #endif /* NA_RELEASE */
 
 #ifdef __cplusplus

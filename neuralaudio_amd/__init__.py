@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "eq_section"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -72,6 +72,34 @@ def gate_params_from_db(sample_rate, open_db, close_db, floor_db=float("-inf"), 
                                                float(attack_ms), float(hold_ms), float(release_ms), C.byref(out)) != 0:
         raise NeuralAudioError(capi.last_error())
     return _gate_dict(out)
+
+
+EQ_FIELDS = ("b0", "b1", "b2", "a1", "a2")
+EQ_KINDS = {"lowpass": 0, "highpass": 1, "lowshelf": 2, "highshelf": 3, "peaking": 4}
+
+
+def _eq_dict(s):
+    return {name: float(getattr(s, name)) for name in EQ_FIELDS}
+
+
+def _eq_section(d):
+    if isinstance(d, capi.NA_EqSection):
+        return d
+    s = capi.NA_EqSection()
+    for name in EQ_FIELDS:
+        setattr(s, name, d[name])
+    return s
+
+
+def eq_section(kind, sample_rate, freq_hz, q=0.7071067811865476, gain_db=0.0):
+    """One biquad section for Batch.SetStreamEq from a design (NA_EqSectionFromDesign, the RBJ cookbook in double): kind 0 / "lowpass",
+    1 / "highpass", 2 / "lowshelf", 3 / "highshelf", 4 / "peaking"; gain_db matters for the shelves and the peak.  Host arithmetic: needs
+    no device."""
+    out = capi.NA_EqSection()
+    kind = EQ_KINDS[kind] if isinstance(kind, str) else int(kind)
+    if capi.load_library().NA_EqSectionFromDesign(kind, float(sample_rate), float(freq_hz), float(q), float(gain_db), C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _eq_dict(out)
 
 
 def rccl_available():
@@ -473,6 +501,48 @@ class Batch:
         if gain < 0:
             raise NeuralAudioError(capi.last_error())
         return gain
+
+    # -- the EQ stage: EnableEqStage is set-up side; SetStreamEq is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableEqStage(self):
+        if self._lib.NA_BatchEnableEqStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetEqInfo(self):
+        info = capi.NA_EqInfo()
+        if self._lib.NA_BatchGetEqInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_EqInfo._fields_}
+
+    def SetStreamEq(self, stream, sections, fadeSamples=0):
+        """A cascade of up to 8 biquad sections on the stream from the next sample on, faded in over fadeSamples samples: `sections` a
+        list of dicts of the NA_EqSection fields (eq_section designs one); None or an empty list is the flat cascade.  The new cascade
+        starts from the state of the one the stream has."""
+        sections = [] if sections is None else list(sections)
+        arr = (capi.NA_EqSection * max(len(sections), 1))(*[_eq_section(s) for s in sections])
+        if self._lib.NA_BatchSetStreamEq(self._h, int(stream), arr if sections else None, len(sections), int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamEq(self, stream):
+        """The sections of the target cascade as a list of dicts; an empty list: flat."""
+        out = (capi.NA_EqSection * capi.NA_EQ_MAX_SECTIONS)()
+        count = int(self._lib.NA_BatchGetStreamEq(self._h, int(stream), out, capi.NA_EQ_MAX_SECTIONS))
+        if count < 0:
+            raise NeuralAudioError(capi.last_error())
+        return [_eq_dict(out[i]) for i in range(count)]
+
+    def StreamEqFadeRemaining(self, stream):
+        left = int(self._lib.NA_BatchStreamEqFadeRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
+
+    def DebugRunEqStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunEqStage)."""
+        assert rows.dtype == np.float32 and rows.flags["C_CONTIGUOUS"] and rows.ndim == 2 and rows.shape[0] == self.NumStreams()
+        n = rows.shape[1] if n is None else int(n)
+        if self._lib.NA_DebugRunEqStage(self._h, _fptr(rows), int(rows.shape[1]), n) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return rows
 
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:

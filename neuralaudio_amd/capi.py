@@ -44,6 +44,8 @@ NA_SYMBOLS = [
     "NA_BatchStreamIRFadeRemaining", "NA_DebugRunCabinetStage", "NA_DebugCabinetLaunches",
     "NA_GateParamsFromDb", "NA_BatchEnableGateStage", "NA_BatchGetGateInfo", "NA_BatchSetStreamGate", "NA_BatchGetStreamGate",
     "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
+    "NA_EqSectionFromDesign", "NA_BatchEnableEqStage", "NA_BatchGetEqInfo", "NA_BatchSetStreamEq", "NA_BatchGetStreamEq",
+    "NA_BatchStreamEqFadeRemaining", "NA_DebugEqLaunches", "NA_DebugRunEqStage",
 ]
 
 
@@ -78,6 +80,17 @@ class NA_GateParams(C.Structure):
 
 class NA_GateInfo(C.Structure):
     _fields_ = [("gainSamples", C.c_int), ("numGates", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+NA_EQ_MAX_SECTIONS = 8
+
+
+class NA_EqSection(C.Structure):
+    _fields_ = [("b0", C.c_double), ("b1", C.c_double), ("b2", C.c_double), ("a1", C.c_double), ("a2", C.c_double)]
+
+
+class NA_EqInfo(C.Structure):
+    _fields_ = [("maxSections", C.c_int), ("numEntries", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 _lib = None
@@ -189,6 +202,14 @@ def load_library():
         "NA_BatchGetStreamGate": (C.c_int, [vp, C.c_int, C.POINTER(NA_GateParams)]),
         "NA_BatchStreamGateGain": (C.c_float, [vp, C.c_int]),
         "NA_DebugGateLaunches": (C.c_longlong, []),
+        "NA_EqSectionFromDesign": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.POINTER(NA_EqSection)]),
+        "NA_BatchEnableEqStage": (C.c_int, [vp]),
+        "NA_BatchGetEqInfo": (C.c_int, [vp, C.POINTER(NA_EqInfo)]),
+        "NA_BatchSetStreamEq": (C.c_int, [vp, C.c_int, C.POINTER(NA_EqSection), C.c_int, C.c_int]),
+        "NA_BatchGetStreamEq": (C.c_int, [vp, C.c_int, C.POINTER(NA_EqSection), C.c_int]),
+        "NA_BatchStreamEqFadeRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_DebugEqLaunches": (C.c_longlong, []),
+        "NA_DebugRunEqStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
         "NA_DebugRecurrentPlan": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "NA_DebugRecurrentShapePlan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
         "NA_DebugRecurrentKernel": (C.c_int, [C.c_int] * 9 + [C.c_char_p, C.c_int]),

@@ -728,6 +728,103 @@ float NA_BatchStreamGateGain(NA_Batch* batch, int stream)
 long long NA_DebugGateLaunches(void) { return (long long)na::GateStageLaunches(); }
 #endif
 
+// ---- the EQ stage (gpu_batch.h EnableEqStage / SetStreamEq) ----
+static_assert(sizeof(NA_EqSection) == sizeof(na::EqSection) && NA_EQ_MAX_SECTIONS == na::kEqMaxSections, "NA_EqSection is na::EqSection");
+namespace
+{
+	void EqSectionIn(const NA_EqSection& p, na::EqSection& s)
+	{
+		s.b0 = p.b0;
+		s.b1 = p.b1;
+		s.b2 = p.b2;
+		s.a1 = p.a1;
+		s.a2 = p.a2;
+	}
+	void EqSectionOut(const na::EqSection& s, NA_EqSection* p)
+	{
+		p->b0 = s.b0;
+		p->b1 = s.b1;
+		p->b2 = s.b2;
+		p->a1 = s.a1;
+		p->a2 = s.a2;
+	}
+}
+
+int NA_EqSectionFromDesign(int kind, double sampleRate, double freqHz, double q, double gainDb, NA_EqSection* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_EqSectionFromDesign: bad argument");
+		na::EqSection s;
+		if (const char* why = na::EqSectionFromDesign(kind, sampleRate, freqHz, q, gainDb, s)) throw std::runtime_error(std::string("NA_EqSectionFromDesign: ") + why);
+		EqSectionOut(s, out);
+	});
+}
+
+int NA_BatchEnableEqStage(NA_Batch* batch)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchEnableEqStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		batch->batch->EnableEqStage();
+	});
+}
+
+int NA_BatchGetEqInfo(NA_Batch* batch, NA_EqInfo* info)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchGetEqInfo: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		if (!info) throw std::runtime_error("NA_BatchGetEqInfo: bad argument");
+		const na::EqStageInfo i = batch->batch->GetEqInfo();
+		info->maxSections = i.maxSections;
+		info->numEntries = i.numEntries;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamEq(NA_Batch* batch, int stream, const NA_EqSection* sections, int numSections, int fadeSamples)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchSetStreamEq: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		na::EqSection s[na::kEqMaxSections];
+		if (sections)
+			for (int i = 0; i < std::min(std::max(numSections, 0), na::kEqMaxSections); i++) EqSectionIn(sections[i], s[i]);
+		batch->batch->SetStreamEq(stream, sections ? s : nullptr, numSections, fadeSamples);
+	});
+}
+
+int NA_BatchGetStreamEq(NA_Batch* batch, int stream, NA_EqSection* out, int capacity)
+{
+	int count = -1;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchGetStreamEq: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		na::EqSection s[na::kEqMaxSections];
+		count = batch->batch->GetStreamEq(stream, s, na::kEqMaxSections);
+		if (out)
+			for (int i = 0; i < std::min(count, capacity); i++) EqSectionOut(s[i], &out[i]);
+	});
+	return rc == 0 ? count : -1;
+}
+
+int NA_BatchStreamEqFadeRemaining(NA_Batch* batch, int stream)
+{
+	int left = 0;
+	const int rc = Guard([&] {
+		if (!batch) throw std::runtime_error("NA_BatchStreamEqFadeRemaining: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+		left = batch->batch->StreamEqFadeRemaining(stream);
+	});
+	return rc == 0 ? left : -1;
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugEqLaunches(void) { return (long long)na::EqStageLaunches(); }
+int NA_DebugRunEqStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunEqStage: null batch");
+		batch->batch->DebugRunEqStage(hostRows, stride, n);
+	});
+}
+#endif
+
 #ifndef NA_RELEASE
 long long NA_DebugDeviceResourceCalls(void) { return na::DeviceResourceCalls(); }
 #endif

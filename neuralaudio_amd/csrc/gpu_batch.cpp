@@ -146,6 +146,7 @@ namespace na
 			(void)resample.release();
 			(void)cabStage.release();
 			(void)gateStage.release();
+			(void)eqStage.release();
 			for (WnLaunchTable& t : wnTable) t.entries.clear();
 			return;
 		}
@@ -337,6 +338,7 @@ namespace na
 		if (outStage) EnsureStageRows((int)streams.size());
 		if (cabStage) EnsureCabinetRows((int)streams.size());
 		if (gateStage) EnsureGateRows((int)streams.size());
+		if (eqStage) EnsureEqRows((int)streams.size());
 		return first;
 	}
 
@@ -624,9 +626,10 @@ namespace na
 	// One processing call on `launch`, and the one place that states its order: the gate detector in front of
 	// everything -- it reads the input rows as the caller passed them, which may be the output rows, so before any model writes --,
 	// the up kernel, the model launches and the down kernel of a resampling batch (ProcessResampledOn) or the model launches alone,
-	// then the per-stream stages (DESIGN.md 2.9 - 2.11) once per call: behind everything the call has launched -- the join of the
-	// units, the graph replay, the down kernel -- on the same stream, outside any capture; every row is gated first, then convolved
-	// with its own IR (the cabinet's tail rings out through a closing gate), then scaled and cross-faded.
+	// then the per-stream stages (DESIGN.md 2.9 - 2.12) once per call: behind everything the call has launched -- the join of the
+	// units, the graph replay, the down kernel -- on the same stream, outside any capture; every row is gated first, then runs through
+	// its own EQ cascade (the tone stack sits between amp and cabinet), then is convolved with its own IR (the cabinet's tail rings out
+	// through a closing gate), then scaled and cross-faded.
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{
@@ -639,6 +642,7 @@ namespace na
 	void GpuBatch::RunStages(hipStream_t launch, float* dOut, size_t n, long outStride)
 	{
 		if (gateStage && gateStage->book.HasEntries()) RunGateApply(launch, dOut, n, outStride);
+		if (eqStage && eqStage->book.HasEntries()) RunEqStage(launch, dOut, n, outStride);
 		if (cabStage && cabStage->book.HasEntries()) RunCabinetStage(launch, dOut, n, outStride);
 		if (outStage && outStage->book.HasEntries()) RunOutputStage(launch, dOut, n, outStride);
 	}

@@ -19,6 +19,7 @@
 
 #include "cabinet_stage.h"
 #include "device_resources.h"
+#include "eq_stage.h"
 #include "gate_stage.h"
 #include "launch_plan.h"
 #include "model_loader.h"
@@ -72,6 +73,12 @@ namespace na
 	struct GateStageInfo
 	{
 		int gainSamples = 0, numGates = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct EqStageInfo
+	{
+		int maxSections = 0, numEntries = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -165,6 +172,21 @@ namespace na
 		void SetStreamGate(int stream, const GateParams* params, bool startOpen); // params == nullptr: the gate goes, click-free
 		bool GetStreamGate(int stream, GateParams& out) const;                    // false: no gate (or one that is being taken away)
 		float StreamGateGain(int stream); // the g of the last sample produced; synchronises the batch: a diagnostic
+
+		// The EQ stage (eq_stage.h): a cascade of up to 8 biquad sections per stream in f64, applied to the row the models
+		// produced behind the gate's apply and in front of the cabinet.  EnableEqStage is the set-up side: two slots of coefficients and
+		// section states per row (CreateStreams grows them) and the tables.  SetStreamEq is host arithmetic on those tables; while an
+		// entry exists -- a stream with a cascade, or one that fades to flat -- every processing call runs on the ordered path and
+		// enqueues ONE table upload and ONE launch, whatever n.  Without an entry the batch launches exactly what it launches without
+		// the stage.
+		void EnableEqStage();
+		bool HasEqStage() const { return eqStage != nullptr; }
+		EqStageInfo GetEqInfo() const;
+		void SetStreamEq(int stream, const EqSection* sections, int numSections, int fadeSamples); // 0 sections: flat
+		int GetStreamEq(int stream, EqSection* out, int capacity) const;                           // the target's section count
+		int StreamEqFadeRemaining(int stream) const;
+		// test hook (NA_DebugRunEqStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
+		void DebugRunEqStage(float* hostRows, long stride, size_t n);
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -339,6 +361,11 @@ namespace na
 		void GateLeave(int stream);       // park / removal: the gate goes at once
 		void RunGateDetector(hipStream_t launch, const float* dIn, size_t n, long inStride); // table upload + the detector launch
 		void RunGateApply(hipStream_t launch, float* dOut, size_t n, long outStride);        // the apply launch + the host mirror's advance
+		struct EqStage; // (gpu_batch_internal.h)
+		std::unique_ptr<EqStage> eqStage;
+		void EnsureEqRows(int rows);      // set-up side: coefficient slots, section states and tables for `rows` rows
+		void EqLeave(int stream);         // park / removal: flat at once, the states dropped
+		void RunEqStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + launch + the host mirror's advance
 		int AllocateIds(int count);
 		void DropTrailingRetiredRows();
 		// the kinds of the groups that have active streams once `leaving` has lost / `entering` has gained one, in group order (`active`:
@@ -469,7 +496,7 @@ namespace na
 		// One processing call on `launch`, the one place that states its order (gpu_batch.cpp): the gate detector, ProcessResampledOn or
 		// LaunchModelsOn, then RunStages
 		void ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
-		void RunStages(hipStream_t launch, float* dOut, size_t n, long outStride); // the stages with entries: gate apply, cabinet, then output
+		void RunStages(hipStream_t launch, float* dOut, size_t n, long outStride); // the stages with entries: gate apply, EQ, cabinet, then output
 		// the model launches of a call, and their parts (gpu_batch.cpp)
 		struct ModelCall; // (gpu_batch_internal.h)
 		void LaunchModelsOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);

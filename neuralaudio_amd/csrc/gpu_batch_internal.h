@@ -207,5 +207,19 @@ namespace na
 	hipError_t LaunchGateDetect(const GateDetectLaunch& L, hipStream_t stream); // (gate_stage_kernels.hip)
 	hipError_t LaunchGateApply(const GateApplyLaunch& L, hipStream_t stream);
 
+	// the EQ stage of a batch (eq_stage.h): the host mirror, the rows' two slots of coefficients and section states on
+	// the device, and the ring of tables -- entries, and behind them the coefficient sets of the set calls since the last call
+	struct GpuBatch::EqStage
+	{
+		static constexpr const char* kNotEnabled = "eq stage not enabled (NA_BatchEnableEqStage)";
+		EqBook book;
+		float* coefs = nullptr;           // [rowCapacity][2] EqCoefSet
+		float* state = nullptr;           // [rowCapacity][2][kEqMaxSections] EqSecState
+		int rowCapacity = 0;
+		StageTables<EqEntry> tables{ "eq stage: table in flight" };
+		~EqStage();
+	};
+	hipError_t LaunchEqStage(const EqLaunch& L, hipStream_t stream); // (eq_stage_kernels.hip)
+
 	bool HostDirect(); // (gpu_batch_host.cpp) the kernels read / write pinned host blocks themselves instead of the copy engines
 }

@@ -24,7 +24,7 @@ namespace na
 	bool GpuBatch::StageHasEntries() const
 	{
 		return (outStage && outStage->book.HasEntries()) || (cabStage && cabStage->book.HasEntries()) ||
-			(gateStage && gateStage->book.HasEntries());
+			(gateStage && gateStage->book.HasEntries()) || (eqStage && eqStage->book.HasEntries());
 	}
 
 	void GpuBatch::RequireRow(int s, const char* who) const
@@ -87,6 +87,7 @@ namespace na
 	void GpuBatch::StageLeave(int s)
 	{
 		GateLeave(s);
+		EqLeave(s);
 		CabinetLeave(s);
 		if (!outStage || s >= outStage->book.Rows()) return;
 		OutputStageBook& book = outStage->book;

@@ -15,10 +15,13 @@
 //       the click-free model switch on a batch that never stops (RunHandover below): every K-th buffer one of 16 sessions is handed over
 //       (NA_BatchHandover) to a parked stream of the other model (--mix), with one model to a second stream of it.
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --cab TAPS [--cab-irs M=1]
+//       the cabinet stage on a batch that never stops (RunCabinet below): M impulse responses of TAPS taps spread over the streams.
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --gate K
 //       the plain run below with the gate stage enabled and noise gates on the first K streams (K = 0: enabled, no gate set: must cost
 //       nothing); adds the device span per buffer of the pipelined loop between the library's event marks.
-//       the cabinet stage on a batch that never stops (RunCabinet below): M impulse responses of TAPS taps spread over the streams.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --eq K [--eq-sections S=3]
+//       the plain run below with the EQ stage enabled and an S-section cascade on the first K streams -- low shelf, peak, high shelf,
+//       then further peaks up to 8 -- (K = 0: enabled, no EQ set: must cost nothing); the same device span as --gate.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -568,13 +571,13 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
-	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1;
+	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3;
 	bool churnLegacy = false;
 	for (int i = 1; i < argc; i++)
 	{
@@ -590,6 +593,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--cab") && i + 1 < argc) cab = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--cab-irs") && i + 1 < argc) cabIRs = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) gate = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--eq") && i + 1 < argc) eq = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--eq-sections") && i + 1 < argc) eqSections = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
 			// rehearsal on a one-GPU box: the multi-GPU host bound to the library's loopback RCCL table (test build only), so that
@@ -663,6 +668,21 @@ int main(int argc, char** argv)
 		CHECK(NA_GateParamsFromDb(48000, -20.0f, -26.0f, -60.0f, 1.0f, 1.0f, 5.0f, 20.0f, &gp) == 0);
 		for (int s = 0; s < std::min(gate, streams); s++) CHECK(NA_BatchSetStreamGate(batch, s, &gp, 1) == 0);
 	}
+	if (eq >= 0)
+	{
+		// a tone stack: low shelf, mid peak, high shelf; more sections are further peaks
+		CHECK(NA_BatchEnableEqStage(batch) == 0);
+		CHECK(eqSections >= 1 && eqSections <= NA_EQ_MAX_SECTIONS);
+		NA_EqSection sec[NA_EQ_MAX_SECTIONS];
+		for (int i = 0; i < eqSections; i++)
+		{
+			const int kind = i == 0 ? 2 : (i == 2 ? 3 : 4);
+			const double freq = i == 0 ? 120.0 : (i == 2 ? 6000.0 : 400.0 * (1 + i));
+			CHECK(NA_EqSectionFromDesign(kind, 48000.0, freq, 0.8, i % 2 ? -4.0 : 5.0, &sec[i]) == 0);
+		}
+		for (int s = 0; s < std::min(eq, streams); s++) CHECK(NA_BatchSetStreamEq(batch, s, sec, eqSections, 0) == 0);
+	}
+	const bool marks = gate >= 0 || eq >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -713,7 +733,7 @@ int main(int argc, char** argv)
 	// copying entry points, two buffers in flight (between the library's event marks: the device's span of the same loop)
 	int pending = NA_BatchSubmit(batch, in.data(), (size_t)frames);
 	CHECK(pending >= 0);
-	if (gate >= 0) CHECK(NA_BatchMarkTime(batch, 0) == 0);
+	if (marks) CHECK(NA_BatchMarkTime(batch, 0) == 0);
 	double t0 = Now();
 	for (int i = 0; i < buffers; i++)
 	{
@@ -724,8 +744,8 @@ int main(int argc, char** argv)
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
-	double usMarked = 0.0; // (--gate only: the plain run stays what it was)
-	if (gate >= 0)
+	double usMarked = 0.0; // (--gate / --eq only)
+	if (marks)
 	{
 		CHECK(NA_BatchMarkTime(batch, 1) == 0);
 		usMarked = (double)NA_BatchElapsedMs(batch) * 1e3 / buffers;
@@ -767,9 +787,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
