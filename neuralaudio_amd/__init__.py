@@ -461,13 +461,16 @@ class Batch:
             raise NeuralAudioError(capi.last_error())
         return left
 
-    def DebugRunCabinetStage(self, rows, n=None):
-        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunCabinetStage)."""
+    def _debug_run_stage(self, hook, rows, n):
         assert rows.dtype == np.float32 and rows.flags["C_CONTIGUOUS"] and rows.ndim == 2 and rows.shape[0] == self.NumStreams()
         n = rows.shape[1] if n is None else int(n)
-        if self._lib.NA_DebugRunCabinetStage(self._h, _fptr(rows), int(rows.shape[1]), n) != 0:
+        if hook(self._h, _fptr(rows), int(rows.shape[1]), n) != 0:
             raise NeuralAudioError(capi.last_error())
         return rows
+
+    def DebugRunCabinetStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunCabinetStage)."""
+        return self._debug_run_stage(self._lib.NA_DebugRunCabinetStage, rows, n)
 
     # -- the gate stage: EnableGateStage is set-up side; SetStreamGate is real-time safe (include/neuralaudio_amd.h) ----
     def EnableGateStage(self):
@@ -538,11 +541,7 @@ class Batch:
 
     def DebugRunEqStage(self, rows, n=None):
         """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunEqStage)."""
-        assert rows.dtype == np.float32 and rows.flags["C_CONTIGUOUS"] and rows.ndim == 2 and rows.shape[0] == self.NumStreams()
-        n = rows.shape[1] if n is None else int(n)
-        if self._lib.NA_DebugRunEqStage(self._h, _fptr(rows), int(rows.shape[1]), n) != 0:
-            raise NeuralAudioError(capi.last_error())
-        return rows
+        return self._debug_run_stage(self._lib.NA_DebugRunEqStage, rows, n)
 
     def SetQuality(self, stream, q):
         if self._lib.NA_BatchSetQuality(self._h, int(stream), float(q)) != 0:

@@ -61,6 +61,24 @@ namespace
 		return -1;
 	}
 
+	// An NA_Batch* entry point: `f` runs on the batch under Guard; a null batch is an error with the entry point's name in front
+	template <typename F>
+	int BatchCall(NA_Batch* batch, const char* who, F&& f)
+	{
+		return Guard([&] {
+			if (!batch) throw std::runtime_error(std::string(who) + ": null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+			f(*batch->batch);
+		});
+	}
+
+	// ... one that returns what `f` returns, or `failed` (the value the header documents for an error)
+	template <typename T, typename F>
+	T BatchValue(NA_Batch* batch, const char* who, T failed, F&& f)
+	{
+		T value = failed;
+		return BatchCall(batch, who, [&](na::GpuBatch& b) { value = f(b); }) == 0 ? value : failed;
+	}
+
 	// wchar_t is UTF-32 on Linux and UTF-16 on Windows (the C# caller marshals LPWStr, NativeApi.cs:17)
 	std::string WideToUtf8(const wchar_t* w)
 	{
@@ -469,31 +487,22 @@ int NA_BatchAddStreams(NA_Batch* batch, NeuralModel* model, float quality, int c
 // ---- the stream pool (gpu_batch.h ReserveStreams / ActivateStream / ParkStream) ----
 int NA_BatchReserveStreams(NA_Batch* batch, NeuralModel* model, int count, int doPrewarm)
 {
-	int first = -1;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchReserveStreams: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchValue(batch, "NA_BatchReserveStreams", -1, [&](na::GpuBatch& b) {
 		if (!model || count < 1) throw std::runtime_error("NA_BatchReserveStreams: bad argument");
 		NeuralAudio::GpuModel* gm = dynamic_cast<NeuralAudio::GpuModel*>(model->model);
 		if (!gm) throw std::runtime_error("NA_BatchReserveStreams: model was not created by this library");
-		first = batch->batch->ReserveStreams(gm->GetLoadedModel(), count, doPrewarm != 0);
+		return b.ReserveStreams(gm->GetLoadedModel(), count, doPrewarm != 0);
 	});
-	return rc == 0 ? first : -1;
 }
 
 int NA_BatchActivateStream(NA_Batch* batch, int stream, float quality)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchActivateStream: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->ActivateStream(stream, quality);
-	});
+	return BatchCall(batch, "NA_BatchActivateStream", [&](na::GpuBatch& b) { b.ActivateStream(stream, quality); });
 }
 
 int NA_BatchParkStream(NA_Batch* batch, int stream)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchParkStream: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->ParkStream(stream);
-	});
+	return BatchCall(batch, "NA_BatchParkStream", [&](na::GpuBatch& b) { b.ParkStream(stream); });
 }
 
 int NA_BatchIsParked(NA_Batch* batch, int stream) { return (batch && batch->batch->IsParked(stream)) ? 1 : 0; }
@@ -509,63 +518,40 @@ int NA_BatchNumParked(NA_Batch* batch) { return batch ? batch->batch->NumParked(
 // ---- the output stage (gpu_batch.h EnableOutputStage / SetStreamGain / Handover) ----
 int NA_BatchEnableOutputStage(NA_Batch* batch)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchEnableOutputStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->EnableOutputStage();
-	});
+	return BatchCall(batch, "NA_BatchEnableOutputStage", [&](na::GpuBatch& b) { b.EnableOutputStage(); });
 }
 
 int NA_BatchSetStreamGain(NA_Batch* batch, int stream, float gain, int rampSamples)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchSetStreamGain: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->SetStreamGain(stream, gain, rampSamples);
-	});
+	return BatchCall(batch, "NA_BatchSetStreamGain", [&](na::GpuBatch& b) { b.SetStreamGain(stream, gain, rampSamples); });
 }
 
 float NA_BatchGetStreamGain(NA_Batch* batch, int stream)
 {
-	float gain = -1.0f;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchGetStreamGain: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		gain = batch->batch->GetStreamGain(stream);
-	});
-	return rc == 0 ? gain : -1.0f;
+	return BatchValue(batch, "NA_BatchGetStreamGain", -1.0f, [&](na::GpuBatch& b) { return b.GetStreamGain(stream); });
 }
 
 int NA_BatchHandover(NA_Batch* batch, int from, int to, float quality, int fadeSamples)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchHandover: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->Handover(from, to, quality, fadeSamples);
-	});
+	return BatchCall(batch, "NA_BatchHandover", [&](na::GpuBatch& b) { b.Handover(from, to, quality, fadeSamples); });
 }
 
 int NA_BatchHandoverRemaining(NA_Batch* batch, int stream)
 {
-	int left = 0;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchHandoverRemaining: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		left = batch->batch->HandoverRemaining(stream);
-	});
-	return rc == 0 ? left : -1;
+	return BatchValue(batch, "NA_BatchHandoverRemaining", -1, [&](na::GpuBatch& b) { return b.HandoverRemaining(stream); });
 }
 
 // ---- the cabinet stage (gpu_batch.h EnableCabinetStage / LoadIR / SetStreamIR) ----
 int NA_BatchEnableCabinetStage(NA_Batch* batch, int maxTaps)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchEnableCabinetStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->EnableCabinetStage(maxTaps);
-	});
+	return BatchCall(batch, "NA_BatchEnableCabinetStage", [&](na::GpuBatch& b) { b.EnableCabinetStage(maxTaps); });
 }
 
 int NA_BatchGetCabinetInfo(NA_Batch* batch, NA_CabinetInfo* info)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchGetCabinetInfo: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchCall(batch, "NA_BatchGetCabinetInfo", [&](na::GpuBatch& b) {
 		if (!info) throw std::runtime_error("NA_BatchGetCabinetInfo: bad argument");
-		const na::CabinetStageInfo i = batch->batch->GetCabinetInfo();
+		const na::CabinetStageInfo i = b.GetCabinetInfo();
 		info->maxTaps = i.maxTaps;
 		info->ringSamples = i.ringSamples;
 		info->pieceSamples = i.pieceSamples;
@@ -576,48 +562,27 @@ int NA_BatchGetCabinetInfo(NA_Batch* batch, NA_CabinetInfo* info)
 
 int NA_BatchLoadIR(NA_Batch* batch, const float* taps, int numTaps)
 {
-	int id = -1;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchLoadIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		id = batch->batch->LoadIR(taps, numTaps);
-	});
-	return rc == 0 ? id : -1;
+	return BatchValue(batch, "NA_BatchLoadIR", -1, [&](na::GpuBatch& b) { return b.LoadIR(taps, numTaps); });
 }
 
 int NA_BatchUnloadIR(NA_Batch* batch, int ir)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchUnloadIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->UnloadIR(ir);
-	});
+	return BatchCall(batch, "NA_BatchUnloadIR", [&](na::GpuBatch& b) { b.UnloadIR(ir); });
 }
 
 int NA_BatchSetStreamIR(NA_Batch* batch, int stream, int ir, int fadeSamples)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchSetStreamIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->SetStreamIR(stream, ir, fadeSamples);
-	});
+	return BatchCall(batch, "NA_BatchSetStreamIR", [&](na::GpuBatch& b) { b.SetStreamIR(stream, ir, fadeSamples); });
 }
 
 int NA_BatchGetStreamIR(NA_Batch* batch, int stream)
 {
-	int ir = -2;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchGetStreamIR: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		ir = batch->batch->GetStreamIR(stream);
-	});
-	return rc == 0 ? ir : -2;
+	return BatchValue(batch, "NA_BatchGetStreamIR", -2, [&](na::GpuBatch& b) { return b.GetStreamIR(stream); });
 }
 
 int NA_BatchStreamIRFadeRemaining(NA_Batch* batch, int stream)
 {
-	int left = 0;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchStreamIRFadeRemaining: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		left = batch->batch->StreamIRFadeRemaining(stream);
-	});
-	return rc == 0 ? left : -1;
+	return BatchValue(batch, "NA_BatchStreamIRFadeRemaining", -1, [&](na::GpuBatch& b) { return b.StreamIRFadeRemaining(stream); });
 }
 
 #ifndef NA_RELEASE
@@ -669,18 +634,14 @@ int NA_GateParamsFromDb(int sampleRate, float openDb, float closeDb, float floor
 
 int NA_BatchEnableGateStage(NA_Batch* batch)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchEnableGateStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->EnableGateStage();
-	});
+	return BatchCall(batch, "NA_BatchEnableGateStage", [&](na::GpuBatch& b) { b.EnableGateStage(); });
 }
 
 int NA_BatchGetGateInfo(NA_Batch* batch, NA_GateInfo* info)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchGetGateInfo: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchCall(batch, "NA_BatchGetGateInfo", [&](na::GpuBatch& b) {
 		if (!info) throw std::runtime_error("NA_BatchGetGateInfo: bad argument");
-		const na::GateStageInfo i = batch->batch->GetGateInfo();
+		const na::GateStageInfo i = b.GetGateInfo();
 		info->gainSamples = i.gainSamples;
 		info->numGates = i.numGates;
 		info->deviceBytes = i.deviceBytes;
@@ -689,39 +650,31 @@ int NA_BatchGetGateInfo(NA_Batch* batch, NA_GateInfo* info)
 
 int NA_BatchSetStreamGate(NA_Batch* batch, int stream, const NA_GateParams* params, int startOpen)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchSetStreamGate: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchCall(batch, "NA_BatchSetStreamGate", [&](na::GpuBatch& b) {
 		if (!params)
 		{
-			batch->batch->SetStreamGate(stream, nullptr, false);
+			b.SetStreamGate(stream, nullptr, false);
 			return;
 		}
 		na::GateParams g;
 		GateParamsIn(*params, g);
-		batch->batch->SetStreamGate(stream, &g, startOpen != 0);
+		b.SetStreamGate(stream, &g, startOpen != 0);
 	});
 }
 
 int NA_BatchGetStreamGate(NA_Batch* batch, int stream, NA_GateParams* out)
 {
-	int has = 0;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchGetStreamGate: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchValue(batch, "NA_BatchGetStreamGate", -1, [&](na::GpuBatch& b) {
 		na::GateParams g;
-		has = batch->batch->GetStreamGate(stream, g) ? 1 : 0;
+		const int has = b.GetStreamGate(stream, g) ? 1 : 0;
 		if (has && out) GateParamsOut(g, out);
+		return has;
 	});
-	return rc == 0 ? has : -1;
 }
 
 float NA_BatchStreamGateGain(NA_Batch* batch, int stream)
 {
-	float gain = -1.0f;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchStreamGateGain: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		gain = batch->batch->StreamGateGain(stream);
-	});
-	return rc == 0 ? gain : -1.0f;
+	return BatchValue(batch, "NA_BatchStreamGateGain", -1.0f, [&](na::GpuBatch& b) { return b.StreamGateGain(stream); });
 }
 
 #ifndef NA_RELEASE
@@ -762,18 +715,14 @@ int NA_EqSectionFromDesign(int kind, double sampleRate, double freqHz, double q,
 
 int NA_BatchEnableEqStage(NA_Batch* batch)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchEnableEqStage: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		batch->batch->EnableEqStage();
-	});
+	return BatchCall(batch, "NA_BatchEnableEqStage", [&](na::GpuBatch& b) { b.EnableEqStage(); });
 }
 
 int NA_BatchGetEqInfo(NA_Batch* batch, NA_EqInfo* info)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchGetEqInfo: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchCall(batch, "NA_BatchGetEqInfo", [&](na::GpuBatch& b) {
 		if (!info) throw std::runtime_error("NA_BatchGetEqInfo: bad argument");
-		const na::EqStageInfo i = batch->batch->GetEqInfo();
+		const na::EqStageInfo i = b.GetEqInfo();
 		info->maxSections = i.maxSections;
 		info->numEntries = i.numEntries;
 		info->deviceBytes = i.deviceBytes;
@@ -782,36 +731,28 @@ int NA_BatchGetEqInfo(NA_Batch* batch, NA_EqInfo* info)
 
 int NA_BatchSetStreamEq(NA_Batch* batch, int stream, const NA_EqSection* sections, int numSections, int fadeSamples)
 {
-	return Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchSetStreamEq: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchCall(batch, "NA_BatchSetStreamEq", [&](na::GpuBatch& b) {
 		na::EqSection s[na::kEqMaxSections];
 		if (sections)
 			for (int i = 0; i < std::min(std::max(numSections, 0), na::kEqMaxSections); i++) EqSectionIn(sections[i], s[i]);
-		batch->batch->SetStreamEq(stream, sections ? s : nullptr, numSections, fadeSamples);
+		b.SetStreamEq(stream, sections ? s : nullptr, numSections, fadeSamples);
 	});
 }
 
 int NA_BatchGetStreamEq(NA_Batch* batch, int stream, NA_EqSection* out, int capacity)
 {
-	int count = -1;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchGetStreamEq: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
+	return BatchValue(batch, "NA_BatchGetStreamEq", -1, [&](na::GpuBatch& b) {
 		na::EqSection s[na::kEqMaxSections];
-		count = batch->batch->GetStreamEq(stream, s, na::kEqMaxSections);
+		const int count = b.GetStreamEq(stream, s, na::kEqMaxSections);
 		if (out)
 			for (int i = 0; i < std::min(count, capacity); i++) EqSectionOut(s[i], &out[i]);
+		return count;
 	});
-	return rc == 0 ? count : -1;
 }
 
 int NA_BatchStreamEqFadeRemaining(NA_Batch* batch, int stream)
 {
-	int left = 0;
-	const int rc = Guard([&] {
-		if (!batch) throw std::runtime_error("NA_BatchStreamEqFadeRemaining: null batch (NA_BatchCreate fails where no HIP device is visible: there is no CPU fallback)");
-		left = batch->batch->StreamEqFadeRemaining(stream);
-	});
-	return rc == 0 ? left : -1;
+	return BatchValue(batch, "NA_BatchStreamEqFadeRemaining", -1, [&](na::GpuBatch& b) { return b.StreamEqFadeRemaining(stream); });
 }
 
 #ifndef NA_RELEASE

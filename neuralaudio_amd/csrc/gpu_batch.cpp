@@ -144,9 +144,7 @@ namespace na
 			for (auto& g : groups) (void)g.release();
 			(void)residentState.release();
 			(void)resample.release();
-			(void)cabStage.release();
-			(void)gateStage.release();
-			(void)eqStage.release();
+			for (auto& stage : stages) (void)stage.release();
 			for (WnLaunchTable& t : wnTable) t.entries.clear();
 			return;
 		}
@@ -335,10 +333,8 @@ namespace na
 			EnsurePoolPipeline();
 			pendingHistoryZero.reserve(streams.size());
 		}
-		if (outStage) EnsureStageRows((int)streams.size());
-		if (cabStage) EnsureCabinetRows((int)streams.size());
-		if (gateStage) EnsureGateRows((int)streams.size());
-		if (eqStage) EnsureEqRows((int)streams.size());
+		for (auto& stage : stages)
+			if (stage) stage->EnsureRows(*this, (int)streams.size());
 		return first;
 	}
 
@@ -406,7 +402,7 @@ namespace na
 	// (the one host-side wait, shared with a quality switch on such a batch -- bounded by the wait limit).
 	void GpuBatch::FlushRearms()
 	{
-		if (outStage) StageParkFinished();
+		if (stages[kOutputStage]) StageParkFinished();
 		if (!rearmPending) return;
 		JoinHalves();
 		if (pipelineUsed && lastKernelEvent && lastKernelStream != stream) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
@@ -623,17 +619,19 @@ namespace na
 		}
 	}
 
-	// One processing call on `launch`, and the one place that states its order: the gate detector in front of
-	// everything -- it reads the input rows as the caller passed them, which may be the output rows, so before any model writes --,
-	// the up kernel, the model launches and the down kernel of a resampling batch (ProcessResampledOn) or the model launches alone,
-	// then the per-stream stages once per call: behind everything the call has launched -- the join of the
-	// units, the graph replay, the down kernel -- on the same stream, outside any capture; every row is gated first, then runs through
-	// its own EQ cascade (the tone stack sits between amp and cabinet), then is convolved with its own IR (the cabinet's tail rings out
-	// through a closing gate), then scaled and cross-faded.
+	// One processing call on `launch`, and the one place that states its order: what a stage runs in front of the models -- the gate
+	// detector: it reads the input rows as the caller passed them, which may be the output rows, so before any model
+	// writes --, the up kernel, the model launches and the down kernel of a resampling batch (ProcessResampledOn) or the model launches
+	// alone, then the per-stream stages once per call: behind everything the call has launched -- the join of
+	// the units, the graph replay, the down kernel -- on the same stream, outside any capture.  The stages' order is the order of
+	// StageId (gpu_batch.h), written there and nowhere else: every row is gated first, then runs through its own EQ cascade (the tone
+	// stack sits between amp and cabinet), then is convolved with its own IR (the cabinet's tail rings out through a closing gate),
+	// then scaled and cross-faded.
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{
-		if (gateStage && gateStage->book.HasEntries()) RunGateDetector(launch, dIn, n, inStride);
+		for (auto& stage : stages)
+			if (stage && stage->HasEntries()) stage->BeforeModels(*this, launch, dIn, n, inStride);
 		if (Resamples()) ProcessResampledOn(launch, dIn, dOut, n, inStride, outStride);
 		else LaunchModelsOn(launch, dIn, dOut, n, inStride, outStride);
 		RunStages(launch, dOut, n, outStride);
@@ -641,10 +639,47 @@ namespace na
 
 	void GpuBatch::RunStages(hipStream_t launch, float* dOut, size_t n, long outStride)
 	{
-		if (gateStage && gateStage->book.HasEntries()) RunGateApply(launch, dOut, n, outStride);
-		if (eqStage && eqStage->book.HasEntries()) RunEqStage(launch, dOut, n, outStride);
-		if (cabStage && cabStage->book.HasEntries()) RunCabinetStage(launch, dOut, n, outStride);
-		if (outStage && outStage->book.HasEntries()) RunOutputStage(launch, dOut, n, outStride);
+		for (auto& stage : stages)
+			if (stage && stage->HasEntries()) stage->Run(*this, launch, dOut, n, outStride);
+	}
+
+	bool GpuBatch::StageHasEntries() const
+	{
+		for (const auto& stage : stages)
+			if (stage && stage->HasEntries()) return true;
+		return false;
+	}
+
+	// The stream leaves (ParkStream, RemoveStreams): a parked stream carries nothing over
+	void GpuBatch::StageLeave(int s)
+	{
+		for (auto& stage : stages)
+			if (stage) stage->Leave(s);
+	}
+
+	// test hooks (NA_DebugRunCabinetStage, NA_DebugRunEqStage): what a processing call of n samples runs for the stage, on host rows in
+	// place of model outputs
+	void GpuBatch::DebugRunStage(Stage& stage, const char* who, float* hostRows, long stride, size_t n)
+	{
+		if (!hostRows || n == 0 || stride < (long)n || streams.empty()) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": bad argument");
+		Quiesce();
+		if (!stage.HasEntries()) return;
+		const size_t floats = (size_t)streams.size() * (size_t)stride;
+		float* dRows = nullptr;
+		CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&dRows), floats * sizeof(float)), "hipMalloc");
+		try
+		{
+			CheckHip(hipMemcpyAsync(dRows, hostRows, floats * sizeof(float), hipMemcpyHostToDevice, stream), "hipMemcpyAsync H2D");
+			stage.Run(*this, stream, dRows, n, stride);
+			CheckHip(hipMemcpyAsync(hostRows, dRows, floats * sizeof(float), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync D2H");
+			WaitStreamBounded(stream, "hipStreamSynchronize");
+		}
+		catch (...)
+		{
+			if (!broken) (void)CountedHipFree(dRows);
+			throw;
+		}
+		(void)CountedHipFree(dRows);
 	}
 
 	// prepareOnly: upload the group tables the list's launches will look up and launch nothing (the pass in front of a stream capture)

@@ -136,7 +136,7 @@ namespace na
 		// from a ring of pinned tables and ONE launch that works in place on the rows the caller sees.  Without an entry the batch
 		// launches exactly what it launches without the stage.
 		void EnableOutputStage();
-		bool HasOutputStage() const { return outStage != nullptr; }
+		bool HasOutputStage() const { return stages[kOutputStage] != nullptr; }
 		void SetStreamGain(int stream, float gain, int rampSamples);
 		float GetStreamGain(int stream) const; // the target; < 0: not a live or parked stream of the batch
 		void Handover(int from, int to, float quality, int fadeSamples);
@@ -149,7 +149,7 @@ namespace na
 		// processing call runs on the ordered path and enqueues ONE table upload and two launches per piece of kCabPieceSamples samples.
 		// Without an entry the batch launches exactly what it launches without the stage.
 		void EnableCabinetStage(int maxTaps);
-		bool HasCabinetStage() const { return cabStage != nullptr; }
+		bool HasCabinetStage() const { return stages[kCabinetStage] != nullptr; }
 		CabinetStageInfo GetCabinetInfo() const;
 		int LoadIR(const float* taps, int numTaps);
 		void UnloadIR(int ir);
@@ -167,7 +167,7 @@ namespace na
 		// processing call runs on the ordered path and enqueues ONE table upload and two launches, whatever n.  Without an entry the
 		// batch launches exactly what it launches without the stage.
 		void EnableGateStage();
-		bool HasGateStage() const { return gateStage != nullptr; }
+		bool HasGateStage() const { return stages[kGateStage] != nullptr; }
 		GateStageInfo GetGateInfo() const;
 		void SetStreamGate(int stream, const GateParams* params, bool startOpen); // params == nullptr: the gate goes, click-free
 		bool GetStreamGate(int stream, GateParams& out) const;                    // false: no gate (or one that is being taken away)
@@ -180,7 +180,7 @@ namespace na
 		// enqueues ONE table upload and ONE launch, whatever n.  Without an entry the batch launches exactly what it launches without
 		// the stage.
 		void EnableEqStage();
-		bool HasEqStage() const { return eqStage != nullptr; }
+		bool HasEqStage() const { return stages[kEqStage] != nullptr; }
 		EqStageInfo GetEqInfo() const;
 		void SetStreamEq(int stream, const EqSection* sections, int numSections, int fadeSamples); // 0 sections: flat
 		int GetStreamEq(int stream, EqSection* out, int capacity) const;                           // the target's section count
@@ -338,34 +338,33 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		struct OutputStage; // (gpu_batch_internal.h)
-		std::unique_ptr<OutputStage> outStage;
+		// The per-stream stages.  StageId is THE place that states the chain: a processing call runs the stages with
+		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kNumStages };
+		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
+		{
+			virtual ~Stage() = default;
+			virtual bool HasEntries() const = 0;
+			virtual void EnsureRows(GpuBatch& batch, int rows) = 0; // set-up side: device blocks and tables for `rows` rows
+			virtual void Leave(int stream) = 0;                     // park / removal: nothing of the stream is carried over
+			// a call with entries: in front of its model launches (the gate's detector), and behind them in chain order
+			virtual void BeforeModels(GpuBatch&, hipStream_t, const float*, size_t, long) {}
+			virtual void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) = 0;
+		};
+		template <class Book, class Entry> struct StageOf;
+		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage;
+		std::unique_ptr<Stage> stages[kNumStages];
+		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
+		template <class S> S& EnableStage();                              // every Enable*Stage call
+		template <class S> S& SettableStage(int stream, const char* who); // a set call's preamble: usable, enabled, not parked, live
+		void DebugRunStage(Stage& stage, const char* who, float* hostRows, long stride, size_t n);
 		bool StageHasEntries() const; // of any stage
 		// the call runs ordered on ONE stream: up kernel -> model launches -> down kernel of a resampling batch, the stages behind the
 		// model launches (no half-batch chains, no resident launch)
 		bool RunsOrdered() const { return Resamples() || StageHasEntries(); }
 		void RequireRow(int stream, const char* who) const; // throws "<who>: stream <s> is not a stream of the batch" (a parked one is)
-		void EnsureStageRows(int rows);  // set-up side: tables for `rows` rows
 		void StageParkFinished();        // top of every processing call: the `from` streams of the fades that ended in the last one are parked
-		void StageLeave(int stream);     // park / removal: its fade ends, its gain is 1 again
-		void RunOutputStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + launch + the host mirror's advance
-		struct CabinetStage; // (gpu_batch_internal.h)
-		std::unique_ptr<CabinetStage> cabStage;
-		void EnsureCabinetRows(int rows); // set-up side: rings and tables for `rows` rows
-		void CabinetLeave(int stream);    // park / removal: dry at once, the history dropped
-		void RunCabinetStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + two launches per piece + the host mirror's advance
-		struct GateStage; // (gpu_batch_internal.h)
-		std::unique_ptr<GateStage> gateStage;
-		void EnsureGateRows(int rows);    // set-up side: states, gain rows and tables for `rows` rows
-		void EnsureGateSamples(size_t n); // gain rows of at least n samples (grows them: not real-time safe)
-		void GateLeave(int stream);       // park / removal: the gate goes at once
-		void RunGateDetector(hipStream_t launch, const float* dIn, size_t n, long inStride); // table upload + the detector launch
-		void RunGateApply(hipStream_t launch, float* dOut, size_t n, long outStride);        // the apply launch + the host mirror's advance
-		struct EqStage; // (gpu_batch_internal.h)
-		std::unique_ptr<EqStage> eqStage;
-		void EnsureEqRows(int rows);      // set-up side: coefficient slots, section states and tables for `rows` rows
-		void EqLeave(int stream);         // park / removal: flat at once, the states dropped
-		void RunEqStage(hipStream_t launch, float* dOut, size_t n, long outStride); // table upload + launch + the host mirror's advance
+		void StageLeave(int stream);     // park / removal: every stage lets go of it
 		int AllocateIds(int count);
 		void DropTrailingRetiredRows();
 		// the kinds of the groups that have active streams once `leaving` has lost / `entering` has gained one, in group order (`active`:
@@ -493,10 +492,10 @@ namespace na
 		void LaunchHalves(const float* dIn, float* dOut, size_t n, long inStride, long outStride, hipEvent_t* done, bool hostRows);
 		void JoinHalves(); // the half-batch chains are done (host-side wait); the next launches go to the batch stream again
 		hipEvent_t marks[1 + kMaxChains][2] = {};
-		// One processing call on `launch`, the one place that states its order (gpu_batch.cpp): the gate detector, ProcessResampledOn or
-		// LaunchModelsOn, then RunStages
+		// One processing call on `launch`, the one place that states its order (gpu_batch.cpp): the stages' BeforeModels,
+		// ProcessResampledOn or LaunchModelsOn, then RunStages
 		void ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);
-		void RunStages(hipStream_t launch, float* dOut, size_t n, long outStride); // the stages with entries: gate apply, EQ, cabinet, then output
+		void RunStages(hipStream_t launch, float* dOut, size_t n, long outStride); // the stages with entries, in StageId order
 		// the model launches of a call, and their parts (gpu_batch.cpp)
 		struct ModelCall; // (gpu_batch_internal.h)
 		void LaunchModelsOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride);

@@ -91,21 +91,21 @@ namespace na
 		}
 	};
 
-	// The ring of entry tables of a per-stream stage (output_stage.cpp, cabinet_stage.cpp): pinned and device blocks of `capacity` entries
-	// and an event each.  One table more than buffers can be in flight (Submit): the table a call takes was read by a launch whose
-	// ticket has been collected.  `inFlight` names the stage in the message of a wait that ran into the limit.
+	// The ring of entry tables of a per-stream stage: pinned and device blocks of `capacity` entries and an event each.  One table more
+	// than buffers can be in flight (Submit): the table a call takes was read by a launch whose ticket has been collected.  `name` is
+	// the stage's in the messages.  A processing call steps through Take, the book's BuildTable, Upload, its launches and Commit.
 	template <class Entry>
 	struct StageTables
 	{
 		static constexpr int kTables = GpuBatch::kPipelineSlots + 1;
-		const char* inFlight;
+		const std::string name, inFlight, uploadWhat;
 		Entry* host[kTables] = {};     // pinned
 		Entry* dev[kTables] = {};
 		hipEvent_t done[kTables] = {}; // the launches that read dev[i] (and the upload that read host[i]) are over
 		bool used[kTables] = {};
 		int next = 0;
 		int capacity = 0;              // entries per table
-		explicit StageTables(const char* what) : inFlight(what) {}
+		explicit StageTables(const char* stage) : name(stage), inFlight(name + ": table in flight"), uploadWhat("hipMemcpyAsync (" + name + " table)") {}
 		~StageTables()
 		{
 			for (int i = 0; i < kTables; i++)
@@ -123,7 +123,7 @@ namespace na
 			if (want <= capacity) return;
 			for (int i = 0; i < kTables; i++)
 			{
-				if (used[i]) batch.WaitEventBounded(done[i], inFlight);
+				if (used[i]) batch.WaitEventBounded(done[i], inFlight.c_str());
 				used[i] = false;
 				if (host[i]) (void)CountedHipHostFree(host[i]);
 				if (dev[i]) (void)CountedHipFree(dev[i]);
@@ -137,15 +137,27 @@ namespace na
 			}
 			capacity = want;
 		}
-		// the next table, pinned block and device twin, once the launch that last read it is over (a bounded wait)
+		// the call does not fit what the set-up side sized (`fits` false): a table with more than `capacity` entries, a row past the stage's blocks
+		void Require(bool fits) const
+		{
+			if (!fits) throw std::runtime_error("neuralaudio_amd: " + name + ": more entries than the tables hold");
+		}
+		// the next table for a call of up to `entries` entries, pinned block and device twin, once the launch that last read it is over (a
+		// bounded wait)
 		struct Table
 		{
 			Entry *host, *dev;
 		};
-		Table Take(GpuBatch& batch)
+		Table Take(GpuBatch& batch, int entries)
 		{
-			if (used[next]) batch.WaitEventBounded(done[next], inFlight);
+			Require(entries <= capacity);
+			if (used[next]) batch.WaitEventBounded(done[next], inFlight.c_str());
 			return { host[next], dev[next] };
+		}
+		// the first `units` entries of the table taken go to its device twin, in front of the launches that read it
+		void Upload(const Table& table, int units, hipStream_t stream) const
+		{
+			CheckHip(hipMemcpyAsync(table.dev, table.host, (size_t)units * sizeof(Entry), hipMemcpyHostToDevice, stream), uploadWhat.c_str());
 		}
 		// behind the upload and the launches that read the table taken: the ring moves on
 		void Commit(hipStream_t stream)
@@ -159,67 +171,122 @@ namespace na
 
 	// the argument checks the stages' calls share: the texts are part of the interface (the tests match on them)
 	inline std::string StreamId(int s) { return "stream " + std::to_string(s); }
-	template <class Stage>
-	Stage& RequireStage(const std::unique_ptr<Stage>& stage, const char* who)
+	inline void RequireFadeRange(int samples, const char* who, const char* argument)
 	{
-		if (!stage) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + Stage::kNotEnabled);
-		return *stage;
+		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// the output stage of a batch (output_stage.h): the host mirror and the ring of entry tables
-	struct GpuBatch::OutputStage
+	// What the four stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// entry tables.
+	template <class Book, class Entry>
+	struct GpuBatch::StageOf : GpuBatch::Stage
 	{
-		static constexpr const char* kNotEnabled = "output stage not enabled (NA_BatchEnableOutputStage)";
-		OutputStageBook book;
-		StageTables<OutStageEntry> tables{ "output stage: table in flight" };
+		Book book;
+		StageTables<Entry> tables;
+		explicit StageOf(const char* name) : tables(name) {}
+		bool HasEntries() const override { return book.HasEntries(); }
 	};
-	hipError_t LaunchOutputStage(const OutStageLaunch& L, hipStream_t stream); // (output_stage_kernels.hip)
 
-	// the cabinet stage of a batch (cabinet_stage.h): the host mirror, the rows' history rings, the IRs' taps (owned
-	// through the book's ids) and the ring of entry tables
-	struct GpuBatch::CabinetStage
+	// the gate stage (gate_stage.h, gate_stage.cpp): the rows' states and gain rows on the device, and -- between the
+	// detector and the apply launch of one call -- the table that call runs on
+	struct GpuBatch::GateStage : StageOf<GateBook, GateEntry>
 	{
-		static constexpr const char* kNotEnabled = "cabinet stage not enabled (NA_BatchEnableCabinetStage)";
-		CabinetBook book;
-		float* rings = nullptr;           // [ringRows][book.RingSamples()]
-		int ringRows = 0;
-		long long tapBytes = 0;           // device bytes of the loaded IRs
-		StageTables<CabEntry> tables{ "cabinet stage: table in flight" };
-		~CabinetStage();
-	};
-	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece
-
-	// the gate stage of a batch (gate_stage.h): the host mirror, the rows' states and gain rows on the device, the ring of
-	// entry tables, and -- between the detector and the apply launch of one call -- the table that call runs on
-	struct GpuBatch::GateStage
-	{
+		static constexpr StageId kId = kGateStage;
 		static constexpr const char* kNotEnabled = "gate stage not enabled (NA_BatchEnableGateStage)";
-		GateBook book;
 		float* state = nullptr;           // [rowCapacity] GateState
 		float* gains = nullptr;           // [rowCapacity][gainSamples]
 		int rowCapacity = 0;
 		int gainSamples = kGateMinGainSamples; // a power of two
-		StageTables<GateEntry> tables{ "gate stage: table in flight" };
 		const GateEntry* dev = nullptr;   // the device table the detector of this call read ...
 		int count = 0;                    // ... and its entries; 0: the call has none
-		~GateStage();
+		GateStage() : StageOf("gate stage") {}
+		~GateStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // its gate goes at once
+		void EnsureSamples(GpuBatch& batch, size_t n); // gain rows of at least n samples (grows them: not real-time safe)
+		void BeforeModels(GpuBatch& batch, hipStream_t launch, const float* dIn, size_t n, long inStride) override; // table upload + the detector launch
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override;              // the apply launch + the host mirror's advance
 	};
 	hipError_t LaunchGateDetect(const GateDetectLaunch& L, hipStream_t stream); // (gate_stage_kernels.hip)
 	hipError_t LaunchGateApply(const GateApplyLaunch& L, hipStream_t stream);
 
-	// the EQ stage of a batch (eq_stage.h): the host mirror, the rows' two slots of coefficients and section states on
-	// the device, and the ring of tables -- entries, and behind them the coefficient sets of the set calls since the last call
-	struct GpuBatch::EqStage
+	// the EQ stage (eq_stage.h, eq_stage.cpp): the rows' two slots of coefficients and section states on the device; its
+	// tables hold the entries and behind them the coefficient sets of the set calls since the last call
+	struct GpuBatch::EqStage : StageOf<EqBook, EqEntry>
 	{
+		static constexpr StageId kId = kEqStage;
 		static constexpr const char* kNotEnabled = "eq stage not enabled (NA_BatchEnableEqStage)";
-		EqBook book;
 		float* coefs = nullptr;           // [rowCapacity][2] EqCoefSet
 		float* state = nullptr;           // [rowCapacity][2][kEqMaxSections] EqSecState
 		int rowCapacity = 0;
-		StageTables<EqEntry> tables{ "eq stage: table in flight" };
-		~EqStage();
+		EqStage() : StageOf("eq stage") {}
+		~EqStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // flat at once, its states dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + launch + the host mirror's advance
 	};
 	hipError_t LaunchEqStage(const EqLaunch& L, hipStream_t stream); // (eq_stage_kernels.hip)
+
+	// the cabinet stage (cabinet_stage.h, cabinet_stage.cpp): the rows' history rings and the IRs' taps (owned through
+	// the book's ids)
+	struct GpuBatch::CabinetStage : StageOf<CabinetBook, CabEntry>
+	{
+		static constexpr StageId kId = kCabinetStage;
+		static constexpr const char* kNotEnabled = "cabinet stage not enabled (NA_BatchEnableCabinetStage)";
+		float* rings = nullptr;           // [ringRows][book.RingSamples()]
+		int ringRows = 0;
+		long long tapBytes = 0;           // device bytes of the loaded IRs
+		CabinetStage() : StageOf("cabinet stage") {}
+		~CabinetStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // dry at once, its history dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + two launches per piece + the host mirror's advance
+	};
+	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece
+
+	// the output stage (output_stage.h, output_stage.cpp)
+	struct GpuBatch::OutputStage : StageOf<OutputStageBook, OutStageEntry>
+	{
+		static constexpr StageId kId = kOutputStage;
+		static constexpr const char* kNotEnabled = "output stage not enabled (NA_BatchEnableOutputStage)";
+		OutputStage() : StageOf("output stage") {}
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override; // its fade ends, its gain is 1 again
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + launch + the host mirror's advance
+	};
+	hipError_t LaunchOutputStage(const OutStageLaunch& L, hipStream_t stream); // (output_stage_kernels.hip)
+
+	// the stage S of the batch; throws "<who>: <stage> not enabled (...)" -- the text is part of the interface
+	template <class S>
+	S& GpuBatch::Require(const char* who) const
+	{
+		Stage* stage = stages[S::kId].get();
+		if (!stage) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + S::kNotEnabled);
+		return static_cast<S&>(*stage);
+	}
+
+	// set-up side of every NA_BatchEnable*Stage: the stage, with what the rows the batch has need on the device
+	template <class S>
+	S& GpuBatch::EnableStage()
+	{
+		CheckUsable();
+		CheckHip(hipSetDevice(device), "hipSetDevice");
+		if (!stages[S::kId]) stages[S::kId].reset(new S());
+		stages[S::kId]->EnsureRows(*this, (int)streams.size());
+		EnsurePoolPipeline(); // (an entry moves Submit's buffers onto the slots' own streams or the copy streams: they exist from here on)
+		return static_cast<S&>(*stages[S::kId]);
+	}
+
+	// the preamble of a set call on a stream: a usable batch, the stage, a stream that is live and not parked
+	template <class S>
+	S& GpuBatch::SettableStage(int s, const char* who)
+	{
+		CheckUsable();
+		S& stage = Require<S>(who);
+		if (IsParked(s)) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + StreamId(s) + " is parked");
+		if (!IsLive(s)) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + StreamId(s) + " is not a live stream of the batch");
+		return stage;
+	}
 
 	bool HostDirect(); // (gpu_batch_host.cpp) the kernels read / write pinned host blocks themselves instead of the copy engines
 }

@@ -89,6 +89,58 @@ def test_a_blocking_host_buffer_gives_up_at_the_limit_returns_silence_and_breaks
     b2.close()
 
 
+def _batch_with_an_entry_in_every_stage(na, std, S):
+    """S streams of the Standard model, all four per-stream stages enabled, stream 1 with an entry in each of them"""
+    b = na.Batch(0)
+    b.AddStreams(std, S)
+    b.EnableGateStage()
+    b.EnableEqStage()
+    b.EnableCabinetStage(64)
+    b.EnableOutputStage()
+    b.SetStreamGate(1, na.gate_params_from_db(48000, -40.0, -50.0))
+    b.SetStreamEq(1, [na.eq_section("peaking", 48000.0, 1000.0, gain_db=6.0)])
+    b.SetStreamIR(1, b.LoadIR(np.array([0.5, 0.25, -0.125], np.float32)))
+    b.SetStreamGain(1, 0.5)
+    return b
+
+
+def test_a_broken_batch_with_every_stage_in_use_is_destroyed_without_waiting_for_the_device(na, std):
+    """The destructor of a batch whose device does not come back leaves the device allocations alone (gpu_batch.h "bounded waits"):
+    those of every per-stream stage too -- tables, rings, state blocks -- so close() returns inside the limit while the stall kernel
+    still runs.  While the batch listed its stages by hand the output stage was missing from that list: its tables were freed behind
+    the stall kernel and close() took 1.0 s (profiles/stage_chain_refactor.txt)."""
+    from neuralaudio_amd import capi
+    lib = capi.load_library()
+    S, n = 4, 64
+    x = np.stack([O.signal_sine(n, start=977 * s) for s in range(S)]).astype(np.float32)
+    b = _batch_with_an_entry_in_every_stage(na, std, S)
+    y_ok = b.Process(x)  # a healthy buffer first: every stage has run
+    assert np.all(np.isfinite(y_ok)) and np.any(y_ok)
+    b.SetWaitLimitMs(LIMIT_MS)
+    b.DebugStallDevice(STALL_MS)
+    y = np.full_like(x, 7.0)
+    _expect_stall(na, lambda: lib.NA_BatchProcess(b._h, _fp(x), _fp(y), n), "NA_BatchProcess")
+    assert not np.any(y), "a failed buffer must be silence"
+    assert b.IsBroken()
+    t0 = time.monotonic()
+    b.close()
+    assert time.monotonic() - t0 < LIMIT_MS / 1000.0 + 0.4
+    _let_the_device_come_back()
+    # the process is fine: a new batch with the same stages and entries computes, and a stream without an entry computes what the
+    # oracle -- and a batch without any stage -- computes
+    b2 = _batch_with_an_entry_in_every_stage(na, std, S)
+    y2 = b2.Process(x)
+    assert np.all(np.isfinite(y2)) and np.any(y2[1])
+    twin = na.Batch(0)
+    twin.AddStreams(std, S)
+    y3 = twin.Process(x)
+    yo = O.oracle_from_file("BossWN-standard.nam").process(x[3])
+    assert O.rms(y2[3] - yo) < 1e-4 and O.rms(y3[3] - yo) < 1e-4
+    assert O.rms(y2[3] - y3[3]) < 1e-4
+    b2.close()
+    twin.close()
+
+
 @pytest.mark.parametrize("resident", [False, True], ids=["half-batch chains", "resident launch"])
 def test_device_pointer_buffers_give_up_at_the_limit(na, std, resident):
     """Contract (b) of NA_BatchProcessDevice: the library schedules the buffer on its own streams (two free-running half-batch launches,

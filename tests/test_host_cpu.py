@@ -61,6 +61,48 @@ def test_library_exports_every_declared_symbol(na):
     assert sorted(capi.LEGACY_SYMBOLS + capi.NA_SYMBOLS) == sorted(declared)
 
 
+def test_every_pool_and_stage_entry_point_refuses_a_null_batch_by_name(na):
+    """NA_BatchCreate returns NULL where no HIP device is visible, so a host without a GPU reaches these calls with a null batch: each
+    returns the failure value include/neuralaudio_amd.h documents for it and leaves an error that begins with its own name.  The
+    entry points of the stream pool and of the four per-stream stages share one null check (capi.cpp BatchCall / BatchValue)."""
+    from neuralaudio_amd import capi
+    lib = capi.load_library()
+    gate, sec = capi.NA_GateParams(), (capi.NA_EqSection * 8)()
+    cab_info, gate_info, eq_info = capi.NA_CabinetInfo(), capi.NA_GateInfo(), capi.NA_EqInfo()
+    taps = (C.c_float * 4)(1.0, 0.0, 0.0, 0.0)
+    nonzero, negative, below_dry = (lambda rc: rc != 0), (lambda rc: rc < 0), (lambda rc: rc <= -2)
+    calls = [("NA_BatchReserveStreams", (None, 4, 1), negative),
+             ("NA_BatchActivateStream", (0, 1.0), nonzero),
+             ("NA_BatchParkStream", (0,), nonzero),
+             ("NA_BatchEnableOutputStage", (), nonzero),
+             ("NA_BatchSetStreamGain", (0, 0.5, 64), nonzero),
+             ("NA_BatchGetStreamGain", (0,), negative),
+             ("NA_BatchHandover", (0, 1, 1.0, 64), nonzero),
+             ("NA_BatchHandoverRemaining", (0,), negative),
+             ("NA_BatchEnableCabinetStage", (2048,), nonzero),
+             ("NA_BatchGetCabinetInfo", (C.byref(cab_info),), nonzero),
+             ("NA_BatchLoadIR", (taps, 4), negative),
+             ("NA_BatchUnloadIR", (0,), nonzero),
+             ("NA_BatchSetStreamIR", (0, 0, 64), nonzero),
+             ("NA_BatchGetStreamIR", (0,), below_dry),
+             ("NA_BatchStreamIRFadeRemaining", (0,), negative),
+             ("NA_BatchEnableGateStage", (), nonzero),
+             ("NA_BatchGetGateInfo", (C.byref(gate_info),), nonzero),
+             ("NA_BatchSetStreamGate", (0, C.byref(gate), 1), nonzero),
+             ("NA_BatchGetStreamGate", (0, C.byref(gate)), negative),
+             ("NA_BatchStreamGateGain", (0,), negative),
+             ("NA_BatchEnableEqStage", (), nonzero),
+             ("NA_BatchGetEqInfo", (C.byref(eq_info),), nonzero),
+             ("NA_BatchSetStreamEq", (0, sec, 1, 0), nonzero),
+             ("NA_BatchGetStreamEq", (0, sec, 8), negative),
+             ("NA_BatchStreamEqFadeRemaining", (0,), negative)]
+    assert len(set(name for name, _, _ in calls)) == 25
+    for name, args, failed in calls:
+        rc =getattr(lib, name)(None, *args)
+        assert failed(rc), (name, rc)
+        assert capi.last_error().startswith(name + ": null batch"), (name, capi.last_error())
+
+
 def test_cpp_api_is_exported_and_a_cpp_host_links(na, tmp_path):
     """The C++ boundary (NeuralModel.h:33-153 of the reference): NeuralModel / NeuralModelLoader are exported from the shared
     library, and a C++ translation unit written against include/NeuralAudio/NeuralModel.h alone links and runs."""
