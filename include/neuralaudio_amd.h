@@ -657,6 +657,23 @@ NA_EXTERN int NA_DebugRecurrentShapePlan(int cell, int hidden, int numLayers, in
  * (the name goes to outName[cap]); -1 on a bad argument. */
 NA_EXTERN int NA_DebugRecurrentKernel(int cell, int hidden, int numLayers, int tailLayers, int tailWidth, int tailHistory, int haveWT, int knobMask, int rpl,
 	char* outName, int cap);
+/* Tests: the WaveNet counterparts, host side only.  Knobs of both: bit i of knobMask set = knob i takes knobs[i], every other knob its
+ * default -- the environment is not read; knobMask -1: the process's own tuning knobs.  Knob order: 0 NA_WN_KERNEL (1 split, 2 frame,
+ * 3 generic), 1 NA_WN_PACK, 2 NA_WN_PAD off, 3 NA_WN_DENSE, 4 NA_SP_T, 5 NA_SP_SPB, 6 NA_SP_GEN, 7 NA_SP_NO_T1, 8 NA_FR_PF, 9 NA_FR_SPB,
+ * 10 specialised chains on (NA_WN_SPEC).
+ * NA_DebugWaveNetKernel: what a batch's model group decides once for `streams` streams of the model at `quality`: out = { family (1
+ * f16-split, 2 frame, 3 generic), pack, dense pack, packed or padded, specialised chain (0 none, 1 Standard, 2 lite 16 / 8, 3 lite 16 / 16,
+ * 4 A2 Full, 5 A2 Lite), launch kind (0 frame list, 1 split list, 2 packed list, 4 a launch of its own, 5 split, joins the packed list),
+ * range proven, weights ok }, the input limit, and the kernel name NA_BatchStreamKernelName would report.  0, or -1.
+ * NA_DebugWaveNetLaunch: what ONE launch of n frames decides.  frame: the frame-kernel list (else a list of the f16-split kernels);
+ * groupFacts: 8 ints per group = { specialised chain, pack, fewest tiles per wave of the fast interpreter (0: generic), (virtual) streams,
+ * index lists present, largest staged block of the frame kernel (floats), most channel groups, most operands per stage }; sharing:
+ * launches that share the chip; beyondCache: the state exceeds the Infinity Cache; cus: compute units.  out = { kernel (0 none, 1 chain,
+ * 2 chain as a table launch, 3 stage interpreter, 4 frame kernel, 5 the caller cuts the list into launches of eight), hipError_t of a
+ * refusal, chain family member (0 Std, 1 Lite, 2 LitePacked, 3 Lite16T1, 4 A2), NF, SPB, NT, T, WPS, GEN, PK, PF }.  0, or -1. */
+NA_EXTERN int NA_DebugWaveNetKernel(NeuralModel* model, float quality, int streams, int knobMask, const int* knobs, int out[8], float* inputLimit, char* outName, int cap);
+NA_EXTERN int NA_DebugWaveNetLaunch(int frame, int n, int numGroups, const int* groupFacts, int sharing, int beyondCache, int cus, int knobMask, const int* knobs,
+	int out[11]);
 /* Tests: export / import kernel launches of the stream snapshots so far (one per model group and call, whatever the stream count) */
 NA_EXTERN long long NA_DebugSnapshotLaunches(void);
 /* Tests: which implementation of the NCCL entry points the multi-GPU host binds.  0 = librccl.so (the product).  1 = a loopback table

@@ -143,6 +143,67 @@ def recurrent_kernel(kind, hidden, layers=1, tail_layers=0, tail_width=0, tail_h
     return name.value.decode()
 
 
+# the knobs of the WaveNet decisions in the order of NA_DebugWaveNetKernel / NA_DebugWaveNetLaunch, by their environment names
+# ("NA_WN_KERNEL": "split" | "frame" | "generic" or 1 | 2 | 3; "NA_WN_PAD": 0 turns padding off; "NA_WN_SPEC": 0 turns the chains off;
+# NA_SP_T and NA_SP_GEN imply NA_WN_SPEC=0, as in the library's own parsing of the environment)
+WAVENET_KNOBS = ("NA_WN_KERNEL", "NA_WN_PACK", "NA_WN_PAD", "NA_WN_DENSE", "NA_SP_T", "NA_SP_SPB", "NA_SP_GEN", "NA_SP_NO_T1", "NA_FR_PF", "NA_FR_SPB",
+                 "NA_WN_SPEC")
+WAVENET_FAMILIES = {1: "f16-split", 2: "frame", 3: "generic"}
+WAVENET_LAUNCH_KERNELS = ("none", "chain", "chain table", "interpreter", "frame", "pieces")
+WAVENET_CHAINS = ("Std", "Lite", "LitePacked", "Lite16T1", "A2")
+
+
+def _wavenet_knob_args(knobs):
+    if knobs is None:
+        return -1, None
+    vals = (C.c_int * len(WAVENET_KNOBS))()
+    mask = 0
+    knobs = dict(knobs)
+    if ("NA_SP_T" in knobs or "NA_SP_GEN" in knobs) and "NA_WN_SPEC" not in knobs:
+        knobs["NA_WN_SPEC"] = 0
+    for name, v in knobs.items():
+        i = WAVENET_KNOBS.index(name)
+        if name == "NA_WN_KERNEL":
+            v = {"split": 1, "frame": 2, "generic": 3}.get(v, v)
+        elif name == "NA_WN_PAD":
+            v = int(int(v) == 0)  # (the knob of the decision is "padding off")
+        elif name in ("NA_SP_GEN", "NA_SP_NO_T1"):
+            v = 1  # (set at all: on)
+        vals[i] = int(v)
+        mask |= 1 << i
+    return mask, vals
+
+
+def wavenet_kernel(model, streams=1, quality=1.0, knobs=()):
+    """Test hook, host side only (NA_DebugWaveNetKernel): what a batch's model group decides once for `streams` streams of a WaveNet `model`
+    (csrc/wavenet_choice.h WaveNetKernelFor).  knobs: a dict of names from WAVENET_KNOBS (the environment is not read), or None for the
+    process's own tuning knobs."""
+    mask, vals = _wavenet_knob_args(knobs)
+    out = (C.c_int * 8)()
+    lim = C.c_float()
+    name = C.create_string_buffer(64)
+    if capi.load_library().NA_DebugWaveNetKernel(model._h, float(quality), int(streams), mask, vals, out, C.byref(lim), name, 64) != 0:
+        raise NeuralAudioError(capi.last_error() or "NA_DebugWaveNetKernel: bad argument")
+    return {"family": WAVENET_FAMILIES[out[0]], "pack": int(out[1]), "dense": bool(out[2]), "virtual": bool(out[3]), "spec_arch": int(out[4]),
+            "launch_kind": int(out[5]), "range_proven": bool(out[6]), "weights_ok": bool(out[7]), "input_limit": float(lim.value),
+            "kernel_name": name.value.decode()}
+
+
+def wavenet_launch(groups, n, frame=False, sharing=1, beyond_cache=False, cus=256, knobs=()):
+    """Test hook, host side only (NA_DebugWaveNetLaunch): the one kernel instantiation a launch of `n` frames of `groups` lands on
+    (csrc/wavenet_choice.h WaveNetLaunchFor).  groups: per group (spec_arch, pack, split_fast_T, streams, has_lists, max_a4_floats[, max_G,
+    max_split_ops]).  Returns (kernel, error, chain, NF, SPB, NT, T, WPS, GEN, PK, PF) as ints."""
+    mask, vals = _wavenet_knob_args(knobs)
+    flat = (C.c_int * (8 * max(len(groups), 1)))()
+    for i, g in enumerate(groups):
+        g = tuple(g) + (1, 16)[len(g) - 6:]
+        flat[8 * i:8 * i + 8] = [int(v) for v in g]
+    out = (C.c_int * 11)()
+    if capi.load_library().NA_DebugWaveNetLaunch(int(bool(frame)), int(n), len(groups), flat, int(sharing), int(bool(beyond_cache)), int(cus), mask, vals, out) != 0:
+        raise NeuralAudioError("NA_DebugWaveNetLaunch: bad argument")
+    return tuple(out)
+
+
 def _fptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 

@@ -39,6 +39,7 @@ NA_SYMBOLS = [
     "NA_RenderOfflineAtRate", "NA_RenderPlanAtRate", "NA_DebugSetRenderTap", "NA_MultiSetResampling", "NA_MultiGetResampleInfo",
     "NA_BatchReserveStreams", "NA_BatchActivateStream", "NA_BatchParkStream", "NA_BatchIsParked", "NA_BatchFindParked", "NA_BatchNumParked",
     "NA_DebugDeviceResourceCalls", "NA_DebugRecurrentPlan", "NA_DebugRecurrentShapePlan", "NA_DebugRecurrentKernel",
+    "NA_DebugWaveNetKernel", "NA_DebugWaveNetLaunch",
     "NA_BatchEnableOutputStage", "NA_BatchSetStreamGain", "NA_BatchGetStreamGain", "NA_BatchHandover", "NA_BatchHandoverRemaining",
     "NA_BatchEnableCabinetStage", "NA_BatchGetCabinetInfo", "NA_BatchLoadIR", "NA_BatchUnloadIR", "NA_BatchSetStreamIR", "NA_BatchGetStreamIR",
     "NA_BatchStreamIRFadeRemaining", "NA_DebugRunCabinetStage", "NA_DebugCabinetLaunches",
@@ -213,6 +214,8 @@ def load_library():
         "NA_DebugRecurrentPlan": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "NA_DebugRecurrentShapePlan": (C.c_int, [C.c_int] * 8 + [C.POINTER(C.c_int)]),
         "NA_DebugRecurrentKernel": (C.c_int, [C.c_int] * 9 + [C.c_char_p, C.c_int]),
+        "NA_DebugWaveNetKernel": (C.c_int, [vp, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_char_p, C.c_int]),
+        "NA_DebugWaveNetLaunch": (C.c_int, [C.c_int] * 3 + [C.POINTER(C.c_int)] + [C.c_int] * 4 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "NA_MultiCreate": (vp, [C.POINTER(C.c_int), C.c_int]),
         "NA_MultiDestroy": (None, [vp]),
         "NA_MultiAddStreams": (C.c_int, [vp, vp, C.c_float, C.c_int, C.c_int]),

@@ -12,6 +12,7 @@
 #include "stream_snapshot.h"
 #include "neural_model_impl.h"
 #include "lstm_launch.h"
+#include "wavenet_choice.h"
 #include "wavenet_launch.h"
 #include "wavenet_plan.h"
 #include "tuning.h"
@@ -319,7 +320,7 @@ int NA_DebugPackedWeights(NeuralModel* model, int* packFactor, float* out, int c
 			r = 0;
 			return;
 		}
-		const bool dense = na::Tuning::Get().wnDense != 0 && na::WaveNetPackCanBeDense(wn, P); // (the layout a batch would give it: four Nano streams at 16 / 8 channels)
+		const bool dense = na::WaveNetDenseFor(wn, P, na::WaveNetKnobs::FromTuning()); // (the layout a batch would give it: four Nano streams at 16 / 8 channels)
 		const na::WaveNetDesc v = na::PackWaveNetDesc(wn, P, dense);
 		na::ValidateWaveNetDesc(v); // weight count and chaining of the virtual model
 		const na::WaveNetPlan plan = na::BuildPackedWaveNetPlan(wn, P, dense);
@@ -383,6 +384,81 @@ int NA_DebugRecurrentKernel(int cell, int hidden, int numLayers, int tailLayers,
 		haveWT != 0, k).kernel;
 	if (outName && cap > 0) snprintf(outName, (size_t)cap, "%s", na::RecurrentKernelName(kernel));
 	return (int)kernel;
+}
+#endif
+
+// The WaveNet counterparts (wavenet_choice.h), host side only; the environment is not read.  Knobs: bit i of knobMask set = knob i takes
+// knobs[i], every other knob its default; knobMask -1 = the process's own tuning knobs.  Knob order: NA_WN_KERNEL (1 split, 2 frame,
+// 3 generic), NA_WN_PACK, NA_WN_PAD off, NA_WN_DENSE, NA_SP_T, NA_SP_SPB, NA_SP_GEN, NA_SP_NO_T1, NA_FR_PF, NA_FR_SPB, chains on (NA_WN_SPEC).
+#ifndef NA_RELEASE
+static bool DebugWaveNetKnobs(int knobMask, const int* v, na::WaveNetKnobs& k)
+{
+	if (knobMask == -1)
+	{
+		k = na::WaveNetKnobs::FromTuning();
+		return true;
+	}
+	if (knobMask < 0 || knobMask >= (1 << 11) || (knobMask != 0 && !v)) return false;
+	auto has = [&](int i) { return (knobMask >> i & 1) != 0; };
+	if (has(0)) k.wnKernel = v[0];
+	if (has(1)) k.wnPack = v[1];
+	if (has(2)) k.wnPadOff = v[2] != 0;
+	if (has(3)) k.wnDense = v[3];
+	if (has(4)) k.spT = v[4];
+	if (has(5)) k.spSpb = v[5];
+	if (has(6)) k.spGen = v[6] != 0;
+	if (has(7)) k.spNoT1 = v[7] != 0;
+	if (has(8)) k.frPrefetch = v[8];
+	if (has(9)) k.frSpb = v[9];
+	if (has(10)) k.specOn = v[10] != 0;
+	return true;
+}
+
+// What a batch's model group would decide for `streams` streams of the model at `quality` (WaveNetKernelFor): out = { family (1 f16-split,
+// 2 frame, 3 generic), pack, dense, packed or padded, specialised chain (WnSpecArch), LaunchKind, range proven, weights ok }, the input
+// limit and the reported kernel name; 0, or -1 on a bad argument or a model that is not a WaveNet.
+int NA_DebugWaveNetKernel(NeuralModel* model, float quality, int streams, int knobMask, const int* knobs, int out[8], float* inputLimit, char* outName, int cap)
+{
+	int r = -1;
+	Guard([&] {
+		NeuralAudio::GpuModel* gm = model ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+		na::WaveNetKnobs k;
+		if (!gm || !out || !DebugWaveNetKnobs(knobMask, knobs, k)) throw std::runtime_error("NA_DebugWaveNetKernel: bad argument");
+		const auto& lm = gm->GetLoadedModel();
+		if (lm->subModels.empty()) throw std::runtime_error("NA_DebugWaveNetKernel: empty model");
+		const na::ModelDesc& d = *lm->subModels[(size_t)(lm->isComposite ? lm->ModelIndexFromQuality(quality) : 0)].desc;
+		if (d.kind != na::MODEL_WAVENET) throw std::runtime_error("NA_DebugWaveNetKernel: not a WaveNet");
+		const na::WaveNetGroupChoice c = na::WaveNetKernelFor(d.wavenet, (!lm->isComposite && lm->subModels.size() == 1) ? streams : 0, k);
+		const int ints[8] = { (int)c.family, c.pack, c.dense, c.isVirtual, c.specArch, (int)c.kind, c.rangeProven, c.weightsOk };
+		memcpy(out, ints, sizeof(ints));
+		if (inputLimit) *inputLimit = c.inputLimit;
+		if (outName && cap > 0) snprintf(outName, (size_t)cap, "%s", c.KernelName(k.specOn));
+		r = 0;
+	});
+	return r;
+}
+
+// What one launch decides (WaveNetLaunchFor).  groupFacts: 8 ints per group = { specialised chain, pack, split_fast_T, streams, index lists
+// present, max_a4_floats, max_G, max_split_ops }.  out = { kernel (WnLaunchKernel: 0 none, 1 chain, 2 chain table, 3 interpreter, 4 frame,
+// 5 cut the list into launches of eight), error of a refusal, chain family member (WnChain), NF, SPB, NT, T, WPS, GEN, PK, PF }; 0, -1 on a bad argument.
+int NA_DebugWaveNetLaunch(int frame, int n, int numGroups, const int* groupFacts, int sharing, int beyondCache, int cus, int knobMask, const int* knobs, int out[11])
+{
+	int r = -1;
+	Guard([&] {
+		na::WaveNetKnobs k;
+		if (!out || numGroups < 0 || (numGroups > 0 && !groupFacts) || !DebugWaveNetKnobs(knobMask, knobs, k)) throw std::runtime_error("NA_DebugWaveNetLaunch: bad argument");
+		std::vector<na::WaveNetGroupFacts> facts((size_t)numGroups);
+		for (int i = 0; i < numGroups; i++)
+		{
+			const int* g = groupFacts + 8 * i;
+			facts[(size_t)i] = { g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7] };
+		}
+		const na::WaveNetLaunchChoice c = na::WaveNetLaunchFor({ frame != 0, n, facts.data(), numGroups, sharing, beyondCache != 0, cus }, k);
+		const int ints[11] = { (int)c.kernel, c.error, (int)c.chain, c.nf, c.spb, c.nt, c.t, c.wps, c.gen, c.pk, c.pf };
+		memcpy(out, ints, sizeof(ints));
+		r = 0;
+	});
+	return r;
 }
 #endif
 

@@ -40,8 +40,8 @@ namespace na
 
 namespace na
 {
-	// Host side only (no device): which kernel family a batch would pick for `streams` streams of this submodel -- the constructor logic
-	// of WaveNetGroup (pack / pad / range proof / FamilyFor) -- and the facts of the range proof behind the choice.
+	// Host side only (no device): which kernel family a batch would pick for `streams` streams of this submodel -- what its WaveNetGroup
+	// would ask (wavenet_choice.h WaveNetKernelFor) -- and the facts of the range proof behind the choice.
 	ModelKernelInfo PredictModelKernel(const LoadedModel& model, float quality, int streams)
 	{
 		ModelKernelInfo info;
@@ -53,17 +53,13 @@ namespace na
 			info.kernel = "recurrent";
 			return info;
 		}
-		const WaveNetPlan real = BuildWaveNetPlan(d.wavenet, true);
-		info.inputLimit = real.condLimit;
-		info.rangeProven = real.splitRangeProven;
-		info.weightsOk = real.splitWeightsOk;
 		const int packHint = (!model.isComposite && model.subModels.size() == 1) ? streams : 0;
-		const int pack = WaveNetGroup::PackFor(d.wavenet, packHint);
-		const bool isVirtual = pack > 1 || WaveNetGroup::PadFor(d.wavenet);
-		const WnFamily fam = isVirtual ? WN_FAMILY_SPLIT : FamilyFor(real);
-		info.pack = pack;
-		info.kernel = fam == WN_FAMILY_SPLIT ? "f16-split" : (fam == WN_FAMILY_GENERIC ? "generic" : "frame");
-		if (fam != WN_FAMILY_SPLIT && fam != WN_FAMILY_GENERIC) info.inputLimit = INFINITY;
+		const WaveNetGroupChoice c = WaveNetKernelFor(d.wavenet, packHint, WaveNetKnobs::FromTuning());
+		info.kernel = c.FamilyName();
+		info.pack = c.pack;
+		info.inputLimit = c.inputLimit;
+		info.rangeProven = c.rangeProven;
+		info.weightsOk = c.weightsOk;
 		return info;
 	}
 
@@ -82,6 +78,7 @@ namespace na
 			const double B = plan.AlgorithmicBytesPerSample(WN_MAX_FRAMES);
 			if (plan.genericOnly) return 1000.0 * plan.maxChannels / 32.0; // 1.0 ms per block at 32 channels (<= 256 streams)
 			const bool composite = model.isComposite;
+			// (deliberately the fit's own predicate, not the dispatch's -- wavenet_choice.h WaveNetKernelFor: the fit was made against it)
 			const bool split = plan.splitFastT == 2 || (!composite && (WaveNetPackFactor(d.wavenet) > 1 || WaveNetWantsPadding(d.wavenet)));
 			return split ? 22.3 + 0.0143 * B : 31.6 + 0.0164 * B;
 		}
@@ -682,45 +679,37 @@ namespace na
 		(void)CountedHipFree(dRows);
 	}
 
-	// prepareOnly: upload the group tables the list's launches will look up and launch nothing (the pass in front of a stream capture)
+	// One choice per chunk (wavenet_choice.h WaveNetLaunchFor) and the launcher it names.  prepareOnly: upload the group tables the list's
+	// launches will look up and launch nothing (the pass in front of a stream capture)
 	void GpuBatch::LaunchWaveNetList(const ModelCall& c, LaunchKind which, const std::vector<WnFrameGroup>& list, hipStream_t s, bool prepareOnly)
 	{
 		WnLaunchTable& table = wnTable[(int)which];
+		const bool frame = which == LaunchKind::Frame;
+		const int sharing = 1 | WnBeyondCacheBit(StateBytes());
+		const WnLaunchContext ctx = WnLaunchContext::Current();
 		bool compact = false;
 		for (const WnFrameGroup& g : list) compact = compact || g.model->compact_rings != 0;
 		size_t offset = 0, left = c.n;
 		while (left > 0)
 		{
 			const int chunk = NextWaveNetChunk(left, compact);
-			// more groups than one launch's kernarg table holds (a batch of many different models): ONE launch with the table in device
-			// memory where the chains have one (128-frame blocks of the A1 families), else launches of eight groups each
-			if (which != LaunchKind::Frame && list.size() > (size_t)WN_FRAME_MAX_GROUPS)
+			const float* in = c.dIn + offset;
+			float* out = c.dOut + offset;
+			const WaveNetLaunchChoice choice = WaveNetLaunchChoiceOf(ctx, frame, list.data(), (int)list.size(), chunk, sharing, &wnFacts);
+			if (choice.kernel == WnLaunchKernel::Pieces)
+			{
+				// more groups than one launch's kernarg table holds (a batch of many different models) and no table launch for them: launches
+				// of eight groups each
+				for (size_t first = 0; first < list.size() && !prepareOnly; first += WN_FRAME_MAX_GROUPS)
+					CheckHip(LaunchWaveNetGroups(ctx, frame, list.data() + first, (int)std::min<size_t>(list.size() - first, (size_t)WN_FRAME_MAX_GROUPS), in, out, c.inStride,
+						c.outStride, chunk, s, sharing), "WaveNet kernel (fused)");
+			}
+			else if (choice.kernel == WnLaunchKernel::ChainTable || !prepareOnly)
 			{
 				table.prepareOnly = prepareOnly;
-				const hipError_t te = LaunchWaveNetSpecTable(list.data(), (int)list.size(), c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s, table);
+				const hipError_t e = LaunchWaveNetChoice(choice, list.data(), (int)list.size(), in, out, c.inStride, c.outStride, chunk, s, &table);
 				table.prepareOnly = false;
-				if (te == hipSuccess)
-				{
-					offset += (size_t)chunk;
-					left -= (size_t)chunk;
-					continue;
-				}
-				if (te != hipErrorNotSupported) CheckHip(te, "WaveNet kernel (table launch)");
-				(void)hipGetLastError();
-			}
-			if (prepareOnly)
-			{
-				offset += (size_t)chunk;
-				left -= (size_t)chunk;
-				continue;
-			}
-			for (size_t first = 0; first < list.size(); first += WN_FRAME_MAX_GROUPS)
-			{
-				const int count = (int)std::min<size_t>(list.size() - first, (size_t)WN_FRAME_MAX_GROUPS);
-				CheckHip(which == LaunchKind::Frame ? LaunchWaveNetFrameFused(list.data() + first, count, c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s)
-													: LaunchWaveNetSplitFused(list.data() + first, count, c.dIn + offset, c.dOut + offset, c.inStride, c.outStride, chunk, s,
-														1 | WnBeyondCacheBit(StateBytes())),
-					"WaveNet kernel (fused)");
+				CheckHip(e, choice.kernel == WnLaunchKernel::ChainTable ? "WaveNet kernel (table launch)" : "WaveNet kernel (fused)");
 			}
 			offset += (size_t)chunk;
 			left -= (size_t)chunk;

@@ -472,6 +472,7 @@ namespace na
 		// ring in pinned host memory -- for the batches the chains serve whose buffer is one launch of 128-frame A1 Standard blocks
 		struct ResidentState;
 		std::unique_ptr<ResidentState> residentState;
+		std::vector<WaveNetGroupFacts> wnFacts; // scratch of LaunchWaveNetList: the facts of a list longer than a launch's kernarg segment (no allocation per buffer)
 		WnLaunchTable wnTable[4]; // device tables of launch lists with more groups than a launch's kernarg segment holds (gpu_batch.cpp LaunchWaveNetList), by LaunchKind
 		bool lastStepResident = false;
 		bool residentWanted = Tuning::Get().residentOn;

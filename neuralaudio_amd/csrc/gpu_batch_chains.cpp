@@ -445,10 +445,11 @@ namespace na
 		{
 			// (a buffer longer than a launch takes: the chunks one after the other on this chain -- the chains still never wait for each other)
 			size_t offset = 0, left = n;
+			const WnLaunchContext ctx = WnLaunchContext::Current();
 			while (left > 0)
 			{
 				const int chunk = NextWaveNetChunk(left, halfLists->compact);
-				CheckHip(LaunchWaveNetSplitFused(part.data(), (int)part.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, halfStream[h],
+				CheckHip(LaunchWaveNetGroups(ctx, false, part.data(), (int)part.size(), dIn + offset, dOut + offset, inStride, outStride, chunk, halfStream[h],
 					(hostRows ? 1 : numChains) | WnBeyondCacheBit(StateBytes())), "WaveNet kernel (half batch)");
 				offset += (size_t)chunk;
 				left -= (size_t)chunk;

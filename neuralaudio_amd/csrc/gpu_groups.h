@@ -22,6 +22,7 @@
 #include "lstm_launch.h"
 #include "stream_snapshot.h"
 #include "tuning.h"
+#include "wavenet_choice.h"
 #include "wavenet_launch.h"
 #include "wavenet_plan.h"
 
@@ -370,51 +371,6 @@ namespace na
 
 	inline namespace groups
 	{
-		// WaveNet kernel families: "split" = the f16-split MFMA kernel (wavenet_split_kernels.hip), "frame" = the f32 4x4x1-MFMA kernel
-		// (wavenet_frame_kernels.hip), "generic" = the runtime-shaped kernel for layer arrays wider than 16 channels
-		// (wavenet_generic_kernels.hip; frame-kernel state format).  NA_WN_KERNEL=split|frame|generic forces one for every model it can
-		// run (tuning / tests); default: chosen per model (FamilyFor).
-		enum WnFamily { WN_FAMILY_AUTO, WN_FAMILY_SPLIT, WN_FAMILY_FRAME, WN_FAMILY_GENERIC };
-		inline WnFamily WaveNetFamilyOverride()
-		{
-			const int k = Tuning::Get().wnKernel;
-			return k == 1 ? WN_FAMILY_SPLIT : (k == 2 ? WN_FAMILY_FRAME : (k == 3 ? WN_FAMILY_GENERIC : WN_FAMILY_AUTO));
-		}
-
-		// Which kernel family runs a model (fixed for the life of its group: the families keep different stream-state formats).
-		// Measured on MI355X, 1024 streams x 128 frames: the f16-split kernel wins where its fast instantiation applies with 2 tiles
-		// per wave (every array has 5..8 or 13..16 channels, K = 3: Standard 50 vs 60 us); narrow (Feather, Nano: <= 4-channel
-		// arrays) and large-kernel (A2) models are faster on the frame kernel (33 / 30 / 71 us vs 44 / 44 / 133 us); a 12-channel model (Lite)
-		// is too as it is (46 vs 50 us), but padded to 16 / 8 channels it runs the fast split flavour (PadFor below: 42.6 us).
-		// May the f16-split kernels run this plan at all?  Their values are (hi, lo) pairs of f16: the plan builder proves statically that
-		// with inputs inside +-condLimit (>= kSplitMinInputLimit) nothing leaves the f16 range and that the weights fit the operand format
-		// (wavenet_plan.cpp).  A model that fails the proof runs on the f32 frame kernel -- no clamp, no overflow, the
-		// reference's own number format -- and NA_BatchStreamKernelName says so.  One exception: the official A2 shapes (LeakyReLU: the
-		// worst-case bound grows with the product of 23 layers' row sums and fails for every trained model) stay on their chains, which
-		// saturate instead of overflowing and count the event (wavenet_split_dev.h SplitQuadSat, NA_BatchStreamRangeEvents).
-		inline bool SplitAllowed(const WaveNetPlan& plan)
-		{
-			if (plan.genericOnly || !plan.splitWeightsOk || plan.rings.size() > (size_t)WN_RANGE_EVENT_SLOT) return false;
-			if (plan.splitRangeProven) return true;
-			const int spec = WaveNetSpecArchId(plan.sstages.data(), (int)plan.sstages.size(), plan.stateF4, (int)(plan.wsplit.size() / 8));
-			return spec == WN_SPEC_A2FULL || spec == WN_SPEC_A2LITE;
-		}
-
-		inline WnFamily FamilyFor(const WaveNetPlan& plan)
-		{
-			if (plan.genericOnly) return WN_FAMILY_GENERIC; // > 16 channels: the runtime-shaped kernel is the only one that runs it
-			const WnFamily o = WaveNetFamilyOverride();
-			if (o == WN_FAMILY_GENERIC && !plan.genericOk) return WN_FAMILY_FRAME; // (conv heads: not in the runtime-shaped kernel)
-			if (o == WN_FAMILY_SPLIT && !SplitAllowed(plan)) return WN_FAMILY_FRAME; // (the range proof outranks the tuning knob)
-			if (o != WN_FAMILY_AUTO) return o;
-			if (!SplitAllowed(plan)) return WN_FAMILY_FRAME;
-			if (plan.splitFastT == 2) return WN_FAMILY_SPLIT;
-			// the A2 submodels have compile-time specialised chains on the split kernels' state format (wavenet_spec_kernels.hip; round 3:
-			// 2048-stream quality sweep 120 us on the frame kernel); blocks that are not 128 / 64 frames fall to the stage interpreter
-			const int spec = WaveNetSpecArchId(plan.sstages.data(), (int)plan.sstages.size(), plan.stateF4, (int)(plan.wsplit.size() / 8));
-			return (spec == WN_SPEC_A2FULL || spec == WN_SPEC_A2LITE) ? WN_FAMILY_SPLIT : WN_FAMILY_FRAME;
-		}
-
 		// Frames of the next launch of a buffer with `left` frames to go.  Models with compact rings (wavenet_dev.h) take 128, 64 or at
 		// most 32 frames per launch -- the lengths for which a block never reads a ring position it writes; everything else 128 at a time
 		// (the reference chunks at 64, InternalModel.h:104-117; results do not depend on the chunking).
@@ -428,68 +384,14 @@ namespace na
 		class WaveNetGroup : public ModelGroup
 		{
 		public:
-			// Stream packing (wavenet_plan.cpp PackWaveNetDesc): several streams of a NARROW model share one virtual stream of the f16-split
-			// kernel -- 4 streams for <= 4-channel arrays (Nano), 2 for <= 8 (Feather).  With the compile-time specialised chains it wins at
-			// every batch size (measured, 128-frame blocks, us per step packed / f32 frame kernel: Nano 64 streams 19.5 / 24.5, 1024: 26.8 /
-			// 30.6, 4096: 61 / 113; Feather 64: 15.4 / 26.5, 1024: 24.3 / 33.6), so every static narrow model that is not a submodel of a
-			// slimmable container (`packHint` > 0: its members are always active) runs packed, whatever the AddStreams call pattern -- the
-			// state layout of a group never depends on how its streams arrived.  NA_WN_PACK=0 turns packing off.
-			static int PackFor(const WaveNetDesc& wn, int packHint)
-			{
-				const int mode = Tuning::Get().wnPack;
-				const WnFamily o = WaveNetFamilyOverride();
-				if (packHint <= 0 || mode == 0 || (o != WN_FAMILY_AUTO && o != WN_FAMILY_SPLIT)) return 1;
-				ValidateWaveNetDesc(wn);
-				for (const WnArrayCfg& cfg : wn.arrays)
-					if (cfg.channels > 16) return 1;
-				const int P = WaveNetPackFactor(wn);
-				if (P < 2) return 1;
-				// packing means the f16-split kernels: only for a model that passes their range proof (block-diagonal packing keeps every
-				// row sum, so the real model's proof is the virtual model's)
-				return SplitAllowed(BuildWaveNetPlan(wn, true)) ? P : 1;
-			}
-
-			// Padding without packing (wavenet_plan.cpp WaveNetWantsPadding): a model whose arrays do not fill their lane mode (A1 Lite:
-			// 12 / 6 channels) is widened to 16 / 8 and runs the fast flavour of the split kernel (1024 streams: 43.8 vs 46.0 us on the
-			// frame kernel, 1365: 66.4 vs 76.0).  NA_WN_PAD=0 turns it off.
-			static bool PadFor(const WaveNetDesc& wn)
-			{
-				const bool off = Tuning::Get().wnPadOff;
-				const WnFamily o = WaveNetFamilyOverride();
-				if (off || (o != WN_FAMILY_AUTO && o != WN_FAMILY_SPLIT)) return false;
-				ValidateWaveNetDesc(wn);
-				return WaveNetWantsPadding(wn) && SplitAllowed(BuildWaveNetPlan(wn, true));
-			}
-
-			// The two state formats size their rings differently (wavenet_plan.cpp AddRing): the plan is built for the f16-split kernels
-			// first, and once more for the others when the family choice (which looks at the stage program, not at the rings) says so
-			static WaveNetPlan PlanForItsFamily(const WaveNetDesc& wn)
-			{
-				WaveNetPlan p = BuildWaveNetPlan(wn, true);
-				if (FamilyFor(p) == WN_FAMILY_SPLIT) return p;
-				return BuildWaveNetPlan(wn, false);
-			}
-
-			// Dense packs (wavenet_plan.cpp WaveNetPackCanBeDense: four Nano streams at 16 / 8 instead of 16 / 16 virtual channels -- half the
-			// ring traffic of the second array, two tiles per MFMA in its thirteen layers).  Faster at every batch size (round 5, us per
-			// 128-frame step dense / 16 x 16: 16 streams 15.3 / 16.0, 1024: 17.7 / 20.0 -- the 16 / 16 layout's one-tile-per-wave chain
-			// included --, 4096: 32.4 / 48.2, 8192: 67.6 / 97.0), so it is the layout of every such group.  NA_WN_DENSE=0: the 16 / 16 layout.
-			static bool DenseFor(const WaveNetDesc& wn, int pack)
-			{
-				return pack > 1 && Tuning::Get().wnDense != 0 && WaveNetPackCanBeDense(wn, pack);
-			}
-
+			// Which kernel family runs the model, packed / padded or not, on which chain and in which launch list: decided ONCE, here, by
+			// WaveNetKernelFor (wavenet_choice.h) -- fixed for the life of the group, the families keep different stream-state formats.
 			// packHint: 0 = never pack (submodel of a container), otherwise the number of streams the creating AddStreams call brings
 			WaveNetGroup(const std::shared_ptr<const ModelDesc>& d, hipStream_t s, int packHint = 0, bool peerWeights = false)
-				: ModelGroup(d, s), columnsPending(peerWeights), pack(PackFor(d->wavenet, packHint)), dense(DenseFor(d->wavenet, pack)),
-				  plan((pack > 1 || PadFor(d->wavenet)) ? BuildPackedWaveNetPlan(d->wavenet, pack, dense) : PlanForItsFamily(d->wavenet)),
-				  family(plan.isVirtual() ? WN_FAMILY_SPLIT : FamilyFor(plan))
+				: ModelGroup(d, s), columnsPending(peerWeights), choice(WaveNetKernelFor(d->wavenet, packHint, WaveNetKnobs::FromTuning())),
+				  pack(choice.pack), plan(choice.plan), family(choice.family)
 			{
-				if (plan.isVirtual())
-				{
-					if (plan.splitFastT != 2) throw std::runtime_error("internal: packed / padded WaveNet plan is not a fast split-kernel plan");
-					realPlan = BuildWaveNetPlan(d->wavenet); // bookkeeping (bytes / MACs per REAL stream)
-				}
+				kind = choice.kind;
 				dStages.Upload(plan.stages, stream);
 				// (the weight images -- WeightImages() below -- may be left for a peer device to fill: the multi-GPU host's RCCL fan-out)
 				dWpack.UploadUnless(peerWeights, plan.wpack, stream);
@@ -571,9 +473,7 @@ namespace na
 				dev.cond_limit = plan.condLimit;
 				dev.saturate = plan.splitRangeProven ? 0 : 1;
 				dev.compact_rings = (family == WN_FAMILY_SPLIT && plan.compactRings) ? 1 : 0;
-				dev.spec_arch = family == WN_FAMILY_SPLIT ? WaveNetSpecArchId(plan.sstages.data(), (int)plan.sstages.size(), plan.stateF4, (int)(plan.wsplit.size() / 8)) : WN_SPEC_NONE;
-				if (family == WN_FAMILY_SPLIT) kind = pack > 1 ? LaunchKind::SplitPacked : (plan.splitFastT == 2 ? LaunchKind::SplitJoinsPacked : LaunchKind::Split);
-				else kind = family == WN_FAMILY_GENERIC ? LaunchKind::Own : LaunchKind::Frame;
+				dev.spec_arch = choice.specArch;
 			}
 
 			// ChannelHistoryBuffer::AllocBuffer zero-fills (WaveNet.h:38-40)
@@ -653,24 +553,23 @@ namespace na
 				const int numActive = (int)hSlots.size();
 				if (numActive == 0) return;
 				size_t offset = 0;
+				const WnLaunchContext ctx = family == WN_FAMILY_GENERIC ? WnLaunchContext{} : WnLaunchContext::Current();
 				while (n > 0)
 				{
 					const int chunk = NextWaveNetChunk(n, dev.compact_rings != 0);
-					const WnFamily which = family;
-					if (which == WN_FAMILY_SPLIT)
-					{
-						const WnFrameGroup g = LaunchArgs(false);
-						// (sharing 1; the state of this group's streams alone beyond the Infinity Cache: non-temporal ring traffic for the long dilations)
-						CheckHip(LaunchWaveNetSplitFused(&g, 1, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream,
-							1 | WnBeyondCacheBit((size_t)numActive * StateBytesPerStream())), "WaveNetSplitKernel");
-					}
-					else if (which == WN_FAMILY_GENERIC)
+					if (family == WN_FAMILY_GENERIC)
 						CheckHip(LaunchWaveNetGeneric(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
 							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, plan.condLimit, !plan.splitRangeProven, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
 							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetGenericKernel");
 					else
-						CheckHip(LaunchWaveNetFrame(dev, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive, dIn + offset, dOut + offset,
-							inStride, outStride, chunk, launchStream, contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0), "WaveNetFrameKernel");
+					{
+						// a launch of this group alone (sharing 1; split family: the state of this group's streams alone beyond the Infinity Cache
+						// means non-temporal ring traffic for the long dilations): facts, one choice, one launcher (wavenet_launch.h)
+						const WnFrameGroup g = LaunchArgs(false);
+						const bool frame = family == WN_FAMILY_FRAME;
+						CheckHip(LaunchWaveNetGroups(ctx, frame, &g, 1, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream,
+							frame ? 1 : (1 | WnBeyondCacheBit((size_t)numActive * StateBytesPerStream()))), frame ? "WaveNetFrameKernel" : "WaveNetSplitKernel");
+					}
 					offset += (size_t)chunk;
 					n -= (size_t)chunk;
 				}
@@ -685,11 +584,11 @@ namespace na
 					contiguous ? hRows[0] : 0, pack };
 			}
 
-			double AlgorithmicBytesPerSample(int blockFrames) const override { return (plan.isVirtual() ? realPlan : plan).AlgorithmicBytesPerSample(blockFrames); }
-			double MacsPerSample() const override { return (plan.isVirtual() ? realPlan : plan).MacsPerSample(); }
+			double AlgorithmicBytesPerSample(int blockFrames) const override { return (choice.isVirtual ? choice.realPlan : plan).AlgorithmicBytesPerSample(blockFrames); }
+			double MacsPerSample() const override { return (choice.isVirtual ? choice.realPlan : plan).MacsPerSample(); }
 			size_t StateBytesPerStream() const override { return (size_t)plan.stateF4 * 16 / (size_t)pack; }
-			int PackFactor() const override { return pack; }
-			float InputLimit() const override { return (family == WN_FAMILY_SPLIT || family == WN_FAMILY_GENERIC) ? plan.condLimit : INFINITY; }
+			int PackFactor() const override { return choice.pack; }
+			float InputLimit() const override { return choice.inputLimit; }
 			void WeightsArrived() override
 			{
 				if (!columnsPending) return;
@@ -717,7 +616,7 @@ namespace na
 				CheckHip(hipStreamSynchronize(stream), "hipStreamSynchronize");
 				return count;
 			}
-			uint32_t SnapshotNativeEncoding() const override { return family == WN_FAMILY_SPLIT ? SNAP_SPLIT : SNAP_F32; }
+			uint32_t SnapshotNativeEncoding() const override { return choice.family == WN_FAMILY_SPLIT ? SNAP_SPLIT : SNAP_F32; }
 			void SaveState(const std::vector<int>& members, uint32_t* dStaging) override
 			{
 				if (members.empty()) return;
@@ -730,12 +629,7 @@ namespace na
 				const WnSnapshotArgs a = SnapshotArgs(members, &encodings);
 				CheckHip(LaunchWaveNetSnapshotImport(a, dStaging, stream), "WaveNetSnapshotImportKernel");
 			}
-			const char* KernelName() const override
-			{
-				// (a model with a specialised chain runs it for blocks of 128 / 64 / 32 frames, the interpreter for other lengths)
-				if (family == WN_FAMILY_SPLIT) return (dev.spec_arch != WN_SPEC_NONE && WaveNetSpecEnabled()) ? "WaveNetSpecKernel" : "WaveNetSplitKernel";
-				return family == WN_FAMILY_GENERIC ? (plan.maxChannels > 64 ? "WaveNetWideKernel" : "WaveNetGenericKernel") : "WaveNetFrameKernel";
-			}
+			const char* KernelName() const override { return choice.KernelName(WaveNetSpecEnabled()); }
 
 			// Packed groups: the launch lists name VIRTUAL streams -- slot = member / pack -- and hold `pack` rows each (-1: no member in
 			// that position yet).  Members of a static model are always active, so a virtual stream runs as soon as it has one member.
@@ -824,11 +718,10 @@ namespace na
 			}
 
 			bool columnsPending;  // the weight images arrive from a peer device: the prewarm columns are computed then (WeightsArrived)
-			const int pack;       // real streams per virtual stream (1: no packing)
-			const bool dense;     // ... two streams per channel group in the last array (DenseFor)
-			WaveNetPlan plan;     // pack > 1: of the VIRTUAL model
-			WaveNetPlan realPlan; // pack > 1: of the real model (bookkeeping only)
-			const WnFamily family;
+			const WaveNetGroupChoice choice; // which kernel runs this model, decided at construction (wavenet_choice.h WaveNetKernelFor), and its plans
+			const int pack;          // choice.pack: real streams per virtual stream (1: no packing)
+			const WaveNetPlan& plan; // choice.plan: what the group runs (pack > 1 or padded: of the VIRTUAL model)
+			const WnFamily family;   // choice.family
 			WnModelDev dev = {};
 			DevArray<WnStage> dStages;
 			DevArray<float> dWpack;

@@ -9,7 +9,7 @@ namespace na
 	struct Tuning
 	{
 		// WaveNet: kernel family and layout
-		int wnKernel = 0;          // NA_WN_KERNEL=split|frame|generic -> 1 | 2 | 3; 0: per model (FamilyFor)
+		int wnKernel = 0;          // NA_WN_KERNEL=split|frame|generic -> 1 | 2 | 3; 0: per model (wavenet_choice.h WaveNetKernelFor)
 		int wnPack = -1;           // NA_WN_PACK=0: no stream packing; -1: default
 		int wnDense = -1;          // NA_WN_DENSE=0: four Nano streams packed at 16 / 16 virtual channels (default: 16 / 8, two streams per channel group of the second array)
 		int wnNtFromMB = 400;      // NA_WN_NT_MB: stream state (MiB) from which a batch's long-dilation ring traffic is non-temporal (wavenet_launch.h WnBeyondCacheBit)

@@ -1,5 +1,5 @@
 // wavenet_dev.h -- device-side data model shared by the host packer (wavenet_plan.cpp) and the gfx950 WaveNet kernels
-// (wavenet_split_kernels.hip and wavenet_frame_kernels.hip, one per model, see FamilyFor() in gpu_batch.cpp; the tile / packed-FMA
+// (wavenet_split_kernels.hip and wavenet_frame_kernels.hip, one per model, see WaveNetKernelFor() in wavenet_choice.h; the tile / packed-FMA
 // fields below belong to the round-1 alternatives kept under tools/alternates/, not built into the library).
 //
 // A WaveNet model (reference: NeuralAudio/WaveNet.h) is lowered at load time into a short "stage program" (WnStage: one per

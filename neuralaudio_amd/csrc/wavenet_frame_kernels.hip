@@ -1,8 +1,8 @@
 // wavenet_frame_kernels.hip -- the "lane = frame" WaveNet block kernel for gfx950 (v_mfma_f32_4x4x1_16b_f32).
 //
 // The f32 kernel of round 1; since round 2 it serves the models the f16-split kernel (wavenet_split_kernels.hip) is not faster on --
-// narrow (<= 4-channel arrays) models in batches of up to 1024 streams and large-kernel (A2) architectures, see FamilyFor() / PackFor() /
-// PadFor() in gpu_batch.cpp (reference functions:
+// narrow (<= 4-channel arrays) models in batches of up to 1024 streams and large-kernel (A2) architectures, see WaveNetKernelFor() in
+// wavenet_choice.h (reference functions:
 // WaveNetModelT/LayerArrayT/LayerT::Process, Conv1DT::Process, DenseLayerT::Process -- NeuralAudio/WaveNet.h:768-799,
 // 632-661,462-494,139-290,336-383; FastMath -- NeuralAudio/Activation.h:83-118), different mapping of the arithmetic:
 //
@@ -1015,7 +1015,7 @@ namespace na
 			static_assert(FrameWeightStrideF4(0, WPS, SPB) == WeightStager<WPS * SPB>::WCOPY * 64 * WPS * SPB, "frame_lds.h restates the stager");
 			const int maxA4F4 = FrameWeightStrideF4(maxA4Floats, WPS, SPB);
 			const size_t lds = FrameLaunchLdsBytes(maxA4Floats, WPS, SPB, PF);
-			if (lds > FRAME_LDS_LIMIT) return hipErrorInvalidValue; // (the callers below choose a shape that fits; a loaded model has one)
+			if (lds > FRAME_LDS_LIMIT) return hipErrorInvalidValue; // (WaveNetLaunchFor chooses a shape that fits; a loaded model has one)
 			auto kernel = WaveNetFrameKernel<WPS, PF, SPB>;
 			if (lds > 64 * 1024)
 			{
@@ -1030,49 +1030,21 @@ namespace na
 		}
 	}
 
-	hipError_t LaunchWaveNetFrameFused(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
-		hipStream_t stream)
+	// WaveNetFrameKernel<WPS, PF, SPB> as WaveNetLaunchFor chose it (wavenet_choice.h FrameFor): a switch over the instantiations
+	hipError_t LaunchWaveNetFrameFused(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream)
 	{
-		if (n <= 0 || numGroups <= 0) return hipSuccess;
-		if (n > WN_MAX_FRAMES || numGroups > WN_FRAME_MAX_GROUPS) return hipErrorInvalidValue;
-		int total = 0;
-		int maxA4 = 0; // the launch's LDS follows the largest staged block among its groups
-		for (int i = 0; i < numGroups; i++)
+		if (c.kernel != WnLaunchKernel::Frame) return hipErrorInvalidValue;
+		switch (c.wps * 100 + c.pf * 10 + c.spb)
 		{
-			if (groups[i].numStreams <= 0) return hipErrorInvalidValue;
-			total += groups[i].numStreams;
-			maxA4 = std::max(maxA4, groups[i].model->max_a4_floats);
+		case 201: return fr::Launch<2, 0, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 214: return fr::Launch<2, 1, 4>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 222: return fr::Launch<2, 2, 2>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 221: return fr::Launch<2, 2, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 212: return fr::Launch<2, 1, 2>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 211: return fr::Launch<2, 1, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 101: return fr::Launch<1, 0, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
 		}
-		const int prefetch = Tuning::Get().frPrefetch; // tuning knob: 0 none, 1 history prefetch into registers, 2 into LDS (LDS-DMA)
-		const int spbEnv = Tuning::Get().frSpb;            // tuning knob: streams per workgroup (1, 2, 4)
-		// streams per workgroup: two streams share one staged copy of the weights once there are enough streams to cover all 256 CUs
-		// (measured 1024 x Standard: SPB 1 / 2 / 4 = 61.5 / 61.3 / 65.0 us -- at 4 the 8-wave barrier skew eats the saving)
-		const int spb = spbEnv > 0 ? spbEnv : (total >= 512 ? 2 : 1);
-		if (n > 64)
-		{
-			// ... the largest count up to that wish whose LDS fits (frame_lds.h): large kernels leave room for fewer block images beside
-			// their staged weights, and the LDS history buffers of prefetch 2 give way to the register prefetch before a launch fails.
-			// Precedence under NA_FR_PF=2: the knob asks for the LDS prefetch, so it is kept over the second stream -- <2,2,2>, then
-			// <2,2,1>, and only where neither fits the register prefetch <2,1,2> / <2,1,1>.  One stream per workgroup with the register
-			// prefetch fits every model that loaded (CheckWaveNetRunnable).
-			if (!prefetch) return fr::Launch<2, 0, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
-			if (spb >= 4 && FrameLaunchFits(maxA4, 2, 4, 1)) return fr::Launch<2, 1, 4>(groups, numGroups, in, out, inStride, outStride, n, stream);
-			if (prefetch == 2)
-			{
-				if (spb >= 2 && FrameLaunchFits(maxA4, 2, 2, 2)) return fr::Launch<2, 2, 2>(groups, numGroups, in, out, inStride, outStride, n, stream);
-				if (FrameLaunchFits(maxA4, 2, 1, 2)) return fr::Launch<2, 2, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
-			}
-			if (spb >= 2 && FrameLaunchFits(maxA4, 2, 2, 1)) return fr::Launch<2, 1, 2>(groups, numGroups, in, out, inStride, outStride, n, stream);
-			return fr::Launch<2, 1, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
-		}
-		return fr::Launch<1, 0, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
-	}
-
-	hipError_t LaunchWaveNetFrame(const WnModelDev& m, float* state, const int* slots, const int* rows, int numStreams, const float* in, float* out,
-		long inStride, long outStride, int n, hipStream_t stream, int slot0, int row0)
-	{
-		if (numStreams <= 0 || n <= 0) return hipSuccess;
-		WnFrameGroup g = { &m, state, slots, rows, numStreams, slot0, row0 };
-		return LaunchWaveNetFrameFused(&g, 1, in, out, inStride, outStride, n, stream);
+		return hipErrorInvalidValue;
 	}
 }

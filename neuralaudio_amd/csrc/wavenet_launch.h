@@ -6,17 +6,17 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include "device_once.h"
 #include "device_resources.h"
 #include "tuning.h"
+#include "wavenet_launch_choice.h"
 #include "wavenet_dev.h"
 
 namespace na
 {
 	// One block of n <= 128 frames for `numStreams` streams of one model:
 	//   slots[i]: state slot of active stream i; rows[i]: its row in `in`/`out` (row stride in floats).
-	// Lane = frame kernel on v_mfma_f32_4x4x1_16b_f32 (wavenet_frame_kernels.hip).
-	// One launch over several model groups (a heterogeneous batch): workgroups are assigned to the groups in order.
-	constexpr int WN_FRAME_MAX_GROUPS = 8;
+	// One launch over several model groups (a heterogeneous batch, at most WN_FRAME_MAX_GROUPS): workgroups are assigned to the groups in order.
 	struct WnFrameGroup
 	{
 		const WnModelDev* model;
@@ -28,21 +28,27 @@ namespace na
 		// streams and rows holds `pack` entries per virtual stream (-1: no real stream in that position); slots must not be nullptr
 		int pack;
 	};
-	hipError_t LaunchWaveNetFrameFused(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
-		hipStream_t stream);
+	struct WnLaunchTable;
 
-	// Same contract, the f16-split MFMA kernel (wavenet_split_kernels.hip) -- the shipped path.  Its stream state uses split quads in
-	// frame-major rings (see WnSplitStage), so a model group stays on one kernel family for its whole life.
-	// sharing: how many launches of this size run on the chip at the same time (the free-running half-batch chains: 2) -- the
-	// workgroup shape is chosen for what is resident, not for what one launch brings
-	hipError_t LaunchWaveNetSplitFused(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
-		hipStream_t stream, int sharing = 1);
+	// ---- the launchers: each is a switch over the instantiations of ONE kernel, on the choice WaveNetLaunchFor made (wavenet_choice.h) --
+	// None of them decides anything: a choice that names another kernel, or an instantiation that does not exist, is hipErrorInvalidValue.
+	// Lane = frame kernel on v_mfma_f32_4x4x1_16b_f32 (wavenet_frame_kernels.hip): WnLaunchKernel::Frame
+	hipError_t LaunchWaveNetFrameFused(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream);
+	// The stage interpreter of the f16-split MFMA kernels (wavenet_split_kernels.hip): WnLaunchKernel::Interpreter.  Its stream state uses
+	// split quads in frame-major rings (see WnSplitStage), so a model group stays on one kernel family for its whole life.
+	hipError_t LaunchWaveNetSplitFused(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream);
+	// The compile-time specialised layer chains of the official architectures (wavenet_spec_kernels.hip), same state as the interpreter:
+	// WnLaunchKernel::Chain, and WnLaunchKernel::ChainTable -- any number of groups in one launch, the group table in device memory (`table`)
+	hipError_t LaunchWaveNetSpecFused(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream);
+	hipError_t LaunchWaveNetSpecTable(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream, WnLaunchTable& table);
 
-	// Same contract on the compile-time specialised layer chains of the official architectures (wavenet_spec_kernels.hip): blocks of
-	// exactly 128 / 64 / 32 frames, every group of the launch from one architecture family (WnModelDev::spec_arch); returns
-	// hipErrorNotSupported otherwise -- LaunchWaveNetSplitFused tries it first and falls back to its stage interpreter.
-	// `sharing` of the fused launches below: the number of launches that share the chip (free-running chains), OR-ed with this bit when the
-	// batch's stream state does not fit the 256 MB Infinity Cache (the chains then mark the long dilations' ring traffic non-temporal)
+	// `sharing` of a launch: how many launches of this size run on the chip at the same time (the free-running half-batch chains: 2) --
+	// the workgroup shape is chosen for what is resident, not for what one launch brings --, OR-ed with this bit when the batch's stream
+	// state does not fit the 256 MB Infinity Cache (the chains then mark the long dilations' ring traffic non-temporal)
 	constexpr int WN_SHARING_BEYOND_CACHE = 1 << 16;
 	// ... for launches over `stateBytes` of stream state: from NA_WN_NT_MB (400 MiB) on, unless NA_WN_NT=0 (measured, us per 1024 A1
 	// Standard streams with / without the non-temporal bits: 1280 streams = 311 MB 40.4 / 39.2 -- part of the state still lives in the
@@ -52,12 +58,63 @@ namespace na
 		const Tuning& t = Tuning::Get();
 		return (!t.wnNtOff && stateBytes > ((size_t)t.wnNtFromMB << 20)) ? WN_SHARING_BEYOND_CACHE : 0;
 	}
-	hipError_t LaunchWaveNetSpecFused(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
-		hipStream_t stream, int sharing = 1);
+
+	// What every launch of one processing call asks with: the process's knobs and the device's CU count, read ONCE per call (the callers
+	// -- GpuBatch::LaunchWaveNetList, the half-batch chains, WaveNetGroup::Process -- make one in front of their chunk loops)
+	struct WnLaunchContext
+	{
+		WaveNetKnobs knobs;
+		int cus;
+		static WnLaunchContext Current() { return { WaveNetKnobs::FromTuning(), CurrentDeviceCUs() }; }
+	};
+	// The facts of one launch of a list (`frame`: the frame-kernel list), put to WaveNetLaunchFor.  `scratch`: where the facts of a list
+	// longer than WN_FRAME_MAX_GROUPS go (a caller on the audio thread keeps one, so that nothing is allocated)
+	inline WaveNetLaunchChoice WaveNetLaunchChoiceOf(const WnLaunchContext& ctx, bool frame, const WnFrameGroup* groups, int numGroups, int n, int sharing = 1,
+		std::vector<WaveNetGroupFacts>* scratch = nullptr)
+	{
+		WaveNetGroupFacts few[WN_FRAME_MAX_GROUPS];
+		std::vector<WaveNetGroupFacts> own;
+		WaveNetGroupFacts* facts = few;
+		if (numGroups > WN_FRAME_MAX_GROUPS)
+		{
+			std::vector<WaveNetGroupFacts>& many = scratch ? *scratch : own;
+			many.resize((size_t)numGroups);
+			facts = many.data();
+		}
+		for (int i = 0; i < numGroups; i++)
+		{
+			const WnModelDev& m = *groups[i].model;
+			facts[i] = { m.spec_arch, groups[i].pack, m.split_fast_T, groups[i].numStreams, groups[i].slots != nullptr, m.max_a4_floats, m.max_G, m.max_split_ops };
+		}
+		return WaveNetLaunchFor({ frame, n, facts, numGroups, sharing & ~WN_SHARING_BEYOND_CACHE, (sharing & WN_SHARING_BEYOND_CACHE) != 0, ctx.cus }, ctx.knobs);
+	}
+	static_assert(WN_REFUSED_INVALID_VALUE == (int)hipErrorInvalidValue, "wavenet_choice.h restates the error code");
+	// ... and the one launcher the choice names.  Pieces is for a caller that cuts its list (GpuBatch::LaunchWaveNetList); a table launch needs `table`.
+	inline hipError_t LaunchWaveNetChoice(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream, WnLaunchTable* table = nullptr)
+	{
+		switch (c.kernel)
+		{
+		case WnLaunchKernel::None: return (hipError_t)c.error;
+		case WnLaunchKernel::Chain: return LaunchWaveNetSpecFused(c, groups, numGroups, in, out, inStride, outStride, n, stream);
+		case WnLaunchKernel::ChainTable: return table ? LaunchWaveNetSpecTable(c, groups, numGroups, in, out, inStride, outStride, n, stream, *table) : hipErrorInvalidValue;
+		case WnLaunchKernel::Interpreter: return LaunchWaveNetSplitFused(c, groups, numGroups, in, out, inStride, outStride, n, stream);
+		case WnLaunchKernel::Frame: return LaunchWaveNetFrameFused(c, groups, numGroups, in, out, inStride, outStride, n, stream);
+		case WnLaunchKernel::Pieces: break;
+		}
+		return hipErrorInvalidValue;
+	}
+	// one launch of at most WN_FRAME_MAX_GROUPS groups: facts, choice, launcher
+	inline hipError_t LaunchWaveNetGroups(const WnLaunchContext& ctx, bool frame, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream, int sharing = 1)
+	{
+		return LaunchWaveNetChoice(WaveNetLaunchChoiceOf(ctx, frame, groups, numGroups, n, sharing), groups, numGroups, in, out, inStride, outStride, n, stream);
+	}
 	// test hook (GpuBatch::DebugStallDevice): one wave that keeps `stream` busy for `ms` milliseconds (s_memrealtime, 100 MHz)
 	hipError_t LaunchStallKernel(double ms, hipStream_t stream);
 	// ---- table launches of the specialised chains (wavenet_spec_impl.h WaveNetSpecTableKernel): any number of model groups in one launch --
 	// The device copies of a launch list's group tables, owned by the batch (one WnLaunchTable per launch list); see LaunchWaveNetSpecTable.
+	// (blocks of 128 / 64 frames of one architecture family: wavenet_choice.h TableFor)
 	// An entry is IMMUTABLE once uploaded -- a table with other contents (another block length, other members) gets its own device
 	// buffer -- so a captured graph that replays a table launch keeps reading what it was captured with, and nothing is allocated,
 	// freed or copied inside a stream capture: the batch runs the launch list once with `prepareOnly` set before it begins the capture
@@ -117,11 +174,6 @@ namespace na
 			return hipSuccess;
 		}
 	};
-	// A launch list of MORE than WN_FRAME_MAX_GROUPS groups of one architecture family (all Standard; lite-family groups, packed or not;
-	// the A2 submodels) as ONE launch of 128-frame blocks; hipErrorNotSupported otherwise (the caller then cuts the list into launches of eight).
-	hipError_t LaunchWaveNetSpecTable(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
-		hipStream_t stream, WnLaunchTable& table);
-
 	// ---- resident ("persistent") launches of the specialised chains (wavenet_spec_impl.h WaveNetSpecResidentKernel) --------------
 	// One launch stays on the chip and walks consecutive buffers by itself: the host posts a command per buffer into a ring, every
 	// workgroup polls the command it needs next, runs its streams' block and counts itself done.  Workgroups never wait for each other
@@ -172,17 +224,15 @@ namespace na
 		unsigned idleTicks;           // s_memrealtime ticks (100 MHz) without a command after which a workgroup leaves
 		unsigned startDelay;          // ticks the second half of the grid (the second workgroup of every CU) waits before its first command
 	};
-	// Starts (or restarts) the resident launch of a launch list that LaunchWaveNetSpecFused would run as ONE launch of 128-frame blocks;
+	// Starts (or restarts) the resident launch of a launch list that runs as ONE launch of full-size workgroups of the A1 Standard chain, 128-frame blocks;
 	// hipErrorNotSupported otherwise.  grid = min(workgroups of the list, what is resident at the kernel's occupancy); *gridOut says how
 	// many workgroups were launched (wgDone must hold that many counters).
 	hipError_t LaunchWaveNetSpecResident(const WnFrameGroup* groups, int numGroups, int n, const ResidentArgs& ra, hipStream_t stream, int* gridOut);
 	// the grid LaunchWaveNetSpecResident would use (0: the list cannot run resident)
 	int WaveNetSpecResidentGrid(const WnFrameGroup* groups, int numGroups, int n);
 
-	bool WaveNetSpecEnabled();
-	void SetWaveNetSpecEnabled(bool on); // process-wide; not for use while launches are being issued from other threads
-	// which specialised chain (WnSpecArch) runs a split-kernel plan, WN_SPEC_NONE if none; host data
-	int WaveNetSpecArchId(const WnSplitStage* stages, int nstages, int stateF4, int wsplitQuads);
+	// the chains' switch (WaveNetSpecEnabled, wavenet_choice.h); process-wide; not for use while launches are being issued from other threads
+	void SetWaveNetSpecEnabled(bool on);
 
 	// The runtime-shaped block kernel (wavenet_generic_kernels.hip): up to 64 channels per layer array, dense heads; walks the
 	// natural-layout tensor table (WaveNetPlan::prewarm) over the flat reference-order weights; frame-kernel stream-state format.
@@ -192,11 +242,6 @@ namespace na
 	hipError_t LaunchWaveNetGeneric(const WnPrewarmLayer* layers, int numLayers, const float* weights, const int* ringOffF4, const int* ringFrames,
 		const int* ringG, int nrings, int stateF4, int maxChannels, float headScale, float condLimit, bool saturate, float* state, const int* slots, const int* rows,
 		int numStreams, int slot0, int row0, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
-
-	// slots == nullptr: the active streams are contiguous -- stream i uses state slot slot0 + i and matrix row row0 + i (saves the
-	// kernel a dependent global load before it can touch the stream's state)
-	hipError_t LaunchWaveNetFrame(const WnModelDev& m, float* state, const int* slots, const int* rows, int numStreams, const float* in,
-		float* out, long inStride, long outStride, int n, hipStream_t stream, int slot0 = 0, int row0 = 0);
 
 	// tuning aid: device buffer of long long[stages*4*waves] that workgroup 0 stamps with the shader clock (nullptr: off)
 	void SetWaveNetTraceBuffer(long long* deviceBuffer);

@@ -401,8 +401,8 @@ namespace na
 			// Range contract of the f16-split kernels: the hi half of every value is an f16 (|v| <= 65504).  With the input clamped to
 			// +-condLimit every split value stays below half of that: G * limit + A <= 32752 for every (G, A) collected above.  A model
 			// of up to 16 channels for which that leaves less than kSplitMinInputLimit -- or whose weights do not fit the operand format --
-			// is not run by the f16-split kernels at all (splitRangeProven / splitWeightsOk -> the f32 frame kernel, gpu_batch.cpp
-			// FamilyFor); a wider one has no f32 kernel and is refused at load (CheckWaveNetRunnable).
+			// is not run by the f16-split kernels at all (splitRangeProven / splitWeightsOk -> the f32 frame kernel, wavenet_choice.h
+			// WaveNetKernelFor); a wider one has no f32 kernel and is refused at load (CheckWaveNetRunnable).
 			void FinishRange()
 			{
 				double limit = 32752.0;
@@ -946,7 +946,7 @@ namespace na
 		const WaveNetPlan plan = BuildWaveNetPlan(desc);
 		if (!plan.genericOnly)
 		{
-			// Up to 16 channels the f32 frame kernel is the kernel of last resort (FamilyFor), and it stages a layer's whole weight block
+			// Up to 16 channels the f32 frame kernel is the kernel of last resort (WaveNetKernelFor), and it stages a layer's whole weight block
 			// -- every conv tap -- in LDS: a block that does not fit beside one stream's 128-frame block images (frame_lds.h) could run
 			// no buffer longer than 64 frames.  Refused here, by name, instead of at the first long buffer on the audio thread.
 			for (size_t a = 0; a < desc.arrays.size(); a++)
@@ -1118,7 +1118,7 @@ namespace na
 			if (cfg.channels != 4 * LaneMode(cfg.channels)) partial = true;
 		}
 		if (desc.arrays.back().headSize != 1) return false;
-		// arrays of <= 4 channels want 4 tiles per wave when they run alone (packing is what helps them), leave those to PackFor
+		// arrays of <= 4 channels want 4 tiles per wave when they run alone (packing is what helps them), leave those to packing (WaveNetKernelFor)
 		for (const WnArrayCfg& cfg : desc.arrays)
 			if (cfg.channels <= 4) return false;
 		return partial;

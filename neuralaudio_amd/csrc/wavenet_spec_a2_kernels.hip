@@ -7,28 +7,17 @@ namespace na
 {
 	namespace spk
 	{
-		hipError_t LaunchSpecA2(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, int spb, hipStream_t stream, bool beyondCache)
+		hipError_t LaunchSpecA2(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
+			hipStream_t stream)
 		{
-#ifdef NA_SP_QUICK
-			return hipErrorNotSupported;
-#else
-			return LaunchNF<FamA2, false>(groups, numGroups, in, out, inStride, outStride, n, spb, stream, beyondCache);
-#endif
+			return LaunchChain<FamA2, false>(c, groups, numGroups, in, out, inStride, outStride, stream);
 		}
 
-		// ... as a table launch (wavenet_launch.h LaunchWaveNetSpecTable): 128-frame blocks
-		hipError_t LaunchSpecA2Table(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, int spb, hipStream_t stream,
-			WnLaunchTable& table)
+		// ... as a table launch (wavenet_launch.h LaunchWaveNetSpecTable)
+		hipError_t LaunchSpecA2Table(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
+			hipStream_t stream, WnLaunchTable& table)
 		{
-#ifdef NA_SP_QUICK
-			return hipErrorNotSupported;
-#else
-			if (n == 64)
-				return spb >= 2 ? LaunchTable<FamA2, 64, 2, false>(groups, numGroups, in, out, inStride, outStride, stream, table)
-								: LaunchTable<FamA2, 64, 1, false>(groups, numGroups, in, out, inStride, outStride, stream, table);
-			return spb >= 2 ? LaunchTable<FamA2, 128, 2, false>(groups, numGroups, in, out, inStride, outStride, stream, table)
-							: LaunchTable<FamA2, 128, 1, false>(groups, numGroups, in, out, inStride, outStride, stream, table);
-#endif
+			return LaunchChainTable<FamA2, false>(c, groups, numGroups, in, out, inStride, outStride, stream, table);
 		}
 	}
 }

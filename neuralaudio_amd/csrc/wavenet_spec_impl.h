@@ -1679,44 +1679,67 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 			return hipGetLastError();
 		}
 
+		// WaveNetSpecKernel<F, NF, SPB, PK, NT> of family F as WaveNetLaunchFor chose it (wavenet_choice.h ChainFor): a switch over the
+		// instantiations that exist.  One tile per wave (FamLite16T1): one stream per workgroup (SPB = 2 in units of four-wave streams), every
+		// block length; the others: 128 / 64 frames at both workgroup sizes, 32 frames where every member runs 2 tiles per wave (a wave of a
+		// 4-tile architecture covers 64 frames), and the non-temporal variant for full-size workgroups of 128-frame blocks.
+#define NA_SPK_ARGS groups, numGroups, in, out, inStride, outStride, stream
 		template <class F, bool PK>
-		static hipError_t LaunchNF(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, int spb, hipStream_t stream,
-			bool beyondCache = false)
+		static hipError_t LaunchChain(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
+			hipStream_t stream)
 		{
-#ifdef NA_SP_QUICK
-			(void)spb; (void)n; (void)beyondCache;
-			return Launch<F, 128, 2, PK>(groups, numGroups, in, out, inStride, outStride, stream);
-#else
-			// (the non-temporal variant exists for full-size workgroups of 128-frame blocks: the regime it is for -- more state than the
-			// Infinity Cache holds -- is thousands of streams)
-			if constexpr (F::A0::T != 1)
-				if (beyondCache && n == 128 && spb >= 2) return Launch<F, 128, 2, PK, true>(groups, numGroups, in, out, inStride, outStride, stream);
-			if constexpr (F::A0::T == 1)
+			constexpr bool oneTile = F::A0::T == 1, twoTiles = F::A0::T == 2 && F::A1::T == 2;
+			if (c.nt)
 			{
-				// one tile per wave: one stream per workgroup (SPB_ = 2 in units of four-wave streams), every block length
-				if (n == 128) return Launch<F, 128, 2, PK>(groups, numGroups, in, out, inStride, outStride, stream);
-				if (n == 64) return Launch<F, 64, 2, PK>(groups, numGroups, in, out, inStride, outStride, stream);
-				return Launch<F, 32, 2, PK>(groups, numGroups, in, out, inStride, outStride, stream);
+				if constexpr (!oneTile)
+					if (c.nf == 128 && c.spb == 2) return Launch<F, 128, 2, PK, true>(NA_SPK_ARGS);
+				return hipErrorInvalidValue;
 			}
-			else
-			{
-			if (n == 128) return spb >= 2 ? Launch<F, 128, 2, PK>(groups, numGroups, in, out, inStride, outStride, stream) : Launch<F, 128, 1, PK>(groups, numGroups, in, out, inStride, outStride, stream);
-			if (n == 64) return spb >= 2 ? Launch<F, 64, 2, PK>(groups, numGroups, in, out, inStride, outStride, stream) : Launch<F, 64, 1, PK>(groups, numGroups, in, out, inStride, outStride, stream);
-			if constexpr (F::A0::T == 2 && F::A1::T == 2)
-				return spb >= 2 ? Launch<F, 32, 2, PK>(groups, numGroups, in, out, inStride, outStride, stream) : Launch<F, 32, 1, PK>(groups, numGroups, in, out, inStride, outStride, stream);
-			else return hipErrorNotSupported; // (a wave of a 4-tile architecture covers 64 frames)
-			}
-#endif
+			if (c.spb == 2)
+				switch (c.nf)
+				{
+				case 128: return Launch<F, 128, 2, PK>(NA_SPK_ARGS);
+				case 64: return Launch<F, 64, 2, PK>(NA_SPK_ARGS);
+				case 32:
+					if constexpr (oneTile || twoTiles) return Launch<F, 32, 2, PK>(NA_SPK_ARGS);
+					break;
+				}
+			if constexpr (!oneTile)
+				if (c.spb == 1)
+					switch (c.nf)
+					{
+					case 128: return Launch<F, 128, 1, PK>(NA_SPK_ARGS);
+					case 64: return Launch<F, 64, 1, PK>(NA_SPK_ARGS);
+					case 32:
+						if constexpr (twoTiles) return Launch<F, 32, 1, PK>(NA_SPK_ARGS);
+						break;
+					}
+			return hipErrorInvalidValue;
 		}
+		// ... and WaveNetSpecTableKernel<F, NF, SPB, PK> (wavenet_choice.h TableFor): 128 / 64 frames at both workgroup sizes
+		template <class F, bool PK>
+		static hipError_t LaunchChainTable(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
+			hipStream_t stream, WnLaunchTable& table)
+		{
+			switch (c.nf * 4 + c.spb)
+			{
+			case 128 * 4 + 2: return LaunchTable<F, 128, 2, PK>(NA_SPK_ARGS, table);
+			case 128 * 4 + 1: return LaunchTable<F, 128, 1, PK>(NA_SPK_ARGS, table);
+			case 64 * 4 + 2: return LaunchTable<F, 64, 2, PK>(NA_SPK_ARGS, table);
+			case 64 * 4 + 1: return LaunchTable<F, 64, 1, PK>(NA_SPK_ARGS, table);
+			}
+			return hipErrorInvalidValue;
+		}
+#undef NA_SPK_ARGS
 
-		// (defined in the family's translation unit)
-		hipError_t LaunchSpecLite(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, int spb, bool packed,
-			hipStream_t stream, bool oneTilePerWave = false, bool beyondCache = false);
-		hipError_t LaunchSpecA2(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, int spb, hipStream_t stream,
-			bool beyondCache = false);
-		hipError_t LaunchSpecA2Table(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, int spb, hipStream_t stream,
-			WnLaunchTable& table);
-		hipError_t LaunchSpecLiteTable(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, int spb, bool packed,
+		// the families of the other translation units (each a switch on the choice's family member)
+		hipError_t LaunchSpecLite(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
+			hipStream_t stream);
+		hipError_t LaunchSpecA2(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
+			hipStream_t stream);
+		hipError_t LaunchSpecLiteTable(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
+			hipStream_t stream, WnLaunchTable& table);
+		hipError_t LaunchSpecA2Table(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride,
 			hipStream_t stream, WnLaunchTable& table);
 	}
 }

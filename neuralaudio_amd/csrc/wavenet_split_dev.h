@@ -21,7 +21,7 @@ namespace na
 		typedef const int __attribute__((address_space(4)))* CInt;
 
 #ifndef NA_ABL
-#define NA_ABL 0 // ablation bit mask for tuning builds only (make SUFFIX=_ablN KEXTRA="-DNA_ABL=N -DNA_SP_QUICK", tools/ab_bench.sh); 0 in
+#define NA_ABL 0 // ablation bit mask for tuning builds only (make SUFFIX=_ablN KEXTRA="-DNA_ABL=N"); 0 in
                  // the product.  1: no activation math, 2: no MFMA, 4: no history loads / ring stores, 8: no barrier, 16: no weight staging,
                  // 32: no split arithmetic, 64: no LDS publish, 128: no A-operand LDS reads (one operand reused), 256: no tap reads,
                  // 512: ring loads and stores issued but all out of range (no traffic), 1024: only the stores so, 2048: only the loads

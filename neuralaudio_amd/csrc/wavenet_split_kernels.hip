@@ -881,8 +881,9 @@ namespace na
 				maxOps = std::max(maxOps, m.max_split_ops);
 			}
 			const int wstride = maxOps * 64; // quads per LDS weight buffer (the LDS-DMA staging always writes its fixed 16 KB part)
-			const size_t lds = (PK ? (size_t)SPB * 4 * FRAMES * 8 : (size_t)SPB * FRAMES * 16) + (size_t)SPB * 2 * maxG * PLANE * 16 + (size_t)2 * wstride * 16 + 1024;
-			if (lds > 160 * 1024) return hipErrorInvalidValue;
+			static_assert(PLANE == SPLIT_PLANE_QUADS && FRAMES == WN_MAX_FRAMES, "wavenet_choice.h restates the LDS layout");
+			const size_t lds = SplitLaunchLdsBytes(SPB, PK, maxG, maxOps);
+			if (lds > SPLIT_LDS_LIMIT) return hipErrorInvalidValue; // (WaveNetLaunchFor asked the same function)
 			auto kernel = WaveNetSplitKernel<T, SPB, WPS, GEN, PK>;
 			if (lds > 64 * 1024)
 			{
@@ -897,74 +898,26 @@ namespace na
 		}
 	}
 
-	hipError_t LaunchWaveNetSplitFused(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n,
-		hipStream_t stream, int sharing)
+	// WaveNetSplitKernel<T, SPB, WPS, GEN, PK> as WaveNetLaunchFor chose it (wavenet_choice.h InterpreterFor): a switch over the instantiations
+	hipError_t LaunchWaveNetSplitFused(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream)
 	{
-		if (n <= 0 || numGroups <= 0) return hipSuccess;
-		if (n > WN_MAX_FRAMES || numGroups > WN_FRAME_MAX_GROUPS) return hipErrorInvalidValue;
+		if (c.kernel != WnLaunchKernel::Interpreter) return hipErrorInvalidValue;
+#define NA_SP_CASE(TT, SS, WW, GG, PP) \
+		case Key(TT, SS, WW, GG, PP): return sp::Launch<TT, SS, WW, GG, PP>(groups, numGroups, in, out, inStride, outStride, n, stream);
+#define NA_SP_CASE_PLAIN(TT, SS, WW) NA_SP_CASE(TT, SS, WW, false, false) NA_SP_CASE(TT, SS, WW, true, false)
+		constexpr auto Key = [](int t, int spb, int wps, bool gen, bool pk) { return (t << 8) | (spb << 4) | (wps << 1) | (gen ? 1 : 0) | (pk ? 1 << 12 : 0); };
+		switch (Key(c.t, c.spb, c.wps, c.gen, c.pk))
 		{
-			// the official architectures run compile-time specialised chains (wavenet_spec_kernels.hip); this file's stage interpreter takes
-			// everything else: runtime-shaped models, other block lengths, mixed launches
-			const hipError_t e = LaunchWaveNetSpecFused(groups, numGroups, in, out, inStride, outStride, n, stream, sharing);
-			if (e != hipErrorNotSupported) return e;
+		NA_SP_CASE_PLAIN(4, 2, 2) NA_SP_CASE_PLAIN(4, 1, 2) NA_SP_CASE_PLAIN(4, 2, 1) NA_SP_CASE_PLAIN(4, 1, 1)
+		NA_SP_CASE_PLAIN(2, 4, 4) NA_SP_CASE_PLAIN(2, 2, 4) NA_SP_CASE_PLAIN(2, 1, 4)
+		NA_SP_CASE_PLAIN(2, 2, 2) NA_SP_CASE_PLAIN(2, 1, 2) NA_SP_CASE_PLAIN(2, 2, 1) NA_SP_CASE_PLAIN(2, 1, 1)
+		// packed groups: the fast instantiation at 2 tiles per wave
+		NA_SP_CASE(2, 2, 4, false, true) NA_SP_CASE(2, 1, 4, false, true) NA_SP_CASE(2, 2, 2, false, true) NA_SP_CASE(2, 1, 2, false, true)
+		NA_SP_CASE(2, 2, 1, false, true) NA_SP_CASE(2, 1, 1, false, true)
 		}
-		int total = 0;
-		for (int i = 0; i < numGroups; i++)
-		{
-			if (groups[i].numStreams <= 0) return hipErrorInvalidValue;
-			total += groups[i].numStreams;
-		}
-		const int tEnv = Tuning::Get().spT;       // tuning knob: tiles per wave (2, 4)
-		const int spbEnv = Tuning::Get().spSpb;   // tuning knob: streams per workgroup (1, 2)
-		const bool genEnv = Tuning::Get().spGen;  // tuning knob: always the generic instantiation
-		const int spb = spbEnv > 0 ? spbEnv : (total >= 512 ? 2 : 1);
-		const int tiles = (n + 15) / 16;
-		// fast instantiation: every layer of every group has K == 3 and fills its lane mode (the official A1 architectures except Lite);
-		// split_fast_T = fewest tiles per wave it can run with (4 when an array has <= 4 channels), 0 = needs the generic one
-		bool gen = genEnv;
-		int t = (tEnv == 2 || tEnv == 4) ? tEnv : 2;
-		for (int i = 0; i < numGroups; i++)
-		{
-			if (groups[i].model->split_fast_T == 0) gen = true;
-			else t = std::max(t, groups[i].model->split_fast_T);
-		}
-		// packed groups (several real streams per virtual stream, WaveNetPlan::pack): their own launch, fast instantiation, 2 tiles per wave
-		bool packed = false;
-		for (int i = 0; i < numGroups; i++) packed = packed || groups[i].pack > 1;
-		if (packed)
-		{
-			for (int i = 0; i < numGroups; i++)
-				if (groups[i].model->split_fast_T != 2) return hipErrorInvalidValue; // plain groups may ride along (pack = 1) if their plan is a fast one
-#ifndef NA_SP_QUICK
-#define NA_SP_LAUNCH_PK(SS, WW) return sp::Launch<2, SS, WW, false, true>(groups, numGroups, in, out, inStride, outStride, n, stream)
-			if (tiles > 4) { if (spb >= 2) NA_SP_LAUNCH_PK(2, 4); NA_SP_LAUNCH_PK(1, 4); }
-			if (tiles > 2) { if (spb >= 2) NA_SP_LAUNCH_PK(2, 2); NA_SP_LAUNCH_PK(1, 2); }
-			if (spb >= 2) NA_SP_LAUNCH_PK(2, 1);
-			NA_SP_LAUNCH_PK(1, 1);
-#undef NA_SP_LAUNCH_PK
-#else
-			return hipErrorInvalidValue;
-#endif
-		}
-#ifdef NA_SP_QUICK
-#define NA_SP_LAUNCH(TT, SS, WW) do { return sp::Launch<2, 2, 4, false, false>(groups, numGroups, in, out, inStride, outStride, n, stream); } while (0)
-#else
-#define NA_SP_LAUNCH(TT, SS, WW) do { return gen ? sp::Launch<TT, SS, WW, true, false>(groups, numGroups, in, out, inStride, outStride, n, stream) \
-	: sp::Launch<TT, SS, WW, false, false>(groups, numGroups, in, out, inStride, outStride, n, stream); } while (0)
-#endif
-#ifdef NA_SP_QUICK // experiment builds: only the headline instantiation
-		NA_SP_LAUNCH(2, 2, 4);
-#endif
-		if (t == 4)
-		{
-			if (tiles > 4) { if (spb >= 2) NA_SP_LAUNCH(4, 2, 2); NA_SP_LAUNCH(4, 1, 2); }
-			if (spb >= 2) NA_SP_LAUNCH(4, 2, 1);
-			NA_SP_LAUNCH(4, 1, 1);
-		}
-		if (tiles > 4) { if (spb >= 4) NA_SP_LAUNCH(2, 4, 4); if (spb >= 2) NA_SP_LAUNCH(2, 2, 4); NA_SP_LAUNCH(2, 1, 4); }
-		if (tiles > 2) { if (spb >= 2) NA_SP_LAUNCH(2, 2, 2); NA_SP_LAUNCH(2, 1, 2); }
-		if (spb >= 2) NA_SP_LAUNCH(2, 2, 1);
-		NA_SP_LAUNCH(2, 1, 1);
-#undef NA_SP_LAUNCH
+#undef NA_SP_CASE_PLAIN
+#undef NA_SP_CASE
+		return hipErrorInvalidValue;
 	}
 }

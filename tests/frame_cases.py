@@ -5,7 +5,7 @@ Shared by tests/test_gpu_frame.py (which runs them) and tests/test_host_cpu.py (
 loads, is predicted to run on the frame kernel at 1 and at 600 streams, and that the generator reaches every path it names).  Pure
 Python and numpy, seeded, never skips.
 
-What lands a model of <= 16 channels on the frame kernel by default (gpu_groups.h FamilyFor / PackFor / PadFor): a layer kernel size
+What lands a model of <= 16 channels on the frame kernel by default (wavenet_choice.h WaveNetKernelFor): a layer kernel size
 other than 3 or a conv head (unless it is one of the two official A2 shapes), or a failed range proof.  Every case below has one of
 the three, and says which path of the kernel it is for.  The complement -- K = 3 everywhere, 1x1 heads and a proven range: the f16-split
 kernels -- is tests/split_cases.py."""

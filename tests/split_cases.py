@@ -6,7 +6,7 @@ loads, is predicted on the f16-split kernel with the pack factor it claims at 1 
 path it names and that every case is well conditioned).  Pure Python and numpy, seeded, never skips.
 
 The complement of tests/frame_cases.py: a WaveNet of at most 16 channels with K = 3 in every layer, 1x1 heads, last head size 1 and a
-proven f16 range lands on the f16-split kernels by default (gpu_groups.h FamilyFor / PackFor / PadFor; wavenet_plan.cpp splitFastT,
+proven f16 range lands on the f16-split kernels by default (wavenet_choice.h WaveNetKernelFor; wavenet_plan.cpp splitFastT,
 WaveNetPackFactor, WaveNetWantsPadding), in one of three layouts -- restated here in Python (layout_of) and held against
 NA_ModelKernelInfo by the CPU proof:
 
@@ -35,7 +35,7 @@ SAMPLES = 1536              # 12 blocks: every ring of every case (at most 736 f
 BLOCK = 128
 TILE = 16
 COMPACT_MAX_HISTORY = 32    # WN_COMPACT_MAX_HISTORY: roundup16(2 d) <= 32 -> a compact ring of three times that (d <= 16)
-MAX_SPLIT_RINGS = 63        # WN_RANGE_EVENT_SLOT: SplitAllowed refuses more rings
+MAX_SPLIT_RINGS = 63        # WN_RANGE_EVENT_SLOT: WaveNetKernelFor keeps more rings off the split kernels
 WORK_CAP = 2e8              # sum over layers of channels^2 x K x samples: oracle plus GPU stay far under a second
 NUM_FUZZ_SEEDS = 24
 # The GPU parity bound is absolute below an output level of 1 (2e-6 RMS), and synth_wavenet_weights' head scale of 0.02 leaves these

@@ -829,7 +829,7 @@ def test_full_size_properties_config5_2048_a2_streams_quality_sweep(na, loader):
 @pytest.mark.parametrize("name,first,more", [("BossWN-nano.nam", 3077, 5), ("BossWN-feather.nam", 1539, 3)])
 def test_packed_narrow_streams_match_oracle_stream_by_stream(na, loader, name, first, more):
     """Large batches of a narrow static model run PACKED: 4 (Nano) / 2 (Feather) real streams as the channel groups of one virtual
-    stream of the f16-split kernel (gpu_batch.cpp PackFor, wavenet_plan.cpp PackWaveNetDesc).  Every stream has its own input; streams
+    stream of the f16-split kernel (wavenet_choice.h WaveNetKernelFor, wavenet_plan.cpp PackWaveNetDesc).  Every stream has its own input; streams
     from all positions of a virtual stream, from the partially filled last one and from a later AddStreams call that completes it
     must match the oracle, across a ragged sequence of block sizes, and a re-prewarm of one stream must not disturb its neighbours."""
     m = loader.CreateFromFile(_path(name), doPrewarm=False)

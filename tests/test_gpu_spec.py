@@ -3,7 +3,7 @@
 * The specialised chains keep the stream-state format, the operand images and the order of floating-point operations of the stage
   interpreter (wavenet_split_kernels.hip), so both must agree BIT FOR BIT on the same stream -- also when a stream alternates between
   them (blocks of 128 / 64 / 32 frames run the chain, every other length the interpreter).
-* Which kernel a default load of every official architecture lands on is asserted here (a silent FamilyFor regression would keep
+* Which kernel a default load of every official architecture lands on is asserted here (a silent WaveNetKernelFor regression would keep
   parity green and halve the bench).
 * Quiet inputs (1e-3 .. 1e-6): the split path must be as accurate as f32 arithmetic, measured against a float64 evaluation.
 * Inputs beyond the f16 range, infinities and NaNs: the contract is "clamped to +-condLimit, NaN reads as silence"; the output stays
