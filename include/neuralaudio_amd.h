@@ -250,8 +250,8 @@ NA_EXTERN int NA_BatchStreamIRFadeRemaining(NA_Batch* batch, int stream); /* sam
  * through the library's device staging block, and it enqueues one table upload from a ring of pinned tables plus two launches
  * (detector, apply) over the gated streams only, whatever n: no device or pinned allocation, no stream or event creation, no unbounded
  * wait.  With the last entry the free-running modes come back.
- * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; a side-chain input; gain-reduction meters that are
- * safe to read from the audio thread. */
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; a side-chain input.  (Gain-reduction meters that are
+ * safe to read from the audio thread are the GATE tap of the meter stage, below.) */
 typedef struct NA_GateParams { float openPower, closePower, floorGain, detectorCoeff; int attackSamples, holdSamples, releaseSamples; } NA_GateParams;
 typedef struct NA_GateInfo { int gainSamples, numGates; long long deviceBytes; } NA_GateInfo;
 NA_EXTERN int NA_GateParamsFromDb(int sampleRate, float openDb, float closeDb, float floorDb, float detectorMs, float attackMs, float holdMs, float releaseMs, NA_GateParams* out);
@@ -321,6 +321,72 @@ NA_EXTERN int NA_BatchGetEqInfo(NA_Batch* batch, NA_EqInfo* info);
 NA_EXTERN int NA_BatchSetStreamEq(NA_Batch* batch, int stream, const NA_EqSection* sections, int numSections, int fadeSamples); /* 0 sections / NULL: flat */
 NA_EXTERN int NA_BatchGetStreamEq(NA_Batch* batch, int stream, NA_EqSection* out, int capacity);   /* section count of the target; <0 bad id / not enabled */
 NA_EXTERN int NA_BatchStreamEqFadeRemaining(NA_Batch* batch, int stream);
+/* ---- the meter stage: per-stream level and gain-reduction meters ----
+ * Every link of a session's chain -- model -> gate -> EQ -> cabinet -> output gain -- can be set from the audio thread; this stage is what
+ * can be READ from it: an input level and clip count, an output level, and what the gate did, per stream, without stopping the batch.
+ * A host of the reference meters the buffers it holds; here the rows stay on the device.  A fifth per-stream stage, off unless enabled.
+ * It never writes an audio row: with or without meters the samples out are the same bits.  A batch that enabled it and set no meter
+ * launches exactly what it launched before.
+ * Order of a processing call: the IN tap in front of everything, beside the gate detector -- it reads the input rows as the caller
+ * passed them (in a resampling batch: the external-rate rows; input and output rows may be the same memory) -- then the models and the
+ * other stages as before, then, behind the output stage, the OUT tap on the row the caller receives and the GATE tap on the gain the
+ * gate stage applied to the same samples in this call.  The GATE tap reads 1 for every sample of a stream that was not an entry of the
+ * gate stage in this call, or when the gate stage is not enabled.
+ * Arithmetic.  This stage is not a recurrence: every quantity is a max, a min or an integer sum, hence exact, so a reading does not
+ * depend on the order of evaluation, on how the signal is cut into calls, on alignment or on stride.  Positions count the samples the
+ * caller sees since the meter was set; W = windowSamples; window k covers positions [kW, (k+1)W).  For each sample of a tap (clipLevel
+ * is clipLevelIn on the IN tap, clipLevelOut on the OUT tap):
+ *     x' = (x is NaN) ? 0 : min(|x|, 1e18f)
+ *     q  = (unsigned) trunc(min(x', 8.0f) * 2^21)     (the product is exact; q <= 2^24)
+ *     peak   = max(peak, x')        over the window      (exact; subnormals kept)
+ *     energy = energy + q * q       over the window, unsigned 64-bit    (<= 2^63 for W <= 32768)
+ *     overs  = overs + (x' >= clipLevel ? 1 : 0)   over the window
+ *     peakHold   = max over every sample since the meter was set
+ *     oversTotal = overs summed over every sample since the meter was set (64-bit)
+ *   For the GATE tap, g the gain of the sample:
+ *     gateGainMin  = min(g) over the window
+ *     gateGainLast = g of the window's last sample
+ *   The RMS of a window is sqrt(energy / W) / 2^21 -- for the host to compute, in whatever precision it likes.  The energy saturates at
+ *   |x| = 8 (+18 dBFS) and reads 0 below 2^-21; the peak does not saturate there.  A reading is published when a window completes;
+ *   peakHold and oversTotal of a reading run through the end of its window.  NA_MeterReading.windows is the number of completed
+ *   windows: the reading describes window `windows - 1`.
+ * NA_BatchEnableMeterStage is the set-up side (allocates; idempotent): a state per row, the stage's device + pinned tables and a
+ *   device + pinned result block per table; later NA_BatchAddStreams / NA_BatchReserveStreams grow them.  Every call below fails
+ *   ("meter stage not enabled (NA_BatchEnableMeterStage)") before it.  NA_BatchGetMeterInfo reports the number of meters and the device
+ *   memory the stage holds.
+ * NA_BatchSetStreamMeter is REAL-TIME SAFE: host arithmetic on tables that exist; no memset travels with it.
+ *   The stream has no meter: the meter starts at the next sample, at position 0.
+ *   The stream has a meter: it RESTARTS at position 0 with the new constants, holds and totals cleared; no reading is available until
+ *     its first window completes, and nothing the earlier meter produced is read again.
+ *   params == NULL: the meter goes at once (it touches no audio, so there is no tail).  On a stream without a meter it does nothing.
+ *   windowSamples must lie in [32, 32768] (any integer, not only powers of two); clipLevelIn and clipLevelOut must be finite and > 0.
+ *     Each failure names the field.
+ * NA_BatchGetStreamMeter returns 1 and fills *out with the constants in effect, 0 when the stream has no meter, < 0 on a bad id or when
+ *   the stage is not enabled.
+ * NA_BatchReadStreamMeter is REAL-TIME SAFE: no wait, no allocation, no device call other than event queries.  It returns 1 and the
+ *   newest reading that has ARRIVED on the host -- a processing call leaves its results in pinned memory behind its launches, and this
+ *   call (like the start of every processing call) asks the events of those copies whether they are over --, 0 if the stream has no
+ *   meter or no completed window has arrived yet, < 0 on a bad id, when the stage is not enabled, or on a broken batch.  Straight
+ *   after a processing call the newest window may still be on its way: the reading says which window it is (`windows`).  After
+ *   NA_BatchSynchronize everything has arrived.  Call it from the thread that drives the batch, like every other call.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a
+ * hand-over, drop the meter at once.  Meters are not part of a NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves them alone.
+ * While an entry exists -- a stream with a meter -- a processing call behaves as it does with entries of the other stages: its
+ * launches run in order on one stream (no half-batch chains, no resident launch), host buffers go through the library's device staging
+ * block, and it enqueues one table upload from a ring of pinned tables, two launches (IN; OUT + GATE) over the metered streams only and
+ * one copy of entries * sizeof(record) into the pinned result block of the same ring slot, whatever n: no device or pinned allocation,
+ * no stream or event creation, no unbounded wait.  With the last entry the free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; true-peak (oversampled) detection; loudness weighting. */
+typedef struct NA_MeterParams  { int windowSamples; float clipLevelIn, clipLevelOut; } NA_MeterParams;
+typedef struct NA_MeterTap     { unsigned long long energy, oversTotal; float peak, peakHold; unsigned int overs, reserved; } NA_MeterTap;
+typedef struct NA_MeterReading { unsigned long long windows; NA_MeterTap in, out; float gateGainMin, gateGainLast; int windowSamples, reserved; } NA_MeterReading;
+typedef struct NA_MeterInfo    { int numMeters; long long deviceBytes; } NA_MeterInfo;
+NA_EXTERN int NA_BatchEnableMeterStage(NA_Batch* batch);                    /* set-up side, allocates, idempotent */
+NA_EXTERN int NA_BatchGetMeterInfo(NA_Batch* batch, NA_MeterInfo* info);
+NA_EXTERN int NA_BatchSetStreamMeter(NA_Batch* batch, int stream, const NA_MeterParams* params); /* params = NULL: the meter goes at once */
+NA_EXTERN int NA_BatchGetStreamMeter(NA_Batch* batch, int stream, NA_MeterParams* out);  /* 1: filled; 0: no meter; < 0: bad id / not enabled */
+NA_EXTERN int NA_BatchReadStreamMeter(NA_Batch* batch, int stream, NA_MeterReading* out); /* 1: filled; 0: nothing to read yet; < 0: bad id / not enabled / broken */
 NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);
@@ -704,6 +770,8 @@ NA_EXTERN int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long str
 NA_EXTERN long long NA_DebugCabinetLaunches(void);
 /* Tests: launches of the gate stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugGateLaunches(void);
+/* Tests: launches of the meter stage's two kernels so far (two per processing call with entries) */
+NA_EXTERN long long NA_DebugMeterLaunches(void);
 /* Tests: launches of the EQ stage's kernel so far (one per processing call with entries) */
 NA_EXTERN long long NA_DebugEqLaunches(void);
 /* Tests: as NA_DebugRunCabinetStage, for the EQ stage: the stage alone on given rows -- table, launch, book advance */

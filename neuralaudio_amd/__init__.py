@@ -74,6 +74,25 @@ def gate_params_from_db(sample_rate, open_db, close_db, floor_db=float("-inf"), 
     return _gate_dict(out)
 
 
+METER_FIELDS = ("windowSamples", "clipLevelIn", "clipLevelOut")
+METER_TAP_FIELDS = ("energy", "oversTotal", "peak", "peakHold", "overs")
+
+
+def _meter_params(d):
+    if isinstance(d, capi.NA_MeterParams):
+        return d
+    p = capi.NA_MeterParams()
+    for name in METER_FIELDS:
+        setattr(p, name, d[name])
+    return p
+
+
+def _meter_reading(r):
+    tap = lambda t: {name: (float if name in ("peak", "peakHold") else int)(getattr(t, name)) for name in METER_TAP_FIELDS}
+    return {"windows": int(r.windows), "in": tap(r.in_), "out": tap(r.out), "gateGainMin": float(r.gateGainMin), "gateGainLast": float(r.gateGainLast),
+            "windowSamples": int(r.windowSamples)}
+
+
 EQ_FIELDS = ("b0", "b1", "b2", "a1", "a2")
 EQ_KINDS = {"lowpass": 0, "highpass": 1, "lowshelf": 2, "highshelf": 3, "peaking": 4}
 
@@ -565,6 +584,41 @@ class Batch:
         if gain < 0:
             raise NeuralAudioError(capi.last_error())
         return gain
+
+    # -- the meter stage: EnableMeterStage is set-up side; SetStreamMeter and ReadStreamMeter are real-time safe (include/neuralaudio_amd.h) ----
+    def EnableMeterStage(self):
+        if self._lib.NA_BatchEnableMeterStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetMeterInfo(self):
+        info = capi.NA_MeterInfo()
+        if self._lib.NA_BatchGetMeterInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_MeterInfo._fields_}
+
+    def SetStreamMeter(self, stream, params):
+        """Level and gain-reduction meters on the stream from the next sample on: `params` a dict of the NA_MeterParams fields
+        (windowSamples, clipLevelIn, clipLevelOut); None takes the meter away at once.  A stream that has a meter restarts it."""
+        p = None if params is None else C.byref(_meter_params(params))
+        if self._lib.NA_BatchSetStreamMeter(self._h, int(stream), p) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamMeter(self, stream):
+        """The constants in effect as a dict; None: no meter."""
+        out = capi.NA_MeterParams()
+        rc = int(self._lib.NA_BatchGetStreamMeter(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return {"windowSamples": int(out.windowSamples), "clipLevelIn": float(out.clipLevelIn), "clipLevelOut": float(out.clipLevelOut)} if rc else None
+
+    def ReadStreamMeter(self, stream):
+        """The newest reading that has arrived on the host, as a dict (windows, in, out, gateGainMin, gateGainLast, windowSamples; the
+        taps: energy, oversTotal, peak, peakHold, overs); None: no meter, or no completed window has arrived yet.  Never waits."""
+        out = capi.NA_MeterReading()
+        rc = int(self._lib.NA_BatchReadStreamMeter(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _meter_reading(out) if rc else None
 
     # -- the EQ stage: EnableEqStage is set-up side; SetStreamEq is real-time safe (include/neuralaudio_amd.h) ----
     def EnableEqStage(self):

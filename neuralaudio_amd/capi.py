@@ -47,6 +47,8 @@ NA_SYMBOLS = [
     "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
     "NA_EqSectionFromDesign", "NA_BatchEnableEqStage", "NA_BatchGetEqInfo", "NA_BatchSetStreamEq", "NA_BatchGetStreamEq",
     "NA_BatchStreamEqFadeRemaining", "NA_DebugEqLaunches", "NA_DebugRunEqStage",
+    "NA_BatchEnableMeterStage", "NA_BatchGetMeterInfo", "NA_BatchSetStreamMeter", "NA_BatchGetStreamMeter", "NA_BatchReadStreamMeter",
+    "NA_DebugMeterLaunches",
 ]
 
 
@@ -92,6 +94,24 @@ class NA_EqSection(C.Structure):
 
 class NA_EqInfo(C.Structure):
     _fields_ = [("maxSections", C.c_int), ("numEntries", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+class NA_MeterParams(C.Structure):
+    _fields_ = [("windowSamples", C.c_int), ("clipLevelIn", C.c_float), ("clipLevelOut", C.c_float)]
+
+
+class NA_MeterTap(C.Structure):
+    _fields_ = [("energy", C.c_ulonglong), ("oversTotal", C.c_ulonglong), ("peak", C.c_float), ("peakHold", C.c_float),
+                ("overs", C.c_uint), ("reserved", C.c_uint)]
+
+
+class NA_MeterReading(C.Structure):
+    _fields_ = [("windows", C.c_ulonglong), ("in_", NA_MeterTap), ("out", NA_MeterTap), ("gateGainMin", C.c_float), ("gateGainLast", C.c_float),
+                ("windowSamples", C.c_int), ("reserved", C.c_int)]
+
+
+class NA_MeterInfo(C.Structure):
+    _fields_ = [("numMeters", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 _lib = None
@@ -203,6 +223,12 @@ def load_library():
         "NA_BatchGetStreamGate": (C.c_int, [vp, C.c_int, C.POINTER(NA_GateParams)]),
         "NA_BatchStreamGateGain": (C.c_float, [vp, C.c_int]),
         "NA_DebugGateLaunches": (C.c_longlong, []),
+        "NA_BatchEnableMeterStage": (C.c_int, [vp]),
+        "NA_BatchGetMeterInfo": (C.c_int, [vp, C.POINTER(NA_MeterInfo)]),
+        "NA_BatchSetStreamMeter": (C.c_int, [vp, C.c_int, C.POINTER(NA_MeterParams)]),
+        "NA_BatchGetStreamMeter": (C.c_int, [vp, C.c_int, C.POINTER(NA_MeterParams)]),
+        "NA_BatchReadStreamMeter": (C.c_int, [vp, C.c_int, C.POINTER(NA_MeterReading)]),
+        "NA_DebugMeterLaunches": (C.c_longlong, []),
         "NA_EqSectionFromDesign": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.POINTER(NA_EqSection)]),
         "NA_BatchEnableEqStage": (C.c_int, [vp]),
         "NA_BatchGetEqInfo": (C.c_int, [vp, C.POINTER(NA_EqInfo)]),

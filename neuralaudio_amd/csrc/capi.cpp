@@ -757,6 +757,69 @@ float NA_BatchStreamGateGain(NA_Batch* batch, int stream)
 long long NA_DebugGateLaunches(void) { return (long long)na::GateStageLaunches(); }
 #endif
 
+// ---- the meter stage (gpu_batch.h EnableMeterStage / SetStreamMeter / ReadStreamMeter) ----
+static_assert(sizeof(NA_MeterTap) == sizeof(na::MeterTapReading) && sizeof(NA_MeterReading) == sizeof(na::MeterReading), "NA_MeterReading is MeterReading, field for field");
+
+int NA_BatchEnableMeterStage(NA_Batch* batch)
+{
+	return BatchCall(batch, "NA_BatchEnableMeterStage", [&](na::GpuBatch& b) { b.EnableMeterStage(); });
+}
+
+int NA_BatchGetMeterInfo(NA_Batch* batch, NA_MeterInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetMeterInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetMeterInfo: bad argument");
+		const na::MeterStageInfo i = b.GetMeterInfo();
+		info->numMeters = i.numMeters;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamMeter(NA_Batch* batch, int stream, const NA_MeterParams* params)
+{
+	return BatchCall(batch, "NA_BatchSetStreamMeter", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamMeter(stream, nullptr);
+			return;
+		}
+		na::MeterParams m;
+		m.windowSamples = params->windowSamples;
+		m.clipLevelIn = params->clipLevelIn;
+		m.clipLevelOut = params->clipLevelOut;
+		b.SetStreamMeter(stream, &m);
+	});
+}
+
+int NA_BatchGetStreamMeter(NA_Batch* batch, int stream, NA_MeterParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamMeter", -1, [&](na::GpuBatch& b) {
+		na::MeterParams m;
+		const int has = b.GetStreamMeter(stream, m) ? 1 : 0;
+		if (has && out)
+		{
+			out->windowSamples = m.windowSamples;
+			out->clipLevelIn = m.clipLevelIn;
+			out->clipLevelOut = m.clipLevelOut;
+		}
+		return has;
+	});
+}
+
+int NA_BatchReadStreamMeter(NA_Batch* batch, int stream, NA_MeterReading* out)
+{
+	return BatchValue(batch, "NA_BatchReadStreamMeter", -1, [&](na::GpuBatch& b) {
+		na::MeterReading r;
+		const int has = b.ReadStreamMeter(stream, r) ? 1 : 0;
+		if (has && out) memcpy(out, &r, sizeof(r));
+		return has;
+	});
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugMeterLaunches(void) { return (long long)na::MeterStageLaunches(); }
+#endif
+
 // ---- the EQ stage (gpu_batch.h EnableEqStage / SetStreamEq) ----
 static_assert(sizeof(NA_EqSection) == sizeof(na::EqSection) && NA_EQ_MAX_SECTIONS == na::kEqMaxSections, "NA_EqSection is na::EqSection");
 namespace

@@ -22,6 +22,7 @@
 #include "eq_stage.h"
 #include "gate_stage.h"
 #include "launch_plan.h"
+#include "meter_stage.h"
 #include "model_loader.h"
 #include "output_stage.h"
 #include "resample.h"
@@ -79,6 +80,12 @@ namespace na
 	struct EqStageInfo
 	{
 		int maxSections = 0, numEntries = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct MeterStageInfo
+	{
+		int numMeters = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -187,6 +194,20 @@ namespace na
 		int StreamEqFadeRemaining(int stream) const;
 		// test hook (NA_DebugRunEqStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
 		void DebugRunEqStage(float* hostRows, long stride, size_t n);
+
+		// The meter stage (meter_stage.h): per-stream level meters on the input row (the IN tap, in front of the model
+		// launches) and on the row the caller receives (the OUT tap, behind the output stage), and a gain-reduction meter on the gate's gain
+		// of the same samples (the GATE tap).  It never writes an audio row.  EnableMeterStage is the set-up side: a state per row
+		// (CreateStreams grows them), the tables and a result block per table.  SetStreamMeter is host arithmetic on those tables; while
+		// an entry exists every processing call runs on the ordered path and enqueues ONE table upload, two launches and ONE result copy,
+		// whatever n.  ReadStreamMeter never waits: it queries the ring's events and returns the newest reading that has arrived.
+		// Without an entry the batch launches exactly what it launches without the stage.
+		void EnableMeterStage();
+		bool HasMeterStage() const { return stages[kMeterStage] != nullptr; }
+		MeterStageInfo GetMeterInfo() const;
+		void SetStreamMeter(int stream, const MeterParams* params); // params == nullptr: the meter goes at once
+		bool GetStreamMeter(int stream, MeterParams& out) const;    // false: no meter
+		bool ReadStreamMeter(int stream, MeterReading& out);        // false: no meter, or no completed window has arrived yet
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -338,21 +359,21 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.13).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.14).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kNumStages };
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kMeterStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
 			virtual bool HasEntries() const = 0;
 			virtual void EnsureRows(GpuBatch& batch, int rows) = 0; // set-up side: device blocks and tables for `rows` rows
 			virtual void Leave(int stream) = 0;                     // park / removal: nothing of the stream is carried over
-			// a call with entries: in front of its model launches (the gate's detector), and behind them in chain order
+			// a call with entries: in front of its model launches (the gate's detector, the meter's IN tap), and behind them in chain order
 			virtual void BeforeModels(GpuBatch&, hipStream_t, const float*, size_t, long) {}
 			virtual void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) = 0;
 		};
 		template <class Book, class Entry> struct StageOf;
-		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage;
+		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage; struct MeterStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -176,7 +176,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the four stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the five stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -255,6 +255,36 @@ namespace na
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + launch + the host mirror's advance
 	};
 	hipError_t LaunchOutputStage(const OutStageLaunch& L, hipStream_t stream); // (output_stage_kernels.hip)
+
+	// the meter stage (meter_stage.h, meter_stage.cpp): the rows' states on the device and -- the one device -> host path
+	// of the stages -- a result block per table of the ring: the OUT launch writes a record per entry, one copy brings them to the pinned
+	// twin, the table's `done` event covers the copy, and the host folds what has arrived into the book without ever waiting for it
+	struct GpuBatch::MeterStage : StageOf<MeterBook, MeterEntry>
+	{
+		static constexpr StageId kId = kMeterStage;
+		static constexpr const char* kNotEnabled = "meter stage not enabled (NA_BatchEnableMeterStage)";
+		static constexpr int kTables = StageTables<MeterEntry>::kTables;
+		float* state = nullptr;             // [rowCapacity] MeterState
+		int rowCapacity = 0;
+		MeterRecord* results[kTables] = {};    // pinned: the records of the call that last used table i ...
+		MeterRecord* devResults[kTables] = {}; // ... and where its OUT launch wrote them
+		int pending[kTables] = {};          // records of results[i] that have not been folded yet (0: none)
+		int resultCapacity = 0;             // records per block
+		const MeterEntry* dev = nullptr;    // the device table the IN launch of this call read ...
+		int count = 0;                      // ... and its entries; 0: the call has none
+		int slot = 0;                       // ... and its place in the ring
+		bool anyGated = false;              // ... and whether one of them is an entry of the gate stage in this call
+		MeterStage() : StageOf("meter stage") {}
+		~MeterStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // its meter goes at once
+		void Fold(int i);            // the records of results[i] go into the book (stale ones are dropped there)
+		void Poll();                 // event queries only: every block whose copy is over is folded, oldest first
+		void BeforeModels(GpuBatch& batch, hipStream_t launch, const float* dIn, size_t n, long inStride) override; // poll + table upload + the IN launch
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override;              // the OUT launch + the result copy + the host mirror's advance
+	};
+	hipError_t LaunchMeterIn(const MeterLaunch& L, hipStream_t stream); // (meter_stage_kernels.hip)
+	hipError_t LaunchMeterOut(const MeterLaunch& L, hipStream_t stream);
 
 	// the stage S of the batch; throws "<who>: <stage> not enabled (...)" -- the text is part of the interface
 	template <class S>

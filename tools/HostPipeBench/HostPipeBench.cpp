@@ -22,6 +22,10 @@
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --eq K [--eq-sections S=3]
 //       the plain run below with the EQ stage enabled and an S-section cascade on the first K streams -- low shelf, peak, high shelf,
 //       then further peaks up to 8 -- (K = 0: enabled, no EQ set: must cost nothing); the same device span as --gate.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --meter K [--meter-window W=1024]
+//       the plain run below with the meter stage enabled and meters of W samples on the first K streams (K = 0: enabled, no meter set:
+//       must cost nothing); the pipelined loop reads the first stream's meter behind every buffer (NA_BatchReadStreamMeter: no wait);
+//       the same device span as --gate.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -571,13 +575,13 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
-	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3;
+	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3, meter = -1, meterWindow = 1024;
 	bool churnLegacy = false;
 	for (int i = 1; i < argc; i++)
 	{
@@ -594,6 +598,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--cab-irs") && i + 1 < argc) cabIRs = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) gate = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--eq") && i + 1 < argc) eq = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--meter") && i + 1 < argc) meter = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--meter-window") && i + 1 < argc) meterWindow = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--eq-sections") && i + 1 < argc) eqSections = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
@@ -682,7 +688,15 @@ int main(int argc, char** argv)
 		}
 		for (int s = 0; s < std::min(eq, streams); s++) CHECK(NA_BatchSetStreamEq(batch, s, sec, eqSections, 0) == 0);
 	}
-	const bool marks = gate >= 0 || eq >= 0; // (the plain run stays what it was)
+	if (meter >= 0)
+	{
+		// a clip light at the input's peak level (+-0.125) and an output clip level of 1
+		CHECK(NA_BatchEnableMeterStage(batch) == 0);
+		NA_MeterParams mp = { meterWindow, 0.12f, 1.0f };
+		for (int s = 0; s < std::min(meter, streams); s++) CHECK(NA_BatchSetStreamMeter(batch, s, &mp) == 0);
+	}
+	unsigned long long meterWindows = 0; // (--meter: `windows` of the last reading of stream 0 in the pipelined loop)
+	const bool marks = gate >= 0 || eq >= 0 || meter >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -741,10 +755,17 @@ int main(int argc, char** argv)
 		CHECK(next >= 0);
 		CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 		pending = next;
+		if (meter > 0)
+		{
+			NA_MeterReading reading;
+			const int have = NA_BatchReadStreamMeter(batch, 0, &reading);
+			CHECK(have >= 0);
+			if (have) meterWindows = reading.windows;
+		}
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
-	double usMarked = 0.0; // (--gate / --eq only)
+	double usMarked = 0.0; // (--gate / --eq / --meter only)
 	if (marks)
 	{
 		CHECK(NA_BatchMarkTime(batch, 1) == 0);
@@ -787,9 +808,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
