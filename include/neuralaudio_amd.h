@@ -751,6 +751,13 @@ NA_EXTERN void NA_DebugSetRcclApi(int mode, int failSendAt, int rendezvousMs);
 /* Tests: a kernel that keeps the batch's streams busy for `milliseconds` (at most 10 000) behind whatever they hold -- a device that
  * does not answer, as far as the waits of this batch can tell (tests/test_gpu_stall.py drives the wait limit with it). */
 NA_EXTERN int NA_DebugStallDevice(NA_Batch* batch, double milliseconds);
+/* Tests: the route the batch's last processing call took (csrc/host_route.h HostRoute, DESIGN.md 2.4 "Routes"), -1 before any call.
+ * NA_BatchProcess: 0 registered blocks in place, 1 staged in halves, 2 staged in place, 3 staged through the copy engines;
+ * NA_BatchSubmit: 4 the chains, 5 in place on the batch stream, 6 the slot's own stream, 7 the copy streams;
+ * NA_BatchProcessDevice: 8 resident launch, 9 the chains, 10 ordered; host rows to device rows (the multi-GPU host): 11 in place, 12 copied. */
+NA_EXTERN int NA_DebugLastHostRoute(NA_Batch* batch);
+/* ... and of the batch of one shard of a multi-GPU host (the only caller of the host-rows-to-device-rows entry point: RCCL fan-in) */
+NA_EXTERN int NA_DebugMultiLastHostRoute(NA_MultiBatch* multi, int shard);
 /* Tests: hipMalloc / hipFree / hipHostMalloc / hipHostFree / hipStreamCreate* / hipEventCreate* calls the library has made in this process
  * so far -- a real-time safe call leaves the count where it was (tests/test_gpu_pool.py) */
 NA_EXTERN long long NA_DebugDeviceResourceCalls(void);

@@ -170,6 +170,9 @@ WAVENET_KNOBS = ("NA_WN_KERNEL", "NA_WN_PACK", "NA_WN_PAD", "NA_WN_DENSE", "NA_S
 WAVENET_FAMILIES = {1: "f16-split", 2: "frame", 3: "generic"}
 WAVENET_LAUNCH_KERNELS = ("none", "chain", "chain table", "interpreter", "frame", "pieces")
 WAVENET_CHAINS = ("Std", "Lite", "LitePacked", "Lite16T1", "A2")
+# csrc/host_route.h HostRoute, in its order: what Batch.DebugLastHostRoute() indexes (tests/test_host_route_cpu.py pins the names)
+HOST_ROUTES = ("RegisteredInPlace", "StagedHalves", "StagedInPlace", "StagedCopies", "SubmitHalves", "SubmitInPlace", "SubmitOwnStream",
+               "SubmitCopyStreams", "DeviceResident", "DeviceHalves", "DeviceOrdered", "ToDeviceInPlace", "ToDeviceCopies")
 
 
 def _wavenet_knob_args(knobs):
@@ -798,6 +801,10 @@ class Batch:
         if self._lib.NA_DebugStallDevice(self._h, float(ms)) != 0:
             raise NeuralAudioError(capi.last_error())
 
+    def DebugLastHostRoute(self):
+        """Test hook: the route the last processing call took, a value of HOST_ROUTES (NA_DebugLastHostRoute); -1 before any call."""
+        return int(self._lib.NA_DebugLastHostRoute(self._h))
+
     def SetResidentLaunch(self, on=True):
         """Opt in to (or out of) the resident launch for device-pointer buffers of this batch (NA_BatchSetResidentLaunch)."""
         if self._lib.NA_BatchSetResidentLaunch(self._h, 1 if on else 0) != 0:
@@ -940,6 +947,10 @@ class MultiBatch:
         if self._lib.NA_MultiCollect(self._h, int(t), _fptr(y)) != 0:
             raise NeuralAudioError(capi.last_error())
         return y
+
+    def DebugLastHostRoute(self, shard):
+        """Test hook: Batch.DebugLastHostRoute of the batch of `shard` (NA_DebugMultiLastHostRoute)."""
+        return int(self._lib.NA_DebugMultiLastHostRoute(self._h, int(shard)))
 
     def GatheredOutput(self, shard, n):
         """RCCL fan-in: the [streams][n] device buffer of the last Process() on `shard`'s GPU, copied to the host (tests)."""

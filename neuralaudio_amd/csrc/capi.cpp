@@ -1109,6 +1109,15 @@ int NA_DebugStallDevice(NA_Batch* batch, double milliseconds)
 	if (!batch) return -1;
 	return Guard([&] { batch->batch->DebugStallDevice(milliseconds); });
 }
+
+int NA_DebugLastHostRoute(NA_Batch* batch) { return batch ? batch->batch->DebugLastHostRoute() : -1; }
+
+int NA_DebugMultiLastHostRoute(NA_MultiBatch* mb, int shard)
+{
+	int route = -1;
+	if (mb) Guard([&] { route = mb->multi->DebugShardLastHostRoute(shard); });
+	return route;
+}
 #endif
 
 void* NA_BatchGetHipStream(NA_Batch* batch) { return batch ? reinterpret_cast<void*>(batch->batch->GetStream()) : nullptr; }

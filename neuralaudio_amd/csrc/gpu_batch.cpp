@@ -93,7 +93,7 @@ namespace na
 
 	// ------------------------------------------------------------------------------------------ GpuBatch
 
-	GpuBatch::GpuBatch(int dev, hipStream_t borrowedStream) : device(dev)
+	GpuBatch::GpuBatch(int dev, hipStream_t borrowedStream) : device(dev), inFlight(new InFlight())
 	{
 		const int count = VisibleDeviceCount();
 		if (count <= 0) throw std::runtime_error("neuralaudio_amd: no HIP device is visible; this library has no CPU fallback");
@@ -163,7 +163,7 @@ namespace na
 				if (e) (void)hipEventDestroy(e);
 			if (p.own) (void)hipStreamDestroy(p.own);
 		}
-		if (mainDone) (void)hipEventDestroy(mainDone);
+		if (inFlight->mainDone) (void)hipEventDestroy(inFlight->mainDone);
 		for (hipStream_t hs : halfStream)
 			if (hs) (void)hipStreamDestroy(hs);
 		for (auto& m : marks)
@@ -402,7 +402,7 @@ namespace na
 		if (stages[kOutputStage]) StageParkFinished();
 		if (!rearmPending) return;
 		JoinHalves();
-		if (pipelineUsed && lastKernelEvent && lastKernelStream != stream) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
+		inFlight->OrderBehindLastKernel(stream);
 		for (auto& g : groups) g->FlushRearm();
 		for (int s : pendingHistoryZero) ZeroResampleHistories(s, 1);
 		pendingHistoryZero.clear();
@@ -580,17 +580,28 @@ namespace na
 		// A batch on its own stream that nobody has seen: a buffer of one contiguous WaveNet group runs as two free-running half-batch
 		// launches (the order of work on the internal streams is not observable from outside; Synchronize() and the host-buffer entry
 		// points wait for all of them).  1024 x A1 Standard x 128 frames: 40.1 -> 37.4 us per step.
-		// (not for a call that runs ordered on the batch stream: a resampling batch, a batch whose stages have entries)
-		if (ownsStream && !streamObserved && !RunsOrdered())
+		DeviceFacts facts = {};
+		facts.ownsStream = ownsStream;
+		facts.streamObserved = streamObserved;
+		facts.resamples = Resamples();
+		facts.stageEntries = StageHasEntries();
+		const bool tries = DeviceTriesFreeRunning(facts);
+		const bool residentTook = tries && TryResident(dIn, dOut, n, inStride, outStride);
+		const HostRoute route = DeviceRouteFor(facts, residentTook, tries && !residentTook && PrepareHalves(n));
+		lastRoute = (int)route;
+		switch (route)
 		{
-			if (TryResident(dIn, dOut, n, inStride, outStride)) return;
-			if (PrepareHalves(n))
-			{
-				LaunchHalves(dIn, dOut, n, inStride, outStride, nullptr, false);
-				return;
-			}
+		case HostRoute::DeviceResident: // (TryResident has posted the command)
+			break;
+		case HostRoute::DeviceHalves:
+			LaunchHalves(dIn, dOut, n, inStride, outStride, nullptr, false);
+			break;
+		case HostRoute::DeviceOrdered:
+			ProcessDeviceOrdered(dIn, dOut, n, inStride, outStride);
+			break;
+		default:
+			throw std::logic_error("neuralaudio_amd: internal: ProcessDevice route");
 		}
-		ProcessDeviceOrdered(dIn, dOut, n, inStride, outStride);
 	}
 
 	// on the batch stream, behind everything launched so far (the host-buffer entry points: their copies are on that stream; a lone
@@ -600,20 +611,11 @@ namespace na
 		lastStepHalves = false;
 		lastStepResident = false;
 		JoinHalves(); // earlier buffers ran on the resident launch / as two half-batch chains: this call's kernels come after them
-		if (pipelineUsed)
-		{
-			// buffers submitted through the pipelined interface run on per-slot streams: this call's kernels come after theirs ...
-			if (lastKernelStream != stream && lastKernelEvent) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
-		}
+		// buffers submitted through the pipelined interface run on per-slot streams: this call's kernels come after theirs ...
+		inFlight->OrderBehindLastKernel(stream);
 		ProcessDeviceOn(stream, dIn, dOut, n, inStride, outStride);
-		if (pipelineUsed)
-		{
-			// ... and the next submitted buffer after this call's
-			if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
-			CheckHip(hipEventRecord(mainDone, stream), "hipEventRecord");
-			lastKernelEvent = mainDone;
-			lastKernelStream = stream;
-		}
+		// ... and the next submitted buffer after this call's
+		if (inFlight->pipelineUsed) inFlight->NoteLastKernel(inFlight->RecordMainDone(stream), stream);
 	}
 
 	// One processing call on `launch`, and the one place that states its order: what a stage runs in front of the models, in StageId

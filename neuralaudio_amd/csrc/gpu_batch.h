@@ -21,6 +21,7 @@
 #include "device_resources.h"
 #include "eq_stage.h"
 #include "gate_stage.h"
+#include "host_route.h"
 #include "launch_plan.h"
 #include "meter_stage.h"
 #include "model_loader.h"
@@ -304,6 +305,8 @@ namespace na
 		// test hook (NA_DebugStallDevice): a kernel that keeps the batch stream busy for `ms` milliseconds (at most 10 s), behind whatever
 		// the stream holds -- a wedged device as far as every wait on this batch can tell
 		void DebugStallDevice(double ms);
+		// test hook (NA_DebugLastHostRoute): the HostRoute (host_route.h) the last processing call took, -1 before any
+		int DebugLastHostRoute() const { return lastRoute; }
 
 		void Synchronize();
 		// every buffer handed to ProcessDevice so far has been processed (host-side wait).  Unlike Synchronize() it leaves the resident
@@ -470,9 +473,8 @@ namespace na
 			std::vector<int> parkedRows; // ... and the rows that were parked then (host output zero)
 			hipEvent_t uploaded = nullptr, computed = nullptr, downloaded = nullptr;
 			hipStream_t own = nullptr; // upload, kernel and download of this slot's buffer, in order (batches that run as one launch)
-			bool onOwnStream = false;
 			hipEvent_t halfDone[kMaxChains] = {}; // free-running half-batch chains (Submit): this buffer's kernel of each chain
-			bool onHalfStreams = false;
+			SlotWait wait = SlotWait::DownloadedEvent; // what Collect waits for: the route the ticket took (host_route.h)
 			bool busy = false;
 		};
 		void DrainPipeline();
@@ -486,7 +488,6 @@ namespace na
 		hipStream_t halfStream[kMaxChains] = {};
 		int numChains = 2; // (tuning knob NA_HOST_CHAINS: 2 .. kMaxChains parts instead of halves)
 		bool markOpen = false; // between MarkTime(0) and MarkTime(1): a chain stream created now gets its start mark right away
-		bool halfChainsUsed = false;
 		bool lastStepHalves = false; // the last device-pointer / submitted buffer ran as two half-batch launches
 		bool streamObserved = false; // GetStream() was called (or the stream is the caller's): launches are ordered on `stream`
 		// The resident launch (gpu_batch_chains.cpp): one launch that stays on the chip and walks consecutive buffers, fed through a command
@@ -534,15 +535,16 @@ namespace na
 		void ZeroResampleHistories(int first, int count);
 		// set-up side: a zeroed [rows][rowFloats] block in place of `block`, the first `keepRows` rows copied over (resample.cpp)
 		void GrowRowBlock(float*& block, size_t rowFloats, int keepRows, int rows, const char* mallocWhat, const char* what);
-		// ordering between the batch stream and the slot streams: the stream state makes every kernel launch depend on the previous one
-		bool pipelineUsed = false;
-		hipEvent_t lastKernelEvent = nullptr, mainDone = nullptr;
-		hipStream_t lastKernelStream = nullptr;
-		bool lastSubmitOnBatchStream = false; // the last Submit ran its kernel on the batch stream (pinned blocks read in place), with no event behind it
-		unsigned long submitTopology = 0;
+		// what is in flight where -- the ordering between the batch stream, the slot streams and the chain streams: the stream state makes
+		// every kernel launch depend on the previous one
+		struct InFlight; // (gpu_batch_internal.h)
+		std::unique_ptr<InFlight> inFlight;
+		void WaitChains(); // every chain stream is idle (host-side wait)
+		int lastRoute = -1; // HostRoute of the last processing call (NA_DebugLastHostRoute)
 		PipeSlot pipe[kPipelineSlots];
 		hipStream_t copyIn = nullptr, copyOut = nullptr;
 		int nextSlot = 0;
+		bool EnsureSlotEvents(PipeSlot& s); // the slot's three events; true: created now
 		void EnsurePipeSlot(PipeSlot& s, size_t floats);
 		void EnsurePoolPipeline(); // ReserveStreams: what Submit / Collect would create on first use, whatever the number of launch units
 	};

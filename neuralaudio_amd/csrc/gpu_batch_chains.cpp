@@ -118,7 +118,7 @@ namespace na
 		CheckHip(hipSetDevice(device), "hipSetDevice");
 		DrainResident();
 		CheckHip(LaunchStallKernel(std::min(std::max(ms, 0.0), 10000.0), stream), "stall kernel");
-		if (halfChainsUsed)
+		if (inFlight->halfChainsUsed)
 			for (hipStream_t hs : halfStream)
 				if (hs) CheckHip(LaunchStallKernel(std::min(std::max(ms, 0.0), 10000.0), hs), "stall kernel");
 	}
@@ -233,15 +233,14 @@ namespace na
 			if (!ResidentConfigure()) return false;
 		}
 		if (!r.configured) return false;
-		if (pipelineUsed)
+		if (inFlight->pipelineUsed)
 			for (PipeSlot& p : pipe) // (buffers submitted through the pipelined host interface run on per-slot streams: behind them as well)
 				if (p.own) WaitStreamBounded(p.own, "hipStreamSynchronize");
-		if (halfChainsUsed)
+		if (inFlight->halfChainsUsed)
 		{
 			// an earlier buffer of another length ran as half-batch launches on the chain streams: the command comes behind them
-			for (hipStream_t hs : halfStream)
-				if (hs) WaitStreamBounded(hs, "hipStreamSynchronize");
-			halfChainsUsed = false;
+			WaitChains();
+			inFlight->halfChainsUsed = false;
 		}
 		if (r.exitRequested) DrainResident(); // a closing mark asked the launch to leave: this command starts the next generation
 		for (size_t offset = 0; offset < n; offset += (size_t)WN_MAX_FRAMES)
@@ -319,9 +318,7 @@ namespace na
 			}
 			return;
 		}
-		if (halfChainsUsed)
-			for (hipStream_t hs : halfStream)
-				if (hs) WaitStreamBounded(hs, "hipStreamSynchronize");
+		if (inFlight->halfChainsUsed) WaitChains();
 		WaitStreamBounded(stream, "hipStreamSynchronize");
 	}
 
@@ -349,10 +346,15 @@ namespace na
 	void GpuBatch::JoinHalves()
 	{
 		DrainResident();
-		if (!halfChainsUsed) return;
+		if (!inFlight->halfChainsUsed) return;
+		WaitChains();
+		inFlight->halfChainsUsed = false;
+	}
+
+	void GpuBatch::WaitChains()
+	{
 		for (hipStream_t hs : halfStream)
 			if (hs) WaitStreamBounded(hs, "hipStreamSynchronize");
-		halfChainsUsed = false;
 	}
 
 	// The buffer as two launch lists of half of every group's streams each (see halfStream); false: it runs as ordered launches.
@@ -372,7 +374,7 @@ namespace na
 		}
 		if (kernelStreams < 512) return false; // (a small batch: nothing below is worth its host time; the exact count is checked at the end)
 		// changed index lists are re-uploaded below (asynchronously, on the batch stream): nothing in flight may still read the old ones
-		if (dirty && (halfChainsUsed || pipelineUsed)) DrainPipeline();
+		if (dirty && (inFlight->halfChainsUsed || inFlight->pipelineUsed)) DrainPipeline();
 		if (!halfLists) halfLists.reset(new HalfLists());
 		HalfLists& hl = *halfLists;
 		for (auto& part : hl.part) part.clear();
@@ -408,12 +410,12 @@ namespace na
 	// the chains are about to take launches: whatever else is in flight for this batch comes first, and their streams exist
 	void GpuBatch::BeginHalves()
 	{
-		if (!halfChainsUsed || submitTopology != topologyVersion || halfLists->listsUploaded)
+		if (!inFlight->halfChainsUsed || inFlight->submitTopology != topologyVersion || halfLists->listsUploaded)
 		{
 			// whatever the batch stream (state resets, prewarms of new streams, index lists) or a slot stream still has in flight comes first
 			DrainPipeline();
 			WaitStreamBounded(stream, "hipStreamSynchronize");
-			submitTopology = topologyVersion;
+			inFlight->submitTopology = topologyVersion;
 		}
 		for (int h = 0; h < numChains; h++)
 		{
@@ -425,7 +427,7 @@ namespace na
 				CheckHip(hipEventRecord(marks[1 + h][0], halfStream[h]), "hipEventRecord");
 			}
 		}
-		halfChainsUsed = true;
+		inFlight->halfChainsUsed = true;
 		lastStepHalves = true;
 		lastStepResident = false;
 	}

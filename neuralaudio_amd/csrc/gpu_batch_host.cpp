@@ -13,9 +13,15 @@ namespace na
 		DrainResident();
 		for (PipeSlot& p : pipe)
 			if (p.own) WaitStreamBounded(p.own, "hipStreamSynchronize");
-		for (hipStream_t hs : halfStream)
-			if (hs) WaitStreamBounded(hs, "hipStreamSynchronize");
-		halfChainsUsed = false; // (the next half-batch launches wait for the batch stream first: LaunchHalves)
+		WaitChains();
+		inFlight->halfChainsUsed = false; // (the next half-batch launches wait for the batch stream first: LaunchHalves)
+	}
+
+	// the address under which the device reads a pinned block itself; nullptr: it cannot (not seen on MI355X)
+	static float* DeviceAlias(float* pinned)
+	{
+		float* d = nullptr;
+		return hipHostGetDevicePointer(reinterpret_cast<void**>(&d), pinned, 0) == hipSuccess ? d : nullptr;
 	}
 
 	void GpuBatch::EnsureStaging(size_t floats)
@@ -102,27 +108,34 @@ namespace na
 		CheckHip(hipSetDevice(device), "hipSetDevice");
 		FlushRearms();
 		const size_t total = streams.size() * n;
-		if (HostDirect())
+		BlockingFacts facts = {};
+		facts.hostDirect = HostDirect();
+		facts.stageEntries = StageHasEntries();
+		float *dIn = nullptr, *dOut = nullptr, *dStage = nullptr;
+		if (facts.hostDirect)
 		{
-			// blocks the caller registered: the kernels run on them as they are (no staging copies: 81 -> ~62 us for 1024 x 128)
-			float* dIn = static_cast<float*>(RegisteredDevicePointer(in, total * sizeof(float)));
-			float* dOut = static_cast<float*>(RegisteredDevicePointer(out, total * sizeof(float)));
-			// (while a stage has entries the rows go through the staging block below: the stages work in place on device memory, not as
-			// a read-modify-write over the bus -- that, not the order of the call, is what !StageHasEntries() means here and in `direct`)
-			if (dIn && dOut && !StageHasEntries())
-			{
-				ProcessDeviceOrdered(dIn, dOut, n, (long)n, (long)n);
-				WaitStreamBounded(stream, "hipStreamSynchronize");
-				ZeroRetiredRows(out, n, streams.size());
-				return;
-			}
+			dIn = static_cast<float*>(RegisteredDevicePointer(in, total * sizeof(float)));
+			dOut = static_cast<float*>(RegisteredDevicePointer(out, total * sizeof(float)));
+			facts.bothRegistered = dIn && dOut;
 		}
-		EnsureStaging(total);
-		float* dStage = nullptr;
-		// (stage entries: the copy engines and the device block, for the same reason)
-		const bool direct = HostDirect() && !StageHasEntries() && hipHostGetDevicePointer(reinterpret_cast<void**>(&dStage), hostStage, 0) == hipSuccess && dStage != nullptr;
-		if (direct && PrepareHalves(n) && halfLists->RowRangesOnly())
+		if (!BlockingRunsOnCallersBlocks(facts))
 		{
+			EnsureStaging(total);
+			if (DirectRows(facts.hostDirect, facts.stageEntries)) dStage = DeviceAlias(hostStage);
+			facts.pinnedAddressable = dStage != nullptr;
+		}
+		const bool halvesPrepared = BlockingTriesHalves(facts) && PrepareHalves(n);
+		facts.rowRangesOnly = halvesPrepared && halfLists->RowRangesOnly();
+		const HostRoute route = BlockingRouteFor(facts, halvesPrepared);
+		lastRoute = (int)route;
+		switch (route)
+		{
+		case HostRoute::RegisteredInPlace:
+			// the kernels run on the caller's blocks as they are (no staging copies: 81 -> ~62 us for 1024 x 128)
+			ProcessDeviceOrdered(dIn, dOut, n, (long)n, (long)n);
+			WaitStreamBounded(stream, "hipStreamSynchronize");
+			break;
+		case HostRoute::StagedHalves:
 			// The blocking call in two halves: the rows of the first half are staged and launched, the second half is staged while the
 			// first runs, and the first half's result is copied out while the second still runs -- the two 512 KB host copies of a
 			// 1024 x 128 buffer (2 x 10 us) hide behind the kernels: p50 75-77 -> 60 us.
@@ -139,23 +152,27 @@ namespace na
 				for (const WnFrameGroup& g : halfLists->part[h])
 					memcpy(out + (size_t)g.row0 * n, hostStage + (size_t)g.row0 * n, (size_t)g.numStreams * n * sizeof(float));
 			}
-			halfChainsUsed = false; // (both chains are idle again)
-			ZeroRetiredRows(out, n, streams.size());
-			return;
+			inFlight->halfChainsUsed = false; // (both chains are idle again)
+			break;
+		case HostRoute::StagedInPlace:
+		case HostRoute::StagedCopies:
+			memcpy(hostStage, in, total * sizeof(float));
+			if (route == HostRoute::StagedInPlace)
+				ProcessDeviceOrdered(dStage, dStage, n, (long)n, (long)n);
+			else
+			{
+				// (the knob is off, a stage has entries, or -- not seen on MI355X -- the device cannot address the pinned block)
+				CheckHip(hipMemcpyAsync(devStage, hostStage, total * sizeof(float), hipMemcpyHostToDevice, stream), "hipMemcpyAsync H2D");
+				ProcessDeviceOrdered(devStage, devStage, n, (long)n, (long)n);
+				CheckHip(hipMemcpyAsync(hostStage, devStage, total * sizeof(float), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync D2H");
+			}
+			JoinHalves();
+			WaitStreamBounded(stream, "hipStreamSynchronize");
+			memcpy(out, hostStage, total * sizeof(float));
+			break;
+		default:
+			throw std::logic_error("neuralaudio_amd: internal: ProcessHost route");
 		}
-		memcpy(hostStage, in, total * sizeof(float));
-		// (a pinned block the device cannot address -- not seen on MI355X -- goes through the copy engines instead of failing)
-		if (direct)
-			ProcessDeviceOrdered(dStage, dStage, n, (long)n, (long)n);
-		else
-		{
-			CheckHip(hipMemcpyAsync(devStage, hostStage, total * sizeof(float), hipMemcpyHostToDevice, stream), "hipMemcpyAsync H2D");
-			ProcessDeviceOrdered(devStage, devStage, n, (long)n, (long)n);
-			CheckHip(hipMemcpyAsync(hostStage, devStage, total * sizeof(float), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync D2H");
-		}
-		JoinHalves();
-		WaitStreamBounded(stream, "hipStreamSynchronize");
-		memcpy(out, hostStage, total * sizeof(float));
 		ZeroRetiredRows(out, n, streams.size());
 	}
 
@@ -170,23 +187,40 @@ namespace na
 		FlushRearms();
 		EnsureStaging(total);
 		memcpy(hostStage, in, total * sizeof(float));
-		float* dStage = nullptr;
-		if (HostDirect() && hipHostGetDevicePointer(reinterpret_cast<void**>(&dStage), hostStage, 0) == hipSuccess && dStage != nullptr)
-			ProcessDeviceOrdered(dStage, dOut, n, (long)n, outStride);
-		else
+		ToDeviceFacts facts = {};
+		facts.hostDirect = HostDirect();
+		float* const dStage = facts.hostDirect ? DeviceAlias(hostStage) : nullptr;
+		facts.pinnedAddressable = dStage != nullptr;
+		const HostRoute route = ToDeviceRouteFor(facts);
+		lastRoute = (int)route;
+		switch (route)
 		{
+		case HostRoute::ToDeviceInPlace:
+			ProcessDeviceOrdered(dStage, dOut, n, (long)n, outStride);
+			break;
+		case HostRoute::ToDeviceCopies:
 			CheckHip(hipMemcpyAsync(devStage, hostStage, total * sizeof(float), hipMemcpyHostToDevice, stream), "hipMemcpyAsync H2D");
 			ProcessDeviceOrdered(devStage, dOut, n, (long)n, outStride);
+			break;
+		default:
+			throw std::logic_error("neuralaudio_amd: internal: ProcessHostToDevice route");
 		}
+	}
+
+	// the three events of a slot; true: they were created now (the slot's first use)
+	bool GpuBatch::EnsureSlotEvents(PipeSlot& p)
+	{
+		if (p.uploaded) return false;
+		CheckHip(CountedHipEventCreateWithFlags(&p.uploaded, hipEventDisableTiming), "hipEventCreate");
+		CheckHip(CountedHipEventCreateWithFlags(&p.computed, hipEventDisableTiming), "hipEventCreate");
+		CheckHip(CountedHipEventCreateWithFlags(&p.downloaded, hipEventDisableTiming), "hipEventCreate");
+		return true;
 	}
 
 	void GpuBatch::EnsurePipeSlot(PipeSlot& p, size_t floats)
 	{
-		if (!p.uploaded)
+		if (EnsureSlotEvents(p))
 		{
-			CheckHip(CountedHipEventCreateWithFlags(&p.uploaded, hipEventDisableTiming), "hipEventCreate");
-			CheckHip(CountedHipEventCreateWithFlags(&p.computed, hipEventDisableTiming), "hipEventCreate");
-			CheckHip(CountedHipEventCreateWithFlags(&p.downloaded, hipEventDisableTiming), "hipEventCreate");
 			// the set-up side of the pipelined interface: the half-batch chains' streams too (creating a HIP stream takes ~13 ms)
 			for (int h = 0; h < numChains; h++)
 				if (!halfStream[h]) CheckHip(CountedHipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
@@ -210,12 +244,7 @@ namespace na
 	{
 		for (PipeSlot& p : pipe)
 		{
-			if (!p.uploaded)
-			{
-				CheckHip(CountedHipEventCreateWithFlags(&p.uploaded, hipEventDisableTiming), "hipEventCreate");
-				CheckHip(CountedHipEventCreateWithFlags(&p.computed, hipEventDisableTiming), "hipEventCreate");
-				CheckHip(CountedHipEventCreateWithFlags(&p.downloaded, hipEventDisableTiming), "hipEventCreate");
-			}
+			(void)EnsureSlotEvents(p);
 			if (!p.own) CheckHip(CountedHipStreamCreateWithFlags(&p.own, hipStreamNonBlocking), "hipStreamCreate");
 			for (int h = 0; h < numChains; h++)
 				if (!p.halfDone[h]) CheckHip(CountedHipEventCreateWithFlags(&p.halfDone[h], hipEventDisableTiming), "hipEventCreate");
@@ -224,7 +253,7 @@ namespace na
 			if (!halfStream[h]) CheckHip(CountedHipStreamCreateWithFlags(&halfStream[h], hipStreamNonBlocking), "hipStreamCreate");
 		if (!copyIn) CheckHip(CountedHipStreamCreateWithFlags(&copyIn, hipStreamNonBlocking), "hipStreamCreate");
 		if (!copyOut) CheckHip(CountedHipStreamCreateWithFlags(&copyOut, hipStreamNonBlocking), "hipStreamCreate");
-		if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
+		inFlight->EnsureMainDone();
 	}
 
 	int GpuBatch::Submit(const float* in, size_t n)
@@ -245,53 +274,52 @@ namespace na
 			for (size_t r = 0; r < streams.size(); r++)
 				if (streams[r].parked) p.parkedRows.push_back((int)r);
 		if (in) memcpy(p.hostIn, in, total * sizeof(float)); // nullptr: the caller filled NextInput() in place
-		const bool direct = HostDirect() && !StageHasEntries(); // (no read-modify-write over the bus: see ProcessHost)
+		SubmitFacts facts = {};
+		facts.hostDirect = HostDirect();
+		facts.stageEntries = StageHasEntries();
+		facts.resamples = Resamples();
 		float *dIn = nullptr, *dOut = nullptr;
-		if (direct && hipHostGetDevicePointer(reinterpret_cast<void**>(&dIn), p.hostIn, 0) == hipSuccess && dIn != nullptr &&
-			hipHostGetDevicePointer(reinterpret_cast<void**>(&dOut), p.hostOut, 0) == hipSuccess && dOut != nullptr)
+		if (DirectRows(facts.hostDirect, facts.stageEntries)) // (no read-modify-write over the bus: see ProcessHost)
 		{
-			// (a lone buffer gains nothing from being split -- 55-58 vs 60 us Submit .. Collect -- so only with another ticket in flight)
-			bool othersInFlight = false;
-			for (const PipeSlot& o : pipe) othersInFlight = othersInFlight || (&o != &p && o.busy);
-			// (nor does a submission whose caller has the library copy its rows: the host thread is the bottleneck there, 2 x 512 KB of
-			// memcpy per buffer, and a second launch only adds to it -- 48-50 vs 52-59 us per buffer)
-			if (in == nullptr && (othersInFlight || halfChainsUsed) && PrepareHalves(n))
-			{
-				// two free-running half-batch chains (see halfStream): each half in submission order on its own stream
-				for (int h = 0; h < numChains; h++)
-					if (!p.halfDone[h]) CheckHip(CountedHipEventCreateWithFlags(&p.halfDone[h], hipEventDisableTiming), "hipEventCreate");
-				LaunchHalves(dIn, dOut, n, (long)n, (long)n, p.halfDone, true);
-				halfChainsUsed = true;
-				pipelineUsed = true;
-				lastKernelEvent = nullptr; // (ProcessDevice after this drains the half streams itself)
-				lastKernelStream = nullptr;
-				p.onOwnStream = false;
-				p.onHalfStreams = true;
-				p.busy = true;
-				nextSlot = (nextSlot + 1) % kPipelineSlots;
-				return ticket;
-			}
+			dIn = DeviceAlias(p.hostIn);
+			dOut = DeviceAlias(p.hostOut);
+		}
+		facts.pinnedAddressable = dIn && dOut;
+		facts.callerPassedIn = in != nullptr;
+		for (const PipeSlot& o : pipe) facts.otherTicketInFlight = facts.otherTicketInFlight || (&o != &p && o.busy);
+		facts.chainsInUse = inFlight->halfChainsUsed;
+		UpdatePlan();
+		facts.launchUnits = (int)plan.units.size();
+		const HostRoute route = SubmitRouteFor(facts, SubmitTriesHalves(facts) && PrepareHalves(n));
+		lastRoute = (int)route;
+		switch (route)
+		{
+		case HostRoute::SubmitHalves:
+			// two free-running half-batch chains (see halfStream): each half in submission order on its own stream
+			for (int h = 0; h < numChains; h++)
+				if (!p.halfDone[h]) CheckHip(CountedHipEventCreateWithFlags(&p.halfDone[h], hipEventDisableTiming), "hipEventCreate");
+			LaunchHalves(dIn, dOut, n, (long)n, (long)n, p.halfDone, true);
+			inFlight->halfChainsUsed = true;
+			inFlight->NoteNoLastKernel(); // (ProcessDevice after this drains the half streams itself)
+			p.wait = SlotWait::ChainEvents;
+			break;
+		case HostRoute::SubmitInPlace:
 			JoinHalves(); // back on the batch stream: the half chains first
 			// (the buffer before this one ran on its slot's own stream while the output stage had entries: this buffer's kernel, and any
 			// index list it uploads again, come behind that one's)
-			if (lastKernelEvent && lastKernelStream != stream) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
+			inFlight->OrderBehindLastKernel(stream);
 			ProcessDeviceOn(stream, dIn, dOut, n, (long)n, (long)n);
-			lastSubmitOnBatchStream = true;
+			inFlight->lastSubmitOnBatchStream = true;
 			CheckHip(hipEventRecord(p.downloaded, stream), "hipEventRecord");
-			p.onOwnStream = false;
-			p.onHalfStreams = false;
-			p.busy = true;
-			nextSlot = (nextSlot + 1) % kPipelineSlots;
-			return ticket;
-		}
-		// One launch per buffer (the usual case): the whole buffer -- upload, kernel, download -- rides on the slot's OWN stream, in order,
-		// with no event between them; the only cross-stream edge is the stream state: this buffer's kernel waits for the previous
-		// buffer's.  The upload of buffer k + 1 (its stream's first operation) overlaps the kernel of buffer k, the download of buffer k
-		// (behind its kernel) overlaps the kernel of buffer k + 1.  Per buffer: 2 copies, 1 launch, 1 event wait, 1 event record --
-		// the round-2 path cost 2 more waits and 2 more records on the compute stream, 15 us per buffer (tools/microbench/host_pipe_probe.cpp).
-		UpdatePlan();
-		if (plan.units.size() <= 1 && !Resamples()) // (a resampling batch: three ordered launches, on the batch stream like a multi-unit batch)
+			p.wait = SlotWait::DownloadedEvent;
+			break;
+		case HostRoute::SubmitOwnStream:
 		{
+			// One launch per buffer (the usual case): the whole buffer -- upload, kernel, download -- rides on the slot's OWN stream, in order,
+			// with no event between them; the only cross-stream edge is the stream state: this buffer's kernel waits for the previous
+			// buffer's.  The upload of buffer k + 1 (its stream's first operation) overlaps the kernel of buffer k, the download of buffer k
+			// (behind its kernel) overlaps the kernel of buffer k + 1.  Per buffer: 2 copies, 1 launch, 1 event wait, 1 event record --
+			// the round-2 path cost 2 more waits and 2 more records on the compute stream, 15 us per buffer (tools/microbench/host_pipe_probe.cpp).
 			JoinHalves(); // (device-pointer steps may have run as half-batch chains: this buffer's kernel comes after both)
 			if (!p.own) CheckHip(CountedHipStreamCreateWithFlags(&p.own, hipStreamNonBlocking), "hipStreamCreate");
 			bool listsChanged = false, dirty = false;
@@ -299,50 +327,48 @@ namespace na
 			if (dirty)
 			{
 				// the index lists are re-uploaded on the batch stream: not before the kernels still reading the old ones are done
-				if (lastKernelEvent && lastKernelStream != stream) CheckHip(hipStreamWaitEvent(stream, lastKernelEvent, 0), "hipStreamWaitEvent");
+				inFlight->OrderBehindLastKernel(stream);
 				for (auto& g : groups)
 					if (g->NumActive() > 0) listsChanged = g->SyncActiveLists() || listsChanged;
 			}
-			if (listsChanged || submitTopology != topologyVersion || !pipelineUsed || lastSubmitOnBatchStream)
+			if (listsChanged || inFlight->submitTopology != topologyVersion || !inFlight->pipelineUsed || inFlight->lastSubmitOnBatchStream)
 			{
 				// everything the batch stream still has in flight for this batch (state resets of new streams, index lists, the buffer
 				// before this one where it ran there: the output stage's first entry moves the buffers of a direct batch over here) comes first
-				if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
-				CheckHip(hipEventRecord(mainDone, stream), "hipEventRecord");
-				CheckHip(hipStreamWaitEvent(p.own, mainDone, 0), "hipStreamWaitEvent");
-				submitTopology = topologyVersion;
-				lastSubmitOnBatchStream = false;
+				CheckHip(hipStreamWaitEvent(p.own, inFlight->RecordMainDone(stream), 0), "hipStreamWaitEvent");
+				inFlight->submitTopology = topologyVersion;
+				inFlight->lastSubmitOnBatchStream = false;
 			}
-			pipelineUsed = true;
+			inFlight->pipelineUsed = true;
 			CheckHip(hipMemcpyAsync(p.dev, p.hostIn, total * sizeof(float), hipMemcpyHostToDevice, p.own), "hipMemcpyAsync H2D");
-			if (lastKernelEvent && lastKernelStream != p.own) CheckHip(hipStreamWaitEvent(p.own, lastKernelEvent, 0), "hipStreamWaitEvent");
+			inFlight->OrderBehindLastKernel(p.own);
 			ProcessDeviceOn(p.own, p.dev, p.dev, n, (long)n, (long)n);
 			CheckHip(hipEventRecord(p.computed, p.own), "hipEventRecord");
-			lastKernelEvent = p.computed;
-			lastKernelStream = p.own;
+			inFlight->NoteLastKernel(p.computed, p.own);
 			CheckHip(hipMemcpyAsync(p.hostOut, p.dev, total * sizeof(float), hipMemcpyDeviceToHost, p.own), "hipMemcpyAsync D2H");
-			p.onOwnStream = true;
-			p.onHalfStreams = false;
-			p.busy = true;
-			nextSlot = (nextSlot + 1) % kPipelineSlots;
-			return ticket;
+			p.wait = SlotWait::OwnStream;
+			break;
 		}
-		// several launch units per buffer (a captured hipGraph on the batch stream): copies on the copy streams, events in between
-		if (!copyIn)
-		{
-			CheckHip(CountedHipStreamCreateWithFlags(&copyIn, hipStreamNonBlocking), "hipStreamCreate");
-			CheckHip(CountedHipStreamCreateWithFlags(&copyOut, hipStreamNonBlocking), "hipStreamCreate");
+		case HostRoute::SubmitCopyStreams:
+			// several launch units per buffer (a captured hipGraph on the batch stream): copies on the copy streams, events in between
+			if (!copyIn)
+			{
+				CheckHip(CountedHipStreamCreateWithFlags(&copyIn, hipStreamNonBlocking), "hipStreamCreate");
+				CheckHip(CountedHipStreamCreateWithFlags(&copyOut, hipStreamNonBlocking), "hipStreamCreate");
+			}
+			CheckHip(hipMemcpyAsync(p.dev, p.hostIn, total * sizeof(float), hipMemcpyHostToDevice, copyIn), "hipMemcpyAsync H2D");
+			CheckHip(hipEventRecord(p.uploaded, copyIn), "hipEventRecord");
+			CheckHip(hipStreamWaitEvent(stream, p.uploaded, 0), "hipStreamWaitEvent");
+			ProcessDeviceOrdered(p.dev, p.dev, n, (long)n, (long)n);
+			CheckHip(hipEventRecord(p.computed, stream), "hipEventRecord");
+			CheckHip(hipStreamWaitEvent(copyOut, p.computed, 0), "hipStreamWaitEvent");
+			CheckHip(hipMemcpyAsync(p.hostOut, p.dev, total * sizeof(float), hipMemcpyDeviceToHost, copyOut), "hipMemcpyAsync D2H");
+			CheckHip(hipEventRecord(p.downloaded, copyOut), "hipEventRecord");
+			p.wait = SlotWait::DownloadedEvent;
+			break;
+		default:
+			throw std::logic_error("neuralaudio_amd: internal: Submit route");
 		}
-		CheckHip(hipMemcpyAsync(p.dev, p.hostIn, total * sizeof(float), hipMemcpyHostToDevice, copyIn), "hipMemcpyAsync H2D");
-		CheckHip(hipEventRecord(p.uploaded, copyIn), "hipEventRecord");
-		CheckHip(hipStreamWaitEvent(stream, p.uploaded, 0), "hipStreamWaitEvent");
-		ProcessDeviceOrdered(p.dev, p.dev, n, (long)n, (long)n);
-		CheckHip(hipEventRecord(p.computed, stream), "hipEventRecord");
-		CheckHip(hipStreamWaitEvent(copyOut, p.computed, 0), "hipStreamWaitEvent");
-		CheckHip(hipMemcpyAsync(p.hostOut, p.dev, total * sizeof(float), hipMemcpyDeviceToHost, copyOut), "hipMemcpyAsync D2H");
-		CheckHip(hipEventRecord(p.downloaded, copyOut), "hipEventRecord");
-		p.onOwnStream = false;
-		p.onHalfStreams = false;
 		p.busy = true;
 		nextSlot = (nextSlot + 1) % kPipelineSlots;
 		return ticket;
@@ -353,12 +379,18 @@ namespace na
 		CheckUsable();
 		if (ticket < 0 || ticket >= kPipelineSlots || !pipe[ticket].busy) throw std::runtime_error("neuralaudio_amd: Collect with an invalid ticket");
 		PipeSlot& p = pipe[ticket];
-		if (p.onHalfStreams)
+		switch (p.wait)
 		{
+		case SlotWait::ChainEvents:
 			for (int h = 0; h < numChains; h++) WaitEventBounded(p.halfDone[h], "hipEventSynchronize");
+			break;
+		case SlotWait::OwnStream:
+			WaitStreamBounded(p.own, "hipStreamSynchronize"); // the download is the stream's last operation
+			break;
+		case SlotWait::DownloadedEvent:
+			WaitEventBounded(p.downloaded, "hipEventSynchronize");
+			break;
 		}
-		else if (p.onOwnStream) WaitStreamBounded(p.own, "hipStreamSynchronize"); // the download is the stream's last operation
-		else WaitEventBounded(p.downloaded, "hipEventSynchronize");
 		// the slot holds the rows the batch had at Submit: ids retired since then are zeroed only inside that block
 		for (int id : retired)
 			if ((size_t)id < p.rows) memset(p.hostOut + (size_t)id * p.n, 0, p.n * sizeof(float));

@@ -1,5 +1,7 @@
 // gpu_batch_internal.h -- declarations shared by the translation units of class GpuBatch (gpu_batch.cpp: lifecycle and launch
-// dispatch; gpu_batch_chains.cpp: half-batch chains, resident launch, timing marks; gpu_batch_host.cpp: host-buffer entry points; gpu_batch_snapshot.cpp: stream snapshots)
+// dispatch; gpu_batch_chains.cpp: half-batch chains, resident launch, timing marks; gpu_batch_host.cpp: host-buffer entry points; gpu_batch_snapshot.cpp: stream snapshots).
+// Which route a processing call takes is not decided here but in host_route.h (host data only); what the next launch has to come
+// behind is InFlight below, the one member of GpuBatch that says what is in flight where.
 #pragma once
 
 #include "gpu_groups.h"
@@ -19,6 +21,53 @@ namespace na
 				for (const WnFrameGroup& g : list)
 					if (g.slots != nullptr || g.pack > 1) return false;
 			return true;
+		}
+	};
+
+	// What of this batch is in flight where, as far as the NEXT launch has to know: the stream state makes every kernel launch depend on
+	// the one before it, whichever stream either runs on (batch stream, a slot's own stream, the chain streams).  The resident launch
+	// keeps its own books (ResidentState).
+	struct GpuBatch::InFlight
+	{
+		// a buffer has gone through Submit on a slot stream or the chains, so work of this batch may sit on streams other than the batch
+		// stream.  Never cleared.  Every assignment of `lastKernelEvent` sets it first, so `lastKernelEvent != nullptr` implies it: the
+		// sites that asked for `pipelineUsed && lastKernelEvent` asked for `lastKernelEvent`.
+		bool pipelineUsed = false;
+		// the event behind the last kernel launched outside the free-running forms, and the stream it was recorded on; both null: none,
+		// or the last kernels ran on the chains (whoever comes next drains those itself: JoinHalves, BeginHalves)
+		hipEvent_t lastKernelEvent = nullptr;
+		hipStream_t lastKernelStream = nullptr;
+		// the last Submit ran its kernel on the batch stream (pinned blocks read in place), with no event behind it: the next buffer on a
+		// slot stream waits for the batch stream first
+		bool lastSubmitOnBatchStream = false;
+		// the topology version whose state resets and index lists the slot streams / the chains have been put behind
+		unsigned long submitTopology = 0;
+		// the chain streams may hold work of this batch; cleared by whoever has waited for all of them (WaitChains)
+		bool halfChainsUsed = false;
+		// recorded on the batch stream for a stream that has to come behind it; created on first use (or by EnsureMainDone on the set-up side)
+		hipEvent_t mainDone = nullptr;
+
+		// `s` comes behind the last kernel (nothing to do when that ran on `s` itself)
+		void OrderBehindLastKernel(hipStream_t s) const
+		{
+			if (lastKernelEvent && lastKernelStream != s) CheckHip(hipStreamWaitEvent(s, lastKernelEvent, 0), "hipStreamWaitEvent");
+		}
+		void NoteLastKernel(hipEvent_t event, hipStream_t s)
+		{
+			pipelineUsed = true;
+			lastKernelEvent = event;
+			lastKernelStream = s;
+		}
+		void NoteNoLastKernel() { NoteLastKernel(nullptr, nullptr); }
+		void EnsureMainDone()
+		{
+			if (!mainDone) CheckHip(CountedHipEventCreateWithFlags(&mainDone, hipEventDisableTiming), "hipEventCreate");
+		}
+		hipEvent_t RecordMainDone(hipStream_t batchStream)
+		{
+			EnsureMainDone();
+			CheckHip(hipEventRecord(mainDone, batchStream), "hipEventRecord");
+			return mainDone;
 		}
 	};
 

@@ -64,6 +64,7 @@ namespace na
 		int NumStreams() const { return total; }
 		int NumShards() const { return (int)shards.size(); }
 		void ShardRange(int shard, int& begin, int& end, int& device) const;
+		int DebugShardLastHostRoute(int shard) const { return shards.at((size_t)shard)->batch->DebugLastHostRoute(); } // (between calls)
 
 		// host arrays [streams][n]: every worker runs its shard's rows through GpuBatch::ProcessHost; returns when all are done
 		void Process(const float* in, float* out, size_t n);
