@@ -191,10 +191,12 @@ def gru_forward_keras(model_json, x, prewarm=2048):
     return out[prewarm:]
 
 
-def keras_stack_forward(model_json, x, prewarm=2048):
+def keras_stack_forward(model_json, x, prewarm=2048, dtype=np.float64):
     """Generic keras stack [lstm | gru]* + dense+ (what the reference hands to RTNeural's json_parser, RTNeuralModel.h:300), in float64
     with the Keras layer definitions and accurate tanh / sigmoid = (tanh(x/2)+1)/2 (the reference's FastMathsProvider,
-    RTNeuralModel.h:10-31).  Output = unit 0 of the last layer; zero initial state, `prewarm` zeros first."""
+    RTNeuralModel.h:10-31).  Output = unit 0 of the last layer; zero initial state, `prewarm` zeros first.
+    dtype: the type that weights, state, input and constants are held in (np.float32: the same walk in single precision, which the CPU
+    tests use to show how much of a GPU bound float32 arithmetic itself may take)."""
     layers = model_json["layers"]
     sig = lambda v: 0.5 * (np.tanh(0.5 * v) + 1.0)
     def softmax(v):
@@ -208,17 +210,17 @@ def keras_stack_forward(model_json, x, prewarm=2048):
     for l in layers:
         H = int(l["shape"][-1])
         if l["type"] in ("lstm", "gru"):
-            state.append([np.zeros(H), np.zeros(H)])
+            state.append([np.zeros(H, dtype=dtype), np.zeros(H, dtype=dtype)])
         elif l["type"] == "conv1d":  # the layer's input history, newest last: (kernel_size - 1) * dilation + 1 rows (zero after reset)
-            state.append(np.zeros(((lastint(l["kernel_size"]) - 1) * lastint(l.get("dilation", 1)) + 1, width)))
+            state.append(np.zeros(((lastint(l["kernel_size"]) - 1) * lastint(l.get("dilation", 1)) + 1, width), dtype=dtype))
         else:
             state.append(None)
         width = H
-    W = [[np.array(w, dtype=np.float64) for w in l["weights"]] for l in layers]
-    xs = np.concatenate([np.zeros(prewarm), np.asarray(x, dtype=np.float64)])
-    out = np.empty(xs.size)
+    W = [[np.array(w, dtype=dtype) for w in l["weights"]] for l in layers]
+    xs = np.concatenate([np.zeros(prewarm, dtype=dtype), np.asarray(x, dtype=dtype)])
+    out = np.empty(xs.size, dtype=dtype)
     for t, xv in enumerate(xs):
-        v = np.array([xv])
+        v = np.array([xv], dtype=dtype)
         for i, l in enumerate(layers):
             H = int(l["shape"][-1])
             if l["type"] == "lstm":
@@ -249,8 +251,8 @@ def keras_stack_forward(model_json, x, prewarm=2048):
             elif l["type"] == "activation":
                 v = acts[l.get("activation", "") or ""](v)
             elif l["type"] == "batchnorm":  # inference form; [gamma, beta, mean, var] or [mean, var]; keras default epsilon
-                eps = float(l.get("epsilon", 1e-3))
-                g, b, m, s2 = (W[i][0].ravel(), W[i][1].ravel(), W[i][2].ravel(), W[i][3].ravel()) if len(W[i]) >= 4 else (1.0, 0.0, W[i][0].ravel(), W[i][1].ravel())
+                eps = dtype(l.get("epsilon", 1e-3))
+                g, b, m, s2 = (W[i][0].ravel(), W[i][1].ravel(), W[i][2].ravel(), W[i][3].ravel()) if len(W[i]) >= 4 else (dtype(1.0), dtype(0.0), W[i][0].ravel(), W[i][1].ravel())
                 v = g * (v - m) / np.sqrt(s2 + eps) + b
             elif l["type"] == "prelu":
                 alpha = W[i][0].ravel()

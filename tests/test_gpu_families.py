@@ -76,6 +76,20 @@ def test_forced_recurrent_regime_passes_the_runtime_shaped_kernel_suite(env):
     forced_run(dict(env, NA_TEST_NO_WARM="1"), [os.path.join(T, "test_gpu_recurrent_rt.py")], 240)
 
 
+# the keras-stack tails over their own file: the lane = stream kernels' DenseTail calls (LstmGenericKernel / GruGenericKernel: 64 streams per
+# workgroup, idle lanes in the last one) under the two knobs that send dense-tail models there, and the runtime-shaped kernel on
+# L2-streamed weights in front of both tail forms.  Conv1d tails stay on the runtime-shaped kernel under all three; a dense-tail case beyond
+# the lane = stream kernels' LDS bound skips under the first two.  (The file's in-place tests import torch: the child keeps the warm import.)
+TAILS = [{"NA_LSTM_NO_WAVE_RT": "1"}, {"NA_LSTM_LANE_KERNEL": "1"}, {"NA_REC_L2W": "1"}]
+
+
+@pytest.mark.gpu
+@pytest.mark.watchdog(260)
+@pytest.mark.parametrize("env", TAILS, ids=ident)
+def test_forced_recurrent_kernel_passes_the_tail_suite(env):
+    forced_run(env, [os.path.join(T, "test_gpu_tails.py")], 240)
+
+
 # the f32 frame kernel's instantiations that ship behind a tuning knob over its own file (the knobs do not skip it): ring history
 # prefetched into LDS (Launch<2, 2, 1> and <2, 2, 2>), no prefetch at all for long buffers too (<2, 0, 1>), and four streams per workgroup
 # (<2, 1, 4>) -- each takes the default shape where its LDS does not fit (frame_lds.h), which the file's large-kernel tests reach.

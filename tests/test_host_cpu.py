@@ -21,6 +21,7 @@ import ref_np
 import frame_cases as FC
 import recurrent_cases as RC
 import split_cases as SC
+import tail_cases as TC
 import wide_cases as WC
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -1042,6 +1043,158 @@ def test_recurrent_oracle_keeps_its_headroom_under_the_gpu_bound(c):
         err = O.rms(got - want)
         print("%s amplitude %g: oracle-float64 rms %.3g, bound %.3g" % (RC.case_id(c), amp, err, RC.bound(want)))
         assert np.all(np.isfinite(got)) and err <= share * RC.bound(want), (RC.case_id(c), amp, err, RC.bound(want))
+
+
+# ---- the keras-stack tails' test shapes (tests/tail_cases.py, run by tests/test_gpu_tails.py) -------------------------------------------
+# These checks are what makes the GPU bound of that file mean something: a case's output depends on its input, float32 arithmetic alone
+# stays far below the bound, and a checker with a wrong tap, a wrong dilation or no softmax would be off by a hundred bounds.
+
+_tail_walks = {}
+
+
+def _tail_walk(c, amp=1.0, zero=False, dtype=np.float64):
+    """The restatement's walk of a case (its own signal at `amp`, or zeros of that length): computed once, shared, never changed."""
+    key = (c["name"], amp, zero, dtype)
+    if key not in _tail_walks:
+        x = TC.signal(c, amp)
+        w = TC.Built(c).f64(np.zeros_like(x) if zero else x, dtype=dtype)
+        w.setflags(write=False)
+        _tail_walks[key] = w
+    return _tail_walks[key]
+
+
+@pytest.mark.parametrize("c", TC.cases(), ids=TC.case_id)
+def test_every_tail_case_loads_and_runs_where_it_is_listed(na, c):
+    """Without a GPU: the loader takes the case, the plan of the loaded model is the plan of the dimensions tests/tail_cases.py lowers
+    the stack to (so the sizes read from the shape predicate mean what the table says), the decision function names the kernel and the
+    plan the regime the case is listed for, and the call partition holds every size it must."""
+    _recurrent_knob_free()
+    m = TC.Built(c).load(na, prewarm=False)
+    p, sp, runs = m.RecurrentPlan(), TC.plan(c["spec"]), c["runs"]
+    assert sp["admitted"] and {k: p[k] for k in p} == {k: sp[k] for k in p}, (c["name"], p, sp)
+    assert p["lds_bytes"] <= 160 * 1024
+    assert na.recurrent_kernel(*TC.dims(c["spec"])) == runs["kernel"] == "RecurrentWaveRtKernel" and p["runs"], (c["name"], p)
+    assert not p["head_in_loop"], "a tail is evaluated behind the block"
+    if "waves" in runs:
+        assert (p["waves"] == 1) == (runs["waves"] == "one"), (c["name"], p)
+    if "l2w" in runs:
+        assert int(p["l2w"]) == runs["l2w"], (c["name"], p)
+    if "tail_layers" in runs:
+        assert len(TC.lowered(c["spec"])) == runs["tail_layers"], c["name"]
+    assert (TC.history(c["spec"]) > 0) == (c["form"] == "conv") and c["hist"] == TC.history(c["spec"])
+    # under the knobs that force the lane = stream kernels a conv1d tail stays where it is, a dense tail moves or has no kernel
+    for knob in ("NA_LSTM_NO_WAVE_RT", "NA_LSTM_LANE_KERNEL"):
+        forced = na.recurrent_kernel(*TC.dims(c["spec"]), knobs=(knob,))
+        if c["form"] == "conv":
+            assert forced == "RecurrentWaveRtKernel", (c["name"], knob, forced)
+        elif knob == "NA_LSTM_NO_WAVE_RT" or TC.dims(c["spec"])[0] == "lstm":
+            assert forced in ("", "LstmGenericKernel", "GruGenericKernel"), (c["name"], knob, forced)
+    sizes = TC.Built(c).sizes()
+    assert sum(sizes) == c["samples"] >= 3 * c["hist"] + 300 and sizes[:4] == [1, 1, 2, 3] and max(sizes) > TC.MAX_FRAMES
+    assert set(TC.FIXED_CALLS) <= set(sizes)
+    if c["form"] == "conv":
+        assert {h for h in (c["hist"] - 1, c["hist"], c["hist"] + 1) if 1 <= h <= 300} <= set(sizes), (c["name"], sizes)
+    m.close()
+
+
+@pytest.mark.parametrize("c", TC.refused_cases(), ids=TC.case_id)
+def test_every_tail_shape_beyond_a_limit_is_refused_by_name(na, c):
+    with pytest.raises(na.NeuralAudioError, match=c["refused"]):
+        na.NeuralModelLoader().CreateFromString(TC.Built(c).doc, ".json", doPrewarm=False)
+
+
+def test_tail_cases_reach_every_path_of_the_tails(na):
+    """The set of cases reaches both tail forms, a tail without and behind recurrent layers, conv1d histories below, at and above
+    LSTM_MAX_FRAMES and at the limit, one-wave and multi-wave shapes, gate weights in LDS and streamed from L2, every activation code in
+    both forms, and the sizes read from the shape predicate are edges of it."""
+    _recurrent_knob_free()
+    cs = TC.cases()
+    plans = {c["name"]: TC.plan(c["spec"]) for c in cs}
+    for form in ("conv", "dense"):
+        mine = [c for c in cs if c["form"] == form]
+        assert {len(TC.recurrent(c["spec"])) > 0 for c in mine} == {False, True}, form                 # Hin == 0 and Hin > 0
+        assert {TC.dims(c["spec"])[0] for c in mine if TC.recurrent(c["spec"])} == {"lstm", "gru"}, form
+        assert {plans[c["name"]]["waves"] == 1 for c in mine} == {False, True}, form
+        assert {bool(plans[c["name"]]["l2w"]) for c in mine} == {False, True}, form
+        acts = set()
+        for c in mine:
+            for l in TC.scaled_stack(c["spec"], c["seed"])["layers"]:
+                if l["type"] in ("dense", "conv1d", "activation"):
+                    acts.add(l.get("activation") or "linear")
+        assert acts >= {"linear", "tanh", "relu", "sigmoid", "elu", "softmax"}, (form, acts)
+    hists = {c["hist"] for c in cs if c["form"] == "conv"}
+    assert {TC.MAX_FRAMES - 1, TC.MAX_FRAMES, TC.MAX_FRAMES + 1, TC.max_history()} <= hists and min(hists) < 64
+    assert (True, 1) in {(plans[c["name"]]["waves"] == 1, int(plans[c["name"]]["l2w"])) for c in cs if c["form"] == "conv"}  # one wave, streamed
+    widths = set()
+    for c in cs:
+        if c["form"] == "dense":
+            widths |= {t[1] for t in TC.lowered(c["spec"])}
+    assert widths >= {1, 63, 64, 65, 256}
+    assert any(len(TC.lowered(c["spec"])) == 8 for c in cs)
+    # a layer whose history is shorter than the longest of its tail, in front of and behind the longest
+    orders = [[(t[2] - 1) * t[3] for t in TC.lowered(c["spec"]) if t[2] > 1] for c in cs if c["form"] == "conv"]
+    assert any(len(o) == 3 and o[1] < o[2] < o[0] for o in orders) and any(len(o) == 3 and o[1] < o[0] < o[2] for o in orders)
+    assert any(TC.lowered(c["spec"])[0][2] == 1 and TC.history(c["spec"]) > 0 and not TC.recurrent(c["spec"]) for c in cs)  # dense first, conv behind
+    # the sizes read from the shape predicate are its edges
+    assert TC.max_history() == 1024 and not RC.shape_plan("lstm", 1, 0, 1, 1, TC.max_history() + 1)["admitted"]
+    for kind in ("lstm", "gru"):
+        w = TC.widest_conv_input(kind)
+        assert plans["conv-widest-" + kind]["waves"] > 1 and not TC.plan(TC._conv_probe(kind, w + 1, 2, 1))["admitted"]
+    wh = TC.dims(TC.by_name("conv-hist-limit")["spec"])[1]
+    assert TC.plan(TC._conv_probe("lstm", wh, 3, 512))["admitted"] and not TC.plan(TC._conv_probe("lstm", wh + 1, 3, 512))["admitted"]
+    # the cases of the batch tests: a short history for the growth test, conv1d tails where one is asked for, softmax in the lane cases
+    assert [TC.by_name(n)["form"] for n in TC.GROWTH_CASES] == ["conv", "dense"] and TC.by_name(TC.GROWTH_CASES[0])["hist"] <= 64
+    assert TC.by_name(TC.LEAVE_JOIN_CASE)["form"] == "conv"
+    assert [TC.by_name(n)["form"] for n in TC.MIXED_CASES] == ["conv", "conv", "dense"]
+    assert [TC.by_name(n)["form"] for n in TC.IN_PLACE_CASES] == ["conv", "dense"] and not TC.recurrent(TC.by_name(TC.IN_PLACE_CASES[0])["spec"])
+    for n in TC.LANE_CASES:
+        c = TC.by_name(n)
+        assert c["form"] == "dense" and any(len(l) > 2 and l[2] == "softmax" for l in c["spec"])
+        assert na.recurrent_kernel(*TC.dims(c["spec"]), knobs=("NA_LSTM_NO_WAVE_RT",)) in ("LstmGenericKernel", "GruGenericKernel"), n
+    assert {TC.dims(TC.by_name(n)["spec"])[0] for n in TC.LANE_CASES} == {"lstm", "gru"}
+
+
+@pytest.mark.parametrize("c", TC.cases(), ids=TC.case_id)
+def test_tail_case_output_depends_on_its_input(c):
+    """The signal path: rms(want - want for a zero input) is at least 0.1 and at least a fifth of rms(want).  A condition, not a
+    measurement: a case that misses it gets another gain in tests/tail_cases.py."""
+    want, zero = _tail_walk(c), _tail_walk(c, zero=True)
+    path = O.rms(want - zero)
+    print("%-28s rms(want) %.3g, rms(want - zero-input want) %.3g" % (c["name"], O.rms(want), path))
+    assert path >= 0.1 and path >= 0.2 * O.rms(want), (c["name"], path, O.rms(want))
+
+
+@pytest.mark.parametrize("c", TC.cases(), ids=TC.case_id)
+def test_float32_walk_of_a_tail_case_keeps_its_headroom_under_the_gpu_bound(c):
+    """The restatement walked in float32 (weights, state, input and constants) is within a quarter of the GPU bound of the float64 walk at
+    amplitudes 1 and 1000: the bound measures the kernel, not the number format."""
+    for amp in (1.0, 1000.0):
+        want, got = _tail_walk(c, amp), _tail_walk(c, amp, dtype=np.float32)
+        err = O.rms(got - want)
+        print("%-28s amplitude %g: float32-float64 rms %.3g, bound %.3g (%.3f of it)" % (c["name"], amp, err, TC.bound(want), err / TC.bound(want)))
+        assert got.dtype == np.float32 and np.all(np.isfinite(got)) and err <= 0.25 * TC.bound(want), (c["name"], amp, err, TC.bound(want))
+
+
+@pytest.mark.parametrize("c", TC.cases(), ids=TC.case_id)
+def test_a_wrong_tap_dilation_or_softmax_would_be_noticed_on_a_tail_case(c):
+    """Each mutant of the restatement, one at a time -- the oldest tap of a conv1d layer reads zeros, its dilation is one larger, softmax
+    is the identity -- is off by at least 100 bounds on every case it applies to."""
+    b, x, want = TC.Built(c), TC.signal(c), _tail_walk(c)
+    muts = TC.mutants(b.mj)
+    assert muts or c["form"] == "dense"
+    for name, mj in muts:
+        off = O.rms(b.f64(x, mj=mj) - want) / TC.bound(want)
+        print("%-28s %-32s off by %.0f bounds" % (c["name"], name, off))
+        assert off >= 100.0, (c["name"], name, off)
+
+
+def test_keras_stack_walk_is_in_float64_unless_asked_otherwise():
+    """The walk's default type is float64 -- asking for it by name changes no bit -- and float32 is held all the way through."""
+    mj = ref_np.synth_keras_stack([("gru", 12), ("conv1d", 16, 4, 64, "elu"), ("batchnorm", 16, "noaffine"), ("dense", 5, "softmax"), ("dense", 1)], seed=8)
+    x = O.signal_noise(200, 3)
+    a, b = ref_np.keras_stack_forward(mj, x, prewarm=64), ref_np.keras_stack_forward(mj, x, prewarm=64, dtype=np.float64)
+    assert a.dtype == np.float64 and np.array_equal(a, b)
+    assert ref_np.keras_stack_forward(mj, x, prewarm=64, dtype=np.float32).dtype == np.float32
 
 
 # ---- the f32 frame kernel's test shapes (tests/frame_cases.py, run by tests/test_gpu_frame.py) -------------------------------------------
