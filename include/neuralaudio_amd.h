@@ -387,6 +387,83 @@ NA_EXTERN int NA_BatchGetMeterInfo(NA_Batch* batch, NA_MeterInfo* info);
 NA_EXTERN int NA_BatchSetStreamMeter(NA_Batch* batch, int stream, const NA_MeterParams* params); /* params = NULL: the meter goes at once */
 NA_EXTERN int NA_BatchGetStreamMeter(NA_Batch* batch, int stream, NA_MeterParams* out);  /* 1: filled; 0: no meter; < 0: bad id / not enabled */
 NA_EXTERN int NA_BatchReadStreamMeter(NA_Batch* batch, int stream, NA_MeterReading* out); /* 1: filled; 0: nothing to read yet; < 0: bad id / not enabled / broken */
+/* ---- the tuner stage: per-stream pitch readings ----
+ * The tuner in front of the amp: every hopSamples it estimates the period of the row a stream takes in, from an autocorrelation of about
+ * 85 ms of signal over several hundred lags -- on the order of a million multiply-adds an evaluation, times the sessions, times 20 - 50
+ * evaluations a second: more than a host wants on its audio thread, and the dry rows are on the device already.  A sixth per-stream
+ * stage, off unless enabled, last in the chain's order.  It never writes an audio row: with or without tuners the samples out are the
+ * same bits.  A batch that enabled it and set no tuner launches exactly what it launched before.
+ * Order of a processing call: everything the stage does runs in front of the models, behind the meter's IN tap -- it reads the input
+ * rows as the caller passed them (in a resampling batch: the external-rate rows; input and output rows may be the same memory).
+ * Arithmetic.  After one float multiply per sample everything is an integer, hence exact: a reading is the same bits however the
+ * signal is cut into calls, at any alignment or stride.  Positions p = 0, 1, ... count the samples the caller sees on the stream's
+ * input row since the set call (in a resampling batch: external-rate samples).  D = decimation, W = windowSamples, H = hopSamples;
+ * W, minLag, maxLag, H and phase count decimated samples.
+ *     c    = (x is NaN) ? 0 : min(max(x, -1.0f), 1.0f)
+ *     q[p] = (int) trunc(c * 32767.0f)                      (one f32 product, then integers only)
+ *     d[m] = q[mD] + q[mD+1] + ... + q[mD+D-1]   for m >= 0;   d[m] = 0 for m < 0        (|d| < 2^18)
+ *     evaluation k = 0, 1, ... ends at m_k = phase + (k+1)*H - 1 and belongs to the call that holds position (m_k+1)*D - 1
+ *     for t = 0 .. maxLag+1, signed / unsigned 64-bit:
+ *         r[t] = sum over j = 0 .. W-1 of d[m_k - j] * d[m_k - j - t]                      (|r| < 2^47)
+ *         e[t] = sum over j = 0 .. W-1 of d[m_k - j - t] * d[m_k - j - t]                  (e[0] = r[0])
+ *     lag = 0 if e[0] < minEnergy
+ *     z   = the smallest t in [1, maxLag+1] with r[t] <= 0;          none: lag = 0
+ *     candidates: t in [max(minLag, z+1), maxLag] with r[t] > 0 and r[t] > r[t-1] and r[t] >= r[t+1];   none: lag = 0
+ *     rmax = max of r[t] over the candidates
+ *     lag  = the smallest candidate t with 1024 * r[t] >= thresholdQ10 * rmax              (< 2^57)
+ *   A reading holds evaluations = k + 1, position = (m_k + 1) * D, lag (0: no pitch), decimation, e0 = e[0], and r[i], e[i] = r and e at
+ *   lag - 1, lag, lag + 1 (all zero when lag = 0).  A call that holds several evaluation ends of a stream computes only the last of
+ *   them; `evaluations` still counts them all: which evaluations are computed depends on the cut, the bits of evaluation k never do.
+ * Limits (each refused with a message that names the field): decimation in [1, 8] (any integer); windowSamples in [32, 2048]; maxLag in
+ *   [4, 1024]; minLag in [2, maxLag]; hopSamples in [16, 65536]; phase in [0, hopSamples); thresholdQ10 in [512, 1024].  minEnergy is any
+ *   value; reserved is ignored.
+ * NA_BatchEnableTunerStage is the set-up side (allocates; idempotent): an open group and a ring of 8192 decimated samples per row, the
+ *   stage's device + pinned tables and a device + pinned result block per table; later NA_BatchAddStreams / NA_BatchReserveStreams grow
+ *   them.  Every call below fails ("tuner stage not enabled (NA_BatchEnableTunerStage)") before it.  NA_BatchGetTunerInfo reports the
+ *   number of tuners and the device memory the stage holds.
+ * NA_BatchSetStreamTuner is REAL-TIME SAFE: host arithmetic on tables that exist; no memset travels with it.
+ *   The stream has no tuner: the tuner starts at the next sample, at position 0.
+ *   The stream has a tuner: it RESTARTS at position 0 with the new constants; no reading is available until its first evaluation has
+ *     arrived, and nothing the earlier tuner took in or produced is read again.
+ *   params == NULL: the tuner goes at once (it touches no audio, so there is no tail).  On a stream without a tuner it does nothing.
+ * NA_BatchGetStreamTuner returns 1 and fills *out with the constants in effect, 0 when the stream has no tuner, < 0 on a bad id or when
+ *   the stage is not enabled.
+ * NA_BatchReadStreamTuner is REAL-TIME SAFE: no wait, no allocation, no device call other than event queries.  It returns 1 and the
+ *   newest reading that has ARRIVED on the host -- a processing call that holds an evaluation end leaves its records in pinned memory
+ *   behind its launches, and this call (like the start of every processing call) asks the events of those copies whether they are
+ *   over --, 0 if the stream has no tuner or no evaluation has arrived yet, < 0 on a bad id, when the stage is not enabled, or on a
+ *   broken batch.  The reading says which evaluation it is (`evaluations`, `position`).  After NA_BatchSynchronize everything has
+ *   arrived.  Call it from the thread that drives the batch, like every other call.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a
+ * hand-over, drop the tuner at once.  Tuners are not part of a NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves them alone.
+ * While an entry exists -- a stream with a tuner -- a processing call behaves as it does with entries of the other stages: its
+ * launches run in order on one stream (no half-batch chains, no resident launch), host buffers go through the library's device staging
+ * block, and it enqueues one table upload from a ring of pinned tables and one append launch over the streams with a tuner per piece of
+ * 4096 samples; a call that holds an evaluation end of an entry adds one evaluate launch over those entries only and one copy of
+ * their records into the pinned result block of the same ring slot: no device or pinned allocation, no stream or event creation, no
+ * unbounded wait.  With the last entry the free-running modes come back.
+ * Host helpers (double precision, not part of the exact contract).  NA_TunerPitch: n_i = 2 r[i] / (e0 + e[i]) (0 on a zero denominator),
+ *   den = n0 - 2 n1 + n2, off = den < 0 ? clamp(0.5 (n0 - n2) / den, +-1) : 0, hz = sampleRate / (D (lag + off)),
+ *   clarity = n1 - 0.25 (n0 - n2) off; it returns 1, or 0 with hz = clarity = 0 when lag == 0, < 0 on a bad argument.
+ *   NA_TunerParamsFromRange: D = the largest of 1..8 with sampleRate / (D highestHz) >= 16; maxLag = ceil(sampleRate / (D lowestHz)) + 2
+ *   (above 1024 it fails with a message); minLag = max(2, floor(sampleRate / (D highestHz)) - 1); W = min(2048, max(32, 3 maxLag));
+ *   H = max(16, round(sampleRate / (D evaluationsPerSecond))); phase 0, thresholdQ10 922, minEnergy = W (33 D)^2 (about -60 dBFS).
+ *   It returns 0, or < 0 with a message.
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; polyphonic detection; a tap behind the gate; note
+ * names. */
+typedef struct NA_TunerParams  { int decimation, windowSamples, minLag, maxLag, hopSamples, phase, thresholdQ10, reserved;
+                                 unsigned long long minEnergy; } NA_TunerParams;
+typedef struct NA_TunerReading { unsigned long long evaluations; long long position; long long r[3];
+                                 unsigned long long e0, e[3]; int lag, decimation; } NA_TunerReading;
+typedef struct NA_TunerInfo    { int numTuners; long long deviceBytes; } NA_TunerInfo;
+NA_EXTERN int NA_BatchEnableTunerStage(NA_Batch* batch);                                   /* set-up side, allocates, idempotent */
+NA_EXTERN int NA_BatchGetTunerInfo(NA_Batch* batch, NA_TunerInfo* info);
+NA_EXTERN int NA_BatchSetStreamTuner(NA_Batch* batch, int stream, const NA_TunerParams* params);  /* REAL-TIME SAFE; NULL: the tuner goes at once */
+NA_EXTERN int NA_BatchGetStreamTuner(NA_Batch* batch, int stream, NA_TunerParams* out);    /* 1 / 0 / < 0 as the meter's */
+NA_EXTERN int NA_BatchReadStreamTuner(NA_Batch* batch, int stream, NA_TunerReading* out);  /* REAL-TIME SAFE; 1 / 0 / < 0 as the meter's */
+NA_EXTERN int NA_TunerParamsFromRange(double sampleRate, double lowestHz, double highestHz, double evaluationsPerSecond, NA_TunerParams* out);
+NA_EXTERN int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, double* hz, double* clarity); /* host arithmetic; 0 when lag == 0 */
 NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);
@@ -779,6 +856,8 @@ NA_EXTERN long long NA_DebugCabinetLaunches(void);
 NA_EXTERN long long NA_DebugGateLaunches(void);
 /* Tests: launches of the meter stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugMeterLaunches(void);
+/* Tests: launches of the tuner stage's two kernels so far (one append per piece of a call with entries, one evaluate where an evaluation ends) */
+NA_EXTERN long long NA_DebugTunerLaunches(void);
 /* Tests: launches of the EQ stage's kernel so far (one per processing call with entries) */
 NA_EXTERN long long NA_DebugEqLaunches(void);
 /* Tests: as NA_DebugRunCabinetStage, for the EQ stage: the stage alone on given rows -- table, launch, book advance */

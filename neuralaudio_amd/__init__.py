@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "eq_section"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "eq_section", "tuner_params_from_range", "tuner_pitch"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -91,6 +91,54 @@ def _meter_reading(r):
     tap = lambda t: {name: (float if name in ("peak", "peakHold") else int)(getattr(t, name)) for name in METER_TAP_FIELDS}
     return {"windows": int(r.windows), "in": tap(r.in_), "out": tap(r.out), "gateGainMin": float(r.gateGainMin), "gateGainLast": float(r.gateGainLast),
             "windowSamples": int(r.windowSamples)}
+
+
+TUNER_FIELDS = ("decimation", "windowSamples", "minLag", "maxLag", "hopSamples", "phase", "thresholdQ10", "minEnergy")
+
+
+def _tuner_params(d):
+    if isinstance(d, capi.NA_TunerParams):
+        return d
+    p = capi.NA_TunerParams()
+    for name in TUNER_FIELDS:
+        setattr(p, name, int(d[name]))
+    return p
+
+
+def _tuner_dict(p):
+    return {name: int(getattr(p, name)) for name in TUNER_FIELDS}
+
+
+def _tuner_reading(r):
+    return {"evaluations": int(r.evaluations), "position": int(r.position), "r": [int(v) for v in r.r], "e0": int(r.e0), "e": [int(v) for v in r.e],
+            "lag": int(r.lag), "decimation": int(r.decimation)}
+
+
+def _tuner_reading_struct(d):
+    if isinstance(d, capi.NA_TunerReading):
+        return d
+    r = capi.NA_TunerReading()
+    r.evaluations, r.position, r.e0, r.lag, r.decimation = d["evaluations"], d["position"], d["e0"], d["lag"], d["decimation"]
+    for i in range(3):
+        r.r[i], r.e[i] = d["r"][i], d["e"][i]
+    return r
+
+
+def tuner_params_from_range(sampleRate, lowestHz, highestHz, evaluationsPerSecond):
+    """The NA_TunerParams fields, as a dict, for notes from lowestHz to highestHz (NA_TunerParamsFromRange)."""
+    out = capi.NA_TunerParams()
+    if capi.load_library().NA_TunerParamsFromRange(float(sampleRate), float(lowestHz), float(highestHz), float(evaluationsPerSecond), C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _tuner_dict(out)
+
+
+def tuner_pitch(reading, sampleRate):
+    """(hz, clarity) of a ReadStreamTuner dict; None when it holds no pitch (lag == 0) (NA_TunerPitch)."""
+    hz, clarity = C.c_double(0.0), C.c_double(0.0)
+    rc = int(capi.load_library().NA_TunerPitch(C.byref(_tuner_reading_struct(reading)), float(sampleRate), C.byref(hz), C.byref(clarity)))
+    if rc < 0:
+        raise NeuralAudioError(capi.last_error())
+    return (hz.value, clarity.value) if rc else None
 
 
 EQ_FIELDS = ("b0", "b1", "b2", "a1", "a2")
@@ -622,6 +670,41 @@ class Batch:
         if rc < 0:
             raise NeuralAudioError(capi.last_error())
         return _meter_reading(out) if rc else None
+
+    # -- the tuner stage: EnableTunerStage is set-up side; SetStreamTuner and ReadStreamTuner are real-time safe (include/neuralaudio_amd.h) ----
+    def EnableTunerStage(self):
+        if self._lib.NA_BatchEnableTunerStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetTunerInfo(self):
+        info = capi.NA_TunerInfo()
+        if self._lib.NA_BatchGetTunerInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_TunerInfo._fields_}
+
+    def SetStreamTuner(self, stream, params):
+        """A pitch reading of the stream's input row every hopSamples from the next sample on: `params` a dict of the NA_TunerParams
+        fields (tuner_params_from_range makes one); None takes the tuner away at once.  A stream that has a tuner restarts it."""
+        p = None if params is None else C.byref(_tuner_params(params))
+        if self._lib.NA_BatchSetStreamTuner(self._h, int(stream), p) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamTuner(self, stream):
+        """The constants in effect as a dict; None: no tuner."""
+        out = capi.NA_TunerParams()
+        rc = int(self._lib.NA_BatchGetStreamTuner(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _tuner_dict(out) if rc else None
+
+    def ReadStreamTuner(self, stream):
+        """The newest reading that has arrived on the host, as a dict (evaluations, position, r, e0, e, lag, decimation; tuner_pitch turns
+        it into Hz); None: no tuner, or no evaluation has arrived yet.  Never waits."""
+        out = capi.NA_TunerReading()
+        rc = int(self._lib.NA_BatchReadStreamTuner(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _tuner_reading(out) if rc else None
 
     # -- the EQ stage: EnableEqStage is set-up side; SetStreamEq is real-time safe (include/neuralaudio_amd.h) ----
     def EnableEqStage(self):

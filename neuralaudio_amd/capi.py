@@ -49,6 +49,8 @@ NA_SYMBOLS = [
     "NA_BatchStreamEqFadeRemaining", "NA_DebugEqLaunches", "NA_DebugRunEqStage",
     "NA_BatchEnableMeterStage", "NA_BatchGetMeterInfo", "NA_BatchSetStreamMeter", "NA_BatchGetStreamMeter", "NA_BatchReadStreamMeter",
     "NA_DebugMeterLaunches",
+    "NA_BatchEnableTunerStage", "NA_BatchGetTunerInfo", "NA_BatchSetStreamTuner", "NA_BatchGetStreamTuner", "NA_BatchReadStreamTuner",
+    "NA_TunerParamsFromRange", "NA_TunerPitch", "NA_DebugTunerLaunches",
 ]
 
 
@@ -112,6 +114,20 @@ class NA_MeterReading(C.Structure):
 
 class NA_MeterInfo(C.Structure):
     _fields_ = [("numMeters", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+class NA_TunerParams(C.Structure):
+    _fields_ = [("decimation", C.c_int), ("windowSamples", C.c_int), ("minLag", C.c_int), ("maxLag", C.c_int), ("hopSamples", C.c_int), ("phase", C.c_int),
+                ("thresholdQ10", C.c_int), ("reserved", C.c_int), ("minEnergy", C.c_ulonglong)]
+
+
+class NA_TunerReading(C.Structure):
+    _fields_ = [("evaluations", C.c_ulonglong), ("position", C.c_longlong), ("r", C.c_longlong * 3), ("e0", C.c_ulonglong), ("e", C.c_ulonglong * 3),
+                ("lag", C.c_int), ("decimation", C.c_int)]
+
+
+class NA_TunerInfo(C.Structure):
+    _fields_ = [("numTuners", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 _lib = None
@@ -231,6 +247,14 @@ def load_library():
         "NA_BatchGetStreamMeter": (C.c_int, [vp, C.c_int, C.POINTER(NA_MeterParams)]),
         "NA_BatchReadStreamMeter": (C.c_int, [vp, C.c_int, C.POINTER(NA_MeterReading)]),
         "NA_DebugMeterLaunches": (C.c_longlong, []),
+        "NA_BatchEnableTunerStage": (C.c_int, [vp]),
+        "NA_BatchGetTunerInfo": (C.c_int, [vp, C.POINTER(NA_TunerInfo)]),
+        "NA_BatchSetStreamTuner": (C.c_int, [vp, C.c_int, C.POINTER(NA_TunerParams)]),
+        "NA_BatchGetStreamTuner": (C.c_int, [vp, C.c_int, C.POINTER(NA_TunerParams)]),
+        "NA_BatchReadStreamTuner": (C.c_int, [vp, C.c_int, C.POINTER(NA_TunerReading)]),
+        "NA_TunerParamsFromRange": (C.c_int, [C.c_double] * 4 + [C.POINTER(NA_TunerParams)]),
+        "NA_TunerPitch": (C.c_int, [C.POINTER(NA_TunerReading), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+        "NA_DebugTunerLaunches": (C.c_longlong, []),
         "NA_EqSectionFromDesign": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.POINTER(NA_EqSection)]),
         "NA_BatchEnableEqStage": (C.c_int, [vp]),
         "NA_BatchGetEqInfo": (C.c_int, [vp, C.POINTER(NA_EqInfo)]),

@@ -820,6 +820,87 @@ int NA_BatchReadStreamMeter(NA_Batch* batch, int stream, NA_MeterReading* out)
 long long NA_DebugMeterLaunches(void) { return (long long)na::MeterStageLaunches(); }
 #endif
 
+// ---- the tuner stage (gpu_batch.h EnableTunerStage / SetStreamTuner / ReadStreamTuner) ----
+static_assert(sizeof(NA_TunerParams) == sizeof(na::TunerParams) && sizeof(NA_TunerReading) == sizeof(na::TunerReading), "NA_TunerParams / NA_TunerReading are TunerParams / TunerReading, field for field");
+
+int NA_BatchEnableTunerStage(NA_Batch* batch)
+{
+	return BatchCall(batch, "NA_BatchEnableTunerStage", [&](na::GpuBatch& b) { b.EnableTunerStage(); });
+}
+
+int NA_BatchGetTunerInfo(NA_Batch* batch, NA_TunerInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetTunerInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetTunerInfo: bad argument");
+		const na::TunerStageInfo i = b.GetTunerInfo();
+		info->numTuners = i.numTuners;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamTuner(NA_Batch* batch, int stream, const NA_TunerParams* params)
+{
+	return BatchCall(batch, "NA_BatchSetStreamTuner", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamTuner(stream, nullptr);
+			return;
+		}
+		na::TunerParams t;
+		memcpy(&t, params, sizeof(t));
+		b.SetStreamTuner(stream, &t);
+	});
+}
+
+int NA_BatchGetStreamTuner(NA_Batch* batch, int stream, NA_TunerParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamTuner", -1, [&](na::GpuBatch& b) {
+		na::TunerParams t;
+		const int has = b.GetStreamTuner(stream, t) ? 1 : 0;
+		if (has && out) memcpy(out, &t, sizeof(t));
+		return has;
+	});
+}
+
+int NA_BatchReadStreamTuner(NA_Batch* batch, int stream, NA_TunerReading* out)
+{
+	return BatchValue(batch, "NA_BatchReadStreamTuner", -1, [&](na::GpuBatch& b) {
+		na::TunerReading r;
+		const int has = b.ReadStreamTuner(stream, r) ? 1 : 0;
+		if (has && out) memcpy(out, &r, sizeof(r));
+		return has;
+	});
+}
+
+int NA_TunerParamsFromRange(double sampleRate, double lowestHz, double highestHz, double evaluationsPerSecond, NA_TunerParams* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_TunerParamsFromRange: bad argument");
+		na::TunerParams t;
+		if (const char* why = na::TunerParamsFromRange(sampleRate, lowestHz, highestHz, evaluationsPerSecond, t)) throw std::runtime_error(std::string("NA_TunerParamsFromRange: ") + why);
+		memcpy(out, &t, sizeof(t));
+	});
+}
+
+int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, double* hz, double* clarity)
+{
+	int has = 0;
+	const int rc = Guard([&] {
+		if (!reading || !(sampleRate > 0.0)) throw std::runtime_error("NA_TunerPitch: bad argument");
+		na::TunerReading r;
+		memcpy(&r, reading, sizeof(r));
+		double f = 0.0, c = 0.0;
+		has = na::TunerPitch(r, sampleRate, f, c) ? 1 : 0;
+		if (hz) *hz = f;
+		if (clarity) *clarity = c;
+	});
+	return rc != 0 ? -1 : has;
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugTunerLaunches(void) { return (long long)na::TunerStageLaunches(); }
+#endif
+
 // ---- the EQ stage (gpu_batch.h EnableEqStage / SetStreamEq) ----
 static_assert(sizeof(NA_EqSection) == sizeof(na::EqSection) && NA_EQ_MAX_SECTIONS == na::kEqMaxSections, "NA_EqSection is na::EqSection");
 namespace

@@ -619,14 +619,15 @@ namespace na
 	}
 
 	// One processing call on `launch`, and the one place that states its order: what a stage runs in front of the models, in StageId
-	// order -- the gate detector, then the meter's IN tap (2.14): they read the input rows as the caller passed them,
-	// which may be the output rows, so before any model writes --, the up kernel, the model launches and the down kernel of a
-	// resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages (DESIGN.md 2.9 - 2.14) once per
+	// order -- the gate detector, then the meter's IN tap (2.14), then the tuner's append and evaluate launches (2.15):
+	// they read the input rows as the caller passed them, which may be the output rows, so before any model writes --, the up kernel, the model launches and the down kernel of a
+	// resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages (DESIGN.md 2.9 - 2.15) once per
 	// call: behind everything the call has launched -- the join of the units, the graph replay, the down kernel -- on the same stream,
 	// outside any capture.  The stages' order is the order of StageId (gpu_batch.h), written there and nowhere else: every row is
 	// gated first, then runs through its own EQ cascade (the tone stack sits between amp and cabinet), then is convolved with its own
 	// IR (the cabinet's tail rings out through a closing gate), then scaled and cross-faded; last the meter's OUT and GATE taps read
-	// the row the caller receives and the gains the gate applied to it -- they write no audio.
+	// the row the caller receives and the gains the gate applied to it -- they write no audio; the tuner, last in StageId, has nothing
+	// left to run there.
 	// `launch` != the batch stream is only used for a batch that runs as ONE launch per buffer (Submit checks)
 	void GpuBatch::ProcessDeviceOn(hipStream_t launch, const float* dIn, float* dOut, size_t n, long inStride, long outStride)
 	{

@@ -24,6 +24,7 @@
 #include "host_route.h"
 #include "launch_plan.h"
 #include "meter_stage.h"
+#include "tuner_stage.h"
 #include "model_loader.h"
 #include "output_stage.h"
 #include "resample.h"
@@ -87,6 +88,12 @@ namespace na
 	struct MeterStageInfo
 	{
 		int numMeters = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct TunerStageInfo
+	{
+		int numTuners = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -209,6 +216,21 @@ namespace na
 		void SetStreamMeter(int stream, const MeterParams* params); // params == nullptr: the meter goes at once
 		bool GetStreamMeter(int stream, MeterParams& out) const;    // false: no meter
 		bool ReadStreamMeter(int stream, MeterReading& out);        // false: no meter, or no completed window has arrived yet
+
+		// The tuner stage (tuner_stage.h): a per-stream pitch reading of the input row -- an integer autocorrelation of the
+		// decimated, quantised row every hopSamples, exact whatever the cut into calls -- behind the meter's IN tap in front of the model
+		// launches.  It never writes an audio row.  EnableTunerStage is the set-up side: an open group and a ring of decimated samples per
+		// row (CreateStreams grows them), the tables and a result block per table.  SetStreamTuner is host arithmetic on those tables;
+		// while an entry exists every processing call runs on the ordered path and enqueues ONE table upload and ONE append launch per
+		// piece of kTunerPieceSamples samples, and a call that holds an evaluation end of an entry ONE evaluate launch and ONE result
+		// copy more.  ReadStreamTuner never waits: it queries the ring's events and returns the newest reading that has arrived.
+		// Without an entry the batch launches exactly what it launches without the stage.
+		void EnableTunerStage();
+		bool HasTunerStage() const { return stages[kTunerStage] != nullptr; }
+		TunerStageInfo GetTunerInfo() const;
+		void SetStreamTuner(int stream, const TunerParams* params); // params == nullptr: the tuner goes at once
+		bool GetStreamTuner(int stream, TunerParams& out) const;    // false: no tuner
+		bool ReadStreamTuner(int stream, TunerReading& out);        // false: no tuner, or no evaluation has arrived yet
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -362,21 +384,21 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.14).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.15).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kMeterStage, kNumStages };
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
 			virtual bool HasEntries() const = 0;
 			virtual void EnsureRows(GpuBatch& batch, int rows) = 0; // set-up side: device blocks and tables for `rows` rows
 			virtual void Leave(int stream) = 0;                     // park / removal: nothing of the stream is carried over
-			// a call with entries: in front of its model launches (the gate's detector, the meter's IN tap), and behind them in chain order
+			// a call with entries: in front of its model launches (the gate's detector, the meter's IN tap, the tuner), and behind them in chain order
 			virtual void BeforeModels(GpuBatch&, hipStream_t, const float*, size_t, long) {}
 			virtual void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) = 0;
 		};
 		template <class Book, class Entry> struct StageOf;
-		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage; struct MeterStage;
+		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -225,7 +225,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the five stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the six stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -334,6 +334,33 @@ namespace na
 	};
 	hipError_t LaunchMeterIn(const MeterLaunch& L, hipStream_t stream); // (meter_stage_kernels.hip)
 	hipError_t LaunchMeterOut(const MeterLaunch& L, hipStream_t stream);
+
+	// the tuner stage (tuner_stage.h, tuner_stage.cpp): the rows' open groups and rings of decimated samples on the
+	// device and a result block per table of the ring, read back the way the meter stage's are; everything a call enqueues is in
+	// BeforeModels (the rows it reads may be the rows the models write)
+	struct GpuBatch::TunerStage : StageOf<TunerBook, TunerEntry>
+	{
+		static constexpr StageId kId = kTunerStage;
+		static constexpr const char* kNotEnabled = "tuner stage not enabled (NA_BatchEnableTunerStage)";
+		static constexpr int kTables = StageTables<TunerEntry>::kTables;
+		float* state = nullptr;             // [rowCapacity] TunerState
+		float* rings = nullptr;             // [rowCapacity][kTunerRingSamples] int32
+		int rowCapacity = 0;
+		TunerRecord* results[kTables] = {};    // pinned: the records of the call that last used table i ...
+		TunerRecord* devResults[kTables] = {}; // ... and where its evaluate launch wrote them
+		int pending[kTables] = {};          // records of results[i] that have not been folded yet (0: none)
+		int resultCapacity = 0;             // records per block
+		TunerStage() : StageOf("tuner stage") {}
+		~TunerStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // its tuner goes at once
+		void Fold(int i);            // the records of results[i] go into the book (stale ones are dropped there)
+		void Poll();                 // event queries only: every block whose copy is over is folded, oldest first
+		void BeforeModels(GpuBatch& batch, hipStream_t launch, const float* dIn, size_t n, long inStride) override; // poll + table upload + append (+ evaluate + result copy) + the host mirror's advance
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override;              // nothing
+	};
+	hipError_t LaunchTunerAppend(const TunerLaunch& L, hipStream_t stream); // (tuner_stage_kernels.hip)
+	hipError_t LaunchTunerEvaluate(const TunerLaunch& L, hipStream_t stream);
 
 	// the stage S of the batch; throws "<who>: <stage> not enabled (...)" -- the text is part of the interface
 	template <class S>

@@ -26,6 +26,12 @@
 //       the plain run below with the meter stage enabled and meters of W samples on the first K streams (K = 0: enabled, no meter set:
 //       must cost nothing); the pipelined loop reads the first stream's meter behind every buffer (NA_BatchReadStreamMeter: no wait);
 //       the same device span as --gate.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --tuner K [--tuner-hop H] [--tuner-stagger]
+//       the plain run below with the tuner stage enabled and a guitar-range tuner (NA_TunerParamsFromRange: 41.2 Hz .. 1320 Hz at 48 kHz,
+//       30 evaluations a second; H: hopSamples instead) on the first K streams (K = 0: enabled, no tuner set: must cost nothing).  Every
+//       phase is 0 -- all K tuners evaluate in the same buffer -- or, with --tuner-stagger, stream i gets phase i * H / K.  The
+//       pipelined loop reads the first stream's tuner behind every buffer (NA_BatchReadStreamTuner: no wait) and times every buffer
+//       period (pipelined_period_us: the median, the 99th percentile and the longest); the same device span as --gate.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -575,14 +581,14 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
-	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3, meter = -1, meterWindow = 1024;
-	bool churnLegacy = false;
+	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3, meter = -1, meterWindow = 1024, tuner = -1, tunerHop = 0;
+	bool churnLegacy = false, tunerStagger = false;
 	for (int i = 1; i < argc; i++)
 	{
 		if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = std::atoi(argv[++i]);
@@ -600,6 +606,9 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--eq") && i + 1 < argc) eq = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--meter") && i + 1 < argc) meter = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--meter-window") && i + 1 < argc) meterWindow = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--tuner") && i + 1 < argc) tuner = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--tuner-hop") && i + 1 < argc) tunerHop = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--tuner-stagger")) tunerStagger = true;
 		else if (!std::strcmp(argv[i], "--eq-sections") && i + 1 < argc) eqSections = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--loopback"))
 		{
@@ -695,8 +704,24 @@ int main(int argc, char** argv)
 		NA_MeterParams mp = { meterWindow, 0.12f, 1.0f };
 		for (int s = 0; s < std::min(meter, streams); s++) CHECK(NA_BatchSetStreamMeter(batch, s, &mp) == 0);
 	}
+	if (tuner >= 0)
+	{
+		CHECK(NA_BatchEnableTunerStage(batch) == 0);
+		NA_TunerParams tp;
+		CHECK(NA_TunerParamsFromRange(48000.0, 41.2, 1320.0, 30.0, &tp) == 0);
+		if (tunerHop > 0) tp.hopSamples = tunerHop;
+		tunerHop = tp.hopSamples;
+		const int tuned = std::min(tuner, streams);
+		for (int s = 0; s < tuned; s++)
+		{
+			tp.phase = tunerStagger ? (int)((long long)s * tp.hopSamples / tuned) : 0;
+			CHECK(NA_BatchSetStreamTuner(batch, s, &tp) == 0);
+		}
+	}
 	unsigned long long meterWindows = 0; // (--meter: `windows` of the last reading of stream 0 in the pipelined loop)
-	const bool marks = gate >= 0 || eq >= 0 || meter >= 0; // (the plain run stays what it was)
+	unsigned long long tunerEvaluations = 0; // (--tuner: `evaluations` of the last reading of stream 0 in the pipelined loop)
+	std::vector<double> periods;             // (--tuner: every buffer period of the pipelined loop)
+	const bool marks = gate >= 0 || eq >= 0 || meter >= 0 || tuner >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -762,10 +787,28 @@ int main(int argc, char** argv)
 			CHECK(have >= 0);
 			if (have) meterWindows = reading.windows;
 		}
+		if (tuner > 0)
+		{
+			NA_TunerReading reading;
+			const int have = NA_BatchReadStreamTuner(batch, 0, &reading);
+			CHECK(have >= 0);
+			if (have) tunerEvaluations = reading.evaluations;
+		}
+		if (tuner >= 0) periods.push_back(Now());
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
-	double usMarked = 0.0; // (--gate / --eq / --meter only)
+	double periodP50 = 0.0, periodP99 = 0.0, periodMax = 0.0;
+	if (periods.size() > 1)
+	{
+		for (size_t i = periods.size() - 1; i > 0; i--) periods[i] = (periods[i] - periods[i - 1]) * 1e6;
+		periods.erase(periods.begin());
+		std::sort(periods.begin(), periods.end());
+		periodP50 = periods[periods.size() / 2];
+		periodP99 = periods[(size_t)(periods.size() * 0.99)];
+		periodMax = periods.back();
+	}
+	double usMarked = 0.0; // (--gate / --eq / --meter / --tuner only)
 	if (marks)
 	{
 		CHECK(NA_BatchMarkTime(batch, 1) == 0);
@@ -808,9 +851,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
