@@ -265,7 +265,7 @@ NA_EXTERN float NA_BatchStreamGateGain(NA_Batch* batch, int stream); /* the g of
  * low-pass around them.  A host of the reference runs a few biquads on the buffer it holds.  Here the rows stay on the device between
  * the model launches and the cabinet stage, so the EQ is a stage of the library: a fourth per-stream stage, off unless enabled -- a
  * cascade of up to NA_EQ_MAX_SECTIONS biquad sections per stream, applied to the row the models produced BEHIND the gate's apply and IN
- * FRONT OF the cabinet stage.  A session's chain is model -> gate -> EQ -> cabinet -> output gain.  In a resampling batch the stage
+ * FRONT OF the cabinet stage.  A session's chain is model -> gate -> EQ -> cabinet -> output gain -> mix.  In a resampling batch the stage
  * acts on the external-rate rows, behind the down kernel, as the cabinet does: coefficients are designed at the rate the caller sees.
  * A batch that enabled the stage and gave no stream an EQ launches exactly what it launched before.
  * Arithmetic.  Every floating-point operation below is one separately rounded IEEE operation (fl(.): f64, fl32(.): f32, round to
@@ -322,7 +322,7 @@ NA_EXTERN int NA_BatchSetStreamEq(NA_Batch* batch, int stream, const NA_EqSectio
 NA_EXTERN int NA_BatchGetStreamEq(NA_Batch* batch, int stream, NA_EqSection* out, int capacity);   /* section count of the target; <0 bad id / not enabled */
 NA_EXTERN int NA_BatchStreamEqFadeRemaining(NA_Batch* batch, int stream);
 /* ---- the meter stage: per-stream level and gain-reduction meters ----
- * Every link of a session's chain -- model -> gate -> EQ -> cabinet -> output gain -- can be set from the audio thread; this stage is what
+ * Every link of a session's chain -- model -> gate -> EQ -> cabinet -> output gain -> mix -- can be set from the audio thread; this stage is what
  * can be READ from it: an input level and clip count, an output level, and what the gate did, per stream, without stopping the batch.
  * A host of the reference meters the buffers it holds; here the rows stay on the device.  A fifth per-stream stage, off unless enabled.
  * It never writes an audio row: with or without meters the samples out are the same bits.  A batch that enabled it and set no meter
@@ -464,6 +464,81 @@ NA_EXTERN int NA_BatchGetStreamTuner(NA_Batch* batch, int stream, NA_TunerParams
 NA_EXTERN int NA_BatchReadStreamTuner(NA_Batch* batch, int stream, NA_TunerReading* out);  /* REAL-TIME SAFE; 1 / 0 / < 0 as the meter's */
 NA_EXTERN int NA_TunerParamsFromRange(double sampleRate, double lowestHz, double highestHz, double evaluationsPerSecond, NA_TunerParams* out);
 NA_EXTERN int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, double* hz, double* clarity); /* host arithmetic; 0 when lag == 0 */
+/* ---- the mix stage: per-session mix groups ----
+ * Every stage above works on one row at a time.  A rig that runs two captures on one input, blended or panned left / right (dual amp),
+ * an amp next to the dry DI (wet / dry), or wet / dry / wet needs rows to MEET, and the output rows never pass through host code that
+ * could sum them: this is the place for it.  A seventh stage, off unless enabled, behind the output stage and in front of the meter
+ * stage: a session's chain is model -> gate -> EQ -> cabinet -> output gain -> mix, and the OUT tap of a meter on an output row of a
+ * group reads the mixed row.  A batch that enabled it and has no group launches exactly what it launched before.
+ * Model.  A mix group has M members, 1 <= M <= 8 (NA_MIX_MAX_MEMBERS).  A member is a pair (stream, tap); the tap is NA_MIX_TAP_OUT --
+ * the stream's row as the output stage left it -- or NA_MIX_TAP_DRY -- the input row the caller passed for that stream in the same call.
+ * The group has D outputs, 1 <= D <= M: the rows of its first D members, which must be OUT taps of distinct streams; the host reads
+ * those rows as the session's mono or L / R signal.  A D x M gain matrix says what each output row becomes; rows that are not outputs
+ * are never written.  A stream is named by at most one group, in one or both taps, and appears at most once per tap within a group.
+ * Arithmetic.  Every operation is one separately rounded f32 operation, with no FMA contraction; fl() is that rounding.  The one
+ * exception is the ramp weight, an f64 quotient rounded once to f32.  A group has one ramp (R, k) and two matrices g0 (from), g1 (to).
+ *     The gain of cell (d, j) at the k-th sample after the set call is g1 for k >= R - 1.
+ *     Before that it is fl(g0 + fl(fl(g1 - g0) * w)), with w = (float)((double)(k + 1) / (double)R).
+ *     k is an integer advanced by whole calls and is never accumulated sample to sample: the samples do not depend on how the signal
+ *     is cut into calls, on alignment or on stride.
+ *     A set call during a ramp starts the new ramp from the gains of the last sample produced (the same function).
+ *     A new group starts from the identity matrix -- output d takes member d at 1, everything else at 0 -- and ramps to the given
+ *     matrix, so a group appears click-free.  R = 0 means the target from the next sample.
+ *     For output d at a sample, the sum runs over the members j in member order whose gain at that sample is not exactly 0:
+ *         acc = fl(g_dj * y_j) for the first such member
+ *         acc = fl(acc + fl(g_dj * y_j)) for each further one
+ *         if there is no such member, the output is +0.0f
+ *     Hence a group at the identity matrix passes its rows bit for bit, and a NaN in a row whose gain is 0 stays where it is.
+ *     Any finite gain is allowed, negatives included (a polarity flip is the point of a dual-amp blend).  Rows are not sanitised.
+ *     The thread that owns a sample position reads that sample from all M sources before it writes any of the D outputs: an output
+ *     row that is also a source of another output is read as the output stage left it.
+ * NA_BatchEnableMixStage is the set-up side (allocates; idempotent): two 8 x 8 matrices and a row of drySamples floats for stashed input
+ *   per row, and the stage's device + pinned tables; later NA_BatchAddStreams / NA_BatchReserveStreams grow them.  Every call below
+ *   fails ("mix stage not enabled (NA_BatchEnableMixStage)") before it.  NA_BatchGetMixInfo reports maxMembers, the number of groups,
+ *   drySamples (a power of two >= 2048) and the device memory the stage holds.
+ * NA_BatchSetMixGroup is REAL-TIME SAFE: host arithmetic on tables that exist.  taps == NULL means all OUT; gains is
+ *   [numOutputs][numMembers], row-major; rampSamples lies in [0, 1 << 20].  If the member list is exactly that of an existing group
+ *   (same order, taps and numOutputs) the call is a gain change on the kept ramp state; otherwise every named stream must be in no
+ *   group, and the call creates a new group.  The matrices travel once, behind the table of the next processing call.
+ * NA_BatchClearMixGroup is REAL-TIME SAFE: the group that names `stream` goes at once; no group is not an error.  The click-free way to
+ *   remove a group is to ramp to the identity and then clear, which is exact by the identity property.
+ * NA_BatchGetStreamMix returns M and fills in the members (up to `capacity`), *numOutputs and -- when capacity >= M -- the target
+ *   matrix [D][M]; 0 means no group; < 0 a bad id or the stage not enabled.  NA_BatchMixRampRemaining returns the samples the ramp of
+ *   the stream's group still has to produce (0: none, or no group).
+ * NA_MixGainsFromPan is host arithmetic, no device: equal power, level = 10^(levelDb / 20), left = level * cos((pan + 1) * pi / 4) and
+ *   right = level * sin((pan + 1) * pi / 4), computed in double and rounded once; pan lies in [-1, 1]; pan = -1 gives exactly
+ *   (level, 0) and pan = +1 exactly (0, level).  It returns 0, or < 0 with a message on a non-finite argument or |pan| > 1.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; every named stream must be live (a
+ * parked one fails with "... is parked"); numMembers in [1, 8] and numOutputs in [1, numMembers]; the outputs are OUT taps of
+ * distinct streams; no (stream, tap) pair twice; a stream already in another group is refused with its id; every gain finite; the ramp
+ * in range; a group with a DRY member is refused on a resampling batch -- the rows lag the input by the resampler's latency, and an
+ * unaligned dry blend is a comb filter --, and NA_BatchSetResampling is refused while such a group exists; a broken batch refuses
+ * everything.
+ * NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a hand-over, dissolve at once the group that names the stream: a
+ * parked stream carries nothing over.  Hand-over recipe: at the call that issues NA_BatchHandover(from, to, ...), clear the group and
+ * set it again with `to` in the place of `from`, at the same gains and with rampSamples = 0.  During the fade row `to` carries the
+ * output stage's cross-fade, so the mix stays continuous, and nothing happens to it when `from` is parked.  Groups are not part of a
+ * NA_BatchSaveStreams blob.
+ * While a group exists a processing call behaves as it does with entries of the other stages: its launches run in order on one stream
+ * (no half-batch chains, no resident launch), host buffers go through the library's device staging block, and it enqueues one table
+ * upload from a ring of pinned tables and ONE launch over the groups, whatever n -- and, while some group has a DRY member, one small
+ * launch in front of the models that keeps those members' input rows (input and output rows may be the same memory): no device or
+ * pinned allocation, no stream or event creation, no unbounded wait.  The one exception: the first call with a DRY member that is
+ * longer than drySamples grows the stash block first, like any first use of a longer buffer.  With the last group the free-running
+ * modes come back.
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; latency-compensated dry taps on resampling batches. */
+#define NA_MIX_MAX_MEMBERS 8
+#define NA_MIX_TAP_OUT 0
+#define NA_MIX_TAP_DRY 1
+typedef struct NA_MixInfo { int maxMembers, numGroups, drySamples; long long deviceBytes; } NA_MixInfo;
+NA_EXTERN int NA_BatchEnableMixStage(NA_Batch* batch);                                     /* set-up side, allocates, idempotent */
+NA_EXTERN int NA_BatchGetMixInfo(NA_Batch* batch, NA_MixInfo* info);
+NA_EXTERN int NA_BatchSetMixGroup(NA_Batch* batch, const int* streams, const int* taps, int numMembers, int numOutputs, const float* gains,
+                                  int rampSamples);                                        /* REAL-TIME SAFE */
+NA_EXTERN int NA_BatchClearMixGroup(NA_Batch* batch, int stream);                          /* REAL-TIME SAFE */
+NA_EXTERN int NA_BatchGetStreamMix(NA_Batch* batch, int stream, int* streams, int* taps, int capacity, int* numOutputs, float* gains);
+NA_EXTERN int NA_BatchMixRampRemaining(NA_Batch* batch, int stream);
+NA_EXTERN int NA_MixGainsFromPan(double levelDb, double pan, float* left, float* right);   /* host arithmetic, no device */
 NA_EXTERN int NA_BatchNumStreams(NA_Batch* batch);     /* rows of the [streams][n] arrays, retired and parked ids included */
 NA_EXTERN int NA_BatchNumLiveStreams(NA_Batch* batch);
 NA_EXTERN int NA_BatchIsLive(NA_Batch* batch, int stream);
@@ -862,6 +937,13 @@ NA_EXTERN long long NA_DebugTunerLaunches(void);
 NA_EXTERN long long NA_DebugEqLaunches(void);
 /* Tests: as NA_DebugRunCabinetStage, for the EQ stage: the stage alone on given rows -- table, launch, book advance */
 NA_EXTERN int NA_DebugRunEqStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
+/* Tests: launches of the mix stage's MixStageKernel so far (one per processing call with groups) and of its MixStashKernel (one per
+ * processing call while some group has a DRY member) */
+NA_EXTERN long long NA_DebugMixLaunches(void);
+NA_EXTERN long long NA_DebugMixStashLaunches(void);
+/* Tests: as NA_DebugRunCabinetStage, for the mix stage, with what the stage runs in front of the models on the input rows `hostIn`
+ * (same shape as hostRows; may be NULL when no group has a DRY member): table, stash launch, mix launch, book advance */
+NA_EXTERN int NA_DebugRunMixStage(NA_Batch* batch, const float* hostIn, float* hostRows, long stride, size_t n);
 #endif /* NA_RELEASE */
 
 #ifdef __cplusplus

@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "eq_section", "tuner_params_from_range", "tuner_pitch"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -139,6 +139,15 @@ def tuner_pitch(reading, sampleRate):
     if rc < 0:
         raise NeuralAudioError(capi.last_error())
     return (hz.value, clarity.value) if rc else None
+
+
+def mix_gains_from_pan(levelDb, pan):
+    """(left, right) float32 gains of one member of a stereo mix group (Batch.SetMixGroup): equal power, level = 10^(levelDb / 20),
+    pan in [-1, 1]; pan = -1 is exactly (level, 0), pan = +1 exactly (0, level) (NA_MixGainsFromPan)."""
+    left, right = C.c_float(0.0), C.c_float(0.0)
+    if capi.load_library().NA_MixGainsFromPan(float(levelDb), float(pan), C.byref(left), C.byref(right)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return left.value, right.value
 
 
 EQ_FIELDS = ("b0", "b1", "b2", "a1", "a2")
@@ -705,6 +714,57 @@ class Batch:
         if rc < 0:
             raise NeuralAudioError(capi.last_error())
         return _tuner_reading(out) if rc else None
+
+    # -- the mix stage: EnableMixStage is set-up side; SetMixGroup and ClearMixGroup are real-time safe (include/neuralaudio_amd.h) ----
+    def EnableMixStage(self):
+        if self._lib.NA_BatchEnableMixStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetMixInfo(self):
+        info = capi.NA_MixInfo()
+        if self._lib.NA_BatchGetMixInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_MixInfo._fields_}
+
+    def SetMixGroup(self, streams, gains, numOutputs=None, taps=None, rampSamples=0):
+        """A mix group of the members `streams` (`taps`: 0 OUT / 1 DRY per member, None: all OUT) whose first numOutputs rows (default:
+        the rows of `gains`) become the sums `gains` [numOutputs][numMembers] says, ramped over rampSamples.  The member list of an
+        existing group: a gain change from the gains reached."""
+        streams = [int(s) for s in streams]
+        g = np.ascontiguousarray(np.asarray(gains, dtype=np.float32))
+        M = len(streams)
+        D = int(numOutputs) if numOutputs is not None else (g.shape[0] if g.ndim == 2 else 1)
+        if g.size != D * M:
+            raise ValueError("gains must be [numOutputs][numMembers]")
+        ids = (C.c_int * max(M, 1))(*streams)
+        t = None if taps is None else (C.c_int * max(M, 1))(*[int(x) for x in taps])
+        if taps is not None and len(taps) != M:
+            raise ValueError("taps must name a tap per member")
+        if self._lib.NA_BatchSetMixGroup(self._h, ids, t, M, D, g.ctypes.data_as(C.POINTER(C.c_float)), int(rampSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def ClearMixGroup(self, stream):
+        if self._lib.NA_BatchClearMixGroup(self._h, int(stream)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamMix(self, stream):
+        """The group that names the stream as a dict (streams, taps, numOutputs, gains [numOutputs][numMembers]: the target); None: no group."""
+        cap = capi.NA_MIX_MAX_MEMBERS
+        ids, taps, D = (C.c_int * cap)(), (C.c_int * cap)(), C.c_int(0)
+        g = (C.c_float * (cap * cap))()
+        M = int(self._lib.NA_BatchGetStreamMix(self._h, int(stream), ids, taps, cap, C.byref(D), g))
+        if M < 0:
+            raise NeuralAudioError(capi.last_error())
+        if M == 0:
+            return None
+        return {"streams": list(ids[:M]), "taps": list(taps[:M]), "numOutputs": int(D.value),
+                "gains": np.array(g[:D.value * M], dtype=np.float32).reshape(D.value, M)}
+
+    def MixRampRemaining(self, stream):
+        rc = int(self._lib.NA_BatchMixRampRemaining(self._h, int(stream)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return rc
 
     # -- the EQ stage: EnableEqStage is set-up side; SetStreamEq is real-time safe (include/neuralaudio_amd.h) ----
     def EnableEqStage(self):

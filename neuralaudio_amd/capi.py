@@ -51,6 +51,8 @@ NA_SYMBOLS = [
     "NA_DebugMeterLaunches",
     "NA_BatchEnableTunerStage", "NA_BatchGetTunerInfo", "NA_BatchSetStreamTuner", "NA_BatchGetStreamTuner", "NA_BatchReadStreamTuner",
     "NA_TunerParamsFromRange", "NA_TunerPitch", "NA_DebugTunerLaunches",
+    "NA_BatchEnableMixStage", "NA_BatchGetMixInfo", "NA_BatchSetMixGroup", "NA_BatchClearMixGroup", "NA_BatchGetStreamMix",
+    "NA_BatchMixRampRemaining", "NA_MixGainsFromPan", "NA_DebugMixLaunches", "NA_DebugMixStashLaunches", "NA_DebugRunMixStage",
 ]
 
 
@@ -128,6 +130,15 @@ class NA_TunerReading(C.Structure):
 
 class NA_TunerInfo(C.Structure):
     _fields_ = [("numTuners", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+NA_MIX_MAX_MEMBERS = 8
+NA_MIX_TAP_OUT = 0
+NA_MIX_TAP_DRY = 1
+
+
+class NA_MixInfo(C.Structure):
+    _fields_ = [("maxMembers", C.c_int), ("numGroups", C.c_int), ("drySamples", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 _lib = None
@@ -255,6 +266,16 @@ def load_library():
         "NA_TunerParamsFromRange": (C.c_int, [C.c_double] * 4 + [C.POINTER(NA_TunerParams)]),
         "NA_TunerPitch": (C.c_int, [C.POINTER(NA_TunerReading), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "NA_DebugTunerLaunches": (C.c_longlong, []),
+        "NA_BatchEnableMixStage": (C.c_int, [vp]),
+        "NA_BatchGetMixInfo": (C.c_int, [vp, C.POINTER(NA_MixInfo)]),
+        "NA_BatchSetMixGroup": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int]),
+        "NA_BatchClearMixGroup": (C.c_int, [vp, C.c_int]),
+        "NA_BatchGetStreamMix": (C.c_int, [vp, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+        "NA_BatchMixRampRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_MixGainsFromPan": (C.c_int, [C.c_double, C.c_double, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+        "NA_DebugMixLaunches": (C.c_longlong, []),
+        "NA_DebugMixStashLaunches": (C.c_longlong, []),
+        "NA_DebugRunMixStage": (C.c_int, [vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_long, C.c_size_t]),
         "NA_EqSectionFromDesign": (C.c_int, [C.c_int] + [C.c_double] * 4 + [C.POINTER(NA_EqSection)]),
         "NA_BatchEnableEqStage": (C.c_int, [vp]),
         "NA_BatchGetEqInfo": (C.c_int, [vp, C.POINTER(NA_EqInfo)]),

@@ -901,6 +901,72 @@ int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, double* hz,
 long long NA_DebugTunerLaunches(void) { return (long long)na::TunerStageLaunches(); }
 #endif
 
+// ---- the mix stage (gpu_batch.h EnableMixStage / SetMixGroup) ----
+static_assert(NA_MIX_MAX_MEMBERS == na::kMixMaxMembers && NA_MIX_TAP_OUT == na::kMixTapOut && NA_MIX_TAP_DRY == na::kMixTapDry, "the header's mix constants are mix_stage.h's");
+
+int NA_BatchEnableMixStage(NA_Batch* batch)
+{
+	return BatchCall(batch, "NA_BatchEnableMixStage", [&](na::GpuBatch& b) { b.EnableMixStage(); });
+}
+
+int NA_BatchGetMixInfo(NA_Batch* batch, NA_MixInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetMixInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetMixInfo: bad argument");
+		const na::MixStageInfo i = b.GetMixInfo();
+		info->maxMembers = i.maxMembers;
+		info->numGroups = i.numGroups;
+		info->drySamples = i.drySamples;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetMixGroup(NA_Batch* batch, const int* streams, const int* taps, int numMembers, int numOutputs, const float* gains, int rampSamples)
+{
+	return BatchCall(batch, "NA_BatchSetMixGroup", [&](na::GpuBatch& b) { b.SetMixGroup(streams, taps, numMembers, numOutputs, gains, rampSamples); });
+}
+
+int NA_BatchClearMixGroup(NA_Batch* batch, int stream)
+{
+	return BatchCall(batch, "NA_BatchClearMixGroup", [&](na::GpuBatch& b) { b.ClearMixGroup(stream); });
+}
+
+int NA_BatchGetStreamMix(NA_Batch* batch, int stream, int* streams, int* taps, int capacity, int* numOutputs, float* gains)
+{
+	return BatchValue(batch, "NA_BatchGetStreamMix", -1, [&](na::GpuBatch& b) { return b.GetStreamMix(stream, streams, taps, capacity, numOutputs, gains); });
+}
+
+int NA_BatchMixRampRemaining(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchMixRampRemaining", -1, [&](na::GpuBatch& b) { return b.MixRampRemaining(stream); });
+}
+
+int NA_MixGainsFromPan(double levelDb, double pan, float* left, float* right)
+{
+	return Guard([&] {
+		if (!left || !right) throw std::runtime_error("NA_MixGainsFromPan: bad argument");
+		if (!std::isfinite(levelDb) || !std::isfinite(pan)) throw std::runtime_error("NA_MixGainsFromPan: every argument must be finite");
+		if (pan < -1.0 || pan > 1.0) throw std::runtime_error("NA_MixGainsFromPan: pan must lie in [-1, 1]");
+		const double level = std::pow(10.0, levelDb / 20.0);
+		const double angle = (pan + 1.0) * (3.14159265358979323846 / 4.0);
+		// (the ends are exact by rule: cos(pi / 2) in double is 6e-17, not 0)
+		*left = pan == 1.0 ? 0.0f : pan == -1.0 ? (float)level : (float)(level * std::cos(angle));
+		*right = pan == -1.0 ? 0.0f : pan == 1.0 ? (float)level : (float)(level * std::sin(angle));
+	});
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugMixLaunches(void) { return (long long)na::MixStageLaunches(); }
+long long NA_DebugMixStashLaunches(void) { return (long long)na::MixStashLaunches(); }
+int NA_DebugRunMixStage(NA_Batch* batch, const float* hostIn, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunMixStage: null batch");
+		batch->batch->DebugRunMixStage(hostIn, hostRows, stride, n);
+	});
+}
+#endif
+
 // ---- the EQ stage (gpu_batch.h EnableEqStage / SetStreamEq) ----
 static_assert(sizeof(NA_EqSection) == sizeof(na::EqSection) && NA_EQ_MAX_SECTIONS == na::kEqMaxSections, "NA_EqSection is na::EqSection");
 namespace

@@ -24,6 +24,7 @@
 #include "host_route.h"
 #include "launch_plan.h"
 #include "meter_stage.h"
+#include "mix_stage.h"
 #include "tuner_stage.h"
 #include "model_loader.h"
 #include "output_stage.h"
@@ -94,6 +95,12 @@ namespace na
 	struct TunerStageInfo
 	{
 		int numTuners = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct MixStageInfo
+	{
+		int maxMembers = 0, numGroups = 0, drySamples = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -231,6 +238,26 @@ namespace na
 		void SetStreamTuner(int stream, const TunerParams* params); // params == nullptr: the tuner goes at once
 		bool GetStreamTuner(int stream, TunerParams& out) const;    // false: no tuner
 		bool ReadStreamTuner(int stream, TunerReading& out);        // false: no tuner, or no evaluation has arrived yet
+
+		// The mix stage (mix_stage.h): per-session mix groups -- the rows of up to 8 members (a stream's row as the output
+		// stage left it, or the input row the caller passed for it) summed through a ramped D x M gain matrix into the rows of the first
+		// D members -- behind the output stage and in front of the meter's OUT tap: the one stage in which rows meet.  EnableMixStage is
+		// the set-up side: a block of two matrices and a row for stashed input per row (CreateStreams grows them; a call with a DRY
+		// member longer than the stash rows grows those first, like any first use of a longer buffer) and the tables.  SetMixGroup /
+		// ClearMixGroup are host arithmetic on those tables; while a group exists every processing call runs on the ordered path and
+		// enqueues ONE table upload and ONE launch, whatever n and however many groups, and ONE stash launch in front of the models
+		// while some group has a DRY member.  Without a group the batch launches exactly what it launches without the stage.
+		void EnableMixStage();
+		bool HasMixStage() const { return stages[kMixStage] != nullptr; }
+		MixStageInfo GetMixInfo() const;
+		void SetMixGroup(const int* streamIds, const int* taps, int numMembers, int numOutputs, const float* gains, int rampSamples); // taps == nullptr: all OUT
+		void ClearMixGroup(int stream); // the group that names `stream` goes at once; none: nothing happens
+		int GetStreamMix(int stream, int* streamIds, int* taps, int capacity, int* numOutputs, float* gains) const; // M; 0: no group
+		int MixRampRemaining(int stream) const;
+		bool HasDryMixGroup() const;
+		// test hook (NA_DebugRunMixStage): the stage of a call of n samples on host rows [NumStreams()][stride], hostIn the input rows of
+		// the same shape (may be nullptr when no group has a DRY member); synchronous, set-up side
+		void DebugRunMixStage(const float* hostIn, float* hostRows, long stride, size_t n);
 
 		// Stream snapshots (stream_snapshot.h): a stream's state as a relocatable blob -- it loads into any stream of the
 		// same model file in any batch, device, process or kernel family.  SaveStreams writes the blobs of ids[0 .. count) back to back
@@ -384,26 +411,26 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.15).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.16).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
 			virtual bool HasEntries() const = 0;
 			virtual void EnsureRows(GpuBatch& batch, int rows) = 0; // set-up side: device blocks and tables for `rows` rows
 			virtual void Leave(int stream) = 0;                     // park / removal: nothing of the stream is carried over
-			// a call with entries: in front of its model launches (the gate's detector, the meter's IN tap, the tuner), and behind them in chain order
+			// a call with entries: in front of its model launches (the gate's detector, the mix stage's stash, the meter's IN tap, the tuner), and behind them in chain order
 			virtual void BeforeModels(GpuBatch&, hipStream_t, const float*, size_t, long) {}
 			virtual void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) = 0;
 		};
 		template <class Book, class Entry> struct StageOf;
-		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage; struct MeterStage; struct TunerStage;
+		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call
 		template <class S> S& SettableStage(int stream, const char* who); // a set call's preamble: usable, enabled, not parked, live
-		void DebugRunStage(Stage& stage, const char* who, float* hostRows, long stride, size_t n);
+		void DebugRunStage(Stage& stage, const char* who, float* hostRows, long stride, size_t n, const float* hostIn = nullptr);
 		bool StageHasEntries() const; // of any stage
 		// the call runs ordered on ONE stream: up kernel -> model launches -> down kernel of a resampling batch, the stages behind the
 		// model launches (no half-batch chains, no resident launch)

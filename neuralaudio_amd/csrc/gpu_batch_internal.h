@@ -225,7 +225,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the six stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the seven stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -304,6 +304,30 @@ namespace na
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + launch + the host mirror's advance
 	};
 	hipError_t LaunchOutputStage(const OutStageLaunch& L, hipStream_t stream); // (output_stage_kernels.hip)
+
+	// the mix stage (mix_stage.h, mix_stage.cpp): the groups' matrices and the stashed input rows of DRY members on the
+	// device; its tables hold the entries and behind them the gain sets of the set calls since the last call, and -- between the stash
+	// launch and the mix launch of one call -- the table that call runs on
+	struct GpuBatch::MixStage : StageOf<MixBook, MixEntry>
+	{
+		static constexpr StageId kId = kMixStage;
+		static constexpr const char* kNotEnabled = "mix stage not enabled (NA_BatchEnableMixStage)";
+		float* gains = nullptr;           // [rowCapacity][2][8][8]: a group's from / to matrices, at the row of its first member
+		float* stash = nullptr;           // [rowCapacity][drySamples]: the input rows of DRY members (nothing of it outlives its call)
+		int rowCapacity = 0;
+		int drySamples = kMixMinDrySamples; // a power of two
+		const MixEntry* dev = nullptr;    // the device table this call runs on ...
+		int count = 0;                    // ... and its entries; 0: the call has none
+		MixStage() : StageOf("mix stage") {}
+		~MixStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // the group that names it goes at once
+		void EnsureSamples(GpuBatch& batch, size_t n); // stash rows of at least n samples (grows them: not real-time safe)
+		void BeforeModels(GpuBatch& batch, hipStream_t launch, const float* dIn, size_t n, long inStride) override; // table upload (+ the stash launch)
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override;              // the mix launch + the host mirror's advance
+	};
+	hipError_t LaunchMixStash(const MixStashLaunch& L, hipStream_t stream); // (mix_stage_kernels.hip)
+	hipError_t LaunchMixStage(const MixLaunch& L, hipStream_t stream);
 
 	// the meter stage (meter_stage.h, meter_stage.cpp): the rows' states on the device and -- the one device -> host path
 	// of the stages -- a result block per table of the ring: the OUT launch writes a record per entry, one copy brings them to the pinned

@@ -128,6 +128,8 @@ namespace na
 	void GpuBatch::SetResampling(int externalRate, int modelRate, int quantum, int maxFrames)
 	{
 		CheckUsable();
+		if (HasDryMixGroup())
+			throw std::runtime_error("neuralaudio_amd: SetResampling: a mix group with a DRY tap exists (the rows of a resampling batch lag the input by the resampler's latency)");
 		if (!streams.empty() || !groups.empty())
 			throw std::runtime_error("neuralaudio_amd: SetResampling: the batch already has streams (it is a set-up call, before the first AddStreams)");
 		if (maxFrames < 1) throw std::runtime_error("neuralaudio_amd: SetResampling: maxFrames must be >= 1");

@@ -32,6 +32,12 @@
 //       phase is 0 -- all K tuners evaluate in the same buffer -- or, with --tuner-stagger, stream i gets phase i * H / K.  The
 //       pipelined loop reads the first stream's tuner behind every buffer (NA_BatchReadStreamTuner: no wait) and times every buffer
 //       period (pipelined_period_us: the median, the 99th percentile and the longest); the same device span as --gate.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --mix N [--mix-dry]
+//       (--mix followed by a NUMBER; followed by a file name it is the second model of the modes above.)  The plain run below with the
+//       mix stage enabled and N mix groups of two neighbouring streams each -- streams 2g and 2g + 1, stereo: both rows are outputs, the
+//       first panned -0.5 and the second +0.5 (NA_MixGainsFromPan) -- (N = 0: enabled, no group: must cost nothing).  With --mix-dry
+//       each group gets the DRY tap of its first stream as a third member, at -6 dB in the centre.  Times every buffer period of the
+//       pipelined loop like --tuner; the same device span as --gate.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -581,19 +587,27 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]] [--mix N [--mix-dry]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
 	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3, meter = -1, meterWindow = 1024, tuner = -1, tunerHop = 0;
-	bool churnLegacy = false, tunerStagger = false;
+	int mixGroups = -1;
+	bool churnLegacy = false, tunerStagger = false, mixDry = false;
 	for (int i = 1; i < argc; i++)
 	{
 		if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--fan-in") && i + 1 < argc) rcclFanIn = !std::strcmp(argv[++i], "rccl");
-		else if (!std::strcmp(argv[i], "--mix") && i + 1 < argc) mixFile = argv[++i];
+		else if (!std::strcmp(argv[i], "--mix") && i + 1 < argc)
+		{
+			// a number: that many mix groups (the mix stage); anything else: the second model's file
+			const char* arg = argv[++i];
+			if (*arg && std::strspn(arg, "0123456789") == std::strlen(arg)) mixGroups = std::atoi(arg);
+			else mixFile = arg;
+		}
+		else if (!std::strcmp(argv[i], "--mix-dry")) mixDry = true;
 		else if (!std::strcmp(argv[i], "--migrate") && i + 1 < argc) migrate = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--churn") && i + 1 < argc) churn = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--churn-every") && i + 1 < argc) churnEvery = std::atoi(argv[++i]);
@@ -718,10 +732,24 @@ int main(int argc, char** argv)
 			CHECK(NA_BatchSetStreamTuner(batch, s, &tp) == 0);
 		}
 	}
+	if (mixGroups >= 0)
+	{
+		CHECK(NA_BatchEnableMixStage(batch) == 0);
+		mixGroups = std::min(mixGroups, streams / 2);
+		float l0, r0, l1, r1, lc, rc;
+		CHECK(NA_MixGainsFromPan(0.0, -0.5, &l0, &r0) == 0 && NA_MixGainsFromPan(0.0, 0.5, &l1, &r1) == 0 && NA_MixGainsFromPan(-6.0, 0.0, &lc, &rc) == 0);
+		for (int g = 0; g < mixGroups; g++)
+		{
+			const int ids[3] = { 2 * g, 2 * g + 1, 2 * g };
+			const int taps[3] = { NA_MIX_TAP_OUT, NA_MIX_TAP_OUT, NA_MIX_TAP_DRY };
+			const float stereo[4] = { l0, l1, r0, r1 }, withDry[6] = { l0, l1, lc, r0, r1, rc };
+			CHECK(NA_BatchSetMixGroup(batch, ids, taps, mixDry ? 3 : 2, 2, mixDry ? withDry : stereo, 0) == 0);
+		}
+	}
 	unsigned long long meterWindows = 0; // (--meter: `windows` of the last reading of stream 0 in the pipelined loop)
 	unsigned long long tunerEvaluations = 0; // (--tuner: `evaluations` of the last reading of stream 0 in the pipelined loop)
-	std::vector<double> periods;             // (--tuner: every buffer period of the pipelined loop)
-	const bool marks = gate >= 0 || eq >= 0 || meter >= 0 || tuner >= 0; // (the plain run stays what it was)
+	std::vector<double> periods;             // (--tuner, --mix N: every buffer period of the pipelined loop)
+	const bool marks = gate >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -794,7 +822,7 @@ int main(int argc, char** argv)
 			CHECK(have >= 0);
 			if (have) tunerEvaluations = reading.evaluations;
 		}
-		if (tuner >= 0) periods.push_back(Now());
+		if (tuner >= 0 || mixGroups >= 0) periods.push_back(Now());
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
@@ -808,7 +836,7 @@ int main(int argc, char** argv)
 		periodP99 = periods[(size_t)(periods.size() * 0.99)];
 		periodMax = periods.back();
 	}
-	double usMarked = 0.0; // (--gate / --eq / --meter / --tuner only)
+	double usMarked = 0.0; // (--gate / --eq / --meter / --tuner / --mix N only)
 	if (marks)
 	{
 		CHECK(NA_BatchMarkTime(batch, 1) == 0);
@@ -851,9 +879,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
