@@ -189,6 +189,71 @@ NA_EXTERN int NA_BatchUnloadIR(NA_Batch* batch, int ir);
 NA_EXTERN int NA_BatchSetStreamIR(NA_Batch* batch, int stream, int ir, int fadeSamples); /* ir = -1: none (dry) */
 NA_EXTERN int NA_BatchGetStreamIR(NA_Batch* batch, int stream); /* the target: id, -1 dry, <= -2 bad id / not enabled */
 NA_EXTERN int NA_BatchStreamIRFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's IR fade; 0: none; < 0: stage not enabled / bad id */
+/* ---- the reverb stage: per-stream convolution with a long impulse response ----
+ * What a player hears behind a real rig is a room.  A room-mic cabinet IR is 0.3 - 1 s, a reverb IR 1 - 3 s; the cabinet stage is direct
+ * form, ends at 8192 taps and costs what its taps cost.  This stage is uniformly partitioned FFT convolution: partitions of P = 128
+ * samples, 256-point transforms, a per-row delay line of input spectra; the first 128 taps run direct form, so the stage has no
+ * latency and a one-sample call works.  An eighth per-stream stage, off unless enabled, BEHIND the cabinet stage and IN FRONT OF the
+ * output stage: a session's chain is model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix.  For every stream that has a reverb
+ * the row's samples x are replaced by dry * x + wet * (x convolved with the IR).  A batch that enabled the stage and set no reverb
+ * launches exactly what it launched before.  In a resampling batch the stage acts on the external-rate rows, as the cabinet does.
+ * Set-up side (not real-time safe: they allocate and may wait for what is in flight):
+ *   NA_BatchEnableReverbStage(maxTaps in [1, 131072]) allocates per row of the batch's capacity a ring of raw samples, a ring of
+ *     `slots` input spectra of 2 KiB each (slots = ceil(maxTaps / 128) - 1 + the blocks a piece can touch; pieceSamples is the longest
+ *     run the stage processes at once, longer calls run in pieces) and the tails of the blocks in work, and the stage's tables; later
+ *     NA_BatchAddStreams / NA_BatchReserveStreams grow them.  Idempotent for an equal or smaller maxTaps; a larger maxTaps is refused
+ *     while any stream has a reverb.  Every call below fails ("reverb stage not enabled") before it.  NA_BatchGetReverbInfo reports the
+ *     sizes in effect and the device memory the stage holds.
+ *   NA_BatchLoadReverbIR takes numTaps in [1, maxTaps] finite taps and returns an IR id >= 0 (-1: failure).  Taps [0, 128) go to the
+ *     device as they are, the partitions behind them as spectra, computed on the device by the stage's own transform; the call waits
+ *     for them under the wait limit.  Many streams may share one IR; ids of unloaded IRs are recycled.  Taps are given at the rate of
+ *     the rows the caller sees.  NA_BatchUnloadReverbIR fails while a stream uses the IR or fades from it.
+ * Arithmetic.  EVERY operation below is one f32 operation, rounded to nearest even, never contracted into an FMA, in the stated order;
+ * f32 subnormals are kept, as operands and as results (nothing is flushed to zero).  Positions t count from T0, the first sample after
+ * the set call that took the stream from no reverb: x[t] = 0 for t < 0 (the history starts empty; nothing is cleared on the device).
+ * Block m is the samples [128 m, 128 m + 128).
+ *   Twiddles.  W[q] = (cos(2 pi q / 256), -sin(2 pi q / 256)) for q in [0, 128), computed once on the host in double and rounded to f32.
+ *   Complex product.  (a + bi)(c + di) = (a c - b d) + (a d + b c) i: four multiplies, one subtract, one add.
+ *   Transform F of 256 complex values v: the FULL radix-2 decimation-in-time form -- all 256 complex bins are carried, also for real
+ *     input (no real-input packing).  u[i] = v[i's 8 bits reversed]; for s = 1 .. 8, half = 2^(s-1), for every i in [0, 128):
+ *     j = i mod half, top = 2 (i - j) + j, bot = top + half, p = W[j * 128 / half] * u[bot], u[bot] = u[top] - p, u[top] = u[top] + p.
+ *     The product is taken also where W = (1, 0).  The inverse F' uses (Re W, -Im W) and no scale.
+ *   Head.  head[t] = sum over k in [0, min(K, 128)) with k <= t of h[k] * x[t - k]: in rising k from +0, a multiply and then an add.
+ *   Input spectra.  X_m = F([x block m-1, x block m]), imaginary parts +0, computed in the call that holds block m's last sample.
+ *     They do not depend on the IR: a switch of IR continues on the history the old one saw.
+ *   IR spectra.  H_j = F([h[128 j], ..., h[128 j + 127], 128 zeros]) for j = 1 .. J - 1, J = ceil(K / 128); taps past K are +0.
+ *   Tail of block b.  A_b = sum over j in [1, min(J - 1, b)] of H_j * X_{b-j}: in rising j from (+0, +0), a complex product and then
+ *     two adds -- an order that is a function of j alone.  tail[128 b + i] = Re(F'(A_b))[128 + i] * 2^-8 (the scale is exact).  It needs
+ *     only blocks that are complete when block b begins; it is computed in the first call that needs it and kept for the rest of the block.
+ *   Output.  c = head + tail;  y = (dry * x) + (wet * c).
+ *   Fade.  NA_BatchSetStreamReverb with length N > 0 cross-fades between the whole outputs y_A, y_B of the old and the new setting
+ *     (IR, wet, dry; "no reverb" has the output x itself): the k-th sample after the call is y_B where w = 1 and
+ *     ((1 - w) * y_A) + (w * y_B) otherwise, w = (min(k, N-1) + 1) / N.  N = 0 means the new setting from k = 0, on the kept history.  A
+ *     change of wet / dry on the same IR is such a fade.  fadeSamples lies in [0, 1 << 20].
+ *   Consequence.  A sample's bits do not depend on how the signal is cut into calls, on the sample's index in a call, on row
+ *     alignment or stride, on the other entries of the launch, or on maxTaps.  A restatement in f32 that follows the lines above
+ *     operation for operation (tests/reverb_cases.py) is bit-exact.  Against the exact convolution the relative RMS error is about
+ *     2e-7 for IRs of a few thousand taps.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); the IR id must be loaded (or -1: no reverb); wet and dry must be finite; a set call while a reverb fade of
+ * that stream is running is refused; a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that
+ * ends a hand-over, take the reverb away at once and drop the history.  The stage's state is not part of a NA_BatchSaveStreams blob.
+ * NA_BatchSetStreamReverb, NA_BatchGetStreamReverb and NA_BatchStreamReverbFadeRemaining are REAL-TIME SAFE: host arithmetic on tables
+ * that exist.  While an entry exists -- a stream with a reverb, or a fade towards none -- a processing call runs its launches in order
+ * on one stream, as with cabinet entries, and enqueues one table upload from a ring of pinned tables plus, per piece of the call and
+ * over the streams with an entry only, the append and apply launches and -- where the piece completes a block / needs a tail -- the
+ * spectrum and tail launches: no device or pinned allocation, no stream or event creation, no unbounded wait.  The tail's cost
+ * follows each IR's own length, not maxTaps.
+ * Not provided: non-uniform partitions; stereo IRs; the stage on NA_Multi* batches and on the one-stream NeuralModel; snapshots of the
+ * stage's state; IR file reading or rate conversion. */
+typedef struct NA_ReverbInfo { int maxTaps, partitionSamples, slots, pieceSamples, numIRs; long long deviceBytes; } NA_ReverbInfo;
+NA_EXTERN int NA_BatchEnableReverbStage(NA_Batch* batch, int maxTaps);
+NA_EXTERN int NA_BatchGetReverbInfo(NA_Batch* batch, NA_ReverbInfo* info);
+NA_EXTERN int NA_BatchLoadReverbIR(NA_Batch* batch, const float* taps, int numTaps); /* an IR id >= 0; -1: failure */
+NA_EXTERN int NA_BatchUnloadReverbIR(NA_Batch* batch, int ir);
+NA_EXTERN int NA_BatchSetStreamReverb(NA_Batch* batch, int stream, int ir, float wet, float dry, int fadeSamples); /* ir = -1: no reverb */
+NA_EXTERN int NA_BatchGetStreamReverb(NA_Batch* batch, int stream, float* wet, float* dry); /* the target: id (wet, dry filled; either may be NULL), -1 none, <= -2 bad id / not enabled */
+NA_EXTERN int NA_BatchStreamReverbFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's reverb fade; 0: none; < 0: stage not enabled / bad id */
 /* ---- the gate stage: a per-stream noise gate ----
  * High-gain captures turn pickup hum into a loud hiss between notes.  A host of the reference gates that itself: it listens to the dry
  * input and scales the amp's output, because it holds both buffers.  Here the rows stay on the device, and a gate needs both ends of a
@@ -265,7 +330,7 @@ NA_EXTERN float NA_BatchStreamGateGain(NA_Batch* batch, int stream); /* the g of
  * low-pass around them.  A host of the reference runs a few biquads on the buffer it holds.  Here the rows stay on the device between
  * the model launches and the cabinet stage, so the EQ is a stage of the library: a fourth per-stream stage, off unless enabled -- a
  * cascade of up to NA_EQ_MAX_SECTIONS biquad sections per stream, applied to the row the models produced BEHIND the gate's apply and IN
- * FRONT OF the cabinet stage.  A session's chain is model -> gate -> EQ -> cabinet -> output gain -> mix.  In a resampling batch the stage
+ * FRONT OF the cabinet stage.  A session's chain is model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix.  In a resampling batch the stage
  * acts on the external-rate rows, behind the down kernel, as the cabinet does: coefficients are designed at the rate the caller sees.
  * A batch that enabled the stage and gave no stream an EQ launches exactly what it launched before.
  * Arithmetic.  Every floating-point operation below is one separately rounded IEEE operation (fl(.): f64, fl32(.): f32, round to
@@ -322,7 +387,7 @@ NA_EXTERN int NA_BatchSetStreamEq(NA_Batch* batch, int stream, const NA_EqSectio
 NA_EXTERN int NA_BatchGetStreamEq(NA_Batch* batch, int stream, NA_EqSection* out, int capacity);   /* section count of the target; <0 bad id / not enabled */
 NA_EXTERN int NA_BatchStreamEqFadeRemaining(NA_Batch* batch, int stream);
 /* ---- the meter stage: per-stream level and gain-reduction meters ----
- * Every link of a session's chain -- model -> gate -> EQ -> cabinet -> output gain -> mix -- can be set from the audio thread; this stage is what
+ * Every link of a session's chain -- model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix -- can be set from the audio thread; this stage is what
  * can be READ from it: an input level and clip count, an output level, and what the gate did, per stream, without stopping the batch.
  * A host of the reference meters the buffers it holds; here the rows stay on the device.  A fifth per-stream stage, off unless enabled.
  * It never writes an audio row: with or without meters the samples out are the same bits.  A batch that enabled it and set no meter
@@ -468,7 +533,7 @@ NA_EXTERN int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, d
  * Every stage above works on one row at a time.  A rig that runs two captures on one input, blended or panned left / right (dual amp),
  * an amp next to the dry DI (wet / dry), or wet / dry / wet needs rows to MEET, and the output rows never pass through host code that
  * could sum them: this is the place for it.  A seventh stage, off unless enabled, behind the output stage and in front of the meter
- * stage: a session's chain is model -> gate -> EQ -> cabinet -> output gain -> mix, and the OUT tap of a meter on an output row of a
+ * stage: a session's chain is model -> gate -> EQ -> cabinet -> output gain -> mix (the reverb stage, where enabled, sits between cabinet and output gain), and the OUT tap of a meter on an output row of a
  * group reads the mixed row.  A batch that enabled it and has no group launches exactly what it launched before.
  * Model.  A mix group has M members, 1 <= M <= 8 (NA_MIX_MAX_MEMBERS).  A member is a pair (stream, tap); the tap is NA_MIX_TAP_OUT --
  * the stream's row as the output stage left it -- or NA_MIX_TAP_DRY -- the input row the caller passed for that stream in the same call.
@@ -927,6 +992,14 @@ NA_EXTERN void NA_DebugSetTraceBuffer(void* deviceBuffer);
 NA_EXTERN int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
 /* Tests: launches of the cabinet stage's kernels so far (two per piece of a call with entries) */
 NA_EXTERN long long NA_DebugCabinetLaunches(void);
+/* Tests: as NA_DebugRunCabinetStage, for the reverb stage: the stage alone on given rows -- table, launches, book advance */
+NA_EXTERN int NA_DebugRunReverbStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
+/* Tests: launches of the reverb stage's processing kernels so far (per piece of a call with entries: append and apply, the spectrum
+ * launch where the piece completes a block of some entry, the tail launch where some entry needs a tail) */
+NA_EXTERN long long NA_DebugReverbLaunches(void);
+/* Tests: copies the reverb transform's twiddle table out -- 256 floats, W[q] = (out[2q], out[2q + 1]), q in [0, 128) -- so that a
+ * restatement uses the library's own values; returns 256, or -1 when `floats` < 256.  Needs no batch. */
+NA_EXTERN int NA_DebugReverbTwiddles(float* out, int floats);
 /* Tests: launches of the gate stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugGateLaunches(void);
 /* Tests: launches of the meter stage's two kernels so far (two per processing call with entries) */

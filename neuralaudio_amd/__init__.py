@@ -612,6 +612,54 @@ class Batch:
         """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunCabinetStage)."""
         return self._debug_run_stage(self._lib.NA_DebugRunCabinetStage, rows, n)
 
+    # -- the reverb stage: EnableReverbStage / LoadReverbIR / UnloadReverbIR are set-up side; SetStreamReverb is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableReverbStage(self, maxTaps):
+        if self._lib.NA_BatchEnableReverbStage(self._h, int(maxTaps)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def ReverbInfo(self):
+        info = capi.NA_ReverbInfo()
+        if self._lib.NA_BatchGetReverbInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_ReverbInfo._fields_}
+
+    def LoadReverbIR(self, taps):
+        """Puts a long impulse response (1-D, at the rate of the rows the caller sees) on the device -- its first 128 taps and the spectra
+        of the partitions behind them; returns its id."""
+        taps = np.ascontiguousarray(taps, np.float32).reshape(-1)
+        ir = int(self._lib.NA_BatchLoadReverbIR(self._h, _fptr(taps), int(taps.size)))
+        if ir < 0:
+            raise NeuralAudioError(capi.last_error())
+        return ir
+
+    def UnloadReverbIR(self, ir):
+        if self._lib.NA_BatchUnloadReverbIR(self._h, int(ir)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def SetStreamReverb(self, stream, ir, wet, dry, fadeSamples=0):
+        """The stream's row x becomes dry * x + wet * (x convolved with IR `ir`) from the next sample on (-1: no reverb), cross-faded
+        over `fadeSamples` samples."""
+        if self._lib.NA_BatchSetStreamReverb(self._h, int(stream), int(ir), float(wet), float(dry), int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamReverb(self, stream):
+        """(ir, wet, dry) of the stream's target setting; ir = -1: no reverb."""
+        wet, dry = C.c_float(0.0), C.c_float(0.0)
+        ir = int(self._lib.NA_BatchGetStreamReverb(self._h, int(stream), C.byref(wet), C.byref(dry)))
+        if ir <= -2:
+            raise NeuralAudioError(capi.last_error())
+        return ir, float(wet.value), float(dry.value)
+
+    def ReverbFadeRemaining(self, stream):
+        left = int(self._lib.NA_BatchStreamReverbFadeRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
+
+    def DebugRunReverbStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunReverbStage)."""
+        return self._debug_run_stage(self._lib.NA_DebugRunReverbStage, rows, n)
+
     # -- the gate stage: EnableGateStage is set-up side; SetStreamGate is real-time safe (include/neuralaudio_amd.h) ----
     def EnableGateStage(self):
         if self._lib.NA_BatchEnableGateStage(self._h) != 0:

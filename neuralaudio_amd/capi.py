@@ -43,6 +43,8 @@ NA_SYMBOLS = [
     "NA_BatchEnableOutputStage", "NA_BatchSetStreamGain", "NA_BatchGetStreamGain", "NA_BatchHandover", "NA_BatchHandoverRemaining",
     "NA_BatchEnableCabinetStage", "NA_BatchGetCabinetInfo", "NA_BatchLoadIR", "NA_BatchUnloadIR", "NA_BatchSetStreamIR", "NA_BatchGetStreamIR",
     "NA_BatchStreamIRFadeRemaining", "NA_DebugRunCabinetStage", "NA_DebugCabinetLaunches",
+    "NA_BatchEnableReverbStage", "NA_BatchGetReverbInfo", "NA_BatchLoadReverbIR", "NA_BatchUnloadReverbIR", "NA_BatchSetStreamReverb",
+    "NA_BatchGetStreamReverb", "NA_BatchStreamReverbFadeRemaining", "NA_DebugRunReverbStage", "NA_DebugReverbLaunches", "NA_DebugReverbTwiddles",
     "NA_GateParamsFromDb", "NA_BatchEnableGateStage", "NA_BatchGetGateInfo", "NA_BatchSetStreamGate", "NA_BatchGetStreamGate",
     "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
     "NA_EqSectionFromDesign", "NA_BatchEnableEqStage", "NA_BatchGetEqInfo", "NA_BatchSetStreamEq", "NA_BatchGetStreamEq",
@@ -78,6 +80,11 @@ class NA_ResampleInfo(C.Structure):
 
 class NA_CabinetInfo(C.Structure):
     _fields_ = [("maxTaps", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numIRs", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+class NA_ReverbInfo(C.Structure):
+    _fields_ = [("maxTaps", C.c_int), ("partitionSamples", C.c_int), ("slots", C.c_int), ("pieceSamples", C.c_int), ("numIRs", C.c_int),
+                ("deviceBytes", C.c_longlong)]
 
 
 class NA_GateParams(C.Structure):
@@ -245,6 +252,16 @@ def load_library():
         "NA_BatchStreamIRFadeRemaining": (C.c_int, [vp, C.c_int]),
         "NA_DebugRunCabinetStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
         "NA_DebugCabinetLaunches": (C.c_longlong, []),
+        "NA_BatchEnableReverbStage": (C.c_int, [vp, C.c_int]),
+        "NA_BatchGetReverbInfo": (C.c_int, [vp, C.POINTER(NA_ReverbInfo)]),
+        "NA_BatchLoadReverbIR": (C.c_int, [vp, fp, C.c_int]),
+        "NA_BatchUnloadReverbIR": (C.c_int, [vp, C.c_int]),
+        "NA_BatchSetStreamReverb": (C.c_int, [vp, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int]),
+        "NA_BatchGetStreamReverb": (C.c_int, [vp, C.c_int, fp, fp]),
+        "NA_BatchStreamReverbFadeRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_DebugRunReverbStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
+        "NA_DebugReverbLaunches": (C.c_longlong, []),
+        "NA_DebugReverbTwiddles": (C.c_int, [fp, C.c_int]),
         "NA_GateParamsFromDb": (C.c_int, [C.c_int] + [C.c_float] * 7 + [C.POINTER(NA_GateParams)]),
         "NA_BatchEnableGateStage": (C.c_int, [vp]),
         "NA_BatchGetGateInfo": (C.c_int, [vp, C.POINTER(NA_GateInfo)]),

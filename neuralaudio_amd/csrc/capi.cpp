@@ -672,6 +672,68 @@ int NA_DebugRunCabinetStage(NA_Batch* batch, float* hostRows, long stride, size_
 long long NA_DebugCabinetLaunches(void) { return (long long)na::CabinetStageLaunches(); }
 #endif
 
+// ---- the reverb stage (gpu_batch.h EnableReverbStage / LoadReverbIR / SetStreamReverb) ----
+int NA_BatchEnableReverbStage(NA_Batch* batch, int maxTaps)
+{
+	return BatchCall(batch, "NA_BatchEnableReverbStage", [&](na::GpuBatch& b) { b.EnableReverbStage(maxTaps); });
+}
+
+int NA_BatchGetReverbInfo(NA_Batch* batch, NA_ReverbInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetReverbInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetReverbInfo: bad argument");
+		const na::ReverbStageInfo i = b.GetReverbInfo();
+		info->maxTaps = i.maxTaps;
+		info->partitionSamples = i.partitionSamples;
+		info->slots = i.slots;
+		info->pieceSamples = i.pieceSamples;
+		info->numIRs = i.numIRs;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchLoadReverbIR(NA_Batch* batch, const float* taps, int numTaps)
+{
+	return BatchValue(batch, "NA_BatchLoadReverbIR", -1, [&](na::GpuBatch& b) { return b.LoadReverbIR(taps, numTaps); });
+}
+
+int NA_BatchUnloadReverbIR(NA_Batch* batch, int ir)
+{
+	return BatchCall(batch, "NA_BatchUnloadReverbIR", [&](na::GpuBatch& b) { b.UnloadReverbIR(ir); });
+}
+
+int NA_BatchSetStreamReverb(NA_Batch* batch, int stream, int ir, float wet, float dry, int fadeSamples)
+{
+	return BatchCall(batch, "NA_BatchSetStreamReverb", [&](na::GpuBatch& b) { b.SetStreamReverb(stream, ir, wet, dry, fadeSamples); });
+}
+
+int NA_BatchGetStreamReverb(NA_Batch* batch, int stream, float* wet, float* dry)
+{
+	return BatchValue(batch, "NA_BatchGetStreamReverb", -2, [&](na::GpuBatch& b) { return b.GetStreamReverb(stream, wet, dry); });
+}
+
+int NA_BatchStreamReverbFadeRemaining(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchStreamReverbFadeRemaining", -1, [&](na::GpuBatch& b) { return b.StreamReverbFadeRemaining(stream); });
+}
+
+#ifndef NA_RELEASE
+int NA_DebugRunReverbStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunReverbStage: null batch");
+		batch->batch->DebugRunReverbStage(hostRows, stride, n);
+	});
+}
+long long NA_DebugReverbLaunches(void) { return (long long)na::ReverbStageLaunches(); }
+int NA_DebugReverbTwiddles(float* out, int floats)
+{
+	if (!out || floats < na::kRevPoints) return -1;
+	std::copy(na::ReverbTwiddles(), na::ReverbTwiddles() + na::kRevPoints, out);
+	return na::kRevPoints;
+}
+#endif
+
 // ---- the gate stage (gpu_batch.h EnableGateStage / SetStreamGate) ----
 namespace
 {

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "cabinet_stage.h"
+#include "reverb_stage.h"
 #include "device_resources.h"
 #include "eq_stage.h"
 #include "gate_stage.h"
@@ -71,6 +72,12 @@ namespace na
 	struct CabinetStageInfo
 	{
 		int maxTaps = 0, ringSamples = 0, pieceSamples = 0, numIRs = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct ReverbStageInfo
+	{
+		int maxTaps = 0, partitionSamples = 0, slots = 0, pieceSamples = 0, numIRs = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -180,6 +187,25 @@ namespace na
 		int StreamIRFadeRemaining(int stream) const;
 		// test hook (NA_DebugRunCabinetStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
 		void DebugRunCabinetStage(float* hostRows, long stride, size_t n);
+
+		// The reverb stage (reverb_stage.h): per-stream partitioned FFT convolution of the row with a long impulse
+		// response (up to kRevMaxTaps taps) and a wet / dry mix, behind the cabinet stage and in front of the output stage.
+		// EnableReverbStage, LoadReverbIR and UnloadReverbIR are the set-up side: a sample ring, a ring of input spectra and the tail
+		// blocks per row (CreateStreams grows them), the tables, the IRs' head taps and partition spectra on the device (LoadReverbIR
+		// computes the spectra there and waits for them, under the wait limit).  SetStreamReverb is host arithmetic on those tables;
+		// while an entry exists -- a stream with a reverb, or a fade towards none -- every processing call runs on the ordered path and
+		// enqueues ONE table upload and two to four launches per piece of kRevPieceSamples samples.  Without an entry the batch launches
+		// exactly what it launches without the stage.
+		void EnableReverbStage(int maxTaps);
+		bool HasReverbStage() const { return stages[kReverbStage] != nullptr; }
+		ReverbStageInfo GetReverbInfo() const;
+		int LoadReverbIR(const float* taps, int numTaps);
+		void UnloadReverbIR(int ir);
+		void SetStreamReverb(int stream, int ir, float wet, float dry, int fadeSamples); // ir = -1: no reverb
+		int GetStreamReverb(int stream, float* wet, float* dry) const;                   // the target
+		int StreamReverbFadeRemaining(int stream) const;
+		// test hook (NA_DebugRunReverbStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
+		void DebugRunReverbStage(float* hostRows, long stride, size_t n);
 
 		// The gate stage (gate_stage.h): a per-stream noise gate that listens to the stream's input row and scales the row
 		// the models produced for it -- the detector launch in front of everything of the call, the apply launch first of the stages, in
@@ -411,9 +437,9 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.16).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.17).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
@@ -425,7 +451,7 @@ namespace na
 			virtual void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) = 0;
 		};
 		template <class Book, class Entry> struct StageOf;
-		struct GateStage; struct EqStage; struct CabinetStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
+		struct GateStage; struct EqStage; struct CabinetStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -225,7 +225,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the seven stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the eight stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -292,6 +292,27 @@ namespace na
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + two launches per piece + the host mirror's advance
 	};
 	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece
+
+	// the reverb stage (reverb_stage.h, reverb_stage.cpp): the rows' sample rings, rings of input spectra and tail blocks,
+	// the transform's twiddles and the IRs' head taps and partition spectra (owned through the book's ids)
+	struct GpuBatch::ReverbStage : StageOf<ReverbBook, RevEntry>
+	{
+		static constexpr StageId kId = kReverbStage;
+		static constexpr const char* kNotEnabled = "reverb stage not enabled (NA_BatchEnableReverbStage)";
+		float* rings = nullptr;           // [ringRows][kRevRingSamples]
+		float* tails = nullptr;           // [ringRows][kRevTailFloats]
+		float* spectra = nullptr;         // [spectraRows][book.Slots()][kRevSpectrumFloats]
+		float* twiddles = nullptr;        // [kRevPoints]
+		int ringRows = 0, spectraRows = 0;
+		long long irBytes = 0;            // device bytes of the loaded IRs
+		ReverbStage() : StageOf("reverb stage") {}
+		~ReverbStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // no reverb at once, its history dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + up to four launches per piece + the host mirror's advance
+	};
+	hipError_t LaunchReverbStage(const RevLaunch& L, hipStream_t stream); // (reverb_stage_kernels.hip) the launches of one piece
+	hipError_t LaunchReverbIR(const RevIRLaunch& L, hipStream_t stream);  // ... and of one IR's spectra, load side
 
 	// the output stage (output_stage.h, output_stage.cpp)
 	struct GpuBatch::OutputStage : StageOf<OutputStageBook, OutStageEntry>

@@ -38,6 +38,12 @@
 //       first panned -0.5 and the second +0.5 (NA_MixGainsFromPan) -- (N = 0: enabled, no group: must cost nothing).  With --mix-dry
 //       each group gets the DRY tap of its first stream as a third member, at -6 dB in the centre.  Times every buffer period of the
 //       pipelined loop like --tuner; the same device span as --gate.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --reverb N [--reverb-taps K=48000] [--reverb-irs M=1]
+//       the plain run below with the reverb stage enabled (maxTaps = K) and a reverb on the first N streams: M synthetic IRs of K taps
+//       (decaying noise), IR s % M on stream s, wet 0.3, dry 1 (N = 0: enabled, no reverb set: must cost nothing).  With N > 0 the run
+//       first feeds ceil(K / 128) buffers, so that every delay line is full before anything is timed.  Times every buffer period like
+//       --tuner; the same device span as --gate; reports the spectrum bytes the tail launch reads per buffer (input spectra: every
+//       stream's own; IR spectra: the same amount, of which M IRs' worth is distinct).
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -587,14 +593,14 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]] [--mix N [--mix-dry]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]] [--mix N [--mix-dry]] [--reverb N [--reverb-taps K] [--reverb-irs M]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
 	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3, meter = -1, meterWindow = 1024, tuner = -1, tunerHop = 0;
-	int mixGroups = -1;
+	int mixGroups = -1, reverb = -1, reverbTaps = 48000, reverbIRs = 1;
 	bool churnLegacy = false, tunerStagger = false, mixDry = false;
 	for (int i = 1; i < argc; i++)
 	{
@@ -616,6 +622,9 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--fade") && i + 1 < argc) fade = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--cab") && i + 1 < argc) cab = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--cab-irs") && i + 1 < argc) cabIRs = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--reverb") && i + 1 < argc) reverb = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--reverb-taps") && i + 1 < argc) reverbTaps = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--reverb-irs") && i + 1 < argc) reverbIRs = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) gate = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--eq") && i + 1 < argc) eq = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--meter") && i + 1 < argc) meter = std::atoi(argv[++i]);
@@ -746,13 +755,49 @@ int main(int argc, char** argv)
 			CHECK(NA_BatchSetMixGroup(batch, ids, taps, mixDry ? 3 : 2, 2, mixDry ? withDry : stereo, 0) == 0);
 		}
 	}
+	long long reverbBytes = 0, reverbInputSpectrumBytes = 0, reverbDistinctIRBytes = 0;
+	double reverbLoadMs = 0.0;
+	if (reverb >= 0)
+	{
+		CHECK(reverbTaps >= 1 && reverbIRs >= 1);
+		CHECK(NA_BatchEnableReverbStage(batch, reverbTaps) == 0);
+		reverb = std::min(reverb, streams);
+		reverbIRs = std::min(reverbIRs, std::max(reverb, 1));
+		std::vector<int> ids;
+		std::vector<float> h((size_t)reverbTaps);
+		const double t0 = Now();
+		for (int m = 0; m < reverbIRs && reverb > 0; m++)
+		{
+			unsigned seed = 12345u + 977u * (unsigned)m;
+			for (int k = 0; k < reverbTaps; k++)
+			{
+				seed = seed * 1664525u + 1013904223u;
+				h[(size_t)k] = ((float)(seed >> 8 & 0xffff) / 32768.0f - 1.0f) * std::exp(-6.0f * (float)k / (float)reverbTaps) * 0.02f;
+			}
+			const int id = NA_BatchLoadReverbIR(batch, h.data(), reverbTaps);
+			CHECK(id >= 0);
+			ids.push_back(id);
+		}
+		reverbLoadMs = (Now() - t0) * 1e3;
+		for (int s = 0; s < reverb; s++) CHECK(NA_BatchSetStreamReverb(batch, s, ids[(size_t)(s % reverbIRs)], 0.3f, 1.0f, 0) == 0);
+		NA_ReverbInfo info;
+		CHECK(NA_BatchGetReverbInfo(batch, &info) == 0);
+		reverbBytes = info.deviceBytes;
+		const long long tailPartitions = (reverbTaps + info.partitionSamples - 1) / info.partitionSamples - 1;
+		reverbInputSpectrumBytes = (long long)reverb * tailPartitions * 2048 * ((frames + info.partitionSamples - 1) / info.partitionSamples);
+		reverbDistinctIRBytes = reverb > 0 ? (long long)reverbIRs * tailPartitions * 2048 : 0;
+	}
 	unsigned long long meterWindows = 0; // (--meter: `windows` of the last reading of stream 0 in the pipelined loop)
 	unsigned long long tunerEvaluations = 0; // (--tuner: `evaluations` of the last reading of stream 0 in the pipelined loop)
 	std::vector<double> periods;             // (--tuner, --mix N: every buffer period of the pipelined loop)
-	const bool marks = gate >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0; // (the plain run stays what it was)
+	const bool marks = gate >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0 || reverb >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
+
+	// (--reverb N > 0: the delay lines fill first -- the tail of a block sums over as many partitions as the history has)
+	if (reverb > 0)
+		for (long long fed = 0; fed < reverbTaps; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 
 	// blocking call, one buffer at a time
 	std::vector<double> lat;
@@ -822,7 +867,7 @@ int main(int argc, char** argv)
 			CHECK(have >= 0);
 			if (have) tunerEvaluations = reading.evaluations;
 		}
-		if (tuner >= 0 || mixGroups >= 0) periods.push_back(Now());
+		if (tuner >= 0 || mixGroups >= 0 || reverb >= 0) periods.push_back(Now());
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
@@ -879,9 +924,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"reverb\": %d, \"reverb_taps\": %d, \"reverb_irs\": %d, \"reverb_device_bytes\": %lld, \"reverb_load_irs_ms\": %.1f, \"reverb_input_spectrum_bytes_per_buffer\": %lld, \"reverb_distinct_ir_spectrum_bytes\": %lld, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, reverb, reverb >= 0 ? reverbTaps : 0, reverb > 0 ? reverbIRs : 0, reverbBytes, reverbLoadMs, reverbInputSpectrumBytes, reverbDistinctIRBytes, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
