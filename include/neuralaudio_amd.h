@@ -194,7 +194,7 @@ NA_EXTERN int NA_BatchStreamIRFadeRemaining(NA_Batch* batch, int stream); /* sam
  * form, ends at 8192 taps and costs what its taps cost.  This stage is uniformly partitioned FFT convolution: partitions of P = 128
  * samples, 256-point transforms, a per-row delay line of input spectra; the first 128 taps run direct form, so the stage has no
  * latency and a one-sample call works.  An eighth per-stream stage, off unless enabled, BEHIND the cabinet stage and IN FRONT OF the
- * output stage: a session's chain is model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix.  For every stream that has a reverb
+ * output stage: a session's chain is model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix (the delay stage, where enabled, sits between cabinet and reverb).  For every stream that has a reverb
  * the row's samples x are replaced by dry * x + wet * (x convolved with the IR).  A batch that enabled the stage and set no reverb
  * launches exactly what it launched before.  In a resampling batch the stage acts on the external-rate rows, as the cabinet does.
  * Set-up side (not real-time safe: they allocate and may wait for what is in flight):
@@ -254,6 +254,75 @@ NA_EXTERN int NA_BatchUnloadReverbIR(NA_Batch* batch, int ir);
 NA_EXTERN int NA_BatchSetStreamReverb(NA_Batch* batch, int stream, int ir, float wet, float dry, int fadeSamples); /* ir = -1: no reverb */
 NA_EXTERN int NA_BatchGetStreamReverb(NA_Batch* batch, int stream, float* wet, float* dry); /* the target: id (wet, dry filled; either may be NULL), -1 none, <= -2 bad id / not enabled */
 NA_EXTERN int NA_BatchStreamReverbFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's reverb fade; 0: none; < 0: stage not enabled / bad id */
+/* ---- the delay stage: a per-stream echo, a feedback delay line ----
+ * The block every guitar rig has between cabinet and room is a delay: echo, slap-back, dotted-eighth repeats.  A host of the reference
+ * runs a delay on the buffer it holds.  Here the rows stay on the device, and an echo added by the host would come BEHIND the reverb:
+ * the wrong order.  A ninth per-stream stage, off unless enabled, BEHIND the cabinet stage and IN FRONT OF the reverb stage: a session's
+ * chain is model -> gate -> EQ -> cabinet -> delay -> reverb -> output gain -> mix.  The line feeds back through a one-pole low-pass and
+ * a one-pole high-pass, so the repeats darken and thin out as a tape echo's do.  In a resampling batch the stage acts on the
+ * external-rate rows, as the cabinet does.  A batch that enabled the stage and set no delay launches exactly what it launched before.
+ * Rows without an entry are never touched.
+ * Set-up side (not real-time safe: it allocates and may wait for what is in flight):
+ *   NA_BatchEnableDelayStage(maxDelaySamples in [1, 1 << 18]) allocates, per row of the batch's capacity, one ring of ringSamples floats
+ *     and a small filter state, plus the stage's tables.  ringSamples is a power of two >= maxDelaySamples + pieceSamples;
+ *     pieceSamples = 2048 is the longest run the stage processes at once, longer calls run in pieces.  Later NA_BatchAddStreams /
+ *     NA_BatchReserveStreams grow the rings and tables.  Idempotent for an equal or smaller maximum; a larger one is refused while any
+ *     stream has a delay.  Every other call fails with "delay stage not enabled (NA_BatchEnableDelayStage)" before it.
+ *     NA_BatchGetDelayInfo reports the sizes in effect and the device memory the stage holds (deviceBytes: 512 MB for 1024 rows at a
+ *     maximum of 2 s at 48 kHz, ringSamples = 131072).
+ * Arithmetic.  Every floating-point operation is one separately rounded f32 operation, fl(.), rounded to nearest even, with no FMA
+ * contraction.  f32 subnormals are kept as operands and as results.  Positions t = 0, 1, ... count the samples the caller sees since
+ * T0, the first sample after the set call that took the stream from no delay.  The line starts empty: w[t] = 0 for t < 0, and nothing
+ * is cleared on the device.  k is the count of samples since the last set call, an integer advanced by whole calls.
+ * Constants of a setting: D = delaySamples in [1, maxDelaySamples]; fb = feedback, |fb| <= 0.99; aL = lowpassCoeff in (0, 1];
+ * aH = highpassCoeff in [0, 1); wet, dry finite, |.| <= 1e6.  State per stream: the ring w, f32 l and q (both 0 at T0).
+ * Per sample, in order, x the row's sample and y what replaces it:
+ *   x' = isnan(x) ? 0 : clamp(x, +-1e18f)
+ *   d  = w[t - D]                                       (+0 where t - D < 0)
+ *   l  = (aL == 1) ? d : fl(l + fl(aL * fl(d - l)))     (aL == 1: l takes d, bit for bit)
+ *   if aH == 0: h = l, q left alone;  else: q = fl(q + fl(aH * fl(l - q))), h = fl(l - q)
+ *   w[t] = clamp(fl(x' + fl(fb * h)), +-1e30f)
+ *   y  = (wet == 0) ? fl(dry * x') : fl(fl(dry * x') + fl(wet * h))
+ * The clamps are exact min / max.  With the limits above every value stays finite whatever the input.
+ * Set calls and fades.  A set call moves the stream from setting A to setting B over N = fadeSamples in [0, 1 << 20].  The weight is
+ * the one the cabinet, EQ and reverb use: wk = 1 for k >= N - 1 and (float)(k + 1) / (float)N otherwise.  There is one ring and one
+ * filter state throughout.
+ *   The filter coefficients are B's from k = 0, on the kept l and q.
+ *   fb, wet and dry each ramp: the value of a sample is B's where wk == 1, else fl(g_A + fl(fl(g_B - g_A) * wk)); the step above runs
+ *     on the ramped values (its test wet == 0 too).
+ *   If D_A != D_B the read head cross-fades: d is w[t - D_B] where wk == 1, else
+ *     fl(fl(fl(1 - wk) * w[t - D_A]) + fl(wk * w[t - D_B])).  If D_A == D_B there is no blend.
+ *   "No delay" as A is B with wet = 0, dry = 1: a new delay fades in on an empty line.  As B (params == NULL) it is A with wet = 0,
+ *     dry = 1: the echo fades out; the entry retires with the sample at which the fade ends -- later samples are not touched -- and
+ *     the history is dropped.  With N = 0 it retires at once.
+ *   A set call while a fade of that stream is running is refused.
+ * Consequences.  A sample's bits do not depend on the cut into calls, on its index in a call, on alignment, on stride, on the other
+ * entries or on maxDelaySamples.  With aL = 1, aH = 0 the line is pure arithmetic on taps: with fb = 0.5 and an impulse the echoes are
+ * exact powers of two.  With wet = 0, dry = 1 the row is x' bit for bit.  A restatement in f32 that follows the lines above operation
+ * for operation (tests/delay_cases.py) is bit-exact.
+ * NA_DelayParamsFromMs is host arithmetic in double, rounded once: delaySamples = max(1, round(ms * rate / 1000)); lowpassCoeff = 1 when
+ * highCutHz <= 0 or >= rate / 2, else 1 - exp(-2 pi highCutHz / rate); highpassCoeff = 0 when lowCutHz <= 0, else
+ * 1 - exp(-2 pi lowCutHz / rate); wet = 10^(wetDb / 20) with -inf -> 0, dry likewise.  It refuses what the set call would refuse (a
+ * delay beyond 1 << 18 samples included).  It needs no batch.
+ * Rules (each fails with a message that names the field or the stream, NA_GetLastError): the stage must be enabled; the stream must be
+ * live (a parked one fails with "... is parked"); every field must be within the limits above; a broken batch refuses everything.
+ * NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a hand-over, drop the delay and its history at once.  Delays are
+ * not part of a NA_BatchSaveStreams blob.
+ * NA_BatchSetStreamDelay, NA_BatchGetStreamDelay and NA_BatchStreamDelayFadeRemaining are REAL-TIME SAFE: host arithmetic on tables
+ * that exist.  While an entry exists -- a stream with a delay, or a fade towards none -- a processing call behaves as it does with the
+ * other stages' entries: it takes the ordered path, host buffers go through the staging block, and it enqueues one table upload from
+ * the ring of pinned tables and one launch per piece over the entries only: no allocation, no stream or event creation, no unbounded
+ * wait.  With the last entry the free-running modes come back.
+ * Not provided: fractional or modulated delay times; ping-pong across rows; tempo helpers; the stage on NA_Multi* batches and on the
+ * one-stream NeuralModel. */
+typedef struct NA_DelayParams { int delaySamples; float feedback, lowpassCoeff, highpassCoeff, wet, dry; } NA_DelayParams;
+typedef struct NA_DelayInfo   { int maxDelaySamples, ringSamples, pieceSamples, numDelays; long long deviceBytes; } NA_DelayInfo;
+NA_EXTERN int NA_DelayParamsFromMs(int sampleRate, double delayMs, double feedback, double lowCutHz, double highCutHz, double wetDb, double dryDb, NA_DelayParams* out);
+NA_EXTERN int NA_BatchEnableDelayStage(NA_Batch* batch, int maxDelaySamples);
+NA_EXTERN int NA_BatchGetDelayInfo(NA_Batch* batch, NA_DelayInfo* info);
+NA_EXTERN int NA_BatchSetStreamDelay(NA_Batch* batch, int stream, const NA_DelayParams* params, int fadeSamples); /* params = NULL: no delay */
+NA_EXTERN int NA_BatchGetStreamDelay(NA_Batch* batch, int stream, NA_DelayParams* out); /* 1: *out filled (the target); 0: no delay (or a fade to none); < 0: stage not enabled / bad id */
+NA_EXTERN int NA_BatchStreamDelayFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's delay fade; 0: none; < 0: stage not enabled / bad id */
 /* ---- the gate stage: a per-stream noise gate ----
  * High-gain captures turn pickup hum into a loud hiss between notes.  A host of the reference gates that itself: it listens to the dry
  * input and scales the amp's output, because it holds both buffers.  Here the rows stay on the device, and a gate needs both ends of a
@@ -330,7 +399,7 @@ NA_EXTERN float NA_BatchStreamGateGain(NA_Batch* batch, int stream); /* the g of
  * low-pass around them.  A host of the reference runs a few biquads on the buffer it holds.  Here the rows stay on the device between
  * the model launches and the cabinet stage, so the EQ is a stage of the library: a fourth per-stream stage, off unless enabled -- a
  * cascade of up to NA_EQ_MAX_SECTIONS biquad sections per stream, applied to the row the models produced BEHIND the gate's apply and IN
- * FRONT OF the cabinet stage.  A session's chain is model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix.  In a resampling batch the stage
+ * FRONT OF the cabinet stage.  A session's chain is model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix (the delay stage, where enabled, sits between cabinet and reverb).  In a resampling batch the stage
  * acts on the external-rate rows, behind the down kernel, as the cabinet does: coefficients are designed at the rate the caller sees.
  * A batch that enabled the stage and gave no stream an EQ launches exactly what it launched before.
  * Arithmetic.  Every floating-point operation below is one separately rounded IEEE operation (fl(.): f64, fl32(.): f32, round to
@@ -387,7 +456,7 @@ NA_EXTERN int NA_BatchSetStreamEq(NA_Batch* batch, int stream, const NA_EqSectio
 NA_EXTERN int NA_BatchGetStreamEq(NA_Batch* batch, int stream, NA_EqSection* out, int capacity);   /* section count of the target; <0 bad id / not enabled */
 NA_EXTERN int NA_BatchStreamEqFadeRemaining(NA_Batch* batch, int stream);
 /* ---- the meter stage: per-stream level and gain-reduction meters ----
- * Every link of a session's chain -- model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix -- can be set from the audio thread; this stage is what
+ * Every link of a session's chain -- model -> gate -> EQ -> cabinet -> reverb -> output gain -> mix (the delay stage, where enabled, sits between cabinet and reverb) -- can be set from the audio thread; this stage is what
  * can be READ from it: an input level and clip count, an output level, and what the gate did, per stream, without stopping the batch.
  * A host of the reference meters the buffers it holds; here the rows stay on the device.  A fifth per-stream stage, off unless enabled.
  * It never writes an audio row: with or without meters the samples out are the same bits.  A batch that enabled it and set no meter
@@ -533,7 +602,7 @@ NA_EXTERN int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, d
  * Every stage above works on one row at a time.  A rig that runs two captures on one input, blended or panned left / right (dual amp),
  * an amp next to the dry DI (wet / dry), or wet / dry / wet needs rows to MEET, and the output rows never pass through host code that
  * could sum them: this is the place for it.  A seventh stage, off unless enabled, behind the output stage and in front of the meter
- * stage: a session's chain is model -> gate -> EQ -> cabinet -> output gain -> mix (the reverb stage, where enabled, sits between cabinet and output gain), and the OUT tap of a meter on an output row of a
+ * stage: a session's chain is model -> gate -> EQ -> cabinet -> output gain -> mix (the reverb stage, where enabled, sits between cabinet and output gain; the delay stage, where enabled, between cabinet and reverb), and the OUT tap of a meter on an output row of a
  * group reads the mixed row.  A batch that enabled it and has no group launches exactly what it launched before.
  * Model.  A mix group has M members, 1 <= M <= 8 (NA_MIX_MAX_MEMBERS).  A member is a pair (stream, tap); the tap is NA_MIX_TAP_OUT --
  * the stream's row as the output stage left it -- or NA_MIX_TAP_DRY -- the input row the caller passed for that stream in the same call.
@@ -1000,6 +1069,10 @@ NA_EXTERN long long NA_DebugReverbLaunches(void);
 /* Tests: copies the reverb transform's twiddle table out -- 256 floats, W[q] = (out[2q], out[2q + 1]), q in [0, 128) -- so that a
  * restatement uses the library's own values; returns 256, or -1 when `floats` < 256.  Needs no batch. */
 NA_EXTERN int NA_DebugReverbTwiddles(float* out, int floats);
+/* Tests: as NA_DebugRunCabinetStage, for the delay stage: the stage alone on given rows -- table, launches, book advance */
+NA_EXTERN int NA_DebugRunDelayStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
+/* Tests: launches of the delay stage's kernel so far (one per piece of a call with entries) */
+NA_EXTERN long long NA_DebugDelayLaunches(void);
 /* Tests: launches of the gate stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugGateLaunches(void);
 /* Tests: launches of the meter stage's two kernels so far (two per processing call with entries) */

@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -72,6 +72,32 @@ def gate_params_from_db(sample_rate, open_db, close_db, floor_db=float("-inf"), 
                                                float(attack_ms), float(hold_ms), float(release_ms), C.byref(out)) != 0:
         raise NeuralAudioError(capi.last_error())
     return _gate_dict(out)
+
+
+DELAY_FIELDS = ("delaySamples", "feedback", "lowpassCoeff", "highpassCoeff", "wet", "dry")
+
+
+def _delay_dict(p):
+    return {name: (int if name == "delaySamples" else float)(getattr(p, name)) for name in DELAY_FIELDS}
+
+
+def _delay_params(d):
+    if isinstance(d, capi.NA_DelayParams):
+        return d
+    p = capi.NA_DelayParams()
+    for name in DELAY_FIELDS:
+        setattr(p, name, d[name])
+    return p
+
+
+def delay_params_from_ms(sample_rate, delay_ms, feedback=0.35, low_cut_hz=0.0, high_cut_hz=0.0, wet_db=-6.0, dry_db=0.0):
+    """The constants Batch.SetStreamDelay takes, from milliseconds, hertz and decibels (NA_DelayParamsFromMs): low_cut_hz <= 0 leaves the
+    high-pass out, high_cut_hz <= 0 or >= rate / 2 the low-pass; -inf dB is 0.  Host arithmetic: needs no device."""
+    out = capi.NA_DelayParams()
+    if capi.load_library().NA_DelayParamsFromMs(int(sample_rate), float(delay_ms), float(feedback), float(low_cut_hz), float(high_cut_hz),
+                                                float(wet_db), float(dry_db), C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _delay_dict(out)
 
 
 METER_FIELDS = ("windowSamples", "clipLevelIn", "clipLevelOut")
@@ -659,6 +685,42 @@ class Batch:
     def DebugRunReverbStage(self, rows, n=None):
         """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunReverbStage)."""
         return self._debug_run_stage(self._lib.NA_DebugRunReverbStage, rows, n)
+
+    # -- the delay stage: EnableDelayStage is set-up side; SetStreamDelay is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableDelayStage(self, maxDelaySamples):
+        if self._lib.NA_BatchEnableDelayStage(self._h, int(maxDelaySamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetDelayInfo(self):
+        info = capi.NA_DelayInfo()
+        if self._lib.NA_BatchGetDelayInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_DelayInfo._fields_}
+
+    def SetStreamDelay(self, stream, params, fadeSamples=0):
+        """An echo on the stream from the next sample on: `params` a dict of the NA_DelayParams fields (delay_params_from_ms makes one);
+        None: no delay.  The change runs over `fadeSamples` samples."""
+        p = None if params is None else C.byref(_delay_params(params))
+        if self._lib.NA_BatchSetStreamDelay(self._h, int(stream), p, int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamDelay(self, stream):
+        """The target setting as a dict; None: no delay (or one that fades to none)."""
+        out = capi.NA_DelayParams()
+        rc = int(self._lib.NA_BatchGetStreamDelay(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _delay_dict(out) if rc else None
+
+    def StreamDelayFadeRemaining(self, stream):
+        left = int(self._lib.NA_BatchStreamDelayFadeRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
+
+    def DebugRunDelayStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunDelayStage)."""
+        return self._debug_run_stage(self._lib.NA_DebugRunDelayStage, rows, n)
 
     # -- the gate stage: EnableGateStage is set-up side; SetStreamGate is real-time safe (include/neuralaudio_amd.h) ----
     def EnableGateStage(self):

@@ -45,6 +45,8 @@ NA_SYMBOLS = [
     "NA_BatchStreamIRFadeRemaining", "NA_DebugRunCabinetStage", "NA_DebugCabinetLaunches",
     "NA_BatchEnableReverbStage", "NA_BatchGetReverbInfo", "NA_BatchLoadReverbIR", "NA_BatchUnloadReverbIR", "NA_BatchSetStreamReverb",
     "NA_BatchGetStreamReverb", "NA_BatchStreamReverbFadeRemaining", "NA_DebugRunReverbStage", "NA_DebugReverbLaunches", "NA_DebugReverbTwiddles",
+    "NA_DelayParamsFromMs", "NA_BatchEnableDelayStage", "NA_BatchGetDelayInfo", "NA_BatchSetStreamDelay", "NA_BatchGetStreamDelay",
+    "NA_BatchStreamDelayFadeRemaining", "NA_DebugRunDelayStage", "NA_DebugDelayLaunches",
     "NA_GateParamsFromDb", "NA_BatchEnableGateStage", "NA_BatchGetGateInfo", "NA_BatchSetStreamGate", "NA_BatchGetStreamGate",
     "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
     "NA_EqSectionFromDesign", "NA_BatchEnableEqStage", "NA_BatchGetEqInfo", "NA_BatchSetStreamEq", "NA_BatchGetStreamEq",
@@ -84,6 +86,16 @@ class NA_CabinetInfo(C.Structure):
 
 class NA_ReverbInfo(C.Structure):
     _fields_ = [("maxTaps", C.c_int), ("partitionSamples", C.c_int), ("slots", C.c_int), ("pieceSamples", C.c_int), ("numIRs", C.c_int),
+                ("deviceBytes", C.c_longlong)]
+
+
+class NA_DelayParams(C.Structure):
+    _fields_ = [("delaySamples", C.c_int), ("feedback", C.c_float), ("lowpassCoeff", C.c_float), ("highpassCoeff", C.c_float),
+                ("wet", C.c_float), ("dry", C.c_float)]
+
+
+class NA_DelayInfo(C.Structure):
+    _fields_ = [("maxDelaySamples", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numDelays", C.c_int),
                 ("deviceBytes", C.c_longlong)]
 
 
@@ -262,6 +274,14 @@ def load_library():
         "NA_DebugRunReverbStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
         "NA_DebugReverbLaunches": (C.c_longlong, []),
         "NA_DebugReverbTwiddles": (C.c_int, [fp, C.c_int]),
+        "NA_DelayParamsFromMs": (C.c_int, [C.c_int] + [C.c_double] * 6 + [C.POINTER(NA_DelayParams)]),
+        "NA_BatchEnableDelayStage": (C.c_int, [vp, C.c_int]),
+        "NA_BatchGetDelayInfo": (C.c_int, [vp, C.POINTER(NA_DelayInfo)]),
+        "NA_BatchSetStreamDelay": (C.c_int, [vp, C.c_int, C.POINTER(NA_DelayParams), C.c_int]),
+        "NA_BatchGetStreamDelay": (C.c_int, [vp, C.c_int, C.POINTER(NA_DelayParams)]),
+        "NA_BatchStreamDelayFadeRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_DebugRunDelayStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
+        "NA_DebugDelayLaunches": (C.c_longlong, []),
         "NA_GateParamsFromDb": (C.c_int, [C.c_int] + [C.c_float] * 7 + [C.POINTER(NA_GateParams)]),
         "NA_BatchEnableGateStage": (C.c_int, [vp]),
         "NA_BatchGetGateInfo": (C.c_int, [vp, C.POINTER(NA_GateInfo)]),

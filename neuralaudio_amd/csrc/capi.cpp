@@ -734,6 +734,98 @@ int NA_DebugReverbTwiddles(float* out, int floats)
 }
 #endif
 
+// ---- the delay stage (gpu_batch.h EnableDelayStage / SetStreamDelay) ----
+namespace
+{
+	void DelayParamsIn(const NA_DelayParams& p, na::DelayParams& d)
+	{
+		d.delaySamples = p.delaySamples;
+		d.feedback = p.feedback;
+		d.lowpassCoeff = p.lowpassCoeff;
+		d.highpassCoeff = p.highpassCoeff;
+		d.wet = p.wet;
+		d.dry = p.dry;
+	}
+	void DelayParamsOut(const na::DelayParams& d, NA_DelayParams* p)
+	{
+		p->delaySamples = d.delaySamples;
+		p->feedback = d.feedback;
+		p->lowpassCoeff = d.lowpassCoeff;
+		p->highpassCoeff = d.highpassCoeff;
+		p->wet = d.wet;
+		p->dry = d.dry;
+	}
+}
+
+int NA_DelayParamsFromMs(int sampleRate, double delayMs, double feedback, double lowCutHz, double highCutHz, double wetDb, double dryDb, NA_DelayParams* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_DelayParamsFromMs: bad argument");
+		na::DelayParams d;
+		if (const char* why = na::DelayParamsFromMs(sampleRate, delayMs, feedback, lowCutHz, highCutHz, wetDb, dryDb, d))
+			throw std::runtime_error(std::string("NA_DelayParamsFromMs: ") + why);
+		DelayParamsOut(d, out);
+	});
+}
+
+int NA_BatchEnableDelayStage(NA_Batch* batch, int maxDelaySamples)
+{
+	return BatchCall(batch, "NA_BatchEnableDelayStage", [&](na::GpuBatch& b) { b.EnableDelayStage(maxDelaySamples); });
+}
+
+int NA_BatchGetDelayInfo(NA_Batch* batch, NA_DelayInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetDelayInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetDelayInfo: bad argument");
+		const na::DelayStageInfo i = b.GetDelayInfo();
+		info->maxDelaySamples = i.maxDelaySamples;
+		info->ringSamples = i.ringSamples;
+		info->pieceSamples = i.pieceSamples;
+		info->numDelays = i.numDelays;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamDelay(NA_Batch* batch, int stream, const NA_DelayParams* params, int fadeSamples)
+{
+	return BatchCall(batch, "NA_BatchSetStreamDelay", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamDelay(stream, nullptr, fadeSamples);
+			return;
+		}
+		na::DelayParams d;
+		DelayParamsIn(*params, d);
+		b.SetStreamDelay(stream, &d, fadeSamples);
+	});
+}
+
+int NA_BatchGetStreamDelay(NA_Batch* batch, int stream, NA_DelayParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamDelay", -1, [&](na::GpuBatch& b) {
+		na::DelayParams d;
+		const int has = b.GetStreamDelay(stream, d) ? 1 : 0;
+		if (has && out) DelayParamsOut(d, out);
+		return has;
+	});
+}
+
+int NA_BatchStreamDelayFadeRemaining(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchStreamDelayFadeRemaining", -1, [&](na::GpuBatch& b) { return b.StreamDelayFadeRemaining(stream); });
+}
+
+#ifndef NA_RELEASE
+int NA_DebugRunDelayStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunDelayStage: null batch");
+		batch->batch->DebugRunDelayStage(hostRows, stride, n);
+	});
+}
+long long NA_DebugDelayLaunches(void) { return (long long)na::DelayStageLaunches(); }
+#endif
+
 // ---- the gate stage (gpu_batch.h EnableGateStage / SetStreamGate) ----
 namespace
 {

@@ -19,6 +19,7 @@
 
 #include "cabinet_stage.h"
 #include "reverb_stage.h"
+#include "delay_stage.h"
 #include "device_resources.h"
 #include "eq_stage.h"
 #include "gate_stage.h"
@@ -78,6 +79,12 @@ namespace na
 	struct ReverbStageInfo
 	{
 		int maxTaps = 0, partitionSamples = 0, slots = 0, pieceSamples = 0, numIRs = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct DelayStageInfo
+	{
+		int maxDelaySamples = 0, ringSamples = 0, pieceSamples = 0, numDelays = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -206,6 +213,21 @@ namespace na
 		int StreamReverbFadeRemaining(int stream) const;
 		// test hook (NA_DebugRunReverbStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
 		void DebugRunReverbStage(float* hostRows, long stride, size_t n);
+
+		// The delay stage (delay_stage.h): a per-stream echo -- a feedback delay line of up to kDelayMaxSamples samples with a
+		// one-pole low-pass and high-pass in the loop and a wet / dry mix -- behind the cabinet stage and in front of the reverb stage.
+		// EnableDelayStage is the set-up side: a ring and a filter state per row (CreateStreams grows them) and the tables.  SetStreamDelay
+		// is host arithmetic on those tables; while an entry exists -- a stream with a delay, or a fade towards none -- every processing
+		// call runs on the ordered path and enqueues ONE table upload and ONE launch per piece of kDelayPieceSamples samples.  Without an
+		// entry the batch launches exactly what it launches without the stage.
+		void EnableDelayStage(int maxDelaySamples);
+		bool HasDelayStage() const { return stages[kDelayStage] != nullptr; }
+		DelayStageInfo GetDelayInfo() const;
+		void SetStreamDelay(int stream, const DelayParams* params, int fadeSamples); // nullptr: no delay
+		bool GetStreamDelay(int stream, DelayParams& out) const;                     // the target; false: none
+		int StreamDelayFadeRemaining(int stream) const;
+		// test hook (NA_DebugRunDelayStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
+		void DebugRunDelayStage(float* hostRows, long stride, size_t n);
 
 		// The gate stage (gate_stage.h): a per-stream noise gate that listens to the stream's input row and scales the row
 		// the models produced for it -- the detector launch in front of everything of the call, the apply launch first of the stages, in
@@ -437,9 +459,9 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.17).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.18).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
@@ -451,7 +473,7 @@ namespace na
 			virtual void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) = 0;
 		};
 		template <class Book, class Entry> struct StageOf;
-		struct GateStage; struct EqStage; struct CabinetStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
+		struct GateStage; struct EqStage; struct CabinetStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -225,7 +225,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the eight stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the nine stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -292,6 +292,22 @@ namespace na
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + two launches per piece + the host mirror's advance
 	};
 	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece
+
+	// the delay stage (delay_stage.h, delay_stage.cpp): the rows' delay lines (rings) and filter states
+	struct GpuBatch::DelayStage : StageOf<DelayBook, DelayEntry>
+	{
+		static constexpr StageId kId = kDelayStage;
+		static constexpr const char* kNotEnabled = "delay stage not enabled (NA_BatchEnableDelayStage)";
+		float* rings = nullptr;           // [ringRows][book.RingSamples()]
+		float* state = nullptr;           // [stateRows] DelayFilter
+		int ringRows = 0, stateRows = 0;
+		DelayStage() : StageOf("delay stage") {}
+		~DelayStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // no delay at once, its history dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + one launch per piece + the host mirror's advance
+	};
+	hipError_t LaunchDelayStage(const DelayLaunch& L, hipStream_t stream); // (delay_stage_kernels.hip) the launch of one piece
 
 	// the reverb stage (reverb_stage.h, reverb_stage.cpp): the rows' sample rings, rings of input spectra and tail blocks,
 	// the transform's twiddles and the IRs' head taps and partition spectra (owned through the book's ids)

@@ -44,6 +44,11 @@
 //       first feeds ceil(K / 128) buffers, so that every delay line is full before anything is timed.  Times every buffer period like
 //       --tuner; the same device span as --gate; reports the spectrum bytes the tail launch reads per buffer (input spectra: every
 //       stream's own; IR spectra: the same amount, of which M IRs' worth is distinct).
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --delay N [--delay-samples D=18000]
+//       the plain run below with the delay stage enabled (maxDelaySamples = D) and an echo on the first N streams: D samples (375 ms at
+//       48 kHz by default), feedback 0.45, both filters in the loop, wet -6 dB, dry 0 dB (NA_DelayParamsFromMs) -- (N = 0: enabled, no
+//       delay set: must cost nothing).  With N > 0 the run first feeds ceil(D / frames) buffers, so that every line is full.  Times every
+//       buffer period like --tuner; the same device span as --gate.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -593,14 +598,14 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]] [--mix N [--mix-dry]] [--reverb N [--reverb-taps K] [--reverb-irs M]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]] [--mix N [--mix-dry]] [--reverb N [--reverb-taps K] [--reverb-irs M]] [--delay N [--delay-samples D]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
 	const char* mixFile = nullptr;
 	bool rcclFanIn = false;
 	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3, meter = -1, meterWindow = 1024, tuner = -1, tunerHop = 0;
-	int mixGroups = -1, reverb = -1, reverbTaps = 48000, reverbIRs = 1;
+	int mixGroups = -1, reverb = -1, reverbTaps = 48000, reverbIRs = 1, delay = -1, delaySamples = 18000;
 	bool churnLegacy = false, tunerStagger = false, mixDry = false;
 	for (int i = 1; i < argc; i++)
 	{
@@ -625,6 +630,8 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--reverb") && i + 1 < argc) reverb = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--reverb-taps") && i + 1 < argc) reverbTaps = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--reverb-irs") && i + 1 < argc) reverbIRs = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--delay") && i + 1 < argc) delay = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--delay-samples") && i + 1 < argc) delaySamples = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) gate = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--eq") && i + 1 < argc) eq = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--meter") && i + 1 < argc) meter = std::atoi(argv[++i]);
@@ -787,10 +794,24 @@ int main(int argc, char** argv)
 		reverbInputSpectrumBytes = (long long)reverb * tailPartitions * 2048 * ((frames + info.partitionSamples - 1) / info.partitionSamples);
 		reverbDistinctIRBytes = reverb > 0 ? (long long)reverbIRs * tailPartitions * 2048 : 0;
 	}
+	long long delayBytes = 0;
+	if (delay >= 0)
+	{
+		CHECK(delaySamples >= 1);
+		CHECK(NA_BatchEnableDelayStage(batch, delaySamples) == 0);
+		delay = std::min(delay, streams);
+		NA_DelayParams echo;
+		CHECK(NA_DelayParamsFromMs(48000, 375.0, 0.45, 120.0, 4500.0, -6.0, 0.0, &echo) == 0);
+		echo.delaySamples = delaySamples;
+		for (int s = 0; s < delay; s++) CHECK(NA_BatchSetStreamDelay(batch, s, &echo, 0) == 0);
+		NA_DelayInfo info;
+		CHECK(NA_BatchGetDelayInfo(batch, &info) == 0);
+		delayBytes = info.deviceBytes;
+	}
 	unsigned long long meterWindows = 0; // (--meter: `windows` of the last reading of stream 0 in the pipelined loop)
 	unsigned long long tunerEvaluations = 0; // (--tuner: `evaluations` of the last reading of stream 0 in the pipelined loop)
 	std::vector<double> periods;             // (--tuner, --mix N: every buffer period of the pipelined loop)
-	const bool marks = gate >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0 || reverb >= 0; // (the plain run stays what it was)
+	const bool marks = gate >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -798,6 +819,10 @@ int main(int argc, char** argv)
 	// (--reverb N > 0: the delay lines fill first -- the tail of a block sums over as many partitions as the history has)
 	if (reverb > 0)
 		for (long long fed = 0; fed < reverbTaps; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
+
+	// (--delay N > 0: the lines fill first -- from then on every read of a ring is a read of a sample the stage wrote)
+	if (delay > 0)
+		for (long long fed = 0; fed < delaySamples; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 
 	// blocking call, one buffer at a time
 	std::vector<double> lat;
@@ -867,7 +892,7 @@ int main(int argc, char** argv)
 			CHECK(have >= 0);
 			if (have) tunerEvaluations = reading.evaluations;
 		}
-		if (tuner >= 0 || mixGroups >= 0 || reverb >= 0) periods.push_back(Now());
+		if (tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0) periods.push_back(Now());
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
@@ -924,9 +949,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"reverb\": %d, \"reverb_taps\": %d, \"reverb_irs\": %d, \"reverb_device_bytes\": %lld, \"reverb_load_irs_ms\": %.1f, \"reverb_input_spectrum_bytes_per_buffer\": %lld, \"reverb_distinct_ir_spectrum_bytes\": %lld, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"reverb\": %d, \"reverb_taps\": %d, \"reverb_irs\": %d, \"reverb_device_bytes\": %lld, \"reverb_load_irs_ms\": %.1f, \"reverb_input_spectrum_bytes_per_buffer\": %lld, \"reverb_distinct_ir_spectrum_bytes\": %lld, \"delay\": %d, \"delay_samples\": %d, \"delay_device_bytes\": %lld,\"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, reverb, reverb >= 0 ? reverbTaps : 0, reverb > 0 ? reverbIRs : 0, reverbBytes, reverbLoadMs, reverbInputSpectrumBytes, reverbDistinctIRBytes, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, reverb, reverb >= 0 ? reverbTaps : 0, reverb > 0 ? reverbIRs : 0, reverbBytes, reverbLoadMs, reverbInputSpectrumBytes, reverbDistinctIRBytes, delay, delay >= 0 ? delaySamples : 0, delayBytes, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
