@@ -41,6 +41,11 @@ namespace na
 #ifndef NA_SPK_DELAY
 #define NA_SPK_DELAY 0
 #endif
+#ifndef NA_SPK_LEAN
+// the parts of Cfg::LEAN: 1 = per-wave ring loads / stores, 2 = live operands only, 4 = one MFMA per straddling tap.  Part 1 is NOT in the
+// default: its extra wave-3 bodies take the 128-frame full-size kernels from 120 VGPRs to 128 with 16 spilled (profiles/r08_lean_ab.txt)
+#define NA_SPK_LEAN 6
+#endif
 #ifndef NA_SPK_AUX2
 #define NA_SPK_AUX2 0 // tuning builds: 1 = read the aux operand again for the 1x1 instead of keeping it in registers across the layer
 #endif
@@ -81,6 +86,7 @@ namespace na
 #define NA_A1_NT_DIL 128
 #endif
 			static constexpr int NT_DIL = NA_A1_NT_DIL; // Cfg::NT: layers from this dilation on move their ring traffic non-temporally
+			static constexpr bool LEAN = false;   // Cfg::LEAN: every wave issues only the memory operations and MFMAs its own frames need
 		};
 #ifndef NA_SPK_SKEW
 #define NA_SPK_SKEW 0
@@ -97,6 +103,7 @@ namespace na
 			// barrier released after ~4400).
 			static constexpr int SKEW = NA_SPK_SKEW;
 			static constexpr bool FOLD = true; // (not padded, not packed: every layer takes the folded operands)
+			static constexpr bool LEAN = true;
 			static constexpr int NA = 2;
 			static constexpr int CH[2] = { 16, 8 };
 			static constexpr int NLA[2] = { 10, 10 };
@@ -142,6 +149,7 @@ namespace na
 			static constexpr int SKEW = 0;
 			static constexpr bool COMPACT = false;
 			static constexpr int NT_DIL = 100;    // (d = 101 and 239)
+			static constexpr bool LEAN = false;
 		};
 		struct ArchA2Full : ArchA2Base { static constexpr int CH[2] = { 8, 0 }; static constexpr int T = 2; };
 		struct ArchA2Lite : ArchA2Base { static constexpr int CH[2] = { 4, 0 }; static constexpr int T = 4; };
@@ -266,6 +274,14 @@ namespace na
 			static constexpr int SKEW = (SPB == 2 && !PK_ && T == 2 && A_::SKEW > 0) ? A_::SKEW : 0;
 			static constexpr int NWB = SKEW > 0 ? SPB : 1;          // weight buffer pairs
 			static constexpr int STG_THREADS = NTHREADS / NWB;      // threads that stage one pair
+			// The one-shot launches of A1 Standard: no wave issues an operation only to keep the instruction counts of a stream's waves alike
+			// (the chain sits on the socket's power cap, DESIGN.md 2.2h: issued work is time).  A wave loads ring history only for taps of its
+			// own that reach in front of the block and stores only sets of which a later block reads something (the counted waits that close a
+			// stage take this wave's own counts: LayerSig, EndFirst); a folded stage moves only the operands it reads into LDS (LiveOps); a
+			// straddling tap of a folded layer is one MFMA (ConvTapFold).  Same values in the rings, same results.  NA_SPK_LEAN picks the
+			// parts; the first (LEAN_MEM) is not in the default build.
+			static constexpr bool LEAN = A_::LEAN && !PK_ && !COH_ && SKEW == 0 && T == 2;
+			static constexpr bool LEAN_MEM = LEAN && (NA_SPK_LEAN & 1), LEAN_STAGE = LEAN && (NA_SPK_LEAN & 2), LEAN_MFMA = LEAN && (NA_SPK_LEAN & 4);
 			// LDS map (bytes)
 			static constexpr bool AUX16 = !PK_ && SKEW == 0;                    // aux entries as whole quads (one LDS read, no unpacking)
 			static constexpr int AUX_OFF = 0;                                   // [SPB][FRAMES] quads; PK: [SPB][4][FRAMES] x 8 bytes; skewed: [SPB][FRAMES] x 8
@@ -323,7 +339,18 @@ namespace na
 			return first;
 		}
 
-		// everything about layer L that depends on the wave: classes of its shifted taps and of the next layer's prefetched ones
+		// Does a later block read anything of what wave w holds of set i of ring RG's writer?  (the last frame of the set lies in the kept
+		// range: the last RingKeep frames of the block)
+		template <class C, int RG>
+		constexpr bool StoreMine(int w, int i)
+		{
+			typedef typename C::TB TB;
+			constexpr int P = Geo<TB::RingG(RG), C::T>::P, KEEP = TB::RingKeep(RG);
+			return C::FW * w + 16 * P * (i + 1) - 1 >= C::NF - KEEP;
+		}
+
+		// everything about layer L that depends on the wave: classes of its shifted taps and of the next layer's prefetched ones (Cfg::LEAN:
+		// and which of its sets it stores to the next layer's ring -- a body issues exactly what its waves need, so its counts are constants)
 		template <class C, int L>
 		struct LayerSig
 		{
@@ -340,6 +367,8 @@ namespace na
 					for (int i = 0; i < S; i++) s = s * 3 + (unsigned)WaveTapClass<C>(w, P, i, d * (K - 1 - k), SmallRing<C, L>());
 				for (int k = 0; k < Kn - 1 && k < C::HPF; k++)
 					for (int i = 0; i < S; i++) s = s * 3 + (unsigned)WaveTapClass<C>(w, P, i, dn * (Kn - 1 - k), SmallRing<C, LN>());
+				if constexpr (C::LEAN_MEM && NEXT)
+					for (int i = 0; i < S; i++) s = s * 2 + (StoreMine<C, LN>(w, i) ? 1u : 0u);
 				return s;
 			}
 			static constexpr int Rep(int w) { int r = w; for (int v = w - 1; v >= 0; v--) if (Of(v) == Of(w)) r = v; return r; }
@@ -489,14 +518,24 @@ namespace na
 		// prefetched taps of layer L: k < min(K - 1, HPF)
 		template <class C, int L>
 		constexpr int PrefetchTaps() { return (C::TB::KS(L) - 1) < C::HPF ? (C::TB::KS(L) - 1) : C::HPF; }
+
+		// does wave w issue the history load of layer L's prefetched tap k for set i?  Every wave whenever any wave needs it -- or
+		// (Cfg::LEAN) only a wave whose own frames reach in front of the block
 		template <class C, int L>
-		constexpr int HistLoadsOf()
+		constexpr bool HistIssuedBy(int w, int k, int i)
 		{
 			typedef typename C::TB TB;
-			constexpr int GP = TB::GPof(TB::ArrOf(L)), S = Geo<GP, C::T>::S;
+			constexpr int GP = TB::GPof(TB::ArrOf(L)), P = Geo<GP, C::T>::P;
+			if (!HistNeededAt<C, GP>(ShiftOf<C, L>(k), i, SmallRing<C, L>())) return false;
+			return !C::LEAN_MEM || WaveTapClass<C>(w, P, i, ShiftOf<C, L>(k), SmallRing<C, L>()) != TAP_LDS;
+		}
+		template <class C, int L>
+		constexpr int HistLoadsOfWave(int w)
+		{
+			constexpr int S = Geo<C::TB::GPof(C::TB::ArrOf(L)), C::T>::S;
 			int n = 0;
 			for (int k = 0; k < PrefetchTaps<C, L>(); k++)
-				for (int i = 0; i < S; i++) n += HistNeededAt<C, GP>(ShiftOf<C, L>(k), i, SmallRing<C, L>()) ? 1 : 0;
+				for (int i = 0; i < S; i++) n += HistIssuedBy<C, L>(w, k, i) ? 1 : 0;
 			return n;
 		}
 
@@ -508,7 +547,7 @@ namespace na
 			for (int k = 0; k < PrefetchTaps<C, L>(); k++)
 #pragma unroll
 				for (int i = 0; i < S; i++)
-					if (HistNeededAt<C, GP>(ShiftOf<C, L>(k), i, SmallRing<C, L>())) st.hist[k][i] = HistLoadAt<C, L, WR>(cx, laneRing, fl, ShiftOf<C, L>(k), i);
+					if (HistIssuedBy<C, L>(WR, k, i)) st.hist[k][i] = HistLoadAt<C, L, WR>(cx, laneRing, fl, ShiftOf<C, L>(k), i);
 		}
 
 		// A stage's output -> the LDS image (in-block taps of the reader, if it has any) and ring RG (history for LATER blocks: only the
@@ -521,16 +560,19 @@ namespace na
 			constexpr int P = Geo<TB::RingG(RG), C::T>::P, KEEP = TB::RingKeep(RG);
 			return (C::NF - C::FW) + 16 * P * (i + 1) - 1 >= C::NF - KEEP; // the last wave's last frame of set i
 		}
+		// ring stores wave w issues for ring RG (Cfg::LEAN: only the sets it keeps something of)
 		template <class C, int RG>
-		constexpr int StoresOf()
+		constexpr int StoresOfWave(int w)
 		{
 			constexpr int S = Geo<C::TB::RingG(RG), C::T>::S;
 			int n = 0;
-			for (int i = 0; i < S; i++) n += StoreNeeded<C, RG>(i) ? 1 : 0;
+			for (int i = 0; i < S; i++) n += (StoreNeeded<C, RG>(i) && (!C::LEAN_MEM || StoreMine<C, RG>(w, i))) ? 1 : 0;
 			return n;
 		}
 
-		template <class C, int RG, int GP, int MINSHIFT>
+		// WR: a wave whose kept sets are those of the calling wave (LayerSig); -1: not known at compile time (the stages all waves run in
+		// one body: a wave-uniform branch)
+		template <class C, int RG, int GP, int MINSHIFT, int WR = -1>
 		__device__ __forceinline__ void Publish(const Ctx& cx, const Lanes<C, GP>& ln, u32x4 v, int i, int imgWrite)
 		{
 			typedef typename C::TB TB;
@@ -539,6 +581,10 @@ namespace na
 			if (!(NA_ABL & 64) && MINSHIFT < C::NF) // the reader takes in-block frames of other lanes
 				LdsWrite16(ln.img + (unsigned)(imgWrite * C::IMG_ONE + 16 * P * i * 16), v);
 			if ((NA_ABL & 4) || !StoreNeeded<C, RG>(i)) return;
+			if constexpr (C::LEAN_MEM)
+			{
+				if (WR >= 0 ? !StoreMine<C, RG>(WR, i) : (C::FW * cx.wave + 16 * P * (i + 1) - 1 < C::NF - KEEP)) return;
+			}
 			const int pos0 = __builtin_amdgcn_readlane(cx.myPos, RG);
 			int base;
 			if constexpr (TB::CompactRing(RG))
@@ -614,9 +660,33 @@ namespace na
 			static constexpr int SRC = TB::AOff(SN) + TB::ChunkBegin(SN, CN) * 64;
 			static constexpr int BUF = TB::ChunkIndex(SN, CN) & 1;
 			static constexpr int NCOPY = (QUADS + C::STG_THREADS - 1) / C::STG_THREADS;
+			// Cfg::LEAN, folded layer stage: only the operands the layer reads.  The fold (WN_FLAG_FOLD) moved the lo of tap 1 into operand
+			// 1, aux into 5 and the 1x1 bias into 8, so 3, 6 and 9 are dead, and the very last layer has no 1x1 (7, 8).  Every live operand
+			// lands in its usual slot (WOp and the weight image do not change); staging wave j moves live operand j
+			static constexpr int LSN = TB::LayerOfStage(SN) < 0 ? 0 : TB::LayerOfStage(SN);
+			static constexpr bool LIVEONLY = C::LEAN_STAGE && TB::LayerOfStage(SN) >= 0 && TB::Fold(LSN) && !TB::Chunked(SN);
+			static constexpr int NLIVE = (TB::LastOfArr(LSN) && TB::ArrOf(LSN) == TB::NA - 1) ? 5 : 7;
+			static constexpr int STG_WAVES = C::STG_THREADS / 64;
+			static constexpr int NCOPY_LIVE = (NLIVE + STG_WAVES - 1) / STG_WAVES;
 			static __device__ __forceinline__ void Begin(const Ctx& cx)
 			{
 				if (NA_ABL & 16) return;
+				if constexpr (LIVEONLY)
+				{
+					static_assert(TB::StageOps(SN) == 10 && CN == 0, "operands of a folded K = 3 layer");
+#pragma unroll
+					for (int c = 0; c < NCOPY_LIVE; c++)
+					{
+						const int j = c * STG_WAVES + cx.stgWave; // (wave-uniform)
+						const bool mine = j < NLIVE;
+						// live operand j: 0, 1, 2, 4, 5, 7, 8 = j + (j > 2) + (j > 4)
+						const int op = j + (j > 2 ? 1 : 0) + (j > 4 ? 1 : 0);
+						const unsigned dst = mine ? cx.wbuf + (unsigned)(BUF * C::WBUF_ONE) + (unsigned)op * 1024u : (unsigned)C::DUMP_OFF;
+						__builtin_amdgcn_raw_ptr_buffer_load_lds(cx.wrsrc, (__attribute__((address_space(3))) void*)(LdsPtr)(size_t)dst, 16,
+							mine ? (SRC + op * 64 + cx.lane) * 16 : OOB, 0, 0, 0);
+					}
+					return;
+				}
 #pragma unroll
 				for (int c = 0; c < NCOPY; c++)
 				{
@@ -711,6 +781,16 @@ namespace na
 			constexpr int P = Geo<GP, C::T>::P;
 			const int cls = WaveTapClass<C>(WR, P, i, shift, SmallRing<C, RG>());
 			th = u32x2{ 0, 0 };
+			if (C::LEAN_MFMA && cls == TAP_BOTH)
+			{
+				// one hi MFMA on the OR-ed columns instead of two: in every lane one of the two columns is all zeros, and adding the products
+				// of an all-zero column is exact -- at most the sign of a zero sum differs, which no later operation can tell (it is added
+				// to, or goes through tanh and the split).  So the interpreter keeps its two MFMAs and the bits still agree.
+				const u32x4 b = TapLds<C, GP>(cx, ln, imgRead, shift, i, cls);
+				acc = Mfma(ah, u32x4{ hist.x | b.x, hist.y | b.y, hist.z | b.z, hist.w | b.w }, acc);
+				th = u32x2{ hist.x | b.x, hist.y | b.y };
+				return acc;
+			}
 			if (cls != TAP_LDS)
 			{
 				acc = Mfma(ah, hist, acc);
@@ -741,7 +821,9 @@ namespace na
 			constexpr int NEXTMINSHIFT = SG::NEXT ? TB::Dil(LN) : (1 << 20); // the reader's smallest tap shift: is the LDS image needed?
 			constexpr bool OWN = 2 * (K - 1) >= CB && 2 * (K - 1) < CE;  // the unshifted tap's operands are in this chunk (every shifted tap is consumed by then)
 			constexpr bool TAIL = 2 * K >= CB && 2 * K < CE;             // aux / 1x1 operands are in this chunk
-			constexpr int LATER = ((OWN && SG::NEXT) ? HistLoadsOf<C, LN>() : 0) + ((TAIL && SG::NEXT && !LASTLAYER) ? StoresOf<C, LN>() : 0);
+			// (what THIS body issues: with Cfg::LEAN that differs from wave class to wave class, and a count that is too high would let the
+			// wave through the barrier before its weight DMA has landed)
+			constexpr int LATER = ((OWN && SG::NEXT) ? HistLoadsOfWave<C, LN>(WR) : 0) + ((TAIL && SG::NEXT && !LASTLAYER) ? StoresOfWave<C, LN>(WR) : 0);
 			typedef typename NextChunk<C, s, c>::St NextStager;
 			if constexpr (c == 0)
 			{
@@ -848,7 +930,7 @@ namespace na
 						if constexpr (SG::NEXT)
 						{
 							st.xs[i] = Split<C>(y, cx);
-							Publish<C, LN, GP, NEXTMINSHIFT>(cx, ln, st.xs[i], i, imgWrite);
+							Publish<C, LN, GP, NEXTMINSHIFT, WR>(cx, ln, st.xs[i], i, imgWrite);
 						}
 					}
 				}
@@ -915,6 +997,26 @@ namespace na
 			}
 		}
 
+		// The counted wait that closes the stage in front of layer L (rechannel / link: one body for all waves) on the staging St: the
+		// VMEM operations a wave issued after St::Begin are its stores to ring L and the prefetch of layer L's history.  Without Cfg::LEAN
+		// that is one constant; with it the wave's own count, picked by a wave-uniform branch between the wait immediates.
+		template <class C, class St, int L, int W>
+		__device__ __forceinline__ void EndFirst(const Ctx& cx)
+		{
+			constexpr int N = StoresOfWave<C, L>(W) + HistLoadsOfWave<C, L>(W);
+			constexpr bool same = [] {
+				bool r = true;
+				for (int w = W + 1; w < C::WPS; w++) r = r && StoresOfWave<C, L>(w) + HistLoadsOfWave<C, L>(w) == N;
+				return r;
+			}();
+			if constexpr (same) St::template End<N>();
+			else
+			{
+				if (cx.wave == W) St::template End<N>();
+				else EndFirst<C, St, L, W + 1>(cx);
+			}
+		}
+
 		// array 0 rechannel: x = w_re * cond (WaveNet.h:637 with InputSize == 1) -- the aux operand against (w_re, 0)
 		template <class C>
 		__device__ __forceinline__ void RechStage(const Ctx& cx, const Lanes<C, C::TB::GPof(0)>& ln, State& st)
@@ -937,7 +1039,7 @@ namespace na
 			}
 			FirstHistDispatch<C, 0, 0>(cx, ln.ring, ln.fl, st);
 			SPK_STAMP(0, 1); SPK_STAMP(0, 2); SPK_STAMP(0, 3);
-			Stager<C, 1, 0>::template End<StoresOf<C, 0>() + HistLoadsOf<C, 0>()>();
+			EndFirst<C, Stager<C, 1, 0>, 0, 0>(cx);
 			SPK_STAMP(0, 4);
 			BlockBarrier<C::NTHREADS / 64>();
 			SPK_STAMP(0, 5);
@@ -990,7 +1092,7 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 			}
 			FirstHistDispatch<C, LN, 0>(cx, ln.ring, ln.fl, st);
 			SPK_STAMP(s, 1); SPK_STAMP(s, 2); SPK_STAMP(s, 3);
-			Stager<C, s + 1, 0>::template End<StoresOf<C, LN>() + HistLoadsOf<C, LN>()>();
+			EndFirst<C, Stager<C, s + 1, 0>, LN, 0>(cx);
 			SPK_STAMP(s, 4);
 			BlockBarrier<C::NTHREADS / 64>();
 			SPK_STAMP(s, 5);
