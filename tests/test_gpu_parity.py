@@ -133,7 +133,8 @@ def test_stdmath_wavenet_matches_stdmath_oracle(na, name):
     x = O.signal_sine(2048)
     y = np.concatenate([m.Process(x[i:i + 128]) for i in range(0, x.size, 128)])
     yo = O.oracle_from_file(name, math_mode=O.MATH_STD).process(x)
-    assert O.rms(y - yo) < 5e-6, (name, O.rms(y - yo))
+    print("%s: StdMath HIP path - StdMath oracle %.3g RMS" % (name, O.rms(y - yo)))
+    assert O.rms(y - yo) < TOL_RMS, (name, O.rms(y - yo))  # (measured: Standard 2.6e-7, Nano 2.1e-7; tests/test_gpu_stdmath.py has the rest)
     yf = O.oracle_from_file(name).process(x)
     assert O.rms(yo - yf) > 1e-5  # the two policies differ measurably (6.6e-4 on Standard / sine)
 
