@@ -218,6 +218,80 @@ namespace na
 		long long Bytes() const { return (long long)kTables * capacity * (long long)sizeof(Entry); }
 	};
 
+	// The result blocks of a stage that reports to the host (meter, tuner) -- the one device -> host path of the stages.  A block per table
+	// of the stage's ring: a launch of the call that took table i writes records to dev[i], one copy brings them to the pinned host[i],
+	// the table's `done` event covers the copy, and the host folds what has arrived into the book without ever waiting for it.
+	template <class Record>
+	struct GpuBatch::StageResults
+	{
+		static constexpr int kTables = GpuBatch::kPipelineSlots + 1;
+		Record* host[kTables] = {}; // pinned: the records of the call that last used table i ...
+		Record* dev[kTables] = {};  // ... and where its launch wrote them
+		int pending[kTables] = {};  // records of host[i] that have not been folded yet (0: none)
+		int capacity = 0;           // records per block
+		~StageResults() { Free(); }
+		// set-up side: blocks of at least `want` records.  Records that have not arrived are given up with their blocks: whatever writes
+		// them is over first, and the entries they belong to report again with their next window
+		void Ensure(GpuBatch& batch, int want)
+		{
+			if (want <= capacity) return;
+			if (capacity > 0) batch.Quiesce();
+			Free();
+			for (int i = 0; i < kTables; i++)
+			{
+				CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&host[i]), (size_t)want * sizeof(Record), hipHostMallocDefault), "hipHostMalloc");
+				CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&dev[i]), (size_t)want * sizeof(Record)), "hipMalloc");
+			}
+			capacity = want;
+		}
+		// the first `count` records of dev[i] come to host[i], behind the launch that wrote them and in front of table i's Commit
+		void Download(int i, int count, hipStream_t stream, const char* what)
+		{
+			CheckHip(hipMemcpyAsync(host[i], dev[i], (size_t)count * sizeof(Record), hipMemcpyDeviceToHost, stream), what);
+			pending[i] = count;
+		}
+		// the pending records of block i go through the stage's `fold(i, count)`; Take of table i folds before the block is written again
+		template <class Fold>
+		void FoldBlock(int i, Fold&& fold)
+		{
+			if (pending[i]) fold(i, pending[i]);
+			pending[i] = 0;
+		}
+		// Event queries only: every block whose copy is over is folded.  The blocks complete in the order of their calls (every call's
+		// launches come behind the call before), so the walk starts at the oldest and ends at the first that is not over.
+		template <class Entry, class Fold>
+		void Poll(const StageTables<Entry>& tables, const char* what, Fold&& fold)
+		{
+			for (int k = 0; k < kTables; k++)
+			{
+				const int i = (tables.next + k) % kTables;
+				if (pending[i] == 0) continue;
+				const hipError_t q = hipEventQuery(tables.done[i]);
+				if (q == hipErrorNotReady)
+				{
+					(void)hipGetLastError(); // (not an error of anything that follows)
+					return;
+				}
+				CheckHip(q, what);
+				FoldBlock(i, fold);
+			}
+		}
+		long long Bytes() const { return (long long)kTables * capacity * (long long)sizeof(Record); }
+
+	private:
+		void Free()
+		{
+			capacity = 0;
+			for (int i = 0; i < kTables; i++)
+			{
+				pending[i] = 0;
+				if (host[i]) (void)CountedHipHostFree(host[i]);
+				if (dev[i]) (void)CountedHipFree(dev[i]);
+				host[i] = dev[i] = nullptr;
+			}
+		}
+	};
+
 	// the argument checks the stages' calls share: the texts are part of the interface (the tests match on them)
 	inline std::string StreamId(int s) { return "stream " + std::to_string(s); }
 	inline void RequireFadeRange(int samples, const char* who, const char* argument)
@@ -366,20 +440,15 @@ namespace na
 	hipError_t LaunchMixStash(const MixStashLaunch& L, hipStream_t stream); // (mix_stage_kernels.hip)
 	hipError_t LaunchMixStage(const MixLaunch& L, hipStream_t stream);
 
-	// the meter stage (meter_stage.h, meter_stage.cpp): the rows' states on the device and -- the one device -> host path
-	// of the stages -- a result block per table of the ring: the OUT launch writes a record per entry, one copy brings them to the pinned
-	// twin, the table's `done` event covers the copy, and the host folds what has arrived into the book without ever waiting for it
+	// the meter stage (meter_stage.h, meter_stage.cpp): the rows' states on the device and the result blocks (StageResults
+	// above) the OUT launch writes a record per entry to
 	struct GpuBatch::MeterStage : StageOf<MeterBook, MeterEntry>
 	{
 		static constexpr StageId kId = kMeterStage;
 		static constexpr const char* kNotEnabled = "meter stage not enabled (NA_BatchEnableMeterStage)";
-		static constexpr int kTables = StageTables<MeterEntry>::kTables;
 		float* state = nullptr;             // [rowCapacity] MeterState
 		int rowCapacity = 0;
-		MeterRecord* results[kTables] = {};    // pinned: the records of the call that last used table i ...
-		MeterRecord* devResults[kTables] = {}; // ... and where its OUT launch wrote them
-		int pending[kTables] = {};          // records of results[i] that have not been folded yet (0: none)
-		int resultCapacity = 0;             // records per block
+		StageResults<MeterRecord> results;
 		const MeterEntry* dev = nullptr;    // the device table the IN launch of this call read ...
 		int count = 0;                      // ... and its entries; 0: the call has none
 		int slot = 0;                       // ... and its place in the ring
@@ -388,8 +457,8 @@ namespace na
 		~MeterStage() override;
 		void EnsureRows(GpuBatch& batch, int rows) override;
 		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // its meter goes at once
-		void Fold(int i);            // the records of results[i] go into the book (stale ones are dropped there)
-		void Poll();                 // event queries only: every block whose copy is over is folded, oldest first
+		void Fold(int i, int records); // the records of results.host[i] go into the book (stale ones are dropped there)
+		void Poll() { results.Poll(tables, "hipEventQuery (meter results)", [this](int i, int records) { Fold(i, records); }); }
 		void BeforeModels(GpuBatch& batch, hipStream_t launch, const float* dIn, size_t n, long inStride) override; // poll + table upload + the IN launch
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override;              // the OUT launch + the result copy + the host mirror's advance
 	};
@@ -403,20 +472,16 @@ namespace na
 	{
 		static constexpr StageId kId = kTunerStage;
 		static constexpr const char* kNotEnabled = "tuner stage not enabled (NA_BatchEnableTunerStage)";
-		static constexpr int kTables = StageTables<TunerEntry>::kTables;
 		float* state = nullptr;             // [rowCapacity] TunerState
 		float* rings = nullptr;             // [rowCapacity][kTunerRingSamples] int32
 		int rowCapacity = 0;
-		TunerRecord* results[kTables] = {};    // pinned: the records of the call that last used table i ...
-		TunerRecord* devResults[kTables] = {}; // ... and where its evaluate launch wrote them
-		int pending[kTables] = {};          // records of results[i] that have not been folded yet (0: none)
-		int resultCapacity = 0;             // records per block
+		StageResults<TunerRecord> results;  // the evaluate launch writes a record per evaluating entry
 		TunerStage() : StageOf("tuner stage") {}
 		~TunerStage() override;
 		void EnsureRows(GpuBatch& batch, int rows) override;
 		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // its tuner goes at once
-		void Fold(int i);            // the records of results[i] go into the book (stale ones are dropped there)
-		void Poll();                 // event queries only: every block whose copy is over is folded, oldest first
+		void Fold(int i, int records); // the records of results.host[i] go into the book (stale ones are dropped there)
+		void Poll() { results.Poll(tables, "hipEventQuery (tuner results)", [this](int i, int records) { Fold(i, records); }); }
 		void BeforeModels(GpuBatch& batch, hipStream_t launch, const float* dIn, size_t n, long inStride) override; // poll + table upload + append (+ evaluate + result copy) + the host mirror's advance
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override;              // nothing
 	};

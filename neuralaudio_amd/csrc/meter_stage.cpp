@@ -10,11 +10,6 @@ namespace na
 	GpuBatch::MeterStage::~MeterStage()
 	{
 		if (state) (void)CountedHipFree(state);
-		for (int i = 0; i < kTables; i++)
-		{
-			if (results[i]) (void)CountedHipHostFree(results[i]);
-			if (devResults[i]) (void)CountedHipFree(devResults[i]);
-		}
 	}
 
 	void GpuBatch::EnableMeterStage() { EnableStage<MeterStage>(); }
@@ -25,26 +20,7 @@ namespace na
 	{
 		book.Resize(rows);
 		const int want = std::max(rows, 16);
-		if (want > resultCapacity)
-		{
-			// (records that have not arrived are given up with their blocks: whatever writes them is over first, and the meters they belong
-			// to publish again with their next window)
-			if (resultCapacity > 0) batch.Quiesce();
-			for (int i = 0; i < kTables; i++)
-			{
-				pending[i] = 0;
-				if (results[i]) (void)CountedHipHostFree(results[i]);
-				if (devResults[i]) (void)CountedHipFree(devResults[i]);
-				results[i] = devResults[i] = nullptr;
-			}
-			resultCapacity = 0;
-			for (int i = 0; i < kTables; i++)
-			{
-				CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&results[i]), (size_t)want * sizeof(MeterRecord), hipHostMallocDefault), "hipHostMalloc");
-				CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&devResults[i]), (size_t)want * sizeof(MeterRecord)), "hipMalloc");
-			}
-			resultCapacity = want;
-		}
+		results.Ensure(batch, want); // (the meters whose records are given up publish again with their next window)
 		tables.Ensure(batch, want);
 		if (want > rowCapacity)
 		{
@@ -62,8 +38,7 @@ namespace na
 		const MeterStage& st = Require<MeterStage>("GetMeterInfo");
 		MeterStageInfo info;
 		info.numMeters = st.book.NumEntries();
-		info.deviceBytes = (long long)st.rowCapacity * (long long)sizeof(MeterState) + st.tables.Bytes() +
-			(long long)MeterStage::kTables * (long long)st.resultCapacity * (long long)sizeof(MeterRecord);
+		info.deviceBytes = (long long)st.rowCapacity * (long long)sizeof(MeterState) + st.tables.Bytes() + st.results.Bytes();
 		return info;
 	}
 
@@ -102,32 +77,12 @@ namespace na
 
 	// the pinned entry table of the same ring slot still says which row each record belongs to; a record of a meter that has been set
 	// again or taken away since carries another generation and is dropped (MeterBook::Accept)
-	void GpuBatch::MeterStage::Fold(int i)
+	void GpuBatch::MeterStage::Fold(int i, int records)
 	{
-		for (int k = 0; k < pending[i]; k++)
+		for (int k = 0; k < records; k++)
 		{
-			const MeterRecord& rec = results[i][k];
+			const MeterRecord& rec = results.host[i][k];
 			if (rec.row == tables.host[i][k].row) (void)book.Accept(rec);
-		}
-		pending[i] = 0;
-	}
-
-	// The blocks complete in the order of their calls (every call's launches come behind the call before), so the walk starts at the
-	// oldest and ends at the first that is not over.
-	void GpuBatch::MeterStage::Poll()
-	{
-		for (int k = 0; k < kTables; k++)
-		{
-			const int i = (tables.next + k) % kTables;
-			if (pending[i] == 0) continue;
-			const hipError_t q = hipEventQuery(tables.done[i]);
-			if (q == hipErrorNotReady)
-			{
-				(void)hipGetLastError(); // (not an error of anything that follows)
-				return;
-			}
-			CheckHip(q, "hipEventQuery (meter results)");
-			Fold(i);
 		}
 	}
 
@@ -139,10 +94,10 @@ namespace na
 	{
 		count = 0;
 		Poll();
-		tables.Require(book.Rows() <= rowCapacity && book.NumEntries() <= resultCapacity);
+		tables.Require(book.Rows() <= rowCapacity && book.NumEntries() <= results.capacity);
 		const auto table = tables.Take(batch, book.NumEntries());
 		slot = tables.next;
-		if (pending[slot]) Fold(slot);
+		results.FoldBlock(slot, [this](int i, int records) { Fold(i, records); });
 		const int entries = book.BuildTable(table.host);
 		if (entries == 0) return;
 		const GateStage* gate = static_cast<const GateStage*>(batch.stages[kGateStage].get());
@@ -170,10 +125,9 @@ namespace na
 		// (the gate's own Run is over: its book may have retired an entry with this call, its gain block still holds the call's gains)
 		const float* gains = (gate && anyGated) ? gate->gains : nullptr;
 		const long gainSamples = (gate && anyGated) ? (long)gate->gainSamples : 0;
-		CheckHip(LaunchMeterOut(MeterLaunch{ dev, count, dOut, outStride, (unsigned long long)n, gains, gainSamples, reinterpret_cast<MeterState*>(state), devResults[slot] }, launch),
+		CheckHip(LaunchMeterOut(MeterLaunch{ dev, count, dOut, outStride, (unsigned long long)n, gains, gainSamples, reinterpret_cast<MeterState*>(state), results.dev[slot] }, launch),
 			"MeterTapKernel (out)");
-		CheckHip(hipMemcpyAsync(results[slot], devResults[slot], (size_t)count * sizeof(MeterRecord), hipMemcpyDeviceToHost, launch), "hipMemcpyAsync (meter results)");
-		pending[slot] = count;
+		results.Download(slot, count, launch, "hipMemcpyAsync (meter results)");
 		tables.Commit(launch);
 		count = 0;
 		book.Advance(n);

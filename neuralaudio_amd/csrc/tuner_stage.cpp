@@ -11,11 +11,6 @@ namespace na
 	{
 		if (state) (void)CountedHipFree(state);
 		if (rings) (void)CountedHipFree(rings);
-		for (int i = 0; i < kTables; i++)
-		{
-			if (results[i]) (void)CountedHipHostFree(results[i]);
-			if (devResults[i]) (void)CountedHipFree(devResults[i]);
-		}
 	}
 
 	void GpuBatch::EnableTunerStage() { EnableStage<TunerStage>(); }
@@ -26,26 +21,7 @@ namespace na
 	{
 		book.Resize(rows);
 		const int want = std::max(rows, 16);
-		if (want > resultCapacity)
-		{
-			// (records that have not arrived are given up with their blocks: whatever writes them is over first, and the tuners they belong
-			// to evaluate again a hop later)
-			if (resultCapacity > 0) batch.Quiesce();
-			for (int i = 0; i < kTables; i++)
-			{
-				pending[i] = 0;
-				if (results[i]) (void)CountedHipHostFree(results[i]);
-				if (devResults[i]) (void)CountedHipFree(devResults[i]);
-				results[i] = devResults[i] = nullptr;
-			}
-			resultCapacity = 0;
-			for (int i = 0; i < kTables; i++)
-			{
-				CheckHip(CountedHipHostMalloc(reinterpret_cast<void**>(&results[i]), (size_t)want * sizeof(TunerRecord), hipHostMallocDefault), "hipHostMalloc");
-				CheckHip(CountedHipMalloc(reinterpret_cast<void**>(&devResults[i]), (size_t)want * sizeof(TunerRecord)), "hipMalloc");
-			}
-			resultCapacity = want;
-		}
+		results.Ensure(batch, want); // (the tuners whose records are given up evaluate again a hop later)
 		tables.Ensure(batch, want);
 		if (want > rowCapacity)
 		{
@@ -64,8 +40,7 @@ namespace na
 		const TunerStage& st = Require<TunerStage>("GetTunerInfo");
 		TunerStageInfo info;
 		info.numTuners = st.book.NumEntries();
-		info.deviceBytes = (long long)st.rowCapacity * ((long long)sizeof(TunerState) + (long long)kTunerRingSamples * (long long)sizeof(int)) + st.tables.Bytes() +
-			(long long)TunerStage::kTables * (long long)st.resultCapacity * (long long)sizeof(TunerRecord);
+		info.deviceBytes = (long long)st.rowCapacity * ((long long)sizeof(TunerState) + (long long)kTunerRingSamples * (long long)sizeof(int)) + st.tables.Bytes() + st.results.Bytes();
 		return info;
 	}
 
@@ -104,33 +79,14 @@ namespace na
 
 	// the pinned entry table of the same ring slot still says which entry -- and so which row -- each record belongs to; a record of a
 	// tuner that has been set again or taken away since carries another generation and is dropped (TunerBook::Accept)
-	void GpuBatch::TunerStage::Fold(int i)
+	void GpuBatch::TunerStage::Fold(int i, int records)
 	{
-		for (int k = 0; k < pending[i]; k++)
+		const TunerEntry* table = tables.host[i];
+		for (int k = 0; k < records; k++)
 		{
-			const TunerRecord& rec = results[i][k];
-			const int entry = tables.host[i][k].evalEntry;
-			if (entry >= 0 && entry < tables.capacity && rec.row == tables.host[i][entry].row) (void)book.Accept(rec);
-		}
-		pending[i] = 0;
-	}
-
-	// The blocks complete in the order of their calls (every call's launches come behind the call before), so the walk starts at the
-	// oldest and ends at the first that is not over.
-	void GpuBatch::TunerStage::Poll()
-	{
-		for (int k = 0; k < kTables; k++)
-		{
-			const int i = (tables.next + k) % kTables;
-			if (pending[i] == 0) continue;
-			const hipError_t q = hipEventQuery(tables.done[i]);
-			if (q == hipErrorNotReady)
-			{
-				(void)hipGetLastError(); // (not an error of anything that follows)
-				return;
-			}
-			CheckHip(q, "hipEventQuery (tuner results)");
-			Fold(i);
+			const TunerRecord& rec = results.host[i][k];
+			const int entry = table[k].evalEntry;
+			if (entry >= 0 && entry < tables.capacity && rec.row == table[entry].row) (void)book.Accept(rec);
 		}
 	}
 
@@ -144,15 +100,15 @@ namespace na
 	{
 		Poll();
 		if (n == 0) return;
-		tables.Require(book.Rows() <= rowCapacity && book.NumEntries() <= resultCapacity);
+		tables.Require(book.Rows() <= rowCapacity && book.NumEntries() <= results.capacity);
 		const auto table = tables.Take(batch, book.NumEntries());
 		const int slot = tables.next;
-		if (pending[slot]) Fold(slot);
+		results.FoldBlock(slot, [this](int i, int records) { Fold(i, records); });
 		int evaluating = 0;
 		const int entries = book.BuildTable(table.host, (unsigned long long)n, &evaluating);
 		if (entries == 0) return;
 		tables.Upload(table, entries, launch);
-		TunerLaunch L{ table.dev, entries, evaluating, dIn, inStride, 0ull, 0ull, reinterpret_cast<TunerState*>(state), reinterpret_cast<int*>(rings), devResults[slot] };
+		TunerLaunch L{ table.dev, entries, evaluating, dIn, inStride, 0ull, 0ull, reinterpret_cast<TunerState*>(state), reinterpret_cast<int*>(rings), results.dev[slot] };
 		for (size_t done = 0; done < n; done += (size_t)kTunerPieceSamples)
 		{
 			L.offset = (unsigned long long)done;
@@ -168,11 +124,7 @@ namespace na
 			}
 			if (here) CheckHip(LaunchTunerEvaluate(L, launch), "TunerEvaluateKernel");
 		}
-		if (evaluating > 0)
-		{
-			CheckHip(hipMemcpyAsync(results[slot], devResults[slot], (size_t)evaluating * sizeof(TunerRecord), hipMemcpyDeviceToHost, launch), "hipMemcpyAsync (tuner results)");
-			pending[slot] = evaluating;
-		}
+		if (evaluating > 0) results.Download(slot, evaluating, launch, "hipMemcpyAsync (tuner results)");
 		tables.Commit(launch);
 		book.Advance(n);
 	}
