@@ -323,6 +323,93 @@ NA_EXTERN int NA_BatchGetDelayInfo(NA_Batch* batch, NA_DelayInfo* info);
 NA_EXTERN int NA_BatchSetStreamDelay(NA_Batch* batch, int stream, const NA_DelayParams* params, int fadeSamples); /* params = NULL: no delay */
 NA_EXTERN int NA_BatchGetStreamDelay(NA_Batch* batch, int stream, NA_DelayParams* out); /* 1: *out filled (the target); 0: no delay (or a fade to none); < 0: stage not enabled / bad id */
 NA_EXTERN int NA_BatchStreamDelayFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's delay fade; 0: none; < 0: stage not enabled / bad id */
+/* ---- the compressor stage: per-stream dynamics, a compressor or limiter ----
+ * The one block of a guitar chain that was left to the host is dynamics: a compressor, or with an infinite ratio a limiter -- also the
+ * block a server needs for its own safety, because two amps summed in a mix group, a makeup gain or a hot capture are not bounded by
+ * anything else on the device.  A host of the reference compresses the buffer it holds.  Here the rows stay on the device, so it is a
+ * tenth per-stream stage, off unless enabled, BEHIND the cabinet stage and IN FRONT OF the delay stage -- dynamics in front of the
+ * time-based effects: a session's chain is model -> gate -> EQ -> cabinet -> compressor -> delay -> reverb -> output gain -> mix.  In
+ * a resampling batch the stage acts on the external-rate rows, as the cabinet does.  A batch that enabled the stage and gave no
+ * stream a compressor launches exactly what it launched before.  Rows without an entry are never touched.
+ * Topology.  Feed-forward: a branching peak follower runs on the row's own samples, a static gain curve is read at the follower's
+ * level, and the row is multiplied.  The gain computer has no transcendental on the device: a curve is a table of 513 gains on a level
+ * axis that is the float's own bit pattern -- 16 knots per octave from 2^-24 to 2^8, interpolated linearly -- so compressor, limiter,
+ * soft knee, makeup gain or any curve a caller designs himself are one mechanism, and the contract is exactly restatable.
+ * Arithmetic.  Every operation is one separately rounded f32 operation, fl(.), round to nearest even.  There is no FMA contraction, and
+ * subnormals are kept.
+ *   Constants of an entry: aA = attackCoeff, aR = releaseCoeff in (0, 1].  Curve t[0..512], every value finite and in [0, 65536].
+ *   Knot i sits at level 2^(-24 + (i >> 4)) * (1 + (i & 15) / 16).
+ *   State per row: f32 e (starts at +0) and the last g.
+ *   Per sample, x the row's sample:
+ *     x' = (x is NaN) ? 0 : min(|x|, 255.0f)
+ *     c  = (x' > e) ? aA : aR
+ *     d  = fl(x' - e);  e = fl(e + fl(c * d))
+ *     b  = bits(e);  q = b >> 19
+ *     curve(t): q < 1648 ? t[0]
+ *               : i = min(q - 1648, 511);  f = fl((float)(b & 0x7FFFF) * 2^-19);
+ *                 fl(t[i] + fl(f * fl(t[i+1] - t[i])))
+ *     g  = curve(tB)                                              where w == 1
+ *     g  = fl(fl(fl(1 - w) * curve(tA)) + fl(w * curve(tB)))      else, w = OutStageWeightAt(N, k)
+ *     y  = fl(x * g)
+ *   w = OutStageWeightAt(N, k) is the fade weight of the other stages, (min(k, N - 1) + 1) / N for the k-th sample since the set call.
+ *   e never leaves [0, 2^8), so i + 1 <= 512: x' lies in [0, 255] and c in (0, 1]; where x' > e, fl(c * d) <= d = fl(x' - e) because
+ *   rounding is monotone, so the new e is at most fl(e + d) <= 255 + 2^-16 and at least e; where x' <= e, |fl(c * d)| <= |d| <= e, so
+ *   the new e lies in [0, e], and an exact cancellation gives +0, never -0.  Hence bits(e) < bits(256.0f) and q <= 1648 + 511.
+ *   A NaN or infinite sample goes through the multiplication as it is.  The follower sees 0 or 255.
+ *   A row has two curve slots, as the EQ has two cascades.  tB is the curve it has or fades to.  tA is the one it fades from.  "No
+ *   compressor" is the unity curve: g = 1, never read from memory.
+ * Consequences: the bits do not depend on how the signal is cut into calls, on alignment, stride, the other streams or in-place use;
+ * an all-ones curve passes the row bit for bit; with aA = aR = 1, samples from {0, +-0.5, +-2} and t[i] = 1 for i < 384, 0.25 for
+ * i >= 384, y is x at |x| = 0.5 and exactly x / 4 at |x| = 2 (knot 384 is level 1.0, knot 368 is level 0.5).
+ * NA_CompressorParamsFromDb is host arithmetic and needs no device.  Coefficients are 1 - exp(-1 / (ms * rate / 1000)) in double,
+ *   rounded once (the gate's formula); ms == 0 gives 1.  Per knot, in double, with L = 20 log10(level_i), o = L - thresholdDb,
+ *   s = 1 / ratio - 1 (ratio in [1, +inf], +inf gives s = -1) and W = kneeDb >= 0:
+ *     G = 0 if 2o < -W;   G = s (o + W/2)^2 / (2W) if 2|o| <= W;   G = s o else;   t[i] = (float)10^((G + makeupDb) / 20).
+ *   Every bad field is refused by name (sampleRate, thresholdDb, ratio, kneeDb, makeupDb, attackMs, releaseMs; a gain outside
+ *   [0, 65536] names the knot).  Between knots the linear interpolation of a power-law stretch of slope s is off by at most
+ *   |s (s - 1)| / 2048 relative (0.0085 dB for a limiter); a segment that straddles a corner is off by at most
+ *   |s| * 20 log10(17 / 16) / 4 dB (0.13 dB for a limiter with a hard knee).
+ * NA_BatchEnableCompressorStage is the set-up side (allocates; idempotent): two curve slots and a state per row (4232 bytes) and the
+ *   stage's device + pinned tables, sized so that every row's entry and the curves of both its slots fit one table; later
+ *   NA_BatchAddStreams / NA_BatchReserveStreams grow them.  Every call below fails before it, with
+ *   "compressor stage not enabled (NA_BatchEnableCompressorStage)".  NA_BatchGetCompressorInfo reports curvePoints = 513, the number
+ *   of entries and the device memory the stage holds.
+ * NA_BatchSetStreamCompressor is REAL-TIME SAFE: host arithmetic on tables that exist.
+ *   A set call on a stream without a compressor fades in from unity over fadeSamples with e = +0.
+ *   On a stream with a compressor the new curve fades in over fadeSamples from the curve it has.  New aA / aR act from the next sample
+ *     on the kept e.  Only curves fade.
+ *   params == NULL fades to unity, and the entry retires when the fade ends (the follower goes on with the coefficients it has).  On
+ *     a stream without a compressor it does nothing.
+ *   fadeSamples == 0 switches at the next sample; fadeSamples must lie in [0, 1 << 20].
+ *   A set call while a fade is running is refused with an error that gives the samples left ("a compressor fade of stream <s> is
+ *     running (<k> samples left)").  The caller polls NA_BatchStreamCompressorFadeRemaining.
+ *   Curves travel once, behind the table of the first call after the set call, from pinned memory sized at enable time.
+ *   attackCoeff and releaseCoeff must lie in (0, 1]; every curve value must be finite and lie in [0, 65536].  Each failure names the
+ *     field ("curve[<i>] must ...").
+ * NA_BatchGetStreamCompressor returns 1 and fills *out with the target, 0 when the stream has no compressor or one that fades to none,
+ *   < 0 on a bad id or when the stage is not enabled.  NA_BatchStreamCompressorGain returns the g of the last sample produced (1
+ *   without a compressor or before its first sample, < 0 on a bad id); it reads the device state and synchronises the batch: a
+ *   diagnostic like NA_BatchStreamGateGain, not for the audio callback.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a
+ * hand-over, drop the compressor at once: a parked stream carries nothing over, and an activated stream has none.  Compressors are not
+ * part of a NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves them alone.
+ * While an entry exists -- a stream with a compressor, or a fade towards none -- a processing call behaves as it does with entries of
+ * the other stages: its launches run in order on one stream (no half-batch chains, no resident launch), host buffers go through the
+ * library's device staging block, and it enqueues one table upload from a ring of pinned tables plus ONE launch over the compressed
+ * streams only, whatever n: no device or pinned allocation, no stream or event creation, no unbounded wait.  With the last entry the
+ * free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; a gain-reduction tap in the meter stage; a side chain
+ * on the dry input; stereo linking across a mix group; look-ahead. */
+typedef struct NA_CompressorParams { float attackCoeff, releaseCoeff; float curve[513]; } NA_CompressorParams;
+typedef struct NA_CompressorInfo { int curvePoints, numCompressors; long long deviceBytes; } NA_CompressorInfo;
+NA_EXTERN int NA_CompressorParamsFromDb(int sampleRate, float thresholdDb, float ratio, float kneeDb, float makeupDb, float attackMs, float releaseMs, NA_CompressorParams* out);
+NA_EXTERN int NA_BatchEnableCompressorStage(NA_Batch* batch);
+NA_EXTERN int NA_BatchGetCompressorInfo(NA_Batch* batch, NA_CompressorInfo* info);
+NA_EXTERN int NA_BatchSetStreamCompressor(NA_Batch* batch, int stream, const NA_CompressorParams* params, int fadeSamples); /* params = NULL: the compressor goes, click-free */
+NA_EXTERN int NA_BatchGetStreamCompressor(NA_Batch* batch, int stream, NA_CompressorParams* out); /* 1: *out filled (the target); 0: none (or a fade to none); < 0: stage not enabled / bad id */
+NA_EXTERN int NA_BatchStreamCompressorFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's curve fade; 0: none; < 0: stage not enabled / bad id */
+NA_EXTERN float NA_BatchStreamCompressorGain(NA_Batch* batch, int stream); /* the g of the last sample produced; 1: no compressor; < 0: bad id / not enabled */
 /* ---- the gate stage: a per-stream noise gate ----
  * High-gain captures turn pickup hum into a loud hiss between notes.  A host of the reference gates that itself: it listens to the dry
  * input and scales the amp's output, because it holds both buffers.  Here the rows stay on the device, and a gate needs both ends of a
@@ -1073,6 +1160,10 @@ NA_EXTERN int NA_DebugReverbTwiddles(float* out, int floats);
 NA_EXTERN int NA_DebugRunDelayStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
 /* Tests: launches of the delay stage's kernel so far (one per piece of a call with entries) */
 NA_EXTERN long long NA_DebugDelayLaunches(void);
+/* Tests: as NA_DebugRunCabinetStage, for the compressor stage: the stage alone on given rows -- table, launch, book advance */
+NA_EXTERN int NA_DebugRunCompressorStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
+/* Tests: launches of the compressor stage's kernel so far (one per processing call with entries) */
+NA_EXTERN long long NA_DebugCompressorLaunches(void);
 /* Tests: launches of the gate stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugGateLaunches(void);
 /* Tests: launches of the meter stage's two kernels so far (two per processing call with entries) */

@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -72,6 +72,33 @@ def gate_params_from_db(sample_rate, open_db, close_db, floor_db=float("-inf"), 
                                                float(attack_ms), float(hold_ms), float(release_ms), C.byref(out)) != 0:
         raise NeuralAudioError(capi.last_error())
     return _gate_dict(out)
+
+
+def _compressor_dict(p):
+    return {"attackCoeff": float(p.attackCoeff), "releaseCoeff": float(p.releaseCoeff), "curve": np.ctypeslib.as_array(p.curve).astype(np.float32)}
+
+
+def _compressor_params(d):
+    if isinstance(d, capi.NA_CompressorParams):
+        return d
+    curve = np.ascontiguousarray(d["curve"], np.float32)
+    if curve.shape != (capi.NA_COMPRESSOR_CURVE_POINTS,):
+        raise NeuralAudioError("a compressor curve has %d values" % capi.NA_COMPRESSOR_CURVE_POINTS)
+    p = capi.NA_CompressorParams()
+    p.attackCoeff, p.releaseCoeff = d["attackCoeff"], d["releaseCoeff"]
+    C.memmove(p.curve, curve.ctypes.data, curve.nbytes)
+    return p
+
+
+def compressor_params_from_db(sample_rate, threshold_db, ratio, knee_db=0.0, makeup_db=0.0, attack_ms=5.0, release_ms=100.0):
+    """The constants Batch.SetStreamCompressor takes, from decibels and milliseconds (NA_CompressorParamsFromDb): attackCoeff,
+    releaseCoeff and the curve of 513 gains as a float32 array.  ratio = inf, knee_db = 0, attack_ms = 0 is a limiter.  Host arithmetic:
+    needs no device."""
+    out = capi.NA_CompressorParams()
+    if capi.load_library().NA_CompressorParamsFromDb(int(sample_rate), float(threshold_db), float(ratio), float(knee_db), float(makeup_db),
+                                                     float(attack_ms), float(release_ms), C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _compressor_dict(out)
 
 
 DELAY_FIELDS = ("delaySamples", "feedback", "lowpassCoeff", "highpassCoeff", "wet", "dry")
@@ -721,6 +748,50 @@ class Batch:
     def DebugRunDelayStage(self, rows, n=None):
         """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunDelayStage)."""
         return self._debug_run_stage(self._lib.NA_DebugRunDelayStage, rows, n)
+
+    # -- the compressor stage: EnableCompressorStage is set-up side; SetStreamCompressor is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableCompressorStage(self):
+        if self._lib.NA_BatchEnableCompressorStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetCompressorInfo(self):
+        info = capi.NA_CompressorInfo()
+        if self._lib.NA_BatchGetCompressorInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_CompressorInfo._fields_}
+
+    def SetStreamCompressor(self, stream, params, fadeSamples=0):
+        """A compressor on the stream from the next sample on: `params` a dict of the NA_CompressorParams fields
+        (compressor_params_from_db makes one) or the struct itself; None: the compressor goes.  The curve fades in over `fadeSamples`
+        samples; the coefficients act at once."""
+        p = None if params is None else C.byref(_compressor_params(params))
+        if self._lib.NA_BatchSetStreamCompressor(self._h, int(stream), p, int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamCompressor(self, stream):
+        """The target as a dict; None: no compressor (or one that fades to none)."""
+        out = capi.NA_CompressorParams()
+        rc = int(self._lib.NA_BatchGetStreamCompressor(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _compressor_dict(out) if rc else None
+
+    def StreamCompressorFadeRemaining(self, stream):
+        left = int(self._lib.NA_BatchStreamCompressorFadeRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
+
+    def StreamCompressorGain(self, stream):
+        """The compressor's gain at the last sample produced (1 without a compressor).  Synchronises the batch: a diagnostic."""
+        gain = float(self._lib.NA_BatchStreamCompressorGain(self._h, int(stream)))
+        if gain < 0:
+            raise NeuralAudioError(capi.last_error())
+        return gain
+
+    def DebugRunCompressorStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunCompressorStage)."""
+        return self._debug_run_stage(self._lib.NA_DebugRunCompressorStage, rows, n)
 
     # -- the gate stage: EnableGateStage is set-up side; SetStreamGate is real-time safe (include/neuralaudio_amd.h) ----
     def EnableGateStage(self):

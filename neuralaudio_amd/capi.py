@@ -47,6 +47,9 @@ NA_SYMBOLS = [
     "NA_BatchGetStreamReverb", "NA_BatchStreamReverbFadeRemaining", "NA_DebugRunReverbStage", "NA_DebugReverbLaunches", "NA_DebugReverbTwiddles",
     "NA_DelayParamsFromMs", "NA_BatchEnableDelayStage", "NA_BatchGetDelayInfo", "NA_BatchSetStreamDelay", "NA_BatchGetStreamDelay",
     "NA_BatchStreamDelayFadeRemaining", "NA_DebugRunDelayStage", "NA_DebugDelayLaunches",
+    "NA_CompressorParamsFromDb", "NA_BatchEnableCompressorStage", "NA_BatchGetCompressorInfo", "NA_BatchSetStreamCompressor",
+    "NA_BatchGetStreamCompressor", "NA_BatchStreamCompressorFadeRemaining", "NA_BatchStreamCompressorGain", "NA_DebugRunCompressorStage",
+    "NA_DebugCompressorLaunches",
     "NA_GateParamsFromDb", "NA_BatchEnableGateStage", "NA_BatchGetGateInfo", "NA_BatchSetStreamGate", "NA_BatchGetStreamGate",
     "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
     "NA_EqSectionFromDesign", "NA_BatchEnableEqStage", "NA_BatchGetEqInfo", "NA_BatchSetStreamEq", "NA_BatchGetStreamEq",
@@ -97,6 +100,17 @@ class NA_DelayParams(C.Structure):
 class NA_DelayInfo(C.Structure):
     _fields_ = [("maxDelaySamples", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numDelays", C.c_int),
                 ("deviceBytes", C.c_longlong)]
+
+
+NA_COMPRESSOR_CURVE_POINTS = 513
+
+
+class NA_CompressorParams(C.Structure):
+    _fields_ = [("attackCoeff", C.c_float), ("releaseCoeff", C.c_float), ("curve", C.c_float * NA_COMPRESSOR_CURVE_POINTS)]
+
+
+class NA_CompressorInfo(C.Structure):
+    _fields_ = [("curvePoints", C.c_int), ("numCompressors", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 class NA_GateParams(C.Structure):
@@ -282,6 +296,15 @@ def load_library():
         "NA_BatchStreamDelayFadeRemaining": (C.c_int, [vp, C.c_int]),
         "NA_DebugRunDelayStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
         "NA_DebugDelayLaunches": (C.c_longlong, []),
+        "NA_CompressorParamsFromDb": (C.c_int, [C.c_int] + [C.c_float] * 6 + [C.POINTER(NA_CompressorParams)]),
+        "NA_BatchEnableCompressorStage": (C.c_int, [vp]),
+        "NA_BatchGetCompressorInfo": (C.c_int, [vp, C.POINTER(NA_CompressorInfo)]),
+        "NA_BatchSetStreamCompressor": (C.c_int, [vp, C.c_int, C.POINTER(NA_CompressorParams), C.c_int]),
+        "NA_BatchGetStreamCompressor": (C.c_int, [vp, C.c_int, C.POINTER(NA_CompressorParams)]),
+        "NA_BatchStreamCompressorFadeRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_BatchStreamCompressorGain": (C.c_float, [vp, C.c_int]),
+        "NA_DebugRunCompressorStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
+        "NA_DebugCompressorLaunches": (C.c_longlong, []),
         "NA_GateParamsFromDb": (C.c_int, [C.c_int] + [C.c_float] * 7 + [C.POINTER(NA_GateParams)]),
         "NA_BatchEnableGateStage": (C.c_int, [vp]),
         "NA_BatchGetGateInfo": (C.c_int, [vp, C.POINTER(NA_GateInfo)]),

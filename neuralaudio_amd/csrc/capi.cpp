@@ -826,6 +826,96 @@ int NA_DebugRunDelayStage(NA_Batch* batch, float* hostRows, long stride, size_t 
 long long NA_DebugDelayLaunches(void) { return (long long)na::DelayStageLaunches(); }
 #endif
 
+// ---- the compressor stage (gpu_batch.h EnableCompressorStage / SetStreamCompressor) ----
+static_assert(sizeof(NA_CompressorParams) == sizeof(na::CompParams) && sizeof(NA_CompressorParams) == 515 * sizeof(float), "NA_CompressorParams is CompParams, field for field");
+namespace
+{
+	void CompParamsIn(const NA_CompressorParams& p, na::CompParams& c)
+	{
+		c.attackCoeff = p.attackCoeff;
+		c.releaseCoeff = p.releaseCoeff;
+		std::memcpy(c.curve, p.curve, sizeof(c.curve));
+	}
+	void CompParamsOut(const na::CompParams& c, NA_CompressorParams* p)
+	{
+		p->attackCoeff = c.attackCoeff;
+		p->releaseCoeff = c.releaseCoeff;
+		std::memcpy(p->curve, c.curve, sizeof(p->curve));
+	}
+}
+
+int NA_CompressorParamsFromDb(int sampleRate, float thresholdDb, float ratio, float kneeDb, float makeupDb, float attackMs, float releaseMs, NA_CompressorParams* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_CompressorParamsFromDb: bad argument");
+		na::CompParams c;
+		const std::string why = na::CompParamsFromDb(sampleRate, thresholdDb, ratio, kneeDb, makeupDb, attackMs, releaseMs, c);
+		if (!why.empty()) throw std::runtime_error("NA_CompressorParamsFromDb: " + why);
+		CompParamsOut(c, out);
+	});
+}
+
+int NA_BatchEnableCompressorStage(NA_Batch* batch)
+{
+	return BatchCall(batch, "NA_BatchEnableCompressorStage", [&](na::GpuBatch& b) { b.EnableCompressorStage(); });
+}
+
+int NA_BatchGetCompressorInfo(NA_Batch* batch, NA_CompressorInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetCompressorInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetCompressorInfo: bad argument");
+		const na::CompressorStageInfo i = b.GetCompressorInfo();
+		info->curvePoints = i.curvePoints;
+		info->numCompressors = i.numCompressors;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamCompressor(NA_Batch* batch, int stream, const NA_CompressorParams* params, int fadeSamples)
+{
+	return BatchCall(batch, "NA_BatchSetStreamCompressor", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamCompressor(stream, nullptr, fadeSamples);
+			return;
+		}
+		na::CompParams c;
+		CompParamsIn(*params, c);
+		b.SetStreamCompressor(stream, &c, fadeSamples);
+	});
+}
+
+int NA_BatchGetStreamCompressor(NA_Batch* batch, int stream, NA_CompressorParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamCompressor", -1, [&](na::GpuBatch& b) {
+		na::CompParams c;
+		const int has = b.GetStreamCompressor(stream, c) ? 1 : 0;
+		if (has && out) CompParamsOut(c, out);
+		return has;
+	});
+}
+
+int NA_BatchStreamCompressorFadeRemaining(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchStreamCompressorFadeRemaining", -1, [&](na::GpuBatch& b) { return b.StreamCompressorFadeRemaining(stream); });
+}
+
+float NA_BatchStreamCompressorGain(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchStreamCompressorGain", -1.0f, [&](na::GpuBatch& b) { return b.StreamCompressorGain(stream); });
+}
+
+#ifndef NA_RELEASE
+int NA_DebugRunCompressorStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunCompressorStage: null batch");
+		batch->batch->DebugRunCompressorStage(hostRows, stride, n);
+	});
+}
+long long NA_DebugCompressorLaunches(void) { return (long long)na::CompressorStageLaunches(); }
+#endif
+
 // ---- the gate stage (gpu_batch.h EnableGateStage / SetStreamGate) ----
 namespace
 {

@@ -19,6 +19,7 @@
 
 #include "cabinet_stage.h"
 #include "reverb_stage.h"
+#include "compressor_stage.h"
 #include "delay_stage.h"
 #include "device_resources.h"
 #include "eq_stage.h"
@@ -85,6 +86,12 @@ namespace na
 	struct DelayStageInfo
 	{
 		int maxDelaySamples = 0, ringSamples = 0, pieceSamples = 0, numDelays = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct CompressorStageInfo
+	{
+		int curvePoints = 0, numCompressors = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -228,6 +235,23 @@ namespace na
 		int StreamDelayFadeRemaining(int stream) const;
 		// test hook (NA_DebugRunDelayStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
 		void DebugRunDelayStage(float* hostRows, long stride, size_t n);
+
+		// The compressor stage (compressor_stage.h): a per-stream feed-forward compressor -- a branching peak follower on the
+		// row's own samples, a gain curve of 513 knots read at the follower's level, a multiplication -- behind the cabinet stage and in
+		// front of the delay stage.  EnableCompressorStage is the set-up side: two curve slots and a state per row (CreateStreams grows
+		// them) and the tables, sized for the curves of both slots of every row.  SetStreamCompressor is host arithmetic on those tables;
+		// while an entry exists -- a stream with a compressor, or a fade towards none -- every processing call runs on the ordered path
+		// and enqueues ONE table upload and ONE launch, whatever n.  Without an entry the batch launches exactly what it launches without
+		// the stage.
+		void EnableCompressorStage();
+		bool HasCompressorStage() const { return stages[kCompressorStage] != nullptr; }
+		CompressorStageInfo GetCompressorInfo() const;
+		void SetStreamCompressor(int stream, const CompParams* params, int fadeSamples); // nullptr: no compressor
+		bool GetStreamCompressor(int stream, CompParams& out) const;                     // the target; false: none
+		int StreamCompressorFadeRemaining(int stream) const;
+		float StreamCompressorGain(int stream); // the g of the last sample produced; 1: no compressor.  Synchronises: a diagnostic
+		// test hook (NA_DebugRunCompressorStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
+		void DebugRunCompressorStage(float* hostRows, long stride, size_t n);
 
 		// The gate stage (gate_stage.h): a per-stream noise gate that listens to the stream's input row and scales the row
 		// the models produced for it -- the detector launch in front of everything of the call, the apply launch first of the stages, in
@@ -459,9 +483,9 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.18).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.19).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kCompressorStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
@@ -474,7 +498,7 @@ namespace na
 		};
 		template <class Book, class Entry> struct StageOf;
 		template <class Record> struct StageResults; // the result blocks of the stages that report to the host (meter, tuner)
-		struct GateStage; struct EqStage; struct CabinetStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
+		struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -299,7 +299,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the nine stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the ten stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -366,6 +366,23 @@ namespace na
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + two launches per piece + the host mirror's advance
 	};
 	hipError_t LaunchCabinetStage(const CabLaunch& L, hipStream_t stream); // (cabinet_stage_kernels.hip) the two launches of one piece
+
+	// the compressor stage (compressor_stage.h, compressor_stage.cpp): the rows' two curve slots and states on the
+	// device; its tables hold the entries and behind them the curves of the set calls since the last call
+	struct GpuBatch::CompressorStage : StageOf<CompBook, CompEntry>
+	{
+		static constexpr StageId kId = kCompressorStage;
+		static constexpr const char* kNotEnabled = "compressor stage not enabled (NA_BatchEnableCompressorStage)";
+		float* curves = nullptr;          // [rowCapacity][2] CompCurve
+		float* state = nullptr;           // [rowCapacity] CompState
+		int rowCapacity = 0;
+		CompressorStage() : StageOf("compressor stage") {}
+		~CompressorStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // no compressor at once, its state dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + launch + the host mirror's advance
+	};
+	hipError_t LaunchCompressorStage(const CompLaunch& L, hipStream_t stream); // (compressor_stage_kernels.hip)
 
 	// the delay stage (delay_stage.h, delay_stage.cpp): the rows' delay lines (rings) and filter states
 	struct GpuBatch::DelayStage : StageOf<DelayBook, DelayEntry>
