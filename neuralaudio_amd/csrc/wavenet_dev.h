@@ -1,6 +1,6 @@
 // wavenet_dev.h -- device-side data model shared by the host packer (wavenet_plan.cpp) and the gfx950 WaveNet kernels
-// (wavenet_split_kernels.hip and wavenet_frame_kernels.hip, one per model, see WaveNetKernelFor() in wavenet_choice.h; the tile / packed-FMA
-// fields below belong to the round-1 alternatives kept under tools/alternates/, not built into the library).
+// (the f16-split interpreter wavenet_split_kernels.hip and its specialised chains wavenet_spec_*_kernels.hip, wavenet_frame_kernels.hip,
+// wavenet_generic_kernels.hip: one per model, see WaveNetKernelFor() in wavenet_choice.h).
 //
 // A WaveNet model (reference: NeuralAudio/WaveNet.h) is lowered at load time into a short "stage program" (WnStage: one per
 // rechannel / layer / array link / head) plus per-kernel weight images.  A workgroup interprets the program for one or two

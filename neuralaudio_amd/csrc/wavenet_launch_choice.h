@@ -179,7 +179,7 @@ namespace na
 			// and 16 / 16 only exists packed
 			if (packed ? (fam != 1 || !lists) : lite16) return false;
 			// Streams per workgroup.  The half-size workgroups (SPB = 1: four waves) are compiled for two waves per SIMD, i.e. with 256 VGPRs
-			// (NA_SPK_OCC): a launch that cannot fill the chip anyway is bound by the latency of its few waves, and the registers let the
+			// (spk::OccOf): a launch that cannot fill the chip anyway is bound by the latency of its few waves, and the registers let the
 			// compiler keep a layer's LDS reads in flight (Nano x 1024 = 256 packed streams 25.1 -> 22.6 us, Feather x 1024 24.3 -> 22.2,
 			// Standard x 512 25.4 -> 23.4).  They are used while every workgroup is resident at that occupancy: at most two per CU --
 			// counting the workgroups of the launches that share the chip with this one (two free-running half-batch chains of 512 Standard

@@ -27,28 +27,6 @@ namespace na
 	{
 		using namespace sp;
 
-// tuning builds: cache policy of the ring traffic of layers with a dilation >= NA_SPK_NT_DIL -- NA_SPK_NT_LD / NA_SPK_NT_ST are the
-// policy immediates of their history loads / ring stores (0 = default policy; 2 = nt; 16 = sc1; 18 = both)
-#ifndef NA_SPK_NT_DIL
-#define NA_SPK_NT_DIL 256
-#endif
-#ifndef NA_SPK_NT_LD
-#define NA_SPK_NT_LD 0
-#endif
-#ifndef NA_SPK_NT_ST
-#define NA_SPK_NT_ST 0
-#endif
-#ifndef NA_SPK_DELAY
-#define NA_SPK_DELAY 0
-#endif
-#ifndef NA_SPK_LEAN
-// the parts of Cfg::LEAN: 1 = per-wave ring loads / stores, 2 = live operands only, 4 = one MFMA per straddling tap.  Part 1 is NOT in the
-// default: its extra wave-3 bodies take the 128-frame full-size kernels from 120 VGPRs to 128 with 16 spilled (profiles/r08_lean_ab.txt)
-#define NA_SPK_LEAN 6
-#endif
-#ifndef NA_SPK_AUX2
-#define NA_SPK_AUX2 0 // tuning builds: 1 = read the aux operand again for the 1x1 instead of keeping it in registers across the layer
-#endif
 		typedef __attribute__((address_space(3))) char* LdsPtr;
 		__device__ __forceinline__ u32x4 LdsRead16(unsigned addr) { return *reinterpret_cast<__attribute__((address_space(3))) const u32x4*>((LdsPtr)(size_t)addr); }
 		__device__ __forceinline__ u32x2 LdsRead8(unsigned addr) { return *reinterpret_cast<__attribute__((address_space(3))) const u32x2*>((LdsPtr)(size_t)addr); }
@@ -80,28 +58,12 @@ namespace na
 			static constexpr bool COARSE = false; // (dilations are powers of two: at most three wave classes per layer, 53 KB of code)
 			static constexpr bool GUARDHIST = false;
 			static constexpr bool FOLD = false;   // folded lo operands (WN_FLAG_FOLD): the plans of natural models only (wavenet_plan.cpp)
-			static constexpr int SKEW = 0;
 			static constexpr bool COMPACT = true; // K <= 3 everywhere, dense heads: histories of <= 32 frames live in compact rings (wavenet_plan.cpp AddRing)
-#ifndef NA_A1_NT_DIL
-#define NA_A1_NT_DIL 128
-#endif
-			static constexpr int NT_DIL = NA_A1_NT_DIL; // Cfg::NT: layers from this dilation on move their ring traffic non-temporally
-			static constexpr bool LEAN = false;   // Cfg::LEAN: every wave issues only the memory operations and MFMAs its own frames need
+			static constexpr int NT_DIL = 128;    // Cfg::NT: layers from this dilation on move their ring traffic non-temporally
+			static constexpr bool LEAN = false;   // Cfg::LEAN: live operands only, one MFMA per straddling tap
 		};
-#ifndef NA_SPK_SKEW
-#define NA_SPK_SKEW 0
-#endif
 		struct ArchStd : ArchA1Base // A1 Standard (16 -> 8)
 		{
-			// Tuning experiment (make KEXTRA=-DNA_SPK_SKEW=5; NOT the default): the two streams of a workgroup run SKEW stages apart
-			// (Cfg::SKEW).  The layers of an array are light (d <= 32: bound by instruction issue) and then heavy (d >= 64: both taps of
-			// every frame come from HBM), and in lock-step every workgroup of the launch is in the same phase -- the memory system idles
-			// through the light layers and the SIMDs through the heavy ones; five stages apart, one stream's heavy layers fall on the other's
-			// light ones.  Measured: 44.3 us against 43.3 in lock-step (profiles/r03_ablation.txt).  The memory system is then loaded all the
-			// time, and the few ring loads of a LIGHT stage -- prefetched one stage ahead, all the 128 VGPRs allow -- come back after
-			// ~1.5 us instead of ~0.5: every slot waits for its light stream (per-slot timeline: both streams done after ~2700 cycles,
-			// barrier released after ~4400).
-			static constexpr int SKEW = NA_SPK_SKEW;
 			static constexpr bool FOLD = true; // (not padded, not packed: every layer takes the folded operands)
 			static constexpr bool LEAN = true;
 			static constexpr int NA = 2;
@@ -146,7 +108,6 @@ namespace na
 			static constexpr bool COARSE = true;
 			static constexpr bool GUARDHIST = true;
 			static constexpr bool FOLD = false;
-			static constexpr int SKEW = 0;
 			static constexpr bool COMPACT = false;
 			static constexpr int NT_DIL = 100;    // (d = 101 and 239)
 			static constexpr bool LEAN = false;
@@ -269,27 +230,18 @@ namespace na
 			static constexpr int MAXOPS = A_::CHUNK; // operands per LDS weight buffer
 			static_assert(TB::MaxChunkOps() <= MAXOPS, "stage operand chunk");
 			static constexpr int HPF = 5;            // shifted taps whose ring history is prefetched a layer ahead (K = 3: both, K = 6: all five)
-			// stages between the two streams of a workgroup (0: lock-step, one set of weight buffers for the workgroup); skewed streams stage
-			// their own operands with their own waves into their own pair of buffers
-			static constexpr int SKEW = (SPB == 2 && !PK_ && T == 2 && A_::SKEW > 0) ? A_::SKEW : 0;
-			static constexpr int NWB = SKEW > 0 ? SPB : 1;          // weight buffer pairs
-			static constexpr int STG_THREADS = NTHREADS / NWB;      // threads that stage one pair
-			// The one-shot launches of A1 Standard: no wave issues an operation only to keep the instruction counts of a stream's waves alike
-			// (the chain sits on the socket's power cap, DESIGN.md 2.2h: issued work is time).  A wave loads ring history only for taps of its
-			// own that reach in front of the block and stores only sets of which a later block reads something (the counted waits that close a
-			// stage take this wave's own counts: LayerSig, EndFirst); a folded stage moves only the operands it reads into LDS (LiveOps); a
-			// straddling tap of a folded layer is one MFMA (ConvTapFold).  Same values in the rings, same results.  NA_SPK_LEAN picks the
-			// parts; the first (LEAN_MEM) is not in the default build.
-			static constexpr bool LEAN = A_::LEAN && !PK_ && !COH_ && SKEW == 0 && T == 2;
-			static constexpr bool LEAN_MEM = LEAN && (NA_SPK_LEAN & 1), LEAN_STAGE = LEAN && (NA_SPK_LEAN & 2), LEAN_MFMA = LEAN && (NA_SPK_LEAN & 4);
+			// The one-shot launches of A1 Standard issue no work that is dead (the chain sits on the socket's power cap, DESIGN.md 2.2h:
+			// issued work is time): a folded stage moves only the operands it reads into LDS (Stager::LIVEONLY); a straddling tap of a
+			// folded layer is one MFMA (ConvTapFold).  Same values in the rings, same results.
+			static constexpr bool LEAN = A_::LEAN && !PK_ && !COH_ && T == 2;
 			// LDS map (bytes)
-			static constexpr bool AUX16 = !PK_ && SKEW == 0;                    // aux entries as whole quads (one LDS read, no unpacking)
-			static constexpr int AUX_OFF = 0;                                   // [SPB][FRAMES] quads; PK: [SPB][4][FRAMES] x 8 bytes; skewed: [SPB][FRAMES] x 8
-			static constexpr int IMG_OFF = AUX_OFF + SPB * FRAMES * (PK_ ? 32 : (AUX16 ? 16 : 8)); // [SPB][2][planes][PLANE] quads
+			// aux entries: whole quads (one LDS read, no unpacking); only PK keeps 8 bytes per frame and real stream, which AuxRead unpacks
+			static constexpr int AUX_OFF = 0;                                   // [SPB][FRAMES] quads; PK: [SPB][4][FRAMES] x 8 bytes
+			static constexpr int IMG_OFF = AUX_OFF + SPB * FRAMES * (PK_ ? 32 : 16); // [SPB][2][planes][PLANE] quads
 			static constexpr int IMG_ONE = TB::MaxGP() * PLANE * 16;            // one image: a plane per channel group
-			static constexpr int WBUF_OFF = IMG_OFF + SPB * 2 * IMG_ONE;        // [NWB][2][MAXOPS] operands of 1 KB
+			static constexpr int WBUF_OFF = IMG_OFF + SPB * 2 * IMG_ONE;        // [2][MAXOPS] operands of 1 KB
 			static constexpr int WBUF_ONE = MAXOPS * 1024;
-			static constexpr int IDOP_OFF = WBUF_OFF + NWB * 2 * WBUF_ONE;      // identity operand
+			static constexpr int IDOP_OFF = WBUF_OFF + 2 * WBUF_ONE;            // identity operand
 			static constexpr int DUMP_OFF = IDOP_OFF + 1024;                    // where the LDS-DMA of a wave with nothing to stage lands
 			static constexpr int FLAG_OFF = DUMP_OFF + 1024;                    // [SPB] x 16 bytes: "a value of this stream was saturated" (LeakyReLU chains)
 			static constexpr int BCAST_OFF = FLAG_OFF + 16 * SPB;                // resident launch: the command wave 0 read, for the other waves (64 bytes)
@@ -339,18 +291,7 @@ namespace na
 			return first;
 		}
 
-		// Does a later block read anything of what wave w holds of set i of ring RG's writer?  (the last frame of the set lies in the kept
-		// range: the last RingKeep frames of the block)
-		template <class C, int RG>
-		constexpr bool StoreMine(int w, int i)
-		{
-			typedef typename C::TB TB;
-			constexpr int P = Geo<TB::RingG(RG), C::T>::P, KEEP = TB::RingKeep(RG);
-			return C::FW * w + 16 * P * (i + 1) - 1 >= C::NF - KEEP;
-		}
-
-		// everything about layer L that depends on the wave: classes of its shifted taps and of the next layer's prefetched ones (Cfg::LEAN:
-		// and which of its sets it stores to the next layer's ring -- a body issues exactly what its waves need, so its counts are constants)
+		// everything about layer L that depends on the wave: classes of its shifted taps and of the next layer's prefetched ones
 		template <class C, int L>
 		struct LayerSig
 		{
@@ -367,8 +308,6 @@ namespace na
 					for (int i = 0; i < S; i++) s = s * 3 + (unsigned)WaveTapClass<C>(w, P, i, d * (K - 1 - k), SmallRing<C, L>());
 				for (int k = 0; k < Kn - 1 && k < C::HPF; k++)
 					for (int i = 0; i < S; i++) s = s * 3 + (unsigned)WaveTapClass<C>(w, P, i, dn * (Kn - 1 - k), SmallRing<C, LN>());
-				if constexpr (C::LEAN_MEM && NEXT)
-					for (int i = 0; i < S; i++) s = s * 2 + (StoreMine<C, LN>(w, i) ? 1u : 0u);
 				return s;
 			}
 			static constexpr int Rep(int w) { int r = w; for (int v = w - 1; v >= 0; v--) if (Of(v) == Of(w)) r = v; return r; }
@@ -385,8 +324,7 @@ namespace na
 			int wave, sub, waveAll;       // wave within the stream's block, stream within the workgroup (wave-uniform)
 			int lane;
 			int gs0, gs1;                 // packed launches: log2(channel groups per real stream) of array 0 / the other arrays
-			unsigned wbuf;                // LDS byte address of this wave's weight buffer pair (skewed streams: the stream's own)
-			int stgWave;                  // wave index among the waves that stage into that pair
+			unsigned wbuf;                // LDS byte address of the workgroup's weight buffer pair
 #ifdef NA_SP_TRACE
 			long long* trace;             // tuning aid (make SUFFIX=_trace EXTRA=-DNA_SP_TRACE, tools/trace_split_timeline.py): nullptr unless this is the traced workgroup
 			int nwaves;
@@ -422,7 +360,7 @@ namespace na
 				ring = (unsigned)((fl * GP + cg) * 16);
 				dual = C::PK && gs < 0;
 				if constexpr (C::PK) aux = (unsigned)(C::AUX_OFF + ((cx.sub * 4 + (gs < 0 ? 2 * cg : (cg >> gs))) * FRAMES + f) * 8);
-				else aux = (unsigned)(C::AUX_OFF + (cx.sub * FRAMES + f) * (C::AUX16 ? 16 : 8));
+				else aux = (unsigned)(C::AUX_OFF + (cx.sub * FRAMES + f) * 16);
 			}
 		};
 
@@ -430,19 +368,16 @@ namespace na
 		__device__ __forceinline__ u32x4 AuxRead(const Lanes<C, GP>& ln, int i)
 		{
 			constexpr int P = Geo<GP, C::T>::P;
-			// [cond_h, 1 | cond_l, 1 | cond_h, 0 | 0, 0] (see FillSplitAux in wavenet_plan.cpp): the whole quad, or from the 8 bytes kept per frame
-			if constexpr (C::AUX16) return LdsRead16(ln.aux + (unsigned)(16 * P * i * 16));
+			// [cond_h, 1 | cond_l, 1 | cond_h, 0 | 0, 0] (see FillSplitAux in wavenet_plan.cpp): the whole quad, or (PK) from the 8 bytes kept per frame
+			if constexpr (!C::PK) return LdsRead16(ln.aux + (unsigned)(16 * P * i * 16));
 			else
 			{
 				const u32x2 v = LdsRead8(ln.aux + (unsigned)(16 * P * i * 8));
-				if constexpr (C::PK)
+				if (ln.dual)
 				{
-					if (ln.dual)
-					{
-						// [cA_h, 1 | cA_l, 1 | cA_h, cB_h | cB_l, cB_h]: the second stream of the pair is FRAMES entries on (FillSplitAux, dense packs)
-						const u32x2 w = LdsRead8(ln.aux + (unsigned)(16 * P * i * 8) + (unsigned)(FRAMES * 8));
-						return u32x4{ v.x, v.y, (v.x & 0xffffu) | (w.x << 16), (w.y & 0xffffu) | (w.x << 16) };
-					}
+					// [cA_h, 1 | cA_l, 1 | cA_h, cB_h | cB_l, cB_h]: the second stream of the pair is FRAMES entries on (FillSplitAux, dense packs)
+					const u32x2 w = LdsRead8(ln.aux + (unsigned)(16 * P * i * 8) + (unsigned)(FRAMES * 8));
+					return u32x4{ v.x, v.y, (v.x & 0xffffu) | (w.x << 16), (w.y & 0xffffu) | (w.x << 16) };
 				}
 				return u32x4{ v.x, v.y, v.x & 0xffffu, 0u };
 			}
@@ -496,12 +431,12 @@ namespace na
 			if (base < 0) base += R;
 			if (base >= R) base -= R;
 			const int addr = RingWrap<GP, R>(laneRing, base);
-			constexpr int NT_LD = C::NT ? 2 : NA_SPK_NT_LD, NT_DIL = C::NT ? C::A::NT_DIL : NA_SPK_NT_DIL;
-			constexpr bool LONG = RG < TB::NL && TB::Dil(RG < TB::NL ? RG : 0) >= NT_DIL;
-			if constexpr (LONG && NT_LD != 0)
+			// Cfg::NT: the long-dilation layers load non-temporally (policy immediate 2 = nt)
+			constexpr bool LONG = RG < TB::NL && TB::Dil(RG < TB::NL ? RG : 0) >= C::A::NT_DIL;
+			if constexpr (C::NT && LONG)
 			{
-				if (cls == TAP_HIST) return RingLoadAux<NT_LD>(cx.srsrc, addr, OFF * 16);
-				return RingLoadAux<NT_LD>(cx.srsrc, (C::FW * cx.wave + 16 * P * i + fl < shift) ? addr : OOB, OFF * 16);
+				if (cls == TAP_HIST) return RingLoadAux<2>(cx.srsrc, addr, OFF * 16);
+				return RingLoadAux<2>(cx.srsrc, (C::FW * cx.wave + 16 * P * i + fl < shift) ? addr : OOB, OFF * 16);
 			}
 			if (cls == TAP_HIST) return RingLoad(cx.srsrc, addr, OFF * 16);
 			return RingLoad(cx.srsrc, (C::FW * cx.wave + 16 * P * i + fl < shift) ? addr : OOB, OFF * 16);
@@ -519,23 +454,20 @@ namespace na
 		template <class C, int L>
 		constexpr int PrefetchTaps() { return (C::TB::KS(L) - 1) < C::HPF ? (C::TB::KS(L) - 1) : C::HPF; }
 
-		// does wave w issue the history load of layer L's prefetched tap k for set i?  Every wave whenever any wave needs it -- or
-		// (Cfg::LEAN) only a wave whose own frames reach in front of the block
+		// is the history load of layer L's prefetched tap k for set i issued?  By every wave whenever any wave needs it
 		template <class C, int L>
-		constexpr bool HistIssuedBy(int w, int k, int i)
+		constexpr bool HistIssued(int k, int i)
 		{
-			typedef typename C::TB TB;
-			constexpr int GP = TB::GPof(TB::ArrOf(L)), P = Geo<GP, C::T>::P;
-			if (!HistNeededAt<C, GP>(ShiftOf<C, L>(k), i, SmallRing<C, L>())) return false;
-			return !C::LEAN_MEM || WaveTapClass<C>(w, P, i, ShiftOf<C, L>(k), SmallRing<C, L>()) != TAP_LDS;
+			return HistNeededAt<C, C::TB::GPof(C::TB::ArrOf(L))>(ShiftOf<C, L>(k), i, SmallRing<C, L>());
 		}
+		// history loads a wave issues for layer L
 		template <class C, int L>
-		constexpr int HistLoadsOfWave(int w)
+		constexpr int HistLoads()
 		{
 			constexpr int S = Geo<C::TB::GPof(C::TB::ArrOf(L)), C::T>::S;
 			int n = 0;
 			for (int k = 0; k < PrefetchTaps<C, L>(); k++)
-				for (int i = 0; i < S; i++) n += HistIssuedBy<C, L>(w, k, i) ? 1 : 0;
+				for (int i = 0; i < S; i++) n += HistIssued<C, L>(k, i) ? 1 : 0;
 			return n;
 		}
 
@@ -547,7 +479,7 @@ namespace na
 			for (int k = 0; k < PrefetchTaps<C, L>(); k++)
 #pragma unroll
 				for (int i = 0; i < S; i++)
-					if (HistIssuedBy<C, L>(WR, k, i)) st.hist[k][i] = HistLoadAt<C, L, WR>(cx, laneRing, fl, ShiftOf<C, L>(k), i);
+					if (HistIssued<C, L>(k, i)) st.hist[k][i] = HistLoadAt<C, L, WR>(cx, laneRing, fl, ShiftOf<C, L>(k), i);
 		}
 
 		// A stage's output -> the LDS image (in-block taps of the reader, if it has any) and ring RG (history for LATER blocks: only the
@@ -560,19 +492,17 @@ namespace na
 			constexpr int P = Geo<TB::RingG(RG), C::T>::P, KEEP = TB::RingKeep(RG);
 			return (C::NF - C::FW) + 16 * P * (i + 1) - 1 >= C::NF - KEEP; // the last wave's last frame of set i
 		}
-		// ring stores wave w issues for ring RG (Cfg::LEAN: only the sets it keeps something of)
+		// ring stores a wave issues for ring RG
 		template <class C, int RG>
-		constexpr int StoresOfWave(int w)
+		constexpr int RingStores()
 		{
 			constexpr int S = Geo<C::TB::RingG(RG), C::T>::S;
 			int n = 0;
-			for (int i = 0; i < S; i++) n += (StoreNeeded<C, RG>(i) && (!C::LEAN_MEM || StoreMine<C, RG>(w, i))) ? 1 : 0;
+			for (int i = 0; i < S; i++) n += StoreNeeded<C, RG>(i) ? 1 : 0;
 			return n;
 		}
 
-		// WR: a wave whose kept sets are those of the calling wave (LayerSig); -1: not known at compile time (the stages all waves run in
-		// one body: a wave-uniform branch)
-		template <class C, int RG, int GP, int MINSHIFT, int WR = -1>
+		template <class C, int RG, int GP, int MINSHIFT>
 		__device__ __forceinline__ void Publish(const Ctx& cx, const Lanes<C, GP>& ln, u32x4 v, int i, int imgWrite)
 		{
 			typedef typename C::TB TB;
@@ -581,10 +511,6 @@ namespace na
 			if (!(NA_ABL & 64) && MINSHIFT < C::NF) // the reader takes in-block frames of other lanes
 				LdsWrite16(ln.img + (unsigned)(imgWrite * C::IMG_ONE + 16 * P * i * 16), v);
 			if ((NA_ABL & 4) || !StoreNeeded<C, RG>(i)) return;
-			if constexpr (C::LEAN_MEM)
-			{
-				if (WR >= 0 ? !StoreMine<C, RG>(WR, i) : (C::FW * cx.wave + 16 * P * (i + 1) - 1 < C::NF - KEEP)) return;
-			}
 			const int pos0 = __builtin_amdgcn_readlane(cx.myPos, RG);
 			int base;
 			if constexpr (TB::CompactRing(RG))
@@ -601,12 +527,11 @@ namespace na
 				if (base >= R) base -= R;
 			}
 			const int addr = RingWrap<GP, R>(ln.ring, base);
-			constexpr int NT_ST = C::NT ? 2 : NA_SPK_NT_ST, NT_DIL = C::NT ? C::A::NT_DIL : NA_SPK_NT_DIL;
-			constexpr bool LONG = RG < TB::NL && TB::Dil(RG < TB::NL ? RG : 0) >= NT_DIL;
-			if constexpr (LONG && NT_ST != 0)
+			constexpr bool LONG = RG < TB::NL && TB::Dil(RG < TB::NL ? RG : 0) >= C::A::NT_DIL;
+			if constexpr (C::NT && LONG) // (see HistLoadAt)
 			{
-				if (KEEP >= C::NF) RingStoreAux<NT_ST>(cx.srsrc, v, addr, OFF * 16);
-				else RingStoreAux<NT_ST>(cx.srsrc, v, (C::FW * cx.wave + 16 * P * i + ln.fl >= C::NF - KEEP) ? addr : OOB, OFF * 16);
+				if (KEEP >= C::NF) RingStoreAux<2>(cx.srsrc, v, addr, OFF * 16);
+				else RingStoreAux<2>(cx.srsrc, v, (C::FW * cx.wave + 16 * P * i + ln.fl >= C::NF - KEEP) ? addr : OOB, OFF * 16);
 				return;
 			}
 			if (KEEP >= C::NF) RingStore(cx.srsrc, v, addr, OFF * 16);
@@ -659,14 +584,14 @@ namespace na
 			static constexpr int QUADS = (TB::ChunkEnd(SN, CN) - TB::ChunkBegin(SN, CN)) * 64;
 			static constexpr int SRC = TB::AOff(SN) + TB::ChunkBegin(SN, CN) * 64;
 			static constexpr int BUF = TB::ChunkIndex(SN, CN) & 1;
-			static constexpr int NCOPY = (QUADS + C::STG_THREADS - 1) / C::STG_THREADS;
+			static constexpr int NCOPY = (QUADS + C::NTHREADS - 1) / C::NTHREADS;
 			// Cfg::LEAN, folded layer stage: only the operands the layer reads.  The fold (WN_FLAG_FOLD) moved the lo of tap 1 into operand
 			// 1, aux into 5 and the 1x1 bias into 8, so 3, 6 and 9 are dead, and the very last layer has no 1x1 (7, 8).  Every live operand
 			// lands in its usual slot (WOp and the weight image do not change); staging wave j moves live operand j
 			static constexpr int LSN = TB::LayerOfStage(SN) < 0 ? 0 : TB::LayerOfStage(SN);
-			static constexpr bool LIVEONLY = C::LEAN_STAGE && TB::LayerOfStage(SN) >= 0 && TB::Fold(LSN) && !TB::Chunked(SN);
+			static constexpr bool LIVEONLY = C::LEAN && TB::LayerOfStage(SN) >= 0 && TB::Fold(LSN) && !TB::Chunked(SN);
 			static constexpr int NLIVE = (TB::LastOfArr(LSN) && TB::ArrOf(LSN) == TB::NA - 1) ? 5 : 7;
-			static constexpr int STG_WAVES = C::STG_THREADS / 64;
+			static constexpr int STG_WAVES = C::NTHREADS / 64;
 			static constexpr int NCOPY_LIVE = (NLIVE + STG_WAVES - 1) / STG_WAVES;
 			static __device__ __forceinline__ void Begin(const Ctx& cx)
 			{
@@ -677,7 +602,7 @@ namespace na
 #pragma unroll
 					for (int c = 0; c < NCOPY_LIVE; c++)
 					{
-						const int j = c * STG_WAVES + cx.stgWave; // (wave-uniform)
+						const int j = c * STG_WAVES + cx.waveAll; // (wave-uniform)
 						const bool mine = j < NLIVE;
 						// live operand j: 0, 1, 2, 4, 5, 7, 8 = j + (j > 2) + (j > 4)
 						const int op = j + (j > 2 ? 1 : 0) + (j > 4 ? 1 : 0);
@@ -692,7 +617,7 @@ namespace na
 				{
 					// operands are 64 quads: a wave's 1 KB slice is one whole operand or lies beyond the block.  An out-of-range LDS-DMA load still
 					// WRITES (zeros), so a wave with nothing to stage aims at the dump slot -- same instruction count on every wave.
-					const int i0 = c * C::STG_THREADS + cx.stgWave * 64; // first quad of this wave's slice (wave-uniform)
+					const int i0 = c * C::NTHREADS + cx.waveAll * 64; // first quad of this wave's slice (wave-uniform)
 					const bool mine = i0 < QUADS;
 					const unsigned dst = mine ? cx.wbuf + (unsigned)(BUF * C::WBUF_ONE) + (unsigned)i0 * 16u : (unsigned)C::DUMP_OFF;
 					__builtin_amdgcn_raw_ptr_buffer_load_lds(cx.wrsrc, (__attribute__((address_space(3))) void*)(LdsPtr)(size_t)dst, 16,
@@ -762,13 +687,13 @@ namespace na
 			if (cls != TAP_LDS)
 			{
 				acc = Mfma(ah, hist, acc);
-				acc = MfmaLo<1>(al, hist, acc);
+				acc = MfmaLo(al, hist, acc);
 			}
 			if (cls != TAP_HIST)
 			{
 				const u32x4 b = TapLds<C, GP>(cx, ln, imgRead, shift, i, cls);
 				acc = Mfma(ah, b, acc);
-				acc = MfmaLo<1>(al, b, acc);
+				acc = MfmaLo(al, b, acc);
 			}
 			return acc;
 		}
@@ -781,7 +706,7 @@ namespace na
 			constexpr int P = Geo<GP, C::T>::P;
 			const int cls = WaveTapClass<C>(WR, P, i, shift, SmallRing<C, RG>());
 			th = u32x2{ 0, 0 };
-			if (C::LEAN_MFMA && cls == TAP_BOTH)
+			if (C::LEAN && cls == TAP_BOTH)
 			{
 				// one hi MFMA on the OR-ed columns instead of two: in every lane one of the two columns is all zeros, and adding the products
 				// of an all-zero column is exact -- at most the sign of a zero sum differs, which no later operation can tell (it is added
@@ -821,9 +746,9 @@ namespace na
 			constexpr int NEXTMINSHIFT = SG::NEXT ? TB::Dil(LN) : (1 << 20); // the reader's smallest tap shift: is the LDS image needed?
 			constexpr bool OWN = 2 * (K - 1) >= CB && 2 * (K - 1) < CE;  // the unshifted tap's operands are in this chunk (every shifted tap is consumed by then)
 			constexpr bool TAIL = 2 * K >= CB && 2 * K < CE;             // aux / 1x1 operands are in this chunk
-			// (what THIS body issues: with Cfg::LEAN that differs from wave class to wave class, and a count that is too high would let the
-			// wave through the barrier before its weight DMA has landed)
-			constexpr int LATER = ((OWN && SG::NEXT) ? HistLoadsOfWave<C, LN>(WR) : 0) + ((TAIL && SG::NEXT && !LASTLAYER) ? StoresOfWave<C, LN>(WR) : 0);
+			// (what this body issues after the staging: a count that is too high would let the wave through the barrier before its weight
+			// DMA has landed)
+			constexpr int LATER = ((OWN && SG::NEXT) ? HistLoads<C, LN>() : 0) + ((TAIL && SG::NEXT && !LASTLAYER) ? RingStores<C, LN>() : 0);
 			typedef typename NextChunk<C, s, c>::St NextStager;
 			if constexpr (c == 0)
 			{
@@ -886,7 +811,7 @@ namespace na
 				{
 					acc[i] = Mfma(ah, st.xs[i], acc[i]);
 					if constexpr (SG::FOLD) acc[i] = Mfma(al, u32x4{ st.xs[i].x, st.xs[i].y, ax[i].x, ax[i].y }, acc[i]);
-					else acc[i] = MfmaLo<1>(al, st.xs[i], acc[i]);
+					else acc[i] = MfmaLo(al, st.xs[i], acc[i]);
 				}
 			}
 			if constexpr (TAIL)
@@ -905,7 +830,7 @@ namespace na
 				for (int i = 0; i < S; i++)
 				{
 					if constexpr (C::A::LEAKY) z[i] = f32x4{ LeakyReLU(acc[i].x), LeakyReLU(acc[i].y), LeakyReLU(acc[i].z), LeakyReLU(acc[i].w) };
-					else z[i] = ActivateTanh<(NA_PK_TANH != 0) && (C::NTHREADS < 512)>(acc[i]);
+					else z[i] = ActivateTanh<(C::NTHREADS < 512)>(acc[i]);
 				}
 				SPK_STAMP(s, 2);
 				const u32x4 idop = LdsRead16((unsigned)C::IDOP_OFF + (unsigned)cx.lane * 16u);
@@ -919,18 +844,17 @@ namespace na
 					{
 						f32x4 y = st.xc[i];
 						y = Mfma(w1h, zs, y);
-						const u32x4 axi = NA_SPK_AUX2 ? AuxRead<C, GP>(ln, i) : ax[i];
-						if constexpr (SG::FOLD) y = Mfma(w1l, u32x4{ zs.x, zs.y, axi.x, axi.y }, y);
+						if constexpr (SG::FOLD) y = Mfma(w1l, u32x4{ zs.x, zs.y, ax[i].x, ax[i].y }, y);
 						else
 						{
-							y = MfmaLo<2>(w1l, zs, y);
-							y = Mfma(b1a, axi, y);
+							y = MfmaLo(w1l, zs, y);
+							y = Mfma(b1a, ax[i], y);
 						}
 						st.xc[i] = y;
 						if constexpr (SG::NEXT)
 						{
 							st.xs[i] = Split<C>(y, cx);
-							Publish<C, LN, GP, NEXTMINSHIFT, WR>(cx, ln, st.xs[i], i, imgWrite);
+							Publish<C, LN, GP, NEXTMINSHIFT>(cx, ln, st.xs[i], i, imgWrite);
 						}
 					}
 				}
@@ -997,26 +921,6 @@ namespace na
 			}
 		}
 
-		// The counted wait that closes the stage in front of layer L (rechannel / link: one body for all waves) on the staging St: the
-		// VMEM operations a wave issued after St::Begin are its stores to ring L and the prefetch of layer L's history.  Without Cfg::LEAN
-		// that is one constant; with it the wave's own count, picked by a wave-uniform branch between the wait immediates.
-		template <class C, class St, int L, int W>
-		__device__ __forceinline__ void EndFirst(const Ctx& cx)
-		{
-			constexpr int N = StoresOfWave<C, L>(W) + HistLoadsOfWave<C, L>(W);
-			constexpr bool same = [] {
-				bool r = true;
-				for (int w = W + 1; w < C::WPS; w++) r = r && StoresOfWave<C, L>(w) + HistLoadsOfWave<C, L>(w) == N;
-				return r;
-			}();
-			if constexpr (same) St::template End<N>();
-			else
-			{
-				if (cx.wave == W) St::template End<N>();
-				else EndFirst<C, St, L, W + 1>(cx);
-			}
-		}
-
 		// array 0 rechannel: x = w_re * cond (WaveNet.h:637 with InputSize == 1) -- the aux operand against (w_re, 0)
 		template <class C>
 		__device__ __forceinline__ void RechStage(const Ctx& cx, const Lanes<C, C::TB::GPof(0)>& ln, State& st)
@@ -1039,7 +943,8 @@ namespace na
 			}
 			FirstHistDispatch<C, 0, 0>(cx, ln.ring, ln.fl, st);
 			SPK_STAMP(0, 1); SPK_STAMP(0, 2); SPK_STAMP(0, 3);
-			EndFirst<C, Stager<C, 1, 0>, 0, 0>(cx);
+			// (after Stager<1, 0>::Begin every wave issued its stores to ring 0 and the prefetch of layer 0's history: the same count on all)
+			Stager<C, 1, 0>::template End<RingStores<C, 0>() + HistLoads<C, 0>()>();
 			SPK_STAMP(0, 4);
 			BlockBarrier<C::NTHREADS / 64>();
 			SPK_STAMP(0, 5);
@@ -1078,9 +983,9 @@ namespace na
 			{
 				const int u = t % NC, so = t / Po, sn = t / Pn;
 hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
-				hn[sn] = MfmaLo<4>(WOp<C>(cx, s, 0, 4 * u + 1), hs[so], hn[sn]);
+				hn[sn] = MfmaLo(WOp<C>(cx, s, 0, 4 * u + 1), hs[so], hn[sn]);
 				xn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u + 2), xq[so], xn[sn]);
-				xn[sn] = MfmaLo<4>(WOp<C>(cx, s, 0, 4 * u + 3), xq[so], xn[sn]);
+				xn[sn] = MfmaLo(WOp<C>(cx, s, 0, 4 * u + 3), xq[so], xn[sn]);
 			}
 #pragma unroll
 			for (int i = 0; i < Sn; i++)
@@ -1092,7 +997,7 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 			}
 			FirstHistDispatch<C, LN, 0>(cx, ln.ring, ln.fl, st);
 			SPK_STAMP(s, 1); SPK_STAMP(s, 2); SPK_STAMP(s, 3);
-			EndFirst<C, Stager<C, s + 1, 0>, LN, 0>(cx);
+			Stager<C, s + 1, 0>::template End<RingStores<C, LN>() + HistLoads<C, LN>()>(); // (as in RechStage)
 			SPK_STAMP(s, 4);
 			BlockBarrier<C::NTHREADS / 64>();
 			SPK_STAMP(s, 5);
@@ -1155,7 +1060,7 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 					for (int i = 0; i < S; i++)
 					{
 						acc[i] = Mfma(ah, hs[i], acc[i]);
-						acc[i] = MfmaLo<8>(al, hs[i], acc[i]);
+						acc[i] = MfmaLo(al, hs[i], acc[i]);
 					}
 				}
 				if (2 * K >= TB::ChunkBegin(s, c) && 2 * K < TB::ChunkEnd(s, c))
@@ -1254,8 +1159,7 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 			cx.wrsrc = MakeRsrc(ga.wsplit, (unsigned)ga.wsplitQuads * 16u);
 			cx.myPos = header[lane];
 			cx.wave = wave; cx.sub = sub; cx.waveAll = waveAll; cx.lane = lane;
-			cx.wbuf = (unsigned)(C::WBUF_OFF + (C::SKEW > 0 ? sub : 0) * 2 * C::WBUF_ONE);
-			cx.stgWave = C::SKEW > 0 ? wave : waveAll;
+			cx.wbuf = (unsigned)C::WBUF_OFF;
 #ifdef NA_SP_TRACE
 			cx.trace = trace;
 			cx.nwaves = C::NTHREADS / 64;
@@ -1303,15 +1207,11 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 			{
 				for (int i = wave * 64 + lane; i < FRAMES; i += C::WPS * 64)
 				{
-					// [cond_h, 1 | cond_l, 1 | cond_h, 0 | 0, 0] (see FillSplitAux in wavenet_plan.cpp; 8-byte entries: AuxRead rebuilds the second half)
+					// [cond_h, 1 | cond_l, 1 | cond_h, 0 | 0, 0] (see FillSplitAux in wavenet_plan.cpp)
 					const float c = (i < NF) ? ClampCond(LoadIn<C::COH>(in + (size_t)row * inStride + i), ga.condLimit) : 0.0f;
 					const _Float16 ch = (_Float16)c, cl = (_Float16)(c - (float)ch);
 					const f16x2 a = { ch, (_Float16)1.0f }, b = { cl, (_Float16)1.0f }, d = { ch, (_Float16)0.0f };
-					if constexpr (C::AUX16)
-						LdsWrite16((unsigned)(C::AUX_OFF + (sub * FRAMES + i) * 16), u32x4{ __builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, d), 0u });
-					else
-						*reinterpret_cast<__attribute__((address_space(3))) u32x2*>((LdsPtr)(size_t)(unsigned)(C::AUX_OFF + (sub * FRAMES + i) * 8)) =
-							u32x2{ __builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b) };
+					LdsWrite16((unsigned)(C::AUX_OFF + (sub * FRAMES + i) * 16), u32x4{ __builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, d), 0u });
 				}
 			}
 			// zero quad in front of frame 0 of every plane of both block images
@@ -1329,23 +1229,12 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 			{
 				if (tid < SPB) *reinterpret_cast<__attribute__((address_space(3))) unsigned*>((LdsPtr)(size_t)(unsigned)(C::FLAG_OFF + 16 * tid)) = 0u;
 			}
-			// stage 0's single operand (offset 0 of every weight image), into every pair of weight buffers
-			if (cx.stgWave == 0) LdsWrite16(cx.wbuf + (unsigned)lane * 16u, BufLoad(cx.wrsrc, lane * 16));
+			// stage 0's single operand (offset 0 of every weight image)
+			if (waveAll == 0) LdsWrite16(cx.wbuf + (unsigned)lane * 16u, BufLoad(cx.wrsrc, lane * 16));
 			BlockBarrier<C::NTHREADS / 64>();
 
-			// skewed streams: stream 1 starts SKEW stages (= barriers) after stream 0 and ends as many after it
-			if constexpr (C::SKEW > 0)
-			{
-				if (sub != 0)
-					for (int k = 0; k < C::SKEW; k++) BlockBarrier<C::NTHREADS / 64>();
-			}
 			State st;
 			RunArrays<C, 0>(cx, st, out, (size_t)row * outStride, outRow, pack, ga.headScale, live);
-			if constexpr (C::SKEW > 0)
-			{
-				if (sub == 0)
-					for (int k = 0; k < C::SKEW; k++) BlockBarrier<C::NTHREADS / 64>();
-			}
 
 #ifdef NA_SP_TRACE
 			if (cx.trace != nullptr && lane == 0) cx.trace[((C::TB::NSTAGES * 8 + 1) * cx.nwaves) + waveAll] = (long long)__builtin_readcyclecounter();
@@ -1374,12 +1263,13 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 		// static LDS), so every LDS offset of the chain is an instruction immediate.
 		// waves per SIMD the kernel is compiled for = what two resident workgroups per CU put on a SIMD: 2 NF SPB threads per workgroup -> 4
 		// for the full-size workgroups (128 VGPRs), 2 for the half-size ones and for 64-frame blocks (256 VGPRs), 1 below (see the launcher)
-#ifndef NA_SPK_OCC
-#define NA_SPK_OCC(nf, spb) (((nf) * (spb) / 64) < 1 ? 1 : ((nf) * (spb) / 64))
-#endif
 		// (one tile per wave: launched with at most one workgroup per CU, i.e. half the waves per SIMD of the same thread count)
 		template <class F, int NF, int SPB>
-		constexpr int OccOf() { return F::A0::T == 1 ? (NA_SPK_OCC(NF, SPB) / 2 < 1 ? 1 : NA_SPK_OCC(NF, SPB) / 2) : NA_SPK_OCC(NF, SPB); }
+		constexpr int OccOf()
+		{
+			const int occ = NF * SPB / 64 / (F::A0::T == 1 ? 2 : 1);
+			return occ < 1 ? 1 : occ;
+		}
 		template <class F, int NF, int SPB, bool PK, bool NT = false>
 		__global__ void __launch_bounds__(64 * (NF / (16 * F::A0::T)) * (SPB * F::A0::T / 2)) __attribute__((amdgpu_waves_per_eu(OccOf<F, NF, SPB>()))) WaveNetSpecKernel(const LaunchArgs args,
 			const float* __restrict__ in, float* __restrict__ out, long inStride, long outStride
@@ -1399,13 +1289,6 @@ hn[sn] = Mfma(WOp<C>(cx, s, 0, 4 * u), hs[so], hn[sn]);
 				if ((int)blockIdx.x >= args.g[i].firstBlock) gi = i;
 			const GroupArgs& ga = args.g[gi];
 			const int groupBlock = (int)blockIdx.x - ga.firstBlock;
-#if NA_SPK_DELAY > 0
-			// tuning builds: the second half of the grid (the workgroups that arrive SECOND on their CUs when the launch is one round of two
-			// workgroups per CU) starts NA_SPK_DELAY x 64 cycles late, so that the two workgroups of a CU are out of phase: one in its
-			// issue-bound stages while the other waits for memory in its d >= 64 stages
-			if (blockIdx.x >= gridDim.x / 2)
-				for (int k = 0; k < NA_SPK_DELAY; k += 100) __builtin_amdgcn_s_sleep(100);
-#endif
 #ifdef NA_SP_TRACE
 			long long* tr = ((int)blockIdx.x == traceBlock) ? trace : nullptr;
 			if (F::N > 1 && ga.arch == 1) RunWorkgroup<C1>(ga, groupBlock, in, out, inStride, outStride, tr);

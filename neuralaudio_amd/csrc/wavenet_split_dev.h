@@ -27,9 +27,6 @@ namespace na
                  // 512: ring loads and stores issued but all out of range (no traffic), 1024: only the stores so, 2048: only the loads
                  // (round-2 measurements: profiles/r02_ablation.txt)
 #endif
-#ifndef NA_PK_TANH
-#define NA_PK_TANH 1 // tuning builds: 0 = the unpacked tanh in the activation phase
-#endif
 #define WOP(m) (((NA_ABL & 128) ? 0 : (m)) * 64)
 		constexpr int OOB = (int)0x80000000;
 		constexpr int FRAMES = WN_MAX_FRAMES; // 128 frames per launch = 8 tiles
@@ -50,7 +47,7 @@ namespace na
 		// nt 2-4 % slower, the others within noise -- default policy)
 		__device__ __forceinline__ u32x4 RingLoad(__amdgpu_buffer_rsrc_t r, int voff, int soff = 0) { return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0); }
 		__device__ __forceinline__ void RingStore(__amdgpu_buffer_rsrc_t r, u32x4 v, int voff, int soff = 0) { __builtin_amdgcn_raw_buffer_store_b128(v, r, voff, soff, 0); }
-		// tuning builds (NA_SPK_NT): the same with a cache-policy immediate (1 sc0, 2 nt, 16 sc1) for the rings of the long dilations
+		// the same with a cache-policy immediate (1 sc0, 2 nt, 16 sc1): the long dilations' rings of a batch beyond the Infinity Cache (spk::Cfg::NT)
 		template <int AUX>
 		__device__ __forceinline__ u32x4 RingLoadAux(__amdgpu_buffer_rsrc_t r, int voff, int soff) { return __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, AUX); }
 		template <int AUX>
@@ -65,30 +62,9 @@ namespace na
 		}
 
 		// the "lo" product of the three-product split, Wl . xh: its A operand is [Wl | 0 0 0 0] per lane and k-block and only the h half
-		// of the split quad B takes part -- the first 64 bits of either are exactly the operands of the K = 16 instruction (lane (i, q): k =
-		// 4 q .. 4 q + 3), which does the same sixteen products per row in half the passes of the matrix pipe (tuning builds: -DNA_LO16=1)
-#ifndef NA_LO16
-#define NA_LO16 0
-#endif
-		// (SITE: 1 conv taps, 2 the 1x1, 4 array links, 8 heads -- NA_LO16 is a mask of the sites that use the K = 16 instruction)
-		template <int SITE>
-		__device__ __forceinline__ f32x4 MfmaLo(u32x4 a, u32x4 b, f32x4 c)
-		{
-#if NA_LO16
-			if (!(NA_LO16 & SITE)) return Mfma(a, b, c);
-			if (NA_ABL & 2) return f32x4{ c.x + __builtin_bit_cast(float, a.x ^ b.x), c.y, c.z, c.w };
-			typedef _Float16 f16x4_t __attribute__((ext_vector_type(4)));
-			const u32x2 a2 = { a.x, a.y }, b2 = { b.x, b.y };
-			f32x4 d = __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4_t, a2), __builtin_bit_cast(f16x4_t, b2), c, 0, 0, 0);
-			// the sources stay live past the instruction: with -amdgpu-mfma-vgpr-form this LLVM lets the result of the K = 16 form land on the
-			// registers of a source that dies here (seen: v_mfma_f32_16x16x16_f16 v[18:21], v[54:55], v[18:19], v[20:23] -- the later passes
-			// then read what the first ones wrote; the K = 32 form is protected)
-			asm("" : "+v"(d) : "v"(a), "v"(b));
-			return d;
-#else
-			return Mfma(a, b, c);
-#endif
-		}
+		// of the split quad B takes part.  (The K = 16 instruction on the first 64 bits of either does the same products in half the
+		// passes, but this compiler lets its result overlap a dying source: DESIGN.md 9, not taken.)
+		__device__ __forceinline__ f32x4 MfmaLo(u32x4 a, u32x4 b, f32x4 c) { return Mfma(a, b, c); }
 
 		__device__ __forceinline__ unsigned PackHalf2(float a, float b)
 		{

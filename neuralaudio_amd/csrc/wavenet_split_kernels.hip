@@ -340,7 +340,7 @@ namespace na
 							{
 								acc[i] = Mfma(ah, hist[k][i], acc[i]);
 								if (fold) th[k < 2 ? k : 0][i] = u32x2{ hist[k][i].x, hist[k][i].y };
-								else acc[i] = MfmaLo<1>(al, hist[k][i], acc[i]);
+								else acc[i] = MfmaLo(al, hist[k][i], acc[i]);
 							}
 						}
 						else if (lo >= 0)
@@ -352,7 +352,7 @@ namespace na
 								if (mask) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 }; // no garbage (NaN) into the MFMA
 								acc[i] = Mfma(ah, b, acc[i]);
 								if (fold) th[k < 2 ? k : 0][i] = u32x2{ b.x, b.y };
-								else acc[i] = MfmaLo<1>(al, b, acc[i]);
+								else acc[i] = MfmaLo(al, b, acc[i]);
 							}
 						}
 						else
@@ -363,10 +363,10 @@ namespace na
 								u32x4 b = TapInBlock(imgCur, f[i] - shift, cg[i]);
 								if (mask) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 };
 								acc[i] = Mfma(ah, hist[k][i], acc[i]);
-								if (!fold) acc[i] = MfmaLo<1>(al, hist[k][i], acc[i]);
+								if (!fold) acc[i] = MfmaLo(al, hist[k][i], acc[i]);
 								acc[i] = Mfma(ah, b, acc[i]);
 								if (fold) th[k < 2 ? k : 0][i] = u32x2{ hist[k][i].x | b.x, hist[k][i].y | b.y };
-								else acc[i] = MfmaLo<1>(al, b, acc[i]);
+								else acc[i] = MfmaLo(al, b, acc[i]);
 							}
 						}
 					}
@@ -402,7 +402,7 @@ namespace na
 						if (mask) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 };
 						acc[i] = Mfma(ah, b, acc[i]);
 						if (fold) th[k < 2 ? k : 0][i] = u32x2{ b.x, b.y };
-						else acc[i] = MfmaLo<1>(al, b, acc[i]);
+						else acc[i] = MfmaLo(al, b, acc[i]);
 					}
 				}
 				if (HPF < 2 && fold)
@@ -425,7 +425,7 @@ namespace na
 						if (fold) acc[i] = Mfma(al, u32x4{ b.x, b.y, ax.x, ax.y }, acc[i]);
 						else
 						{
-							acc[i] = MfmaLo<1>(al, b, acc[i]);
+							acc[i] = MfmaLo(al, b, acc[i]);
 							acc[i] = Mfma(xa, ax, acc[i]);
 						}
 					}
@@ -449,12 +449,8 @@ namespace na
 #pragma unroll
 					for (int i = 0; i < S; i++)
 					{
-						if (NA_PK_TANH)
-						{
-							const f32x2 lo = FastTanh2(f32x2{ acc[i].x, acc[i].y }), hi = FastTanh2(f32x2{ acc[i].z, acc[i].w });
-							z[i] = f32x4{ lo.x, lo.y, hi.x, hi.y };
-						}
-						else z[i] = f32x4{ FastTanh(acc[i].x), FastTanh(acc[i].y), FastTanh(acc[i].z), FastTanh(acc[i].w) };
+						const f32x2 lo = FastTanh2(f32x2{ acc[i].x, acc[i].y }), hi = FastTanh2(f32x2{ acc[i].z, acc[i].w });
+						z[i] = f32x4{ lo.x, lo.y, hi.x, hi.y };
 					}
 				}
 				SP_STAMP(2);
@@ -477,7 +473,7 @@ namespace na
 						if (fold) y = Mfma(w1l, u32x4{ zs.x, zs.y, ax.x, ax.y }, y);
 						else
 						{
-							y = MfmaLo<2>(w1l, zs, y);
+							y = MfmaLo(w1l, zs, y);
 							y = Mfma(b1a, ax, y);
 						}
 						st.xc[i] = y;
@@ -584,9 +580,9 @@ namespace na
 			{
 				const int u = t % NC, so = t / Po, sn = t / Pn;
 				hn[sn] = Mfma(wl[(4 * u) * 64], hs[so], hn[sn]);
-				hn[sn] = MfmaLo<4>(wl[(4 * u + 1) * 64], hs[so], hn[sn]);
+				hn[sn] = MfmaLo(wl[(4 * u + 1) * 64], hs[so], hn[sn]);
 				xn[sn] = Mfma(wl[(4 * u + 2) * 64], xs[so], xn[sn]);
-				xn[sn] = MfmaLo<4>(wl[(4 * u + 3) * 64], xs[so], xn[sn]);
+				xn[sn] = MfmaLo(wl[(4 * u + 3) * 64], xs[so], xn[sn]);
 			}
 #pragma unroll
 			for (int i = 0; i < Sn; i++)
@@ -647,7 +643,7 @@ namespace na
 						u32x4 b = TapOperandInline(cx, imgNext, sd.ring_off, sd.ring_frames, G, pos0, f[i], cg[i] < G ? cg[i] : 0, shift, lo, lo + 16 * P - 1);
 						if (Geo<GP, T>::PARTIAL || GP == 4) b = (live[i] && cg[i] < G) ? b : u32x4{ 0, 0, 0, 0 };
 						acc[i] = Mfma(ah, b, acc[i]);
-						acc[i] = MfmaLo<8>(al, b, acc[i]);
+						acc[i] = MfmaLo(al, b, acc[i]);
 					}
 				}
 			}
@@ -657,7 +653,7 @@ namespace na
 				for (int i = 0; i < S; i++)
 				{
 					acc[i] = Mfma(ah, hs[i], acc[i]);
-					acc[i] = MfmaLo<8>(al, hs[i], acc[i]);
+					acc[i] = MfmaLo(al, hs[i], acc[i]);
 					if (sd.flags & WN_FLAG_BIAS)
 					{
 						const u32x4 ax = AuxOf<PK>(cx, f[i], 0, 0); // bias only
