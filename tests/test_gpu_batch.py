@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import chain_wrap_cases as CW
 import na_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -939,6 +940,53 @@ def test_many_distinct_models_run_as_one_table_launch_and_match_one_model_batch(
     one.close()
 
 
+@pytest.mark.parametrize("model,per,chain,spb,pk", CW.TABLE_CASES, ids=["%s-%d" % c[:2] for c in CW.TABLE_CASES])
+def test_table_launches_match_one_model_batch_and_the_oracle_behind_the_ring_wraps(na, loader, model, per, chain, spb, pk):
+    """The 741 frames above wrap no exact ring and read no self-stored frame through a long tap.  Nine handles of one file with `per`
+    streams each -- one stream: the half-size table workgroups, more: the full-size ones with a partly filled last workgroup or virtual
+    stream per group (tests/chain_wrap_cases.py TABLE_CASES; tests/test_chain_wraps_cpu.py holds the workgroup sizes to the library's
+    prediction) -- over [128] x 22 and [64] x 44: bit for bit the one-handle batch, which runs the kernarg chains, and the last stream on
+    the oracle over the whole run and over the last 1024 frames alone."""
+    import torch
+    dev = torch.device("cuda", 0)
+    name = CW.MODEL_FILES[model]
+    handles = [loader.CreateFromFile(_path(name), doPrewarm=False) for _ in range(CW.TABLE_HANDLES)]
+    S = CW.TABLE_HANDLES * per
+    ts = torch.cuda.Stream(device=dev)
+    forced = any(k.startswith(("NA_WN_", "NA_SP_")) for k in os.environ)  # (tests/test_gpu_families.py: the workgroup size is then not asserted)
+    for seq in CW.TABLE_SEQUENCES:
+        lengths = CW.SEQUENCES[seq]
+        total = sum(lengths)
+        if not forced:
+            r = na.wavenet_launch(CW.table_groups(na, handles[0], model, per), lengths[0], cus=int(torch.cuda.get_device_properties(0).multi_processor_count), knobs=None)
+            assert (r[0], r[2], r[3], r[4], r[9]) == (CW.K_TABLE, chain, lengths[0], spb, pk), (model, per, seq, r)
+        many, one = na.Batch(0, hip_stream=ts.cuda_stream), na.Batch(0, hip_stream=ts.cuda_stream)
+        for i, h in enumerate(handles):
+            many.AddStreams(h, per, quality=CW.table_quality(model, i))
+        for i in range(CW.TABLE_HANDLES if model == "a2" else 1):
+            one.AddStreams(handles[0], per if model == "a2" else S, quality=CW.table_quality(model, i))
+        assert many.NumStreams() == one.NumStreams() == S
+        x = torch.from_numpy(CW.base_rows(seq)).to(dev)[torch.arange(S, device=dev) % CW.BASE_ROWS].contiguous()
+        want, got = torch.zeros_like(x), torch.zeros_like(x)
+        torch.cuda.synchronize(dev)
+        with torch.cuda.stream(ts):
+            for bb, y in ((one, want), (many, got)):
+                at = 0
+                for n in lengths:
+                    bb.ProcessDevice(x[:, at:].data_ptr(), y[:, at:].data_ptr(), n, total, total)
+                    at += n
+                bb.Synchronize()
+        assert many.DebugLastHostRoute() == one.DebugLastHostRoute() == na.HOST_ROUTES.index("DeviceOrdered")
+        assert torch.equal(want, got), (model, per, seq, float((want - got).abs().max()))
+        y = got[S - 1].cpu().numpy()
+        yo = O.oracle_from_file(name, quality=CW.table_quality(model, CW.TABLE_HANDLES - 1)).process(CW.base_rows(seq)[(S - 1) % CW.BASE_ROWS])
+        whole, late = O.rms(y - yo), O.rms(y[-CW.LATE:] - yo[-CW.LATE:])
+        print("table-wrap-error %s x %d, %s: last stream - oracle RMS: whole run %.3g, last %d frames %.3g" % (model, per, seq, whole, CW.LATE, late))
+        assert whole < TOL_RMS and late < TOL_RMS, (model, per, seq, whole, late)
+        many.close()
+        one.close()
+
+
 def test_table_launches_inside_a_captured_multi_unit_batch_replay_their_own_tables(na, loader):
     """More than eight WaveNet model groups AND more than eight recurrent groups in ONE batch: several launch units, so the buffer is
     captured into a hipGraph and replayed (gpu_batch.cpp ProcessDeviceOn) -- with table launches inside the capture.  The group tables
@@ -991,11 +1039,13 @@ def test_table_launches_inside_a_captured_multi_unit_batch_replay_their_own_tabl
 def test_batches_beyond_the_infinity_cache_mark_their_ring_traffic_non_temporal_and_compute_the_same(na, loader):
     """More A1 Standard state than the 256 MB Infinity Cache holds (1760 streams = 428 MB, beyond the 400 MB from which the variant is used): the chains of such a batch mark the ring traffic
     of the d >= 128 layers non-temporal (Cfg::NT, wavenet_spec_impl.h) -- a cache-policy bit, so two batches of 880 streams (inside the
-    cache: the ordinary variant) must compute the same bits; both against the oracle on one stream."""
+    cache: the ordinary variant) must compute the same bits; both against the oracle on one stream.  22 steps: the exact 1024-frame rings
+    of the d = 512 layers -- the traffic the variant marks -- wrap twice, and the last 1024 frames read nothing but frames the variant
+    stored itself (tests/test_gpu_chain_wraps.py runs the variant of the other families)."""
     import torch
     dev = torch.device("cuda", 0)
     m = loader.CreateFromFile(_path("BossWN-standard.nam"), doPrewarm=False)
-    S, n, steps = 1760, 128, 5
+    S, n, steps = 1760, 128, 22
     big = na.Batch(0)
     big.AddStreams(m, S)
     assert big.StateBytes() > 400 * 1024 * 1024
@@ -1016,7 +1066,8 @@ def test_batches_beyond_the_infinity_cache_mark_their_ring_traffic_non_temporal_
         h.Synchronize()
     assert torch.equal(got, want)
     yo = O.oracle_from_file("BossWN-standard.nam").process(np.concatenate([x[k][S - 1].cpu().numpy() for k in range(steps)]))
-    assert O.rms(np.concatenate([got[k][S - 1].cpu().numpy() for k in range(steps)]) - yo) < TOL_RMS
+    y = np.concatenate([got[k][S - 1].cpu().numpy() for k in range(steps)])
+    assert O.rms(y - yo) < TOL_RMS and O.rms(y[-CW.LATE:] - yo[-CW.LATE:]) < TOL_RMS
     big.close()
     for h in halves:
         h.close()

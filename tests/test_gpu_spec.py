@@ -80,8 +80,9 @@ SEQUENCES = [[128] * 6, [64] * 8, [32] * 8, [128, 37, 64, 100, 32, 128, 1, 64, 1
 @pytest.mark.parametrize("which,streams", [("standard", 3), ("standard", 515), ("lite", 2), ("lite", 513), ("feather", 1030), ("nano", 1031),
                                            ("nano", 6), ("nano", 1003)])
 def test_specialised_chain_is_bit_identical_to_the_interpreter(na, loader, spec_switch, which, streams):
-    """(Nano x 6 / x 1003: at most one packed virtual stream per CU -> the one-tile-per-wave chain, eight waves per stream, partly filled
-    last virtual stream; Nano x 1031: more virtual streams than CUs -> two tiles per wave.)"""
+    """(Nano x 6 / x 1003 / x 1031: partly filled last virtual stream.  Which instantiation these host-buffer calls land on is not what this
+    test is about -- 512 kernel-level streams or more run as two half-batch launches, both at SPB = 1, and the default dense Nano pack
+    never takes the one-tile-per-wave chain: tests/test_gpu_chain_wraps.py pins every instantiation and runs it past its ring wraps.)"""
     m, make_oracle = _models(loader, which)
     rng = np.random.default_rng(11)
     for sizes in SEQUENCES:
