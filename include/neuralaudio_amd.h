@@ -258,7 +258,7 @@ NA_EXTERN int NA_BatchStreamReverbFadeRemaining(NA_Batch* batch, int stream); /*
  * The block every guitar rig has between cabinet and room is a delay: echo, slap-back, dotted-eighth repeats.  A host of the reference
  * runs a delay on the buffer it holds.  Here the rows stay on the device, and an echo added by the host would come BEHIND the reverb:
  * the wrong order.  A ninth per-stream stage, off unless enabled, BEHIND the cabinet stage and IN FRONT OF the reverb stage: a session's
- * chain is model -> gate -> EQ -> cabinet -> delay -> reverb -> output gain -> mix.  The line feeds back through a one-pole low-pass and
+ * chain is model -> gate -> EQ -> cabinet -> delay -> reverb -> output gain -> mix.  (The compressor and modulation stages below sit between cabinet and delay.)  The line feeds back through a one-pole low-pass and
  * a one-pole high-pass, so the repeats darken and thin out as a tape echo's do.  In a resampling batch the stage acts on the
  * external-rate rows, as the cabinet does.  A batch that enabled the stage and set no delay launches exactly what it launched before.
  * Rows without an entry are never touched.
@@ -328,7 +328,7 @@ NA_EXTERN int NA_BatchStreamDelayFadeRemaining(NA_Batch* batch, int stream); /* 
  * block a server needs for its own safety, because two amps summed in a mix group, a makeup gain or a hot capture are not bounded by
  * anything else on the device.  A host of the reference compresses the buffer it holds.  Here the rows stay on the device, so it is a
  * tenth per-stream stage, off unless enabled, BEHIND the cabinet stage and IN FRONT OF the delay stage -- dynamics in front of the
- * time-based effects: a session's chain is model -> gate -> EQ -> cabinet -> compressor -> delay -> reverb -> output gain -> mix.  In
+ * time-based effects: a session's chain is model -> gate -> EQ -> cabinet -> compressor -> delay -> reverb -> output gain -> mix.  (The modulation stage below sits between compressor and delay.)  In
  * a resampling batch the stage acts on the external-rate rows, as the cabinet does.  A batch that enabled the stage and gave no
  * stream a compressor launches exactly what it launched before.  Rows without an entry are never touched.
  * Topology.  Feed-forward: a branching peak follower runs on the row's own samples, a static gain curve is read at the follower's
@@ -410,6 +410,98 @@ NA_EXTERN int NA_BatchSetStreamCompressor(NA_Batch* batch, int stream, const NA_
 NA_EXTERN int NA_BatchGetStreamCompressor(NA_Batch* batch, int stream, NA_CompressorParams* out); /* 1: *out filled (the target); 0: none (or a fade to none); < 0: stage not enabled / bad id */
 NA_EXTERN int NA_BatchStreamCompressorFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's curve fade; 0: none; < 0: stage not enabled / bad id */
 NA_EXTERN float NA_BatchStreamCompressorGain(NA_Batch* batch, int stream); /* the g of the last sample produced; 1: no compressor; < 0: bad id / not enabled */
+/* ---- the modulation stage: per-stream chorus, flanger, vibrato and tremolo ----
+ * A guitar rig has modulation between dynamics and echo, and the delay stage above reads its line at an integer delay that is constant
+ * for a call.  A host that added a chorus itself would add it BEHIND reverb and mix, or give up the zero-copy path.  So it is an
+ * eleventh per-stream stage, off unless enabled, BEHIND the compressor stage and IN FRONT OF the delay stage: a session's chain is
+ * model -> gate -> EQ -> cabinet -> compressor -> modulation -> delay -> reverb -> output gain -> mix.  In a resampling batch the stage
+ * acts on the external-rate rows, as the cabinet does.  A batch that enabled the stage and set nothing launches exactly what it launched
+ * before.  Rows without an entry are never touched.
+ * One mechanism: up to four voices read a short line w of the row's own samples at a fractional delay that an LFO sweeps between
+ * baseSamples and baseSamples + depthSamples; the first voice may feed back into the line; the voices' sum is mixed with the dry sample;
+ * the result may be scaled by the LFO.  A chorus is three voices a third of a cycle apart around 7 ms; a flanger one voice around 1 ms
+ * with feedback; a vibrato one voice with dry = 0; a tremolo wet = 0 and tremoloDepth > 0.
+ * Set-up side (not real-time safe: it allocates and may wait for what is in flight):
+ *   NA_BatchEnableModStage(maxDelaySamples in [8, 4096]) allocates, per row of the batch's capacity, one ring of ringSamples floats, plus
+ *     the stage's tables.  ringSamples is a power of two >= maxDelaySamples + pieceSamples; pieceSamples = 2048 is the longest run the
+ *     stage processes at once, longer calls run in pieces: 16 KB or 32 KB a row, at most 32 MB for 1024 rows.  Later NA_BatchAddStreams /
+ *     NA_BatchReserveStreams grow the rings and tables; the lines of streams that play are kept.  Idempotent for an equal or smaller
+ *     maximum; a larger one is refused while any stream has a modulation.  Every other call fails with
+ *     "modulation stage not enabled (NA_BatchEnableModStage)" before it.  NA_BatchGetModInfo reports the sizes in effect, the number of
+ *     entries and the device memory the stage holds (deviceBytes).
+ * Arithmetic.  Every floating-point operation is one separately rounded f32 operation, fl(.), rounded to nearest even, with no FMA
+ * contraction.  f32 subnormals are kept as operands and as results.  Integers are exact.
+ * Positions.  t counts the samples since T0, the first sample after the set call that took the stream from no modulation.  k counts the
+ * samples since the last set call.  The line starts empty: w[t] = +0 for t < 0, decided by comparing positions, never by what the ring
+ * holds; nothing is cleared on the device.
+ * Limits of a setting: baseSamples >= 2; depthSamples >= 0; fl(baseSamples + depthSamples) <= maxDelaySamples - 2; numVoices in [1, 4];
+ * |voiceGain| <= 4; |feedback| <= 0.95; wet and dry finite, |.| <= 1e6; tremoloDepth in [0, 1]; shape is NA_MOD_TRIANGLE or NA_MOD_SINE.
+ * LFO, with no transcendental and no accumulation:
+ *   u_v = phaseAtSet + (unsigned)(k * phaseInc) + voicePhase[v]                 (modulo 2^32: the low word of the 64-bit product)
+ *   h   = (u_v & 0x80000000) ? ~u_v : u_v
+ *   tri = fl((float)(h >> 7) * 2^-24)                                           (exact, in [0, 1))
+ *   s_v = tri                                                                   for NA_MOD_TRIANGLE
+ *   s_v = min(fl(fl(tri * tri) * fl(3 - fl(2 * tri))), 1)                       for NA_MOD_SINE: the smoothstep of the triangle
+ *   phaseAtSet is 0 at T0.  Every set call advances it by the old (unsigned)(k * phaseInc): a new rate acts at once on a continuous phase.
+ *   Both shapes stay in [0, 1] for every one of the 2^24 values of tri.  The "sine" lies within about 0.01 of the raised cosine
+ *   (1 - cos(pi tri)) / 2 (measured maximum 0.010009, at tri = 0.7215 and its mirror; tests/test_mod_cpu.py).
+ * Per sample, in order, x the row's sample and y what replaces it; base, depth, fb, wet, dry, td = tremoloDepth and the gains g_v are
+ * the (ramped) values of the sample:
+ *   x'    = isnan(x) ? 0 : clamp(x, +-1e18f)
+ *   per voice v < numVoices:
+ *     D   = fl(base + fl(depth * s_v));  Di = (int)D;  fr = fl(D - (float)Di)
+ *     a   = w[t - Di];  b = w[t - Di - 1]                                       (+0 in front of the line's start)
+ *     tap_v = fl(a + fl(fr * fl(b - a)))
+ *   m     = fl(g_0 * tap_0), then m = fl(m + fl(g_v * tap_v)) in voice order
+ *   w[t]  = (fb == 0) ? x' : clamp(fl(x' + fl(fb * tap_0)), +-1e30f)
+ *   y0    = (wet == 0) ? fl(dry * x') : fl(fl(dry * x') + fl(wet * m))
+ *   y     = (td == 0) ? y0 : fl(y0 * fl(1 - fl(td * s_0)))
+ * The clamps are exact min / max.  With the limits above every value stays finite whatever the input.
+ * Set calls and fades.  A set call moves the stream from setting A to setting B over N = fadeSamples in [0, 1 << 20], with the weight
+ * the other stages use: wk = 1 for k >= N - 1 and (float)(k + 1) / (float)N otherwise.
+ *   base, depth, fb, wet, dry, td and the four voice gains each take B's value where wk == 1, else fl(g_A + fl(fl(g_B - g_A) * wk)).  The
+ *     delay is fractional already, so a new delay time glides: there is no read-head cross-fade.
+ *   A voice absent from a setting has gain 0 in it.
+ *   numVoices, voicePhase and phaseInc are B's from k = 0.  A set call that changes voicePhase[v] of a voice whose gain in A is non-zero
+ *     is refused by name ("voicePhase[<v>] of a sounding voice must not change").
+ *   If the shapes differ, s_v = fl(fl(fl(1 - wk) * sA_v) + fl(wk * sB_v)) while wk != 1.
+ *   "None" as A is B with wet = 0, dry = 1, td = 0, fb = 0: a new effect fades in on an empty line.
+ *   "None" as B (params == NULL) is A with wet = 0, dry = 1, td = 0: the effect fades out; the entry retires with the sample at which the
+ *     fade ends -- later samples of that call's row are not touched -- and the history is dropped.  With N = 0 it retires at once.
+ *   A set call while a fade of that stream is running is refused with the samples left ("a modulation fade of stream <s> is running
+ *     (<k> samples left)").  The caller polls NA_BatchStreamModFadeRemaining.
+ * Consequences.  A sample's bits do not depend on the cut into calls, on alignment, on stride, on in-place use, on the other entries or
+ * on maxDelaySamples.  With wet = 0, dry = 1, td = 0 the row is x' bit for bit.  With depth = 0, an integer base = D, one voice of gain 1,
+ * wet = 1, dry = 0 and fb = 0.5 an impulse gives exact powers of two at the multiples of D, down through the subnormals.  With
+ * base = D + 0.5 and fb = 0 an impulse gives exactly 0.5 at D and at D + 1.  With td = 1, wet = 0, dry = 1 and a constant input of 1,
+ * y = fl(1 - s_0).  A restatement in f32 that follows the lines above operation for operation (tests/mod_cases.py) is bit-exact.
+ * NA_ModParamsFromMs is host arithmetic in double, each value rounded once: baseSamples and depthSamples are ms * rate / 1000;
+ * phaseInc = round(rateHz / rate * 2^32), rateHz in [0, rate / 2]; voicePhase[v] = floor(v * 2^32 / voices); voiceGain[v] = 1 / voices;
+ * wet = 10^(wetDb / 20) with -inf -> 0, dry likewise.  It refuses what the set call would refuse (a reach beyond 4094 samples
+ * included).  It needs no batch.
+ * Rules (each fails with a message that names the field or the stream, NA_GetLastError): the stage must be enabled; the stream must be
+ * live (a parked one fails with "... is parked"); every field must be within the limits above; a broken batch refuses everything.
+ * NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a hand-over, drop the modulation and its history at once.
+ * Modulations are not part of a NA_BatchSaveStreams blob.
+ * NA_BatchSetStreamMod, NA_BatchGetStreamMod and NA_BatchStreamModFadeRemaining are REAL-TIME SAFE: host arithmetic on tables that
+ * exist.  While an entry exists -- a stream with a modulation, or a fade towards none -- a processing call behaves as it does with the
+ * other stages' entries: it takes the ordered path, host buffers go through the staging block, and it enqueues one table upload from
+ * the ring of pinned tables and one launch per piece over the entries only: no allocation, no stream or event creation, no unbounded
+ * wait.  With the last entry the free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches and on the one-stream NeuralModel; more than four voices; through-zero flanging; a phaser
+ * (all-pass stages); stereo spread across the rows of a mix group; tempo helpers. */
+#define NA_MOD_TRIANGLE 0
+#define NA_MOD_SINE     1
+typedef struct NA_ModParams { float baseSamples, depthSamples; unsigned phaseInc; int shape, numVoices;
+                              unsigned voicePhase[4]; float voiceGain[4]; float feedback, wet, dry, tremoloDepth; } NA_ModParams; /* 68 bytes */
+typedef struct NA_ModInfo   { int maxDelaySamples, ringSamples, pieceSamples, numMods; long long deviceBytes; } NA_ModInfo;
+NA_EXTERN int NA_ModParamsFromMs(int sampleRate, double baseMs, double depthMs, double rateHz, int shape, int voices,
+                                 double feedback, double wetDb, double dryDb, double tremoloDepth, NA_ModParams* out);
+NA_EXTERN int NA_BatchEnableModStage(NA_Batch* batch, int maxDelaySamples);     /* [8, 4096]; idempotent for equal or smaller; larger refused while entries exist */
+NA_EXTERN int NA_BatchGetModInfo(NA_Batch* batch, NA_ModInfo* info);
+NA_EXTERN int NA_BatchSetStreamMod(NA_Batch* batch, int stream, const NA_ModParams* params, int fadeSamples);  /* params = NULL: the effect goes, click-free */
+NA_EXTERN int NA_BatchGetStreamMod(NA_Batch* batch, int stream, NA_ModParams* out); /* 1: *out filled (the target); 0: none (or a fade to none); < 0: stage not enabled / bad id */
+NA_EXTERN int NA_BatchStreamModFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's modulation fade; 0: none; < 0: stage not enabled / bad id */
 /* ---- the gate stage: a per-stream noise gate ----
  * High-gain captures turn pickup hum into a loud hiss between notes.  A host of the reference gates that itself: it listens to the dry
  * input and scales the amp's output, because it holds both buffers.  Here the rows stay on the device, and a gate needs both ends of a
@@ -1164,6 +1256,10 @@ NA_EXTERN long long NA_DebugDelayLaunches(void);
 NA_EXTERN int NA_DebugRunCompressorStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
 /* Tests: launches of the compressor stage's kernel so far (one per processing call with entries) */
 NA_EXTERN long long NA_DebugCompressorLaunches(void);
+/* Tests: as NA_DebugRunCabinetStage, for the modulation stage: the stage alone on given rows -- table, launches, book advance */
+NA_EXTERN int NA_DebugRunModStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
+/* Tests: launches of the modulation stage's kernel so far (one per piece of a call with entries) */
+NA_EXTERN long long NA_DebugModLaunches(void);
 /* Tests: launches of the gate stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugGateLaunches(void);
 /* Tests: launches of the meter stage's two kernels so far (two per processing call with entries) */

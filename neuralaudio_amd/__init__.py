@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "mod_params_from_ms", "MOD_TRIANGLE", "MOD_SINE", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -99,6 +99,42 @@ def compressor_params_from_db(sample_rate, threshold_db, ratio, knee_db=0.0, mak
                                                      float(attack_ms), float(release_ms), C.byref(out)) != 0:
         raise NeuralAudioError(capi.last_error())
     return _compressor_dict(out)
+
+
+MOD_TRIANGLE, MOD_SINE = 0, 1
+MOD_SCALARS = (("baseSamples", float), ("depthSamples", float), ("phaseInc", int), ("shape", int), ("numVoices", int), ("feedback", float),
+               ("wet", float), ("dry", float), ("tremoloDepth", float))
+
+
+def _mod_dict(p):
+    d = {name: kind(getattr(p, name)) for name, kind in MOD_SCALARS}
+    d["voicePhase"] = [int(v) for v in p.voicePhase]
+    d["voiceGain"] = [float(v) for v in p.voiceGain]
+    return d
+
+
+def _mod_params(d):
+    if isinstance(d, capi.NA_ModParams):
+        return d
+    p = capi.NA_ModParams()
+    for name, _ in MOD_SCALARS:
+        setattr(p, name, d[name])
+    if len(d["voicePhase"]) != 4 or len(d["voiceGain"]) != 4:
+        raise NeuralAudioError("a modulation has four voicePhase and four voiceGain values")
+    for v in range(4):
+        p.voicePhase[v] = int(d["voicePhase"][v])
+        p.voiceGain[v] = d["voiceGain"][v]
+    return p
+
+
+def mod_params_from_ms(sample_rate, base_ms, depth_ms, rate_hz, shape=MOD_SINE, voices=1, feedback=0.0, wet_db=0.0, dry_db=0.0, tremolo_depth=0.0):
+    """The constants Batch.SetStreamMod takes, from milliseconds, hertz and decibels (NA_ModParamsFromMs): the voices lie 1 / voices of a
+    cycle apart with gain 1 / voices each; -inf dB is 0.  Host arithmetic: needs no device."""
+    out = capi.NA_ModParams()
+    if capi.load_library().NA_ModParamsFromMs(int(sample_rate), float(base_ms), float(depth_ms), float(rate_hz), int(shape), int(voices), float(feedback),
+                                              float(wet_db), float(dry_db), float(tremolo_depth), C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _mod_dict(out)
 
 
 DELAY_FIELDS = ("delaySamples", "feedback", "lowpassCoeff", "highpassCoeff", "wet", "dry")
@@ -748,6 +784,42 @@ class Batch:
     def DebugRunDelayStage(self, rows, n=None):
         """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunDelayStage)."""
         return self._debug_run_stage(self._lib.NA_DebugRunDelayStage, rows, n)
+
+    # -- the modulation stage: EnableModStage is set-up side; SetStreamMod is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableModStage(self, maxDelaySamples):
+        if self._lib.NA_BatchEnableModStage(self._h, int(maxDelaySamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetModInfo(self):
+        info = capi.NA_ModInfo()
+        if self._lib.NA_BatchGetModInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_ModInfo._fields_}
+
+    def SetStreamMod(self, stream, params, fadeSamples=0):
+        """A chorus, flanger, vibrato or tremolo on the stream from the next sample on: `params` a dict of the NA_ModParams fields
+        (mod_params_from_ms makes one) or the struct itself; None: the effect goes.  The change runs over `fadeSamples` samples."""
+        p = None if params is None else C.byref(_mod_params(params))
+        if self._lib.NA_BatchSetStreamMod(self._h, int(stream), p, int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamMod(self, stream):
+        """The target setting as a dict; None: no modulation (or one that fades to none)."""
+        out = capi.NA_ModParams()
+        rc = int(self._lib.NA_BatchGetStreamMod(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _mod_dict(out) if rc else None
+
+    def StreamModFadeRemaining(self, stream):
+        left = int(self._lib.NA_BatchStreamModFadeRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
+
+    def DebugRunModStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunModStage)."""
+        return self._debug_run_stage(self._lib.NA_DebugRunModStage, rows, n)
 
     # -- the compressor stage: EnableCompressorStage is set-up side; SetStreamCompressor is real-time safe (include/neuralaudio_amd.h) ----
     def EnableCompressorStage(self):

@@ -50,6 +50,8 @@ NA_SYMBOLS = [
     "NA_CompressorParamsFromDb", "NA_BatchEnableCompressorStage", "NA_BatchGetCompressorInfo", "NA_BatchSetStreamCompressor",
     "NA_BatchGetStreamCompressor", "NA_BatchStreamCompressorFadeRemaining", "NA_BatchStreamCompressorGain", "NA_DebugRunCompressorStage",
     "NA_DebugCompressorLaunches",
+    "NA_ModParamsFromMs", "NA_BatchEnableModStage", "NA_BatchGetModInfo", "NA_BatchSetStreamMod", "NA_BatchGetStreamMod",
+    "NA_BatchStreamModFadeRemaining", "NA_DebugRunModStage", "NA_DebugModLaunches",
     "NA_GateParamsFromDb", "NA_BatchEnableGateStage", "NA_BatchGetGateInfo", "NA_BatchSetStreamGate", "NA_BatchGetStreamGate",
     "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
     "NA_EqSectionFromDesign", "NA_BatchEnableEqStage", "NA_BatchGetEqInfo", "NA_BatchSetStreamEq", "NA_BatchGetStreamEq",
@@ -111,6 +113,17 @@ class NA_CompressorParams(C.Structure):
 
 class NA_CompressorInfo(C.Structure):
     _fields_ = [("curvePoints", C.c_int), ("numCompressors", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+class NA_ModParams(C.Structure):
+    _fields_ = [("baseSamples", C.c_float), ("depthSamples", C.c_float), ("phaseInc", C.c_uint), ("shape", C.c_int), ("numVoices", C.c_int),
+                ("voicePhase", C.c_uint * 4), ("voiceGain", C.c_float * 4), ("feedback", C.c_float), ("wet", C.c_float), ("dry", C.c_float),
+                ("tremoloDepth", C.c_float)]
+
+
+class NA_ModInfo(C.Structure):
+    _fields_ = [("maxDelaySamples", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numMods", C.c_int),
+                ("deviceBytes", C.c_longlong)]
 
 
 class NA_GateParams(C.Structure):
@@ -305,6 +318,14 @@ def load_library():
         "NA_BatchStreamCompressorGain": (C.c_float, [vp, C.c_int]),
         "NA_DebugRunCompressorStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
         "NA_DebugCompressorLaunches": (C.c_longlong, []),
+        "NA_ModParamsFromMs": (C.c_int, [C.c_int] + [C.c_double] * 3 + [C.c_int] * 2 + [C.c_double] * 4 + [C.POINTER(NA_ModParams)]),
+        "NA_BatchEnableModStage": (C.c_int, [vp, C.c_int]),
+        "NA_BatchGetModInfo": (C.c_int, [vp, C.POINTER(NA_ModInfo)]),
+        "NA_BatchSetStreamMod": (C.c_int, [vp, C.c_int, C.POINTER(NA_ModParams), C.c_int]),
+        "NA_BatchGetStreamMod": (C.c_int, [vp, C.c_int, C.POINTER(NA_ModParams)]),
+        "NA_BatchStreamModFadeRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_DebugRunModStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
+        "NA_DebugModLaunches": (C.c_longlong, []),
         "NA_GateParamsFromDb": (C.c_int, [C.c_int] + [C.c_float] * 7 + [C.POINTER(NA_GateParams)]),
         "NA_BatchEnableGateStage": (C.c_int, [vp]),
         "NA_BatchGetGateInfo": (C.c_int, [vp, C.POINTER(NA_GateInfo)]),

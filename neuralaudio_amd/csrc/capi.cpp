@@ -916,6 +916,117 @@ int NA_DebugRunCompressorStage(NA_Batch* batch, float* hostRows, long stride, si
 long long NA_DebugCompressorLaunches(void) { return (long long)na::CompressorStageLaunches(); }
 #endif
 
+// ---- the modulation stage (gpu_batch.h EnableModStage / SetStreamMod) ----
+static_assert(sizeof(NA_ModParams) == sizeof(na::ModParams) && sizeof(NA_ModParams) == 68, "NA_ModParams is ModParams, field for field");
+static_assert(NA_MOD_TRIANGLE == na::kModTriangle && NA_MOD_SINE == na::kModSine, "the shapes' constants");
+namespace
+{
+	void ModParamsIn(const NA_ModParams& p, na::ModParams& c)
+	{
+		c.baseSamples = p.baseSamples;
+		c.depthSamples = p.depthSamples;
+		c.phaseInc = p.phaseInc;
+		c.shape = p.shape;
+		c.numVoices = p.numVoices;
+		for (int v = 0; v < na::kModMaxVoices; v++)
+		{
+			c.voicePhase[v] = p.voicePhase[v];
+			c.voiceGain[v] = p.voiceGain[v];
+		}
+		c.feedback = p.feedback;
+		c.wet = p.wet;
+		c.dry = p.dry;
+		c.tremoloDepth = p.tremoloDepth;
+	}
+	void ModParamsOut(const na::ModParams& c, NA_ModParams* p)
+	{
+		p->baseSamples = c.baseSamples;
+		p->depthSamples = c.depthSamples;
+		p->phaseInc = c.phaseInc;
+		p->shape = c.shape;
+		p->numVoices = c.numVoices;
+		for (int v = 0; v < na::kModMaxVoices; v++)
+		{
+			p->voicePhase[v] = c.voicePhase[v];
+			p->voiceGain[v] = c.voiceGain[v];
+		}
+		p->feedback = c.feedback;
+		p->wet = c.wet;
+		p->dry = c.dry;
+		p->tremoloDepth = c.tremoloDepth;
+	}
+}
+
+int NA_ModParamsFromMs(int sampleRate, double baseMs, double depthMs, double rateHz, int shape, int voices, double feedback, double wetDb, double dryDb, double tremoloDepth,
+	NA_ModParams* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_ModParamsFromMs: bad argument");
+		na::ModParams c;
+		if (const char* why = na::ModParamsFromMs(sampleRate, baseMs, depthMs, rateHz, shape, voices, feedback, wetDb, dryDb, tremoloDepth, c))
+			throw std::runtime_error(std::string("NA_ModParamsFromMs: ") + why);
+		ModParamsOut(c, out);
+	});
+}
+
+int NA_BatchEnableModStage(NA_Batch* batch, int maxDelaySamples)
+{
+	return BatchCall(batch, "NA_BatchEnableModStage", [&](na::GpuBatch& b) { b.EnableModStage(maxDelaySamples); });
+}
+
+int NA_BatchGetModInfo(NA_Batch* batch, NA_ModInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetModInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetModInfo: bad argument");
+		const na::ModStageInfo i = b.GetModInfo();
+		info->maxDelaySamples = i.maxDelaySamples;
+		info->ringSamples = i.ringSamples;
+		info->pieceSamples = i.pieceSamples;
+		info->numMods = i.numMods;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamMod(NA_Batch* batch, int stream, const NA_ModParams* params, int fadeSamples)
+{
+	return BatchCall(batch, "NA_BatchSetStreamMod", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamMod(stream, nullptr, fadeSamples);
+			return;
+		}
+		na::ModParams c;
+		ModParamsIn(*params, c);
+		b.SetStreamMod(stream, &c, fadeSamples);
+	});
+}
+
+int NA_BatchGetStreamMod(NA_Batch* batch, int stream, NA_ModParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamMod", -1, [&](na::GpuBatch& b) {
+		na::ModParams c;
+		const int has = b.GetStreamMod(stream, c) ? 1 : 0;
+		if (has && out) ModParamsOut(c, out);
+		return has;
+	});
+}
+
+int NA_BatchStreamModFadeRemaining(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchStreamModFadeRemaining", -1, [&](na::GpuBatch& b) { return b.StreamModFadeRemaining(stream); });
+}
+
+#ifndef NA_RELEASE
+int NA_DebugRunModStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunModStage: null batch");
+		batch->batch->DebugRunModStage(hostRows, stride, n);
+	});
+}
+long long NA_DebugModLaunches(void) { return (long long)na::ModStageLaunches(); }
+#endif
+
 // ---- the gate stage (gpu_batch.h EnableGateStage / SetStreamGate) ----
 namespace
 {

@@ -621,11 +621,11 @@ namespace na
 	// One processing call on `launch`, and the one place that states its order: what a stage runs in front of the models, in StageId
 	// order -- the gate detector, then the mix stage's stash of the input rows its DRY members name (2.16), then the meter's IN tap (2.14), then the tuner's append and evaluate launches (2.15):
 	// they read the input rows as the caller passed them, which may be the output rows, so before any model writes --, the up kernel, the model launches and the down kernel of a
-	// resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages (DESIGN.md 2.9 - 2.19) once per
+	// resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages (DESIGN.md 2.9 - 2.20) once per
 	// call: behind everything the call has launched -- the join of the units, the graph replay, the down kernel -- on the same stream,
 	// outside any capture.  The stages' order is the order of StageId (gpu_batch.h), written there and nowhere else: every row is
 	// gated first, then runs through its own EQ cascade (the tone stack sits between amp and cabinet), then is convolved with its own
-	// IR (the cabinet's tail rings out through a closing gate), then is compressed by its own level follower and gain curve (dynamics in front of the time-based effects: the compressor stage, 2.19), then runs through its delay line (the echo sits between cabinet and room: the delay stage, 2.18), then runs through its reverb (the room comes behind the cabinet: the reverb stage, 2.17), then is scaled and cross-faded, then the rows of a mix group meet in its
+	// IR (the cabinet's tail rings out through a closing gate), then is compressed by its own level follower and gain curve (dynamics in front of the time-based effects: the compressor stage, 2.19), then is modulated -- chorus, flanger, vibrato, tremolo -- by its own swept line (modulation between dynamics and echo: the modulation stage, 2.20), then runs through its delay line (the echo sits between cabinet and room: the delay stage, 2.18), then runs through its reverb (the room comes behind the cabinet: the reverb stage, 2.17), then is scaled and cross-faded, then the rows of a mix group meet in its
 	// output rows (the one stage in which rows meet: behind everything a row goes through on its own); last the meter's OUT and GATE taps read
 	// the row the caller receives and the gains the gate applied to it -- they write no audio; the tuner, last in StageId, has nothing
 	// left to run there.
@@ -659,7 +659,7 @@ namespace na
 			if (stage) stage->Leave(s);
 	}
 
-	// test hooks (NA_DebugRunCabinetStage, NA_DebugRunCompressorStage, NA_DebugRunDelayStage, NA_DebugRunReverbStage, NA_DebugRunEqStage, NA_DebugRunMixStage): what a processing call of n samples runs for the stage, on host rows in
+	// test hooks (NA_DebugRunCabinetStage, NA_DebugRunCompressorStage, NA_DebugRunModStage, NA_DebugRunDelayStage, NA_DebugRunReverbStage, NA_DebugRunEqStage, NA_DebugRunMixStage): what a processing call of n samples runs for the stage, on host rows in
 	// place of model outputs
 	void GpuBatch::DebugRunStage(Stage& stage, const char* who, float* hostRows, long stride, size_t n, const float* hostIn)
 	{

@@ -27,6 +27,7 @@
 #include "host_route.h"
 #include "launch_plan.h"
 #include "meter_stage.h"
+#include "mod_stage.h"
 #include "mix_stage.h"
 #include "tuner_stage.h"
 #include "model_loader.h"
@@ -92,6 +93,12 @@ namespace na
 	struct CompressorStageInfo
 	{
 		int curvePoints = 0, numCompressors = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct ModStageInfo
+	{
+		int maxDelaySamples = 0, ringSamples = 0, pieceSamples = 0, numMods = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -252,6 +259,21 @@ namespace na
 		float StreamCompressorGain(int stream); // the g of the last sample produced; 1: no compressor.  Synchronises: a diagnostic
 		// test hook (NA_DebugRunCompressorStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
 		void DebugRunCompressorStage(float* hostRows, long stride, size_t n);
+
+		// The modulation stage (mod_stage.h): per-stream chorus, flanger, vibrato and tremolo -- up to four voices that read a
+		// line of up to kModMaxDelaySamples samples at a fractional, LFO-swept delay, a feedback of the first voice, a wet / dry mix and an
+		// amplitude modulation -- behind the compressor stage and in front of the delay stage.  EnableModStage is the set-up side: a ring per
+		// row (CreateStreams grows them) and the tables.  SetStreamMod is host arithmetic on those tables; while an entry exists -- a stream
+		// with a modulation, or a fade towards none -- every processing call runs on the ordered path and enqueues ONE table upload and ONE
+		// launch per piece of kModPieceSamples samples.  Without an entry the batch launches exactly what it launches without the stage.
+		void EnableModStage(int maxDelaySamples);
+		bool HasModStage() const { return stages[kModStage] != nullptr; }
+		ModStageInfo GetModInfo() const;
+		void SetStreamMod(int stream, const ModParams* params, int fadeSamples); // nullptr: no modulation
+		bool GetStreamMod(int stream, ModParams& out) const;                     // the target; false: none
+		int StreamModFadeRemaining(int stream) const;
+		// test hook (NA_DebugRunModStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
+		void DebugRunModStage(float* hostRows, long stride, size_t n);
 
 		// The gate stage (gate_stage.h): a per-stream noise gate that listens to the stream's input row and scales the row
 		// the models produced for it -- the detector launch in front of everything of the call, the apply launch first of the stages, in
@@ -483,9 +505,9 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.19).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.20).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kCompressorStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kGateStage, kEqStage, kCabinetStage, kCompressorStage, kModStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
@@ -498,7 +520,7 @@ namespace na
 		};
 		template <class Book, class Entry> struct StageOf;
 		template <class Record> struct StageResults; // the result blocks of the stages that report to the host (meter, tuner)
-		struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
+		struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct ModStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -299,7 +299,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the ten stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the eleven stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -383,6 +383,21 @@ namespace na
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + launch + the host mirror's advance
 	};
 	hipError_t LaunchCompressorStage(const CompLaunch& L, hipStream_t stream); // (compressor_stage_kernels.hip)
+
+	// the modulation stage (mod_stage.h, mod_stage.cpp): the rows' lines (rings)
+	struct GpuBatch::ModStage : StageOf<ModBook, ModEntry>
+	{
+		static constexpr StageId kId = kModStage;
+		static constexpr const char* kNotEnabled = "modulation stage not enabled (NA_BatchEnableModStage)";
+		float* rings = nullptr;           // [ringRows][book.RingSamples()]
+		int ringRows = 0;
+		ModStage() : StageOf("modulation stage") {}
+		~ModStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // no modulation at once, its history dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + one launch per piece + the host mirror's advance
+	};
+	hipError_t LaunchModStage(const ModLaunch& L, hipStream_t stream); // (mod_stage_kernels.hip) the launch of one piece
 
 	// the delay stage (delay_stage.h, delay_stage.cpp): the rows' delay lines (rings) and filter states
 	struct GpuBatch::DelayStage : StageOf<DelayBook, DelayEntry>

@@ -53,6 +53,12 @@
 //       the plain run below with the compressor stage enabled and a compressor on the first N streams: threshold -24 dB, ratio 4, knee
 //       6 dB, makeup 3 dB, attack A ms, release R ms at 48 kHz (NA_CompressorParamsFromDb) -- (N = 0: enabled, no compressor set: must
 //       cost nothing).  Times every buffer period like --tuner; the same device span as --gate.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --mod N [--mod-base-ms B=7 --mod-depth-ms 3 --mod-rate-hz 0.8 --mod-voices 3 --mod-fb 0]
+//       the plain run below with the modulation stage enabled (maxDelaySamples = 4096) and a modulation on the first N streams: voices a
+//       1 / voices of a cycle apart around B ms at 48 kHz, "sine" shape, wet -3 dB, dry 0 dB (NA_ModParamsFromMs); the defaults are a
+//       chorus, --mod-base-ms 1 --mod-fb 0.7 (depth then defaults to 0.9 ms, one voice) a flanger -- (N = 0: enabled, nothing set: must
+//       cost nothing).  With N > 0 the run first feeds 4096 samples, so that every line is full.  Times every buffer period like --tuner;
+//       the same device span as --gate.
 // Prints one JSON object: microseconds per buffer for the copying entry points (caller-owned buffers) and for the zero-copy ones
 // (NA_BatchNextInput / NA_BatchOutputView: the host produces into / consumes from the pinned staging buffers), two buffers in
 // flight, plus the blocking NA_BatchProcess latency.  bench.py reports these as "pcie_inclusive" (never as `value`).
@@ -602,7 +608,7 @@ static int RunCabinet(NeuralModel* model, int streams, int frames, int buffers, 
 
 int main(int argc, char** argv)
 {
-	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]] [--mix N [--mix-dry]] [--reverb N [--reverb-taps K] [--reverb-irs M]] [--delay N [--delay-samples D]] [--comp N [--comp-ms A] [--comp-release-ms R]]\n"); return 2; }
+	if (argc < 2) { std::fprintf(stderr, "usage: HostPipeBench <model> [streams] [frames] [buffers] [--gpus N] [--devices a,b,...] [--mix <model 2>] [--fan-in rccl] [--loopback] [--migrate K] [--churn K [--churn-legacy] [--churn-every E]] [--handover K [--fade N]] [--cab TAPS [--cab-irs M]] [--gate K] [--eq K [--eq-sections S]] [--meter K [--meter-window W]] [--tuner K [--tuner-hop H] [--tuner-stagger]] [--mix N [--mix-dry]] [--reverb N [--reverb-taps K] [--reverb-irs M]] [--delay N [--delay-samples D]] [--comp N [--comp-ms A] [--comp-release-ms R]] [--mod N [--mod-base-ms B] [--mod-depth-ms D] [--mod-rate-hz R] [--mod-voices V] [--mod-fb F]]\n"); return 2; }
 	std::vector<const char*> pos;
 	std::vector<int> devices;
 	int gpus = 0;
@@ -611,6 +617,8 @@ int main(int argc, char** argv)
 	int migrate = 0, churn = 0, churnEvery = 10, handover = 0, fade = 256, cab = 0, cabIRs = 1, gate = -1, eq = -1, eqSections = 3, meter = -1, meterWindow = 1024, tuner = -1, tunerHop = 0;
 	int mixGroups = -1, reverb = -1, reverbTaps = 48000, reverbIRs = 1, delay = -1, delaySamples = 18000;
 	int comp = -1;
+	int mod = -1, modVoices = -1;
+	double modBaseMs = 7.0, modDepthMs = -1.0, modRateHz = 0.8, modFb = 0.0;
 	float compAttackMs = 5.0f, compReleaseMs = 100.0f;
 	bool churnLegacy = false, tunerStagger = false, mixDry = false;
 	for (int i = 1; i < argc; i++)
@@ -639,6 +647,12 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--delay") && i + 1 < argc) delay = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--delay-samples") && i + 1 < argc) delaySamples = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--comp") && i + 1 < argc) comp = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--mod") && i + 1 < argc) mod = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--mod-base-ms") && i + 1 < argc) modBaseMs = std::atof(argv[++i]);
+		else if (!std::strcmp(argv[i], "--mod-depth-ms") && i + 1 < argc) modDepthMs = std::atof(argv[++i]);
+		else if (!std::strcmp(argv[i], "--mod-rate-hz") && i + 1 < argc) modRateHz = std::atof(argv[++i]);
+		else if (!std::strcmp(argv[i], "--mod-voices") && i + 1 < argc) modVoices = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--mod-fb") && i + 1 < argc) modFb = std::atof(argv[++i]);
 		else if (!std::strcmp(argv[i], "--comp-ms") && i + 1 < argc) compAttackMs = (float)std::atof(argv[++i]);
 		else if (!std::strcmp(argv[i], "--comp-release-ms") && i + 1 < argc) compReleaseMs = (float)std::atof(argv[++i]);
 		else if (!std::strcmp(argv[i], "--gate") && i + 1 < argc) gate = std::atoi(argv[++i]);
@@ -811,6 +825,21 @@ int main(int argc, char** argv)
 		reverbInputSpectrumBytes = (long long)reverb * tailPartitions * 2048 * ((frames + info.partitionSamples - 1) / info.partitionSamples);
 		reverbDistinctIRBytes = reverb > 0 ? (long long)reverbIRs * tailPartitions * 2048 : 0;
 	}
+	long long modBytes = 0;
+	if (mod >= 0)
+	{
+		// a chorus by default; with feedback a flanger: one voice, a sweep just below the base
+		if (modVoices < 0) modVoices = modFb != 0.0 ? 1 : 3;
+		if (modDepthMs < 0.0) modDepthMs = modFb != 0.0 ? 0.9 * modBaseMs : 3.0;
+		CHECK(NA_BatchEnableModStage(batch, 4096) == 0);
+		mod = std::min(mod, streams);
+		NA_ModParams mp;
+		CHECK(NA_ModParamsFromMs(48000, modBaseMs, modDepthMs, modRateHz, NA_MOD_SINE, modVoices, modFb, -3.0, 0.0, 0.0, &mp) == 0);
+		for (int s = 0; s < mod; s++) CHECK(NA_BatchSetStreamMod(batch, s, &mp, 0) == 0);
+		NA_ModInfo info;
+		CHECK(NA_BatchGetModInfo(batch, &info) == 0);
+		modBytes = info.deviceBytes;
+	}
 	long long delayBytes = 0;
 	if (delay >= 0)
 	{
@@ -828,7 +857,7 @@ int main(int argc, char** argv)
 	unsigned long long meterWindows = 0; // (--meter: `windows` of the last reading of stream 0 in the pipelined loop)
 	unsigned long long tunerEvaluations = 0; // (--tuner: `evaluations` of the last reading of stream 0 in the pipelined loop)
 	std::vector<double> periods;             // (--tuner, --mix N: every buffer period of the pipelined loop)
-	const bool marks = gate >= 0 || comp >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0; // (the plain run stays what it was)
+	const bool marks = gate >= 0 || comp >= 0 || mod >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -838,6 +867,8 @@ int main(int argc, char** argv)
 		for (long long fed = 0; fed < reverbTaps; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 
 	// (--delay N > 0: the lines fill first -- from then on every read of a ring is a read of a sample the stage wrote)
+	if (mod > 0)
+		for (long long fed = 0; fed < 4096; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 	if (delay > 0)
 		for (long long fed = 0; fed < delaySamples; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 
@@ -909,7 +940,7 @@ int main(int argc, char** argv)
 			CHECK(have >= 0);
 			if (have) tunerEvaluations = reading.evaluations;
 		}
-		if (tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0 || comp >= 0) periods.push_back(Now());
+		if (tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0 || comp >= 0 || mod >= 0) periods.push_back(Now());
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
@@ -966,9 +997,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"reverb\": %d, \"reverb_taps\": %d, \"reverb_irs\": %d, \"reverb_device_bytes\": %lld, \"reverb_load_irs_ms\": %.1f, \"reverb_input_spectrum_bytes_per_buffer\": %lld, \"reverb_distinct_ir_spectrum_bytes\": %lld, \"delay\": %d, \"delay_samples\": %d, \"delay_device_bytes\": %lld, \"comp\": %d, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"reverb\": %d, \"reverb_taps\": %d, \"reverb_irs\": %d, \"reverb_device_bytes\": %lld, \"reverb_load_irs_ms\": %.1f, \"reverb_input_spectrum_bytes_per_buffer\": %lld, \"reverb_distinct_ir_spectrum_bytes\": %lld, \"delay\": %d, \"delay_samples\": %d, \"delay_device_bytes\": %lld, \"comp\": %d, \"mod\": %d, \"mod_voices\": %d, \"mod_feedback\": %.3g, \"mod_device_bytes\": %lld, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, reverb, reverb >= 0 ? reverbTaps : 0, reverb > 0 ? reverbIRs : 0, reverbBytes, reverbLoadMs, reverbInputSpectrumBytes, reverbDistinctIRBytes, delay, delay >= 0 ? delaySamples : 0, delayBytes, comp, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, reverb, reverb >= 0 ? reverbTaps : 0, reverb > 0 ? reverbIRs : 0, reverbBytes, reverbLoadMs, reverbInputSpectrumBytes, reverbDistinctIRBytes, delay, delay >= 0 ? delaySamples : 0, delayBytes, comp, mod, mod >= 0 ? modVoices : 0, mod >= 0 ? modFb : 0.0, modBytes, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
