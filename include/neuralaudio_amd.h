@@ -864,7 +864,9 @@ NA_EXTERN int NA_BatchPrewarm(NA_Batch* batch, int stream); /* stream < 0: all *
 NA_EXTERN int NA_BatchProcess(NA_Batch* batch, const float* in, float* out, size_t n);
 /* Optional, for hosts that reuse their buffers: a registered block (pinned and mapped: hipHostRegister) is read / written by the kernels
  * as it is when NA_BatchProcess is handed pointers inside it -- no staging copies (1024 x 128: 81 -> ~62 us per call).  Register once,
- * outside the audio path (it pins pages: milliseconds); the block must stay allocated until NA_UnregisterHostBuffer.  0 on success. */
+ * outside the audio path (it pins pages: milliseconds); the block must stay allocated until NA_UnregisterHostBuffer.  0 on success.
+ * A block that was allocated pinned (hipHostMalloc) is taken as it is, and is what a host passes where the runtime cannot pin pages a
+ * process already has (hipHostRegister fails on some virtual machines: the call then returns -1 and the copies stay). */
 NA_EXTERN int NA_RegisterHostBuffer(void* ptr, size_t bytes);
 NA_EXTERN int NA_UnregisterHostBuffer(void* ptr);
 /* Pipelined host-buffer interface: NA_BatchSubmit copies `in` ([streams][n]) and enqueues upload, kernels and download, returning a

@@ -58,25 +58,57 @@ namespace na
 			char* host;
 			char* dev;
 			size_t bytes;
+			bool pinnedHere; // hipHostRegister was ours: UnregisterHostBuffer undoes it
 		};
 		std::mutex gHostBlocksMutex;
 		std::vector<HostBlock> gHostBlocks;
+
+		// the device address of a byte the caller allocated pinned (hipHostMalloc); nullptr: pageable memory, or memory of the device
+		char* PinnedDeviceAddress(const char* p)
+		{
+			hipPointerAttribute_t a = {};
+			if (hipPointerGetAttributes(&a, p) != hipSuccess)
+			{
+				(void)hipGetLastError(); // (older runtimes answer a pageable pointer with an error: none of anything that follows)
+				return nullptr;
+			}
+			return a.type == hipMemoryTypeHost ? static_cast<char*>(a.devicePointer) : nullptr;
+		}
 	}
 	bool RegisterHostBuffer(void* p, size_t bytes, std::string& error)
 	{
 		if (!p || bytes == 0) { error = "neuralaudio_amd: RegisterHostBuffer with an empty block"; return false; }
+		char* const c = static_cast<char*>(p);
+		std::lock_guard<std::mutex> lock(gHostBlocksMutex);
+		for (const HostBlock& b : gHostBlocks)
+			if (c < b.host + b.bytes && b.host < c + bytes) { error = "neuralaudio_amd: RegisterHostBuffer: the block overlaps a registered one"; return false; }
+		// A block that is pinned already (hipHostMalloc, or a framework's pinned allocator on top of it) is taken as it is: where the
+		// runtime cannot pin pages a process already has (hipHostRegister fails on virtual machines that pass the GPU through), that is
+		// the one way to the in-place route.
+		char* const dFirst = PinnedDeviceAddress(c);
+		if (dFirst)
+		{
+			if (PinnedDeviceAddress(c + bytes - 1) != dFirst + (bytes - 1)) { error = "neuralaudio_amd: RegisterHostBuffer: the block ends outside its pinned allocation"; return false; }
+			gHostBlocks.push_back({ c, dFirst, bytes, false });
+			return true;
+		}
 		hipError_t e = hipHostRegister(p, bytes, hipHostRegisterPortable | hipHostRegisterMapped);
-		if (e != hipSuccess) { error = std::string("neuralaudio_amd: hipHostRegister: ") + hipGetErrorString(e); return false; }
+		if (e != hipSuccess)
+		{
+			(void)hipGetLastError(); // (or the next kernel launch of the process reports it as its own)
+			error = std::string("neuralaudio_amd: hipHostRegister: ") + hipGetErrorString(e) + " (a block allocated pinned, hipHostMalloc, needs no pinning)";
+			return false;
+		}
 		void* d = nullptr;
 		e = hipHostGetDevicePointer(&d, p, 0);
 		if (e != hipSuccess || !d)
 		{
 			(void)hipHostUnregister(p);
+			(void)hipGetLastError();
 			error = std::string("neuralaudio_amd: hipHostGetDevicePointer: ") + hipGetErrorString(e);
 			return false;
 		}
-		std::lock_guard<std::mutex> lock(gHostBlocksMutex);
-		gHostBlocks.push_back({ static_cast<char*>(p), static_cast<char*>(d), bytes });
+		gHostBlocks.push_back({ c, static_cast<char*>(d), bytes, true });
 		return true;
 	}
 	bool UnregisterHostBuffer(void* p)
@@ -85,8 +117,9 @@ namespace na
 		for (size_t i = 0; i < gHostBlocks.size(); i++)
 		{
 			if (gHostBlocks[i].host != p) continue;
+			const bool pinnedHere = gHostBlocks[i].pinnedHere;
 			gHostBlocks.erase(gHostBlocks.begin() + (long)i);
-			return hipHostUnregister(p) == hipSuccess;
+			return !pinnedHere || hipHostUnregister(p) == hipSuccess;
 		}
 		return false;
 	}

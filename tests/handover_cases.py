@@ -181,6 +181,20 @@ def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def registered_block(shape):
+    """A zeroed float32 block behind NA_RegisterHostBuffer (the caller hands it to NA_UnregisterHostBuffer): ordinary pageable memory
+    where the runtime pins it (hipHostRegister); where it cannot (virtual machines that pass the GPU through), a block allocated
+    pinned, which the library takes as it is -- what INTEGRATION.md section 6 tells a host to do there."""
+    from neuralaudio_amd import capi
+    lib = capi.load_library()
+    block = np.zeros(shape, np.float32)
+    if lib.NA_RegisterHostBuffer(block.ctypes.data_as(C.c_void_p), block.nbytes) != 0:
+        import torch
+        block = torch.zeros(shape, dtype=torch.float32, pin_memory=True).numpy()
+        assert lib.NA_RegisterHostBuffer(block.ctypes.data_as(C.c_void_p), block.nbytes) == 0, capi.last_error()
+    return block
+
+
 class Runner:
     """Feeds a batch call by call through one entry point; every call returns host rows [ROWS, n] (device paths: copied back)."""
 
@@ -203,8 +217,7 @@ class Runner:
         if self.path == "registered":
             if self.reg is None or self.reg.shape[2] != n:
                 self.close()
-                self.reg = np.zeros((2, rows, n), np.float32)
-                assert lib.NA_RegisterHostBuffer(self.reg.ctypes.data_as(C.c_void_p), self.reg.nbytes) == 0
+                self.reg = registered_block((2, rows, n))
             self.reg[0] = x
             assert lib.NA_BatchProcess(b._h, _fp(self.reg[0]), _fp(self.reg[1]), n) == 0, capi.last_error()
             return self.reg[1].copy()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import chain_wrap_cases as CW
+import handover_cases as H
 import na_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -876,9 +877,7 @@ def test_registered_host_blocks_are_processed_in_place(na, loader):
         b.AddStreams(m, S)
         b.RemoveStreams(5, 1)
         # one block holding [in | out] back to back: the call gets pointers INSIDE it
-        block = np.zeros((2, S, n), dtype=np.float32)
-        if registered:
-            assert lib.NA_RegisterHostBuffer(block.ctypes.data_as(C.c_void_p), block.nbytes) == 0
+        block = H.registered_block((2, S, n)) if registered else np.zeros((2, S, n), dtype=np.float32)
         outs = []
         for k in range(3):
             block[0] = x[:, k * n:(k + 1) * n]

@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import handover_cases as H
 import na_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -117,8 +118,7 @@ def test_every_route_of_a_small_batch(na, models):
     x = next(xs)
     four.check(x, four.batch.Process(x), "StagedInPlace" if DIRECT else "StagedCopies", "blocking call")
     # blocks the caller registered: [in | out] back to back, the call gets pointers inside
-    block = np.zeros((2, four.rows, N), dtype=np.float32)
-    assert lib.NA_RegisterHostBuffer(block.ctypes.data_as(C.c_void_p), block.nbytes) == 0
+    block = H.registered_block((2, four.rows, N))
     try:
         block[0], block[1] = next(xs), 7.0
         assert lib.NA_BatchProcess(four.batch._h, block[0].ctypes.data_as(C.POINTER(C.c_float)), block[1].ctypes.data_as(C.POINTER(C.c_float)), N) == 0

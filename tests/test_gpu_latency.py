@@ -13,6 +13,7 @@ import time
 import numpy as np
 import pytest
 
+import handover_cases as H
 import na_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -30,10 +31,9 @@ def test_the_tail_of_5000_blocking_host_buffers_stays_below_half_a_millisecond()
     b = na.Batch(0)
     b.AddStreams(model, S)
     rng = np.random.default_rng(3)
-    x = np.clip(0.3 * rng.standard_normal((S, n)), -1.0, 1.0).astype(np.float32)
-    y = np.empty_like(x)
     # what INTEGRATION.md asks of a host: its blocks registered once (the kernels then read / write them directly, no staging copy)
-    registered = lib.NA_RegisterHostBuffer(x.ctypes.data_as(C.c_void_p), x.nbytes) == 0 and lib.NA_RegisterHostBuffer(y.ctypes.data_as(C.c_void_p), y.nbytes) == 0
+    x, y = H.registered_block((S, n)), H.registered_block((S, n))
+    x[:] = np.clip(0.3 * rng.standard_normal((S, n)), -1.0, 1.0).astype(np.float32)
     xp, yp = x.ctypes.data_as(C.POINTER(C.c_float)), y.ctypes.data_as(C.POINTER(C.c_float))
     for _ in range(warm):
         assert lib.NA_BatchProcess(b._h, xp, yp, n) == 0
@@ -49,7 +49,7 @@ def test_the_tail_of_5000_blocking_host_buffers_stays_below_half_a_millisecond()
     finally:
         gc.enable()
     ms = np.sort(t) * 1e3
-    stats = {"calls": calls, "streams": S, "block": n, "registered_blocks": bool(registered), "p50_ms": float(ms[calls // 2]), "p99_ms": float(ms[int(calls * 0.99)]),
+    stats = {"calls": calls, "streams": S, "block": n, "registered_blocks": True, "p50_ms": float(ms[calls // 2]), "p99_ms": float(ms[int(calls * 0.99)]),
              "p99_9_ms": float(ms[int(calls * 0.999)]), "max_ms": float(ms[-1]), "over_one_buffer_period": int(np.sum(ms >= 2.667))}
     print("host buffer latency: " + json.dumps(stats))
     try:
@@ -61,7 +61,6 @@ def test_the_tail_of_5000_blocking_host_buffers_stays_below_half_a_millisecond()
     assert np.all(np.isfinite(y)) and np.any(y)
     assert stats["p99_9_ms"] < 0.5, stats
     assert stats["over_one_buffer_period"] <= 1, stats  # (see the header: one hiccup of this non-real-time harness is tolerated, two are not)
-    if registered:
-        lib.NA_UnregisterHostBuffer(x.ctypes.data_as(C.c_void_p))
-        lib.NA_UnregisterHostBuffer(y.ctypes.data_as(C.c_void_p))
+    lib.NA_UnregisterHostBuffer(x.ctypes.data_as(C.c_void_p))
+    lib.NA_UnregisterHostBuffer(y.ctypes.data_as(C.c_void_p))
     b.close()

@@ -18,6 +18,7 @@ import time
 import numpy as np
 import pytest
 
+import handover_cases as H
 import na_oracle as O
 import wide_cases as WC
 
@@ -402,8 +403,7 @@ def test_a_join_between_two_tickets_and_through_host_blocks(na):
     y2 = b.Collect(b.Submit(blk(2)))
     y3 = b.Process(blk(3))  # pageable
     b.ActivateStream(2, 1.0)
-    reg = np.zeros((2, rows, n), np.float32)
-    assert lib.NA_RegisterHostBuffer(reg.ctypes.data_as(C.c_void_p), reg.nbytes) == 0
+    reg = H.registered_block((2, rows, n))
     try:
         ys = [y0, y1, y2, y3]
         for k in (4, 5):

@@ -15,6 +15,7 @@ import time
 import numpy as np
 import pytest
 
+import handover_cases as H
 import na_oracle as O
 import wide_cases as WC
 
@@ -248,8 +249,7 @@ def test_every_entry_point_gives_the_same_samples(na):
 
     # a registered block: the stages read and write the caller's rows in place
     b = fresh()
-    block = np.zeros((2, S, n), dtype=np.float32)
-    assert lib.NA_RegisterHostBuffer(block.ctypes.data_as(C.c_void_p), block.nbytes) == 0
+    block = H.registered_block((2, S, n))
     got = []
     for k in range(calls):
         block[0] = x[:, k * n:(k + 1) * n]

@@ -1,5 +1,6 @@
 // HostPipeBench: PCIe-inclusive throughput of the batched engine from a plain C++ host, through the C ABI only
-// (include/neuralaudio_amd.h): host buffers in, host buffers out, pipelined with NA_BatchSubmit / NA_BatchCollect.
+// (include/neuralaudio_amd.h): host buffers in, host buffers out, pipelined with NA_BatchSubmit / NA_BatchCollect.  (Its one HIP call
+// is hipHostMalloc, for the two blocks it registers with NA_RegisterHostBuffer.)
 //   HostPipeBench <model file> [streams=1024] [frames=128] [buffers=2000]
 //   HostPipeBench <model file> [streams] [frames] [buffers] --gpus N [--devices 0,0,...] [--fan-in rccl] [--loopback]
 //       the multi-GPU host (NA_Multi*: one batch + one host thread + one HIP stream per device, the global stream list sharded by
@@ -70,6 +71,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include <hip/hip_runtime_api.h>
 #include "neuralaudio_amd.h"
 
 static double Now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -885,17 +887,23 @@ int main(int argc, char** argv)
 	// blocking call on blocks the host registered once (NA_RegisterHostBuffer): the kernels run on the caller's memory, no staging copies
 	std::vector<double> latReg;
 	{
-		std::vector<float> rin(in), rout(count);
-		CHECK(NA_RegisterHostBuffer(rin.data(), count * sizeof(float)) == 0);
-		CHECK(NA_RegisterHostBuffer(rout.data(), count * sizeof(float)) == 0);
+		// (allocated pinned, which the library takes as it is: not every runtime pins pages the process already has)
+		float *rin = nullptr, *rout = nullptr;
+		CHECK(hipHostMalloc(reinterpret_cast<void**>(&rin), count * sizeof(float), hipHostMallocDefault) == hipSuccess);
+		CHECK(hipHostMalloc(reinterpret_cast<void**>(&rout), count * sizeof(float), hipHostMallocDefault) == hipSuccess);
+		std::memcpy(rin, in.data(), count * sizeof(float));
+		CHECK(NA_RegisterHostBuffer(rin, count * sizeof(float)) == 0);
+		CHECK(NA_RegisterHostBuffer(rout, count * sizeof(float)) == 0);
 		for (int i = 0; i < 300; i++)
 		{
 			const double t0 = Now();
-			CHECK(NA_BatchProcess(batch, rin.data(), rout.data(), (size_t)frames) == 0);
+			CHECK(NA_BatchProcess(batch, rin, rout, (size_t)frames) == 0);
 			if (i >= 50) latReg.push_back((Now() - t0) * 1e6);
 		}
-		CHECK(NA_UnregisterHostBuffer(rin.data()) == 0);
-		CHECK(NA_UnregisterHostBuffer(rout.data()) == 0);
+		CHECK(NA_UnregisterHostBuffer(rin) == 0);
+		CHECK(NA_UnregisterHostBuffer(rout) == 0);
+		CHECK(hipHostFree(rin) == hipSuccess);
+		CHECK(hipHostFree(rout) == hipSuccess);
 		std::sort(latReg.begin(), latReg.end());
 	}
 
