@@ -1008,6 +1008,12 @@ NA_EXTERN double NA_ModelStreamCost(NeuralModel* model, float quality);
 NA_EXTERN int NA_ModelKernelInfo(NeuralModel* model, float quality, int streams, char* kernelBuf, int bufSize, float* inputLimit, int* rangeProven,
 	int* weightsOk, int* packFactor);
 
+/* Host side only: 1 when the (sub)model that `quality` selects is a WaveNet with a gated layer array (the A1-format key "gated":
+ * z = act(filter half) * sigmoid(gate half), up to 16 channels), 0 when not, -1 on a bad argument.  Such a model runs on the f32 frame
+ * kernel whatever the tuning knobs say: NA_ModelKernelInfo reports "frame" without a range proof, NA_BatchStreamKernelName
+ * "WaveNetFrameKernel". */
+NA_EXTERN int NA_ModelIsGated(NeuralModel* model, float quality);
+
 /* Range contract of the kernel that runs the stream: input samples beyond +-limit are clamped, NaN reads as silence.  +inf for the f32
  * kernels (they follow the reference's f32 chain at any amplitude); a per-model bound <= 32752 for the f16-split WaveNet kernels, whose
  * values carry an f16 exponent -- far above any audio level (0 on a bad argument). */

@@ -457,6 +457,13 @@ class NeuralModel:
         return {"kernel": name.value.decode(), "input_limit": float(lim.value), "range_proven": bool(proven.value), "weights_ok": bool(wok.value),
                 "pack": int(pack.value)}
 
+    def IsGated(self, quality=1.0):
+        """Host side only: the (sub)model `quality` selects is a WaveNet with a gated layer array (A1 key "gated")."""
+        r = self._lib.NA_ModelIsGated(self._h, float(quality))
+        if r < 0:
+            raise NeuralAudioError(capi.last_error())
+        return bool(r)
+
     def RecurrentPlan(self):
         """Test hook, host side only (NA_DebugRecurrentPlan): how the runtime-shaped recurrent kernel runs this LSTM / GRU / keras stack."""
         out = (C.c_int * 6)()

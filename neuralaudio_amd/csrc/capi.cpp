@@ -1715,6 +1715,18 @@ int NA_ModelKernelInfo(NeuralModel* model, float quality, int streams, char* ker
 	return r;
 }
 
+// Host side only: 1 when the (sub)model `quality` selects is a WaveNet with a gated layer array, 0 when not, -1 on a bad argument
+int NA_ModelIsGated(NeuralModel* model, float quality)
+{
+	int r = -1;
+	Guard([&] {
+		NeuralAudio::GpuModel* gm = model ? dynamic_cast<NeuralAudio::GpuModel*>(model->model) : nullptr;
+		if (!gm) throw std::runtime_error("NA_ModelIsGated: model was not created by this library");
+		r = na::PredictModelKernel(*gm->GetLoadedModel(), quality, 1).gated ? 1 : 0;
+	});
+	return r;
+}
+
 int NA_BatchStreamRangeEvents(NA_Batch* b, int stream)
 {
 	int r = -1;

@@ -19,6 +19,15 @@ namespace na
 	// mix-in | 1x1 bias (4 G floats each)
 	constexpr int FrameLayerBlockFloats(int ksize, int G) { return (ksize + 1) * 64 * G + 12 * G; }
 
+	// ... of a GATED layer stage (conv and mix-in 2 C wide: filter rows 0 .. C-1, gate rows C .. 2C-1).  Layout, in floats:
+	//   tap k       [k * 128 G, (k + 1) * 128 G)   [lane 0..63][half: filter, gate][og 0..G-1] -- a lane's A operands of BOTH halves of a tap are
+	//               2 G consecutive floats: one ds_read_b64 (G = 1) / b128 (G = 2), three b64 (G = 3) or two b128 (G = 4) instead of two
+	//               reads G floats wide half a tap apart
+	//   1x1         [K * 128 G, K * 128 G + 64 G)  [lane][og], as in the plain block
+	//   vectors     conv bias filter | conv bias gate | mix-in filter | mix-in gate | 1x1 bias, 4 G floats each (broadcast float4 reads)
+	constexpr int FrameGatedBlockFloats(int ksize, int G) { return ksize * 128 * G + 64 * G + 20 * G; }
+	constexpr int FrameBlockFloats(int ksize, int G, bool gated) { return gated ? FrameGatedBlockFloats(ksize, G) : FrameLayerBlockFloats(ksize, G); }
+
 	// float4 stride of the two LDS weight buffers: the largest staged block of the launch's groups, at least what the stager always writes
 	constexpr int FrameWeightStrideF4(int maxA4Floats, int wps, int spb)
 	{
@@ -42,10 +51,10 @@ namespace na
 	constexpr bool FrameModelFits(int maxA4Floats) { return FrameLaunchFits(maxA4Floats, 2, 1, 1); }
 
 	// the largest layer kernel size that loads at G channel groups
-	inline int FrameMaxKernelSize(int G)
+	inline int FrameMaxKernelSize(int G, bool gated = false)
 	{
 		int k = 1;
-		while (FrameModelFits(FrameLayerBlockFloats(k + 1, G))) k++;
+		while (FrameModelFits(FrameBlockFloats(k + 1, G, gated))) k++;
 		return k;
 	}
 }

@@ -60,6 +60,7 @@ namespace na
 		info.inputLimit = c.inputLimit;
 		info.rangeProven = c.rangeProven;
 		info.weightsOk = c.weightsOk;
+		info.gated = c.gated;
 		return info;
 	}
 
@@ -79,7 +80,7 @@ namespace na
 			if (plan.genericOnly) return 1000.0 * plan.maxChannels / 32.0; // 1.0 ms per block at 32 channels (<= 256 streams)
 			const bool composite = model.isComposite;
 			// (deliberately the fit's own predicate, not the dispatch's -- wavenet_choice.h WaveNetKernelFor: the fit was made against it)
-			const bool split = plan.splitFastT == 2 || (!composite && (WaveNetPackFactor(d.wavenet) > 1 || WaveNetWantsPadding(d.wavenet)));
+			const bool split = !plan.frameOnly && (plan.splitFastT == 2 || (!composite && (WaveNetPackFactor(d.wavenet) > 1 || WaveNetWantsPadding(d.wavenet))));
 			return split ? 22.3 + 0.0143 * B : 31.6 + 0.0164 * B;
 		}
 		const LSTMDesc& l = d.lstm;

@@ -69,6 +69,7 @@ namespace na
 		int pack = 1;
 		float inputLimit = INFINITY;
 		bool rangeProven = true, weightsOk = true;
+		bool gated = false; // WaveNet with a gated layer array (A1 key "gated"): the frame kernel's gated instantiations
 	};
 	ModelKernelInfo PredictModelKernel(const LoadedModel& model, float quality, int streams);
 

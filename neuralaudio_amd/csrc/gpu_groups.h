@@ -474,6 +474,7 @@ namespace na
 				dev.saturate = plan.splitRangeProven ? 0 : 1;
 				dev.compact_rings = (family == WN_FAMILY_SPLIT && plan.compactRings) ? 1 : 0;
 				dev.spec_arch = choice.specArch;
+				dev.gated = choice.gated ? 1 : 0;
 			}
 
 			// ChannelHistoryBuffer::AllocBuffer zero-fills (WaveNet.h:38-40)

@@ -25,6 +25,8 @@ namespace na
 		int channels = 0;
 		bool hasHeadBias = false;
 		int activation = ACT_TANH;
+		// A1 key "gated": conv and mix-in are 2 * channels wide, z = act(rows 0 .. C-1) * sigmoid(rows C .. 2C-1); f32 frame kernel only
+		bool gated = false;
 		std::vector<int> kernelSizes;
 		std::vector<int> dilations;
 	};

@@ -154,8 +154,7 @@ namespace na
 			cfg.conditionSize = lc.At("condition_size").AsInt();
 			cfg.channels = lc.At("channels").AsInt();
 			cfg.dilations = IntArray(lc.At("dilations"));
-			if (lc.Contains("gated") && Truthy(lc.At("gated")))
-				throw std::runtime_error("gated WaveNet layers are not supported by the Internal path");
+			cfg.gated = lc.Contains("gated") && Truthy(lc.At("gated")); // (A1 key; the A2-format gating modes stay refused below)
 			if (lc.Contains("activation")) cfg.activation = ActivationFromJson(lc.At("activation"));
 			if (lc.Contains("kernel_sizes"))
 			{
@@ -183,6 +182,8 @@ namespace na
 		// NeuralModel.cpp:389-465: which configurations the reference runs on its static (templated) engines
 		bool IsOfficialArchitecture(const std::vector<WnArrayCfg>& arrays)
 		{
+			for (const WnArrayCfg& a : arrays)
+				if (a.gated) return false; // (NeuralModel.cpp:389-465 tests !gated first)
 			if (arrays.size() == 1)
 			{
 				const WnArrayCfg& a = arrays[0];

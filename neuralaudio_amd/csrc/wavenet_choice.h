@@ -35,6 +35,7 @@ namespace na
 		LaunchKind kind = LaunchKind::Frame;
 		float inputLimit = INFINITY; // samples beyond +-limit are clamped by the kernel (f16-split arithmetic: split and generic families)
 		bool rangeProven = true, weightsOk = true; // the range proof of the real model (wavenet_plan.cpp)
+		bool gated = false;      // some layer array is gated (A1 key "gated"): the frame family whatever the knobs say
 		WaveNetPlan plan;        // the plan the group runs, in its family's state format
 		WaveNetPlan realPlan;    // isVirtual: the real model's plan (bookkeeping: bytes / MACs per REAL stream); empty otherwise
 
@@ -84,6 +85,14 @@ namespace na
 		WaveNetPlan real = BuildWaveNetPlan(wn, true);
 		c.rangeProven = real.splitRangeProven;
 		c.weightsOk = real.splitWeightsOk;
+		if (real.frameOnly)
+		{
+			// Gated layer arrays exist on the f32 frame kernel alone (the plan has no f16-split program and is in the frame state format
+			// already): like a failed range proof this outranks NA_WN_KERNEL
+			c.gated = true;
+			c.plan = std::move(real);
+			return c;
+		}
 		const int realSpec = real.genericOnly ? WN_SPEC_NONE : WaveNetSpecArchId(real.sstages.data(), (int)real.sstages.size(), real.stateF4, (int)(real.wsplit.size() / 8));
 		const bool splitAllowed = !real.genericOnly && real.splitWeightsOk && real.rings.size() <= (size_t)WN_RANGE_EVENT_SLOT && (real.splitRangeProven || WnSpecIsA2(realSpec));
 		const WnFamily o = k.FamilyOverride();

@@ -61,8 +61,9 @@ namespace na
 		WN_FLAG_NEED_OUTPUT = 2, // compute the 1x1 + residual (NeedOutput, WaveNet.h:486-491)
 		WN_FLAG_PUBLISH = 4,     // write the layer output to LDS + the next layer's ring
 		WN_FLAG_BIAS = 8,        // dense/head stage has a bias
-		WN_FLAG_STD_TANH = 16,   // StdMath policy: std::tanh instead of the rational FastMath tanh (Activation.h:37-40)
+		WN_FLAG_STD_TANH = 16,   // StdMath policy: std::tanh instead of the rational FastMath tanh (Activation.h:37-40); on a gated layer also its sigmoid
 		WN_FLAG_FOLD = 32,       // f16-split K = 3 layer with folded lo operands (wavenet_plan.cpp FillSplitFoldAux): 8 MFMAs per tile, not 11
+		WN_FLAG_GATED = 64,      // frame kernel: gated layer, z = act(filter half) * sigmoid(gate half); staged block: frame_lds.h FrameGatedBlockFloats
 	};
 
 	struct WnStage
@@ -137,6 +138,8 @@ namespace na
 		int rechannel;  // >=0: before this layer apply rechannel weights at this offset (first layer of an array)
 		int rech_in;
 		int dilation;   // layer conv / head conv dilation (the generic block kernel walks this table; the prewarm kernel ignores it)
+		int gated;      // layer: conv / bias / mix-in have 2 * cout rows, z = act(rows 0 .. cout-1) * sigmoid(rows cout ..); 1 FastMath sigmoid, 2 StdMath
+		                // (prewarm kernel only: a gated model never runs on the runtime-shaped kernel)
 	};
 
 	// Everything the kernels need about one model; passed by value.
@@ -165,6 +168,7 @@ namespace na
 		float cond_limit;     // f16-split kernels: input samples are clamped to +-cond_limit (WaveNetPlan::condLimit)
 		int compact_rings;    // f16-split state format: some ring is a compact one -- launches take WnCompactSafeFrames() lengths only
 		int saturate;         // f16-split kernels: 1 = no static range proof (WaveNetPlan::splitRangeProven): saturating split + range events
+		int gated;            // frame kernel: some layer stage has WN_FLAG_GATED -- its launches take the gated instantiations
 	};
 
 	enum WnSpecArch : int

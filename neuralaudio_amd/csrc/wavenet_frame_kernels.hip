@@ -128,6 +128,24 @@ namespace na
 			return r;
 		}
 
+		// Gated layers: the sigmoid of the gate half by the model's math policy.  FastMath (Activation.h:93-96): 0.5 (FastTanh(0.5 g) + 1);
+		// StdMath (Activation.h:40-43): 1 / (1 + e^-g) on the exp2 / rcp units, as StdTanh2 uses them.  Both are exactly 0.5 at g == 0.
+		// (contraction off: FastTanh2 ends in a product, and whether "+ 1" fuses with it must not be the compiler's choice per instantiation)
+		__device__ __forceinline__ f32x2 FastSigmoid2(f32x2 g)
+		{
+#pragma clang fp contract(off)
+			const f32x2 t = FastTanh2(g * 0.5f);
+			return 0.5f * (t + 1.0f);
+		}
+
+		__device__ __forceinline__ f32x2 StdSigmoid2(f32x2 g)
+		{
+			f32x2 r;
+			r.x = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g.x * -1.4426950408889634f));
+			r.y = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g.y * -1.4426950408889634f));
+			return r;
+		}
+
 		template <int WPS>
 		__device__ __forceinline__ void BlockBarrier()
 		{
@@ -520,6 +538,190 @@ namespace na
 #undef FR_SUB
 		}
 
+		// One tap of a gated layer: the input frame x, fetched once, feeds the MFMA chains of both halves.  a: this lane's 2 G floats of the
+		// tap's image, [filter og 0..G-1 | gate og 0..G-1] (frame_lds.h FrameGatedBlockFloats, wavenet_plan.cpp PackGatedConvA4) -- one
+		// ds_read_b64 (G = 1) / b128 (G = 2), three b64 (G = 3: a lane's 24 bytes are 8-byte aligned) or two b128 (G = 4).  Each half is
+		// DenseMfma's chain over its own registers: the filter half issues what the plain layer issues for the same weights.
+		template <int G>
+		__device__ __forceinline__ void GatedTap(f32x4 (&accA)[G], f32x4 (&accG)[G], const float* a, const float (&x)[4 * G])
+		{
+			if (NA_ABL & 2) // (tuning builds: no MFMA, as in DenseMfma)
+			{
+#pragma unroll
+				for (int og = 0; og < G; og++)
+				{
+					accA[og].x += x[og];
+					accG[og].x += x[og];
+				}
+				return;
+			}
+			float wf[G], wg[G];
+			if constexpr (G == 4)
+			{
+				const f32x4 u = *reinterpret_cast<const f32x4*>(a), v = *reinterpret_cast<const f32x4*>(a + 4);
+				wf[0] = u.x; wf[1] = u.y; wf[2] = u.z; wf[3] = u.w;
+				wg[0] = v.x; wg[1] = v.y; wg[2] = v.z; wg[3] = v.w;
+			}
+			else if constexpr (G == 3)
+			{
+				const f32x2 u = *reinterpret_cast<const f32x2*>(a), v = *reinterpret_cast<const f32x2*>(a + 2), w = *reinterpret_cast<const f32x2*>(a + 4);
+				wf[0] = u.x; wf[1] = u.y; wf[2] = v.x;
+				wg[0] = v.y; wg[1] = w.x; wg[2] = w.y;
+			}
+			else if constexpr (G == 2)
+			{
+				const f32x4 u = *reinterpret_cast<const f32x4*>(a);
+				wf[0] = u.x; wf[1] = u.y;
+				wg[0] = u.z; wg[1] = u.w;
+			}
+			else
+			{
+				const f32x2 u = *reinterpret_cast<const f32x2*>(a);
+				wf[0] = u.x;
+				wg[0] = u.y;
+			}
+			DenseMfmaRegs<4 * G, 4 * G, 0>(accA, wf, x);
+			DenseMfmaRegs<4 * G, 4 * G, 0>(accG, wg, x);
+		}
+
+		// A gated layer (the A1 key "gated": conv and mix-in 2 C wide) for one frame per lane:
+		//     a = bconv[0:C] + wmix[0:C] cond + sum_k Wconv[0:C, :, k] x[t - d (K-1-k)],   g likewise from rows C .. 2C-1,
+		//     z = act(a) * sigmoid(g);   head += z;   x_next = x + W1 z + b1
+		// The taps come from where LayerFr takes them -- the register prefetch (PF == 1), the LDS block image, the in-line ring load -- in
+		// the same ascending order; head accumulation, 1x1, residual and publish are LayerFr's.  Only instantiated by the gated
+		// instantiations of the kernel (GT), which have no PF == 2 form.
+		// VMEM instructions of a layer: none but the G ring stores of PublishFrame, exactly as in LayerFr -- the weights of both halves come
+		// from the staged LDS block -- so what follows a WeightStager::Begin() on every path of a gated layer is the HPF * G history loads
+		// of the next layer (RunLayers) and these G stores: End<(HPF + 1) * G> holds for either body.  (A gated block is about twice a
+		// plain one: K = 3 at 16 channels is 468 float4, beyond the 384 the stager copies by LDS-DMA at two waves -- End()'s tail loop
+		// finishes it, as for every plain layer with K >= 5.)  Tuning builds: the NA_ABL switches act here as in LayerFr (through the shared
+		// helpers and GatedTap); NA_FR_TRACE builds have no in-layer stamps for a gated layer, only RunLayers' four per stage.
+		template <int G, int WPS, int PF, int HPF>
+		__device__ __forceinline__ void LayerFrGated(const FrStage& sd, const f32x4* wl, const f32x4* xbCur, f32x4* xbNext, __amdgpu_buffer_rsrc_t srsrc,
+			int inPos0, int outPos0, int nSt, int f, int wave, int lane, float cond, float (&xc)[MAXC], float (&hd)[MAXC], const f32x4 (&hcur)[HPF][G])
+		{
+			// No contraction in this body: z = act(a) * sigmoid(g) is a rounded product and head += z a plain add in EVERY instantiation
+			// (left to the compiler, the two fused into an FMA in some instantiations and not in others: 1 ulp between block lengths).  The
+			// one fused operation, bias + mix-in * cond, is written out -- it is the FMA LayerFr's expression compiles to.
+#pragma clang fp contract(off)
+			static_assert(PF == 0 || PF == 1, "gated layers: no prefetch or the register prefetch");
+			constexpr int C = 4 * G;
+			const int K = sd.ksize;
+			const int d = sd.dilation;
+			const float* a4 = reinterpret_cast<const float*>(wl) + lane * (2 * G);                   // taps: stride 128 G floats
+			const float* a1 = reinterpret_cast<const float*>(wl) + K * (128 * G) + lane * G;         // the 1x1, LayerFr's image
+			const f32x4* vl = wl + K * (32 * G) + 16 * G; // conv bias filter | gate | mix-in filter | gate | 1x1 bias, G float4 each
+
+			f32x4 accA[G], accG[G];
+#pragma unroll
+			for (int og = 0; og < G; og++)
+			{
+				accA[og] = __builtin_elementwise_fma(vl[2 * G + og], f32x4{ cond, cond, cond, cond }, vl[og]);
+				accG[og] = __builtin_elementwise_fma(vl[3 * G + og], f32x4{ cond, cond, cond, cond }, vl[G + og]);
+			}
+
+			int kFirst = 0;
+			if constexpr (PF == 1)
+			{
+#pragma unroll
+				for (int k = 0; k < HPF; k++)
+				{
+					if (k < K - 1)
+					{
+						float x[C];
+						FetchFramePre<G>(x, xbCur, f - d * (K - 1 - k), hcur[k]);
+						GatedTap<G>(accA, accG, a4 + k * (128 * G), x);
+					}
+				}
+				kFirst = HPF;
+			}
+			for (int k = kFirst; k < K - 1; k++)
+			{
+				const int shift = d * (K - 1 - k);
+				const int lo = wave * 64 - shift;
+				float x[C];
+				FetchFrame<G>(x, xbCur, srsrc, sd.ring_off, f - shift, lo, lo + 63, inPos0, sd.ring_frames);
+				GatedTap<G>(accA, accG, a4 + k * (128 * G), x);
+			}
+			{
+				float x[C];
+#pragma unroll
+				for (int c = 0; c < C; c++) x[c] = xc[c];
+				GatedTap<G>(accA, accG, a4 + (K - 1) * (128 * G), x);
+			}
+
+			// activation of the filter half as LayerFr evaluates it, sigmoid of the gate half, product; head accumulate
+			float z[C];
+			if (sd.flags & WN_FLAG_LEAKY)
+			{
+#pragma unroll
+				for (int og = 0; og < G; og++)
+				{
+					const f32x2 lo2 = LeakyReLU2(f32x2{ accA[og].x, accA[og].y });
+					const f32x2 hi2 = LeakyReLU2(f32x2{ accA[og].z, accA[og].w });
+					z[4 * og] = lo2.x; z[4 * og + 1] = lo2.y; z[4 * og + 2] = hi2.x; z[4 * og + 3] = hi2.y;
+				}
+			}
+			else if (sd.flags & WN_FLAG_STD_TANH)
+			{
+#pragma unroll
+				for (int og = 0; og < G; og++)
+				{
+					const f32x2 lo2 = StdTanh2(f32x2{ accA[og].x, accA[og].y });
+					const f32x2 hi2 = StdTanh2(f32x2{ accA[og].z, accA[og].w });
+					z[4 * og] = lo2.x; z[4 * og + 1] = lo2.y; z[4 * og + 2] = hi2.x; z[4 * og + 3] = hi2.y;
+				}
+			}
+			else
+			{
+#pragma unroll
+				for (int og = 0; og < G; og++)
+				{
+					const f32x2 lo2 = FastTanh2(f32x2{ accA[og].x, accA[og].y });
+					const f32x2 hi2 = FastTanh2(f32x2{ accA[og].z, accA[og].w });
+					z[4 * og] = lo2.x; z[4 * og + 1] = lo2.y; z[4 * og + 2] = hi2.x; z[4 * og + 3] = hi2.y;
+				}
+			}
+			if (sd.flags & WN_FLAG_STD_TANH) // (the plan sets it on a gated layer of a StdMath model also beside LeakyReLU)
+			{
+#pragma unroll
+				for (int og = 0; og < G; og++)
+				{
+					const f32x2 lo2 = StdSigmoid2(f32x2{ accG[og].x, accG[og].y });
+					const f32x2 hi2 = StdSigmoid2(f32x2{ accG[og].z, accG[og].w });
+					z[4 * og] *= lo2.x; z[4 * og + 1] *= lo2.y; z[4 * og + 2] *= hi2.x; z[4 * og + 3] *= hi2.y;
+				}
+			}
+			else
+			{
+#pragma unroll
+				for (int og = 0; og < G; og++)
+				{
+					const f32x2 lo2 = FastSigmoid2(f32x2{ accG[og].x, accG[og].y });
+					const f32x2 hi2 = FastSigmoid2(f32x2{ accG[og].z, accG[og].w });
+					z[4 * og] *= lo2.x; z[4 * og + 1] *= lo2.y; z[4 * og + 2] *= hi2.x; z[4 * og + 3] *= hi2.y;
+				}
+			}
+#pragma unroll
+			for (int c = 0; c < C; c++) hd[c] += z[c];
+
+			if (sd.flags & WN_FLAG_NEED_OUTPUT)
+			{
+				f32x4 y[G];
+#pragma unroll
+				for (int og = 0; og < G; og++)
+					y[og] = vl[4 * G + og] + f32x4{ xc[4 * og], xc[4 * og + 1], xc[4 * og + 2], xc[4 * og + 3] };
+				DenseMfma<C, C>(y, a1, z);
+#pragma unroll
+				for (int og = 0; og < G; og++)
+				{
+					xc[4 * og] = y[og].x; xc[4 * og + 1] = y[og].y; xc[4 * og + 2] = y[og].z; xc[4 * og + 3] = y[og].w;
+				}
+			}
+			if (PF) PublishFrame<G>(xc, xbNext, srsrc, sd.out_ring_off, outPos0, sd.out_ring_frames, (sd.flags & WN_FLAG_PUBLISH) ? nSt : 0, f);
+			else if (sd.flags & WN_FLAG_PUBLISH) PublishFrame<G>(xc, xbNext, srsrc, sd.out_ring_off, outPos0, sd.out_ring_frames, nSt, f);
+		}
+
 		__device__ __forceinline__ void PublishAny(int G, const float (&x)[MAXC], f32x4* xb, __amdgpu_buffer_rsrc_t srsrc, int ringOff, int pos0, int R,
 			int n, int f)
 		{
@@ -742,7 +944,9 @@ namespace na
 		// A run of consecutive WaveNet layer stages with the same channel-group count G.  With `pre`, sd is the rechannel / array-link
 		// stage in front of the run and sdFirst its first layer: the ring history of that layer is requested BEFORE the pre-stage
 		// computes, so its HBM latency hides behind it (the per-frame state stays in registers typed by G either way).
-		template <int G, int WPS, int PF, int SPB, int HPF>
+		// GT (the gated instantiations of the kernel): every layer picks the gated or the plain body from its wave-uniform stage flag -- a
+		// file may mix gated and plain arrays, and a fused launch carries gated and plain models together.
+		template <int G, int WPS, int PF, int SPB, int HPF, bool GT>
 		__device__ __forceinline__ void RunLayers(const FrCtx& cx, int& s, FrStage& sd, const FrStage& sdFirst, bool pre, int& cur, float (&xc)[MAXC], float (&hd)[MAXC])
 		{
 			constexpr int NTB = WPS * 4;
@@ -794,7 +998,15 @@ namespace na
 				}
 				const NextHistory nh = { haveNext, sdn.ring_off, sdn.dilation, sdn.ksize, nextPos0, sdn.ring_frames };
 
-				LayerFr<G, WPS, PF, WPS * SPB, HPF>(sd, wl, cx.wvec + sd.vec_off * 4, cx.xbuf + cur * (NTB * 64), cx.xbuf + (cur ^ 1) * (NTB * 64), cx.srsrc, inPos0,
+				bool gatedLayer = false;
+				if constexpr (GT)
+				{
+					gatedLayer = (sd.flags & WN_FLAG_GATED) != 0;
+					if (gatedLayer)
+						LayerFrGated<G, WPS, PF, HPF>(sd, wl, cx.xbuf + cur * (NTB * 64), cx.xbuf + (cur ^ 1) * (NTB * 64), cx.srsrc, inPos0, outPos0, cx.nSt, f, cx.wave, lane,
+							cx.cond, xc, hd, hcur);
+				}
+				if (!gatedLayer) LayerFr<G, WPS, PF, WPS * SPB, HPF>(sd, wl, cx.wvec + sd.vec_off * 4, cx.xbuf + cur * (NTB * 64), cx.xbuf + (cur ^ 1) * (NTB * 64), cx.srsrc, inPos0,
 					outPos0, cx.n, cx.nSt, f, cx.wave, lane, cx.cond, xc, hd, hcur, haveCur, hb, nh, cx.lrsrc, counted,
 #ifdef NA_FR_TRACE
 					(trace != nullptr && (int)blockIdx.x == traceBlock) ? trace + ((cx.nstages + 1) * 4 + s * 8) * (WPS * SPB) + waveAll * 8 : nullptr
@@ -849,7 +1061,8 @@ namespace na
 			int numGroups;
 		};
 
-		template <int WPS, int PF, int SPB>
+		// GT: the instantiations that also run gated layers (LayerFrGated), compiled in wavenet_frame_gated_kernels.hip
+		template <int WPS, int PF, int SPB, bool GT>
 		__global__ void __launch_bounds__(64 * WPS * SPB) WaveNetFrameKernel(const FrLaunchArgs args, int maxA4F4, const float* __restrict__ in,
 			float* __restrict__ out, long inStride, long outStride, int n, long long* __restrict__ trace, int traceBlock)
 		{
@@ -952,17 +1165,17 @@ namespace na
 					const FrStage& first = pre ? sdn : sd;
 					// narrow layers of a model with kernels larger than 3 (A2): request 5 taps ahead instead of 2
 					const bool wide = PF == 1 && ga.maxKsize > 3;
-					if (first.G == 4) RunLayers<4, WPS, PF, SPB, HPF_NARROW>(cx, s, sd, first, pre, cur, xc, hd);
-					else if (first.G == 3) RunLayers<3, WPS, PF, SPB, HPF_NARROW>(cx, s, sd, first, pre, cur, xc, hd);
+					if (first.G == 4) RunLayers<4, WPS, PF, SPB, HPF_NARROW, GT>(cx, s, sd, first, pre, cur, xc, hd);
+					else if (first.G == 3) RunLayers<3, WPS, PF, SPB, HPF_NARROW, GT>(cx, s, sd, first, pre, cur, xc, hd);
 					else if (first.G == 2)
 					{
-						if (wide) RunLayers<2, WPS, PF, SPB, PF == 1 ? HPF_WIDE : HPF_NARROW>(cx, s, sd, first, pre, cur, xc, hd);
-						else RunLayers<2, WPS, PF, SPB, HPF_NARROW>(cx, s, sd, first, pre, cur, xc, hd);
+						if (wide) RunLayers<2, WPS, PF, SPB, PF == 1 ? HPF_WIDE : HPF_NARROW, GT>(cx, s, sd, first, pre, cur, xc, hd);
+						else RunLayers<2, WPS, PF, SPB, HPF_NARROW, GT>(cx, s, sd, first, pre, cur, xc, hd);
 					}
 					else
 					{
-						if (wide) RunLayers<1, WPS, PF, SPB, PF == 1 ? HPF_WIDE : HPF_NARROW>(cx, s, sd, first, pre, cur, xc, hd);
-						else RunLayers<1, WPS, PF, SPB, HPF_NARROW>(cx, s, sd, first, pre, cur, xc, hd);
+						if (wide) RunLayers<1, WPS, PF, SPB, PF == 1 ? HPF_WIDE : HPF_NARROW, GT>(cx, s, sd, first, pre, cur, xc, hd);
+						else RunLayers<1, WPS, PF, SPB, HPF_NARROW, GT>(cx, s, sd, first, pre, cur, xc, hd);
 					}
 					continue;
 				}
@@ -989,7 +1202,7 @@ namespace na
 			}
 		}
 
-		template <int WPS, int PF, int SPB>
+		template <int WPS, int PF, int SPB, bool GT = false>
 		static hipError_t Launch(const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
 		{
 			FrLaunchArgs args = {};
@@ -1016,7 +1229,7 @@ namespace na
 			const int maxA4F4 = FrameWeightStrideF4(maxA4Floats, WPS, SPB);
 			const size_t lds = FrameLaunchLdsBytes(maxA4Floats, WPS, SPB, PF);
 			if (lds > FRAME_LDS_LIMIT) return hipErrorInvalidValue; // (WaveNetLaunchFor chooses a shape that fits; a loaded model has one)
-			auto kernel = WaveNetFrameKernel<WPS, PF, SPB>;
+			auto kernel = WaveNetFrameKernel<WPS, PF, SPB, GT>;
 			if (lds > 64 * 1024)
 			{
 				// per instantiation and device: the whole LDS of a CU once (granting it does not change what a launch uses)
@@ -1030,11 +1243,31 @@ namespace na
 		}
 	}
 
+#ifdef NA_FRAME_GATED_TU
+	// the gated instantiations WaveNetFrameKernel<WPS, PF, SPB, true> (wavenet_launch_choice.h FrameFor: `gated`)
+	hipError_t LaunchWaveNetFrameGated(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream)
+	{
+		if (c.kernel != WnLaunchKernel::Frame || !c.gated) return hipErrorInvalidValue;
+		switch (c.wps * 100 + c.pf * 10 + c.spb)
+		{
+		case 212: return fr::Launch<2, 1, 2, true>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 211: return fr::Launch<2, 1, 1, true>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 201: return fr::Launch<2, 0, 1, true>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		case 101: return fr::Launch<1, 0, 1, true>(groups, numGroups, in, out, inStride, outStride, n, stream);
+		}
+		return hipErrorInvalidValue;
+	}
+#else
+	hipError_t LaunchWaveNetFrameGated(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
+		long outStride, int n, hipStream_t stream); // wavenet_frame_gated_kernels.hip
+
 	// WaveNetFrameKernel<WPS, PF, SPB> as WaveNetLaunchFor chose it (wavenet_choice.h FrameFor): a switch over the instantiations
 	hipError_t LaunchWaveNetFrameFused(const WaveNetLaunchChoice& c, const WnFrameGroup* groups, int numGroups, const float* in, float* out, long inStride,
 		long outStride, int n, hipStream_t stream)
 	{
 		if (c.kernel != WnLaunchKernel::Frame) return hipErrorInvalidValue;
+		if (c.gated) return LaunchWaveNetFrameGated(c, groups, numGroups, in, out, inStride, outStride, n, stream);
 		switch (c.wps * 100 + c.pf * 10 + c.spb)
 		{
 		case 201: return fr::Launch<2, 0, 1>(groups, numGroups, in, out, inStride, outStride, n, stream);
@@ -1047,4 +1280,5 @@ namespace na
 		}
 		return hipErrorInvalidValue;
 	}
+#endif
 }

@@ -84,7 +84,7 @@ namespace na
 		for (int i = 0; i < numGroups; i++)
 		{
 			const WnModelDev& m = *groups[i].model;
-			facts[i] = { m.spec_arch, groups[i].pack, m.split_fast_T, groups[i].numStreams, groups[i].slots != nullptr, m.max_a4_floats, m.max_G, m.max_split_ops };
+			facts[i] = { m.spec_arch, groups[i].pack, m.split_fast_T, groups[i].numStreams, groups[i].slots != nullptr, m.max_a4_floats, m.max_G, m.max_split_ops, m.gated };
 		}
 		return WaveNetLaunchFor({ frame, n, facts, numGroups, sharing & ~WN_SHARING_BEYOND_CACHE, (sharing & WN_SHARING_BEYOND_CACHE) != 0, ctx.cus }, ctx.knobs);
 	}

@@ -59,6 +59,7 @@ namespace na
 		int hasLists;    // the index lists are passed (slots != nullptr)
 		int maxA4Floats; // frame kernel: largest staged block
 		int maxG = 1, maxSplitOps = 16; // stage interpreter: what sizes its LDS (WnModelDev::max_G, max_split_ops)
+		int gated = 0;   // frame kernel: the model has gated layers (WnModelDev::gated)
 	};
 	struct WaveNetLaunchFacts
 	{
@@ -95,6 +96,7 @@ namespace na
 		bool gen = false;   // interpreter: the generic instantiation
 		bool pk = false;    // chains / interpreter: the packed flavour
 		int pf = 0;         // frame kernel: history prefetch (0 none, 1 registers, 2 LDS)
+		bool gated = false; // frame kernel: the gated instantiation (some group of the launch has gated layers)
 	};
 
 	// dynamic LDS of WaveNetSplitKernel<T, spb, WPS, GEN, pk>: block images | planes | two weight buffers (wavenet_split_kernels.hip sp::Launch)
@@ -253,11 +255,13 @@ namespace na
 		{
 			int total = 0;
 			int maxA4 = 0; // the launch's LDS follows the largest staged block among its groups
+			bool gated = false;
 			for (int i = 0; i < f.numGroups; i++)
 			{
 				if (f.groups[i].numStreams <= 0) return Refused(WN_REFUSED_INVALID_VALUE);
 				total += f.groups[i].numStreams;
 				maxA4 = std::max(maxA4, f.groups[i].maxA4Floats);
+				gated = gated || f.groups[i].gated != 0;
 			}
 			// streams per workgroup: two streams share one staged copy of the weights once there are enough streams to cover all 256 CUs
 			// (measured 1024 x Standard: SPB 1 / 2 / 4 = 61.5 / 61.3 / 65.0 us -- at 4 the 8-wave barrier skew eats the saving)
@@ -266,6 +270,20 @@ namespace na
 			c.kernel = WnLaunchKernel::Frame;
 			c.wps = f.n > 64 ? 2 : 1;
 			c.spb = 1;
+			c.gated = gated;
+			// A launch with a gated group runs the gated instantiations, every group of it (they pick the layer body per stage): <1, 0, 1>,
+			// <2, 0, 1>, <2, 1, 1> and <2, 1, 2>.  One prefetch form -- registers; results do not depend on it -- so NA_FR_PF=2 means 1 here,
+			// and at most two streams per workgroup whatever NA_FR_SPB asks.
+			if (gated)
+			{
+				if (f.n > 64 && k.frPrefetch != 0)
+				{
+					c.pf = 1;
+					if (wish >= 2 && FrameLaunchFits(maxA4, 2, 2, 1)) c.spb = 2;
+				}
+				if (!FrameLaunchFits(maxA4, c.wps, c.spb, c.pf)) return Refused(WN_REFUSED_INVALID_VALUE);
+				return c;
+			}
 			// ... the largest count up to that wish whose LDS fits (frame_lds.h): large kernels leave room for fewer block images beside
 			// their staged weights, and the LDS history buffers of prefetch 2 give way to the register prefetch before a launch fails.
 			// Precedence under NA_FR_PF=2: the knob asks for the LDS prefetch, so it is kept over the second stream -- <2,2,2>, then

@@ -23,12 +23,12 @@ namespace na
 		size_t n = 0;
 		for (const auto& a : arrays)
 		{
-			const size_t c = (size_t)a.channels;
+			const size_t c = (size_t)a.channels, c2 = a.gated ? 2 * c : c; // gated: conv, its bias and the mix-in have a filter and a gate half
 			n += c * a.inputSize;
 			for (size_t l = 0; l < a.kernelSizes.size(); l++)
 			{
-				n += c * c * a.kernelSizes[l] + c; // conv + bias
-				n += c * a.conditionSize;         // mix-in
+				n += c2 * c * a.kernelSizes[l] + c2; // conv + bias
+				n += c2 * a.conditionSize;          // mix-in
 				n += c * c + c;                   // 1x1 + bias
 			}
 			n += (size_t)a.headSize * c * a.headKernelSize + (a.hasHeadBias ? a.headSize : 0);
@@ -54,6 +54,8 @@ namespace na
 		if (desc.arrays.empty()) throw std::runtime_error("WaveNet without layer arrays");
 		const int numArrays = (int)desc.arrays.size();
 		int rings = 0;
+		bool anyGated = false;
+		for (const WnArrayCfg& cfg : desc.arrays) anyGated = anyGated || cfg.gated;
 		for (int a = 0; a < numArrays; a++)
 		{
 			const WnArrayCfg& cfg = desc.arrays[a];
@@ -63,6 +65,21 @@ namespace na
 			if (cfg.headKernelSize > 1 && (cfg.channels > 64 || cfg.headSize > 64))
 				throw std::runtime_error("WaveNet: a conv head on a layer array wider than 64 channels is not supported");
 			if (cfg.conditionSize != 1) throw std::runtime_error("WaveNet condition_size != 1 is not supported");
+			if (cfg.gated && cfg.channels > 16)
+			{
+				std::stringstream str;
+				str << "WaveNet layer array " << a << ": gated layers at " << cfg.channels << " channels are not supported (gated layer arrays run on the f32 frame kernel: at most 16 channels)";
+				throw std::runtime_error(str.str());
+			}
+			// ... and a model with ANY gated array is frame-only: every array of it, gated or plain, with its head and its input, must be
+			// one the frame kernel takes (the runtime-shaped kernels that run wider arrays have no gating and walk the plain weight count)
+			if (anyGated && (cfg.channels > 16 || cfg.headSize > 16 || cfg.inputSize > 16))
+			{
+				std::stringstream str;
+				str << "WaveNet layer array " << a << ": " << std::max(cfg.channels, std::max(cfg.headSize, cfg.inputSize))
+				    << " channels (channels, head_size or input_size) in a model with gated layer arrays are not supported (such a model runs on the f32 frame kernel: at most 16 channels everywhere)";
+				throw std::runtime_error(str.str());
+			}
 			if (cfg.kernelSizes.size() != cfg.dilations.size() || cfg.kernelSizes.empty())
 				throw std::runtime_error("WaveNet kernel_sizes/dilations mismatch");
 			for (size_t l = 0; l < cfg.kernelSizes.size(); l++)
@@ -229,6 +246,22 @@ namespace na
 							const int o = 4 * og + (lane & 3), c = lane >> 2;
 							if (o < cout && c < cin) plan.wpk[(size_t)off + ((size_t)k * 64 + lane) * G + og] = W(wOff + (o * cin + c) * ksize + k);
 						}
+				return off;
+			}
+
+			// ... of a gated layer's conv [2C][C][K]: per tap [lane][half 0 filter, 1 gate][og], so that a lane's operands of both halves are
+			// 2 G consecutive floats (frame_lds.h FrameGatedBlockFloats); each half is PackConvA4's image of its C rows
+			int PackGatedConvA4(int wOff, int C, int ksize, int G)
+			{
+				const int off = AllocPk(ksize * 128 * G);
+				for (int k = 0; k < ksize; k++)
+					for (int lane = 0; lane < 64; lane++)
+						for (int half = 0; half < 2; half++)
+							for (int og = 0; og < G; og++)
+							{
+								const int o = 4 * og + (lane & 3), c = lane >> 2;
+								if (o < C && c < C) plan.wpk[(size_t)off + (((size_t)k * 64 + lane) * 2 + half) * G + og] = W(wOff + ((half * C + o) * C + c) * ksize + k);
+							}
 				return off;
 			}
 
@@ -739,6 +772,10 @@ namespace na
 
 				plan.arrays = desc.arrays;
 				plan.receptiveField = desc.ReceptiveFieldSize();
+				// A model with a gated layer array runs on the f32 frame kernel only: its state format whatever the caller asked for, no
+				// f16-split stage program (BuildSplit would walk the plain weight count), hence no range proof, no packing and no padding
+				for (const WnArrayCfg& cfg : desc.arrays) plan.frameOnly = plan.frameOnly || cfg.gated;
+				if (plan.frameOnly) exactRings = false;
 				compactOk = exactRings;
 				for (const WnArrayCfg& cfg : desc.arrays)
 				{
@@ -755,6 +792,7 @@ namespace na
 				}
 				if (plan.maxChannels > 16)
 				{
+					if (plan.frameOnly) throw std::runtime_error("internal: a WaveNet with gated layer arrays wider than 16 channels passed validation");
 					plan.genericOnly = true;
 					BuildGenericOnly();
 					return;
@@ -816,9 +854,10 @@ namespace na
 					{
 						const int K = cfg.kernelSizes[l];
 						const int d = cfg.dilations[l];
-						const int wconv = Take((size_t)C * C * K);
-						const int bconv = Take((size_t)C);
-						const int wmix = Take((size_t)C * cfg.conditionSize);
+						const int C2 = cfg.gated ? 2 * C : C; // gated: rows 0 .. C-1 filter, C .. 2C-1 gate
+						const int wconv = Take((size_t)C2 * C * K);
+						const int bconv = Take((size_t)C2);
+						const int wmix = Take((size_t)C2 * cfg.conditionSize);
 						const int w1 = Take((size_t)C * C);
 						const int b1 = Take((size_t)C);
 
@@ -831,9 +870,27 @@ namespace na
 						SetVec(st, 2, b1, C);
 						st.ksize = K;
 						st.dilation = d;
-						st.a4_off = PackConvA4(wconv, C, C, K, st.G);       // [conv taps | 1x1 | vectors], one contiguous block
-						PackDenseA4(w1, C, C, st.G);
+						if (cfg.gated)
 						{
+							// the gated block (frame_lds.h FrameGatedBlockFloats): [taps: lane, half, og | 1x1 | bias f, g | mix-in f, g | 1x1 bias]
+							st.flags |= WN_FLAG_GATED;
+							st.a4_off = PackGatedConvA4(wconv, C, K, st.G);
+							PackDenseA4(w1, C, C, st.G);
+							const int CP = 4 * st.G;
+							const int tail = AllocPk(5 * CP);
+							for (int c = 0; c < C; c++)
+							{
+								plan.wpk[(size_t)tail + c] = W(bconv + c);
+								plan.wpk[(size_t)tail + CP + c] = W(bconv + C + c);
+								plan.wpk[(size_t)tail + 2 * CP + c] = W(wmix + c);
+								plan.wpk[(size_t)tail + 3 * CP + c] = W(wmix + C + c);
+								plan.wpk[(size_t)tail + 4 * CP + c] = W(b1 + c);
+							}
+						}
+						else
+						{
+							st.a4_off = PackConvA4(wconv, C, C, K, st.G);       // [conv taps | 1x1 | vectors], one contiguous block
+							PackDenseA4(w1, C, C, st.G);
 							// tail of the block: conv bias | mixin | 1x1 bias, 4G floats each, read back from LDS as broadcast float4s
 							const int CP = 4 * st.G;
 							const int tail = AllocPk(3 * CP);
@@ -844,10 +901,11 @@ namespace na
 								plan.wpk[(size_t)tail + 2 * CP + c] = W(b1 + c);
 							}
 						}
-						st.a4_floats = FrameLayerBlockFloats(K, st.G);
+						st.a4_floats = FrameBlockFloats(K, st.G, cfg.gated);
 						SetRing(st, layerRing[a][l]);
 						if (cfg.activation == ACT_LEAKYRELU) st.flags |= WN_FLAG_LEAKY;
 						else if (desc.mathMode == MATH_STD) st.flags |= WN_FLAG_STD_TANH;
+						if (cfg.gated && desc.mathMode == MATH_STD) st.flags |= WN_FLAG_STD_TANH; // (a gated layer's sigmoid follows the policy also beside LeakyReLU)
 						// NeedOutput=false for the very last layer (WaveNet.h:643,785); for a single-array model the
 						// reference still computes it but nothing reads it.
 						if (!(lastLayer && lastArray)) st.flags |= WN_FLAG_NEED_OUTPUT;
@@ -869,6 +927,7 @@ namespace na
 						pw.rechannel = (l == 0) ? rechOff : -1;
 						pw.rech_in = cfg.inputSize;
 						pw.dilation = d;
+						pw.gated = cfg.gated ? (desc.mathMode == MATH_STD ? 2 : 1) : 0;
 						plan.prewarm.push_back(pw);
 					}
 
@@ -925,7 +984,12 @@ namespace na
 				}
 
 				plan.headScale = W(Take(1));
-				BuildSplit(layerRing, headRing);
+				if (plan.frameOnly)
+				{
+					plan.splitRangeProven = false;
+					plan.genericOk = false; // (the runtime-shaped kernel has no gating either)
+				}
+				else BuildSplit(layerRing, headRing);
 				for (const WnStage& st : plan.stages) plan.maxA4Floats = std::max(plan.maxA4Floats, st.a4_floats);
 				// round the state up to a 256-byte multiple so every stream's state starts float4/line aligned
 				plan.stateF4 = CeilDiv(plan.stateF4, 16) * 16;
@@ -956,11 +1020,11 @@ namespace na
 				for (size_t l = 0; l < cfg.kernelSizes.size(); l++)
 				{
 					const int K = cfg.kernelSizes[l];
-					if (FrameModelFits(FrameLayerBlockFloats(K, G))) continue;
+					if (FrameModelFits(FrameBlockFloats(K, G, cfg.gated))) continue;
 					std::stringstream str;
-					str << "WaveNet layer array " << a << ", layer " << l << ": kernel size " << K << " at " << cfg.channels
-					    << " channels needs " << FrameLaunchLdsBytes(FrameLayerBlockFloats(K, G), 2, 1, 1) << " bytes of LDS on the f32 frame kernel (limit "
-					    << FRAME_LDS_LIMIT << "); the largest kernel size at this width is " << FrameMaxKernelSize(G);
+					str << "WaveNet layer array " << a << ", layer " << l << ": kernel size " << K << " at " << cfg.channels << (cfg.gated ? " gated" : "")
+					    << " channels needs " << FrameLaunchLdsBytes(FrameBlockFloats(K, G, cfg.gated), 2, 1, 1) << " bytes of LDS on the f32 frame kernel (limit "
+					    << FRAME_LDS_LIMIT << "); the largest kernel size at this width is " << FrameMaxKernelSize(G, cfg.gated);
 					throw std::runtime_error(str.str());
 				}
 			}
@@ -1176,7 +1240,7 @@ namespace na
 			for (size_t l = 0; l < a.kernelSizes.size(); l++)
 			{
 				const bool last = (ai == numArrays - 1) && (l == a.kernelSizes.size() - 1) && numArrays > 1;
-				macs += c * c * a.kernelSizes[l] + c * a.conditionSize + (last ? 0.0 : c * c);
+				macs += (a.gated ? 2.0 : 1.0) * (c * c * a.kernelSizes[l] + c * a.conditionSize) + (last ? 0.0 : c * c); // gated: filter and gate half
 			}
 			macs += (double)a.headSize * c * a.headKernelSize;
 		}

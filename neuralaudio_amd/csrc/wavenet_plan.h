@@ -39,6 +39,7 @@ namespace na
 		std::vector<float> packedWeights;  // pack > 1: flat weights of the virtual model (reference order)
 		bool genericOnly = false;          // > 16 channels: only rings + the natural-layout table are built (runtime-shaped block kernel)
 		bool genericOk = false;            // the runtime-shaped block kernel can run it (dense heads only)
+		bool frameOnly = false;            // some layer array is gated: frame-kernel stages and state format only, no f16-split program, no range proof
 		int stateF4 = 0;            // per-stream state in float4 units
 		int maxA4Floats = 0;        // largest per-stage A-operand block of the frame kernel (floats)
 		float headScale = 0.0f;

@@ -63,6 +63,16 @@ namespace na
 					acc += w[L.bconv + i];
 					// mix-in * condition(0) adds nothing
 					acc = (L.act == 1) ? LeakyReLU(acc) : (L.act == 2 ? (1.0f - 2.0f * __builtin_amdgcn_rcpf(__builtin_amdgcn_exp2f(acc * 2.885390081777927f) + 1.0f)) : FastTanh(acc));
+					if (L.gated)
+					{
+						// gated layer: rows cout .. 2 cout - 1 of conv and bias are the gate half; z = act(filter) * sigmoid(gate), the sigmoid by
+						// the model's math policy (gated == 2: StdMath) -- Activation.h:40-43,93-96
+						float g = 0.0f;
+						for (int k = 0; k < L.ksize; k++)
+							for (int c = 0; c < L.cin; c++) g += w[L.wconv + ((L.cout + i) * L.cin + c) * L.ksize + k] * x[c];
+						g += w[L.bconv + L.cout + i];
+						acc *= (L.gated == 2) ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g * -1.4426950408889634f)) : 0.5f * (FastTanh(0.5f * g) + 1.0f);
+					}
 				}
 				__syncthreads();
 				z[i] = (i < L.cout) ? acc : 0.0f;
