@@ -136,6 +136,11 @@ namespace NeuralAudio
 		// math policy of the models created next (the reference's WAVENET_MATH / LSTM_MATH build options)
 		void SetWaveNetMathMode(EMathMode mode) { wavenetMath = mode; }
 		EMathMode GetWaveNetMathMode() { return wavenetMath; }
+		// Exact f32 arithmetic for the WaveNet models created next (default off): no f16-split kernel runs them -- no load refusal of the
+		// f16 operand format, no input clamp, no saturation; several times the cost at 17 .. 128 channels (WaveNetWideF32Kernel), and NaN /
+		// inf input samples are not cleaned
+		void SetWaveNetExactF32(bool on) { wavenetExactF32 = on; }
+		bool GetWaveNetExactF32() { return wavenetExactF32; }
 		void SetLSTMMathMode(EMathMode mode) { lstmMath = mode; }
 		EMathMode GetLSTMMathMode() { return lstmMath; }
 		// Opt-in (default off: the reference's behaviour): a model created while the external sample rate is neither its model-side rate
@@ -156,6 +161,7 @@ namespace NeuralAudio
 		int device = 0;
 		EMathMode wavenetMath = EMathMode::FastMath;
 		EMathMode lstmMath = EMathMode::FastMath;
+		bool wavenetExactF32 = false;
 		bool resampleToExternalRate = false;
 	};
 }

@@ -313,7 +313,7 @@ def recurrent_kernel(kind, hidden, layers=1, tail_layers=0, tail_width=0, tail_h
 # NA_SP_T and NA_SP_GEN imply NA_WN_SPEC=0, as in the library's own parsing of the environment)
 WAVENET_KNOBS = ("NA_WN_KERNEL", "NA_WN_PACK", "NA_WN_PAD", "NA_WN_DENSE", "NA_SP_T", "NA_SP_SPB", "NA_SP_GEN", "NA_SP_NO_T1", "NA_FR_PF", "NA_FR_SPB",
                  "NA_WN_SPEC")
-WAVENET_FAMILIES = {1: "f16-split", 2: "frame", 3: "generic"}
+WAVENET_FAMILIES = {1: "f16-split", 2: "frame", 3: "generic", 4: "wide-f32"}
 WAVENET_LAUNCH_KERNELS = ("none", "chain", "chain table", "interpreter", "frame", "pieces")
 WAVENET_CHAINS = ("Std", "Lite", "LitePacked", "Lite16T1", "A2")
 # csrc/host_route.h HostRoute, in its order: what Batch.DebugLastHostRoute() indexes (tests/test_host_route_cpu.py pins the names)
@@ -536,6 +536,11 @@ class NeuralModelLoader:
 
     def SetWaveNetMathMode(self, mode):
         self._lib.NA_SetWaveNetMathMode(self._h, int(mode))
+
+    def SetWaveNetExactF32(self, on):
+        """Exact f32 arithmetic for the WaveNet models created next: no f16-split kernel, no load refusal of the operand format, no input
+        clamp (17 .. 128 channels: WaveNetWideF32Kernel, several times the default's cost; NaN / inf inputs are not cleaned)."""
+        self._lib.NA_SetWaveNetExactF32(self._h, 1 if on else 0)
 
     def SetLSTMMathMode(self, mode):
         self._lib.NA_SetLSTMMathMode(self._h, int(mode))

@@ -398,9 +398,9 @@ namespace na
 				dWpk.UploadUnless(peerWeights, plan.wpk, stream);
 				dPrewarm.Upload(plan.prewarm, stream);
 				dWeights.UploadUnless(peerWeights, plan.isVirtual() ? plan.packedWeights : d->wavenet.weights, stream);
-				if (family == WN_FAMILY_GENERIC)
+				if (family == WN_FAMILY_GENERIC || family == WN_FAMILY_WIDE_F32)
 				{
-					// the runtime-shaped kernel reads a layer conv tap by tap as a [cout x cin] matrix: its copy of the weights keeps every
+					// the runtime-shaped kernels read a layer conv tap by tap as a [cout x cin] matrix: its copy of the weights keeps every
 					// layer conv tap-major ([k][out][in] instead of the reference's [out][in][k], WaveNet.h:99-111), so that a lane's four
 					// input channels are one 16-byte load and a row is contiguous
 					std::vector<float> wg = d->wavenet.weights;
@@ -554,7 +554,7 @@ namespace na
 				const int numActive = (int)hSlots.size();
 				if (numActive == 0) return;
 				size_t offset = 0;
-				const WnLaunchContext ctx = family == WN_FAMILY_GENERIC ? WnLaunchContext{} : WnLaunchContext::Current();
+				const WnLaunchContext ctx = (family == WN_FAMILY_GENERIC || family == WN_FAMILY_WIDE_F32) ? WnLaunchContext{} : WnLaunchContext::Current();
 				while (n > 0)
 				{
 					const int chunk = NextWaveNetChunk(n, dev.compact_rings != 0);
@@ -562,6 +562,10 @@ namespace na
 						CheckHip(LaunchWaveNetGeneric(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
 							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, plan.condLimit, !plan.splitRangeProven, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
 							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetGenericKernel");
+					else if (family == WN_FAMILY_WIDE_F32)
+						CheckHip(LaunchWaveNetWideF32(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
+							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
+							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetWideF32Kernel");
 					else
 					{
 						// a launch of this group alone (sharing 1; split family: the state of this group's streams alone beyond the Infinity Cache
@@ -729,7 +733,7 @@ namespace na
 			DevArray<float> dWpk;
 			DevArray<WnPrewarmLayer> dPrewarm;
 			DevArray<float> dWeights;
-			DevArray<float> dWeightsGen; // WN_FAMILY_GENERIC: layer convs tap-major
+			DevArray<float> dWeightsGen; // WN_FAMILY_GENERIC / WN_FAMILY_WIDE_F32: layer convs tap-major
 			DevArray<int> dRingOff, dRingFrames, dRingG;
 			DevArray<int> dSnapTab, dSnapLists; // stream snapshots: the per-ring table, the lists of the current call
 			DevArray<float> dCols;

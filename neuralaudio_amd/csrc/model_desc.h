@@ -37,6 +37,7 @@ namespace na
 		std::vector<float> weights; // flat, reference order (WaveNet.h:700-719)
 		bool isStatic = false;      // matched one of the official architectures (InternalModel.h:12-20)
 		int mathMode = MATH_FAST;   // tanh policy of ACT_TANH layers
+		bool exactF32 = false;      // the loader asked for f32 arithmetic (NA_SetWaveNetExactF32): no f16-split kernel runs this model (wavenet_choice.h)
 
 		size_t ExpectedNumWeights() const;
 		int ReceptiveFieldSize() const; // WaveNet.h:534-542,674-684

@@ -44,9 +44,14 @@ namespace na
 		const char* KernelName(bool specOn) const
 		{
 			if (family == WN_FAMILY_SPLIT) return (specArch != WN_SPEC_NONE && specOn) ? "WaveNetSpecKernel" : "WaveNetSplitKernel";
+			if (family == WN_FAMILY_WIDE_F32) return "WaveNetWideF32Kernel";
 			return family == WN_FAMILY_GENERIC ? (plan.maxChannels > 64 ? "WaveNetWideKernel" : "WaveNetGenericKernel") : "WaveNetFrameKernel";
 		}
-		const char* FamilyName() const { return family == WN_FAMILY_SPLIT ? "f16-split" : (family == WN_FAMILY_GENERIC ? "generic" : "frame"); }
+		const char* FamilyName() const
+		{
+			if (family == WN_FAMILY_WIDE_F32) return "wide-f32";
+			return family == WN_FAMILY_SPLIT ? "f16-split" : (family == WN_FAMILY_GENERIC ? "generic" : "frame");
+		}
 	};
 
 	// the layout of a pack of `pack` streams (see "Dense packs" below; NA_DebugPackedWeights shows the weights of the same layout)
@@ -91,6 +96,17 @@ namespace na
 			// already): like a failed range proof this outranks NA_WN_KERNEL
 			c.gated = true;
 			c.plan = std::move(real);
+			return c;
+		}
+		if (wn.exactF32)
+		{
+			// Exact f32 on request (NA_SetWaveNetExactF32): the same rule as a failed range proof, and like it this outranks NA_WN_KERNEL -- no
+			// f16-split kernel, hence no pack and no padding.  Up to 16 channels that is the frame kernel; wider models run the f32 kernel of
+			// the runtime-shaped family (wavenet_wide_f32_kernels.hip), on the generic state format (genericOnly plans have no other), with
+			// no input limit
+			c.family = real.genericOnly ? WN_FAMILY_WIDE_F32 : WN_FAMILY_FRAME;
+			c.kind = real.genericOnly ? LaunchKind::Own : LaunchKind::Frame;
+			c.plan = BuildWaveNetPlan(wn, false);
 			return c;
 		}
 		const int realSpec = real.genericOnly ? WN_SPEC_NONE : WaveNetSpecArchId(real.sstages.data(), (int)real.sstages.size(), real.stateF4, (int)(real.wsplit.size() / 8));

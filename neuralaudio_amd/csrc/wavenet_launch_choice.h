@@ -20,8 +20,9 @@ namespace na
 	// WaveNet kernel families: "split" = the f16-split MFMA kernels (wavenet_split_kernels.hip and the chains of wavenet_spec_kernels.hip),
 	// "frame" = the f32 4x4x1-MFMA kernel (wavenet_frame_kernels.hip), "generic" = the runtime-shaped kernel for layer arrays wider than 16
 	// channels (wavenet_generic_kernels.hip; frame-kernel state format).  A group stays in its family for life: the families keep
-	// different stream-state formats.
-	enum WnFamily { WN_FAMILY_AUTO, WN_FAMILY_SPLIT, WN_FAMILY_FRAME, WN_FAMILY_GENERIC };
+	// different stream-state formats.  "wide-f32" = the same widths in exact f32 on request (wavenet_wide_f32_kernels.hip, WaveNetDesc::exactF32;
+	// the generic family's state format).  (Appended: the numeric codes of NA_DebugWaveNetKernel keep their meaning.)
+	enum WnFamily { WN_FAMILY_AUTO, WN_FAMILY_SPLIT, WN_FAMILY_FRAME, WN_FAMILY_GENERIC, WN_FAMILY_WIDE_F32 };
 
 	// the tuning knobs that take part in a choice (tuning.h: NA_WN_KERNEL, NA_WN_PACK, NA_WN_PAD, NA_WN_DENSE, NA_SP_T, NA_SP_SPB, NA_SP_GEN,
 	// NA_SP_NO_T1, NA_FR_PF, NA_FR_SPB) and the chains' switch (NA_WN_SPEC)

@@ -1040,6 +1040,9 @@ namespace na
 			}
 			return;
 		}
+		// Exact f32 on request (WaveNetDesc::exactF32): WaveNetWideF32Kernel runs the model, and neither the operand format nor the range
+		// bound concerns it.  (The shape limits -- ValidateWaveNetDesc, inside BuildWaveNetPlan above -- are the same.)
+		if (desc.exactF32) return;
 		const std::string who = "WaveNet with layer arrays wider than 16 channels (f16-split arithmetic only): ";
 		if (!plan.splitWeightsOk)
 			throw std::runtime_error(who + "the weights do not fit the (hi, lo) f16 operand format (a weight beyond 32752, or a weight matrix whose largest entry is below 2^-12)");
