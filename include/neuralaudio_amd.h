@@ -783,6 +783,76 @@ NA_EXTERN int NA_BatchGetStreamTuner(NA_Batch* batch, int stream, NA_TunerParams
 NA_EXTERN int NA_BatchReadStreamTuner(NA_Batch* batch, int stream, NA_TunerReading* out);  /* REAL-TIME SAFE; 1 / 0 / < 0 as the meter's */
 NA_EXTERN int NA_TunerParamsFromRange(double sampleRate, double lowestHz, double highestHz, double evaluationsPerSecond, NA_TunerParams* out);
 NA_EXTERN int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, double* hz, double* clarity); /* host arithmetic; 0 when lag == 0 */
+/* ---- the drive stage: a per-stream oversampled boost / overdrive in front of the model ----
+ * The first pedal of a board: a static nonlinearity that shapes the signal the capture sees.  At the base rate a shaper aliases audibly,
+ * so the stage oversamples: an L-fold interpolating FIR, the shaper, the same FIR as decimator.  A twelfth per-stream stage, off unless
+ * enabled, FIRST in the chain's order and the only one that changes what a MODEL READS: a session's chain is drive -> gate -> model ->
+ * EQ -> cabinet -> ...  Only the model's input changes: the gate's detector, the tuner, the meter's IN tap and a mix group's DRY tap keep
+ * reading the rows the caller passed, and those rows are never written (dIn == dOut in NA_BatchProcessDevice stays legal).  A batch that
+ * enabled the stage and set no drive launches exactly what it launched before and produces the same bits.
+ * Order of a processing call: while an entry exists ONE launch in front of everything else fills a [rows][samples] block the stage
+ * owns -- a driven row processed, every other row copied -- and the model launches of the call read that block.
+ * LATENCY: a driven stream is delayed by exactly NA_DRIVE_TAPS_PER_PHASE = 32 samples, at every oversampling factor (up and down filter
+ * are each delayed by half their length); the dry part of `mix` is delayed alike.  Rows without a drive are not delayed: the host
+ * compensates where it sums them.
+ * Arithmetic.  L = oversample, T = 32, N = L T.  The prototype h[0 .. N] is computed once on the host in double and rounded to f32:
+ *     h[j] ~ sinc((j - N/2) / L) * I0(9 sqrt(1 - (2 (j - N/2) / N)^2)) / I0(9),  sinc(x) = sin(pi x) / (pi x),  normalised to sum 1
+ *   (flat within +-0.00025 dB up to 0.4 of the base rate, -3.9e-3 dB at 20 kHz / 48 kHz, <= -90.9 dB from 0.6 of the base rate upward).
+ *   Positions n = 0, 1, ... count the samples of the stream's input row since the set call that created the entry; x[n] = 0 for n < 0;
+ *   a NaN sample reads as 0 (infinities are the caller's to keep out).
+ *     u[L n + p] = sum over t >= 0, p + L t <= N, ascending t, of (L h[p + L t]) * x[n - t]          (p = 0 .. L-1)
+ *     s[m]       = shape(g u[m] + b) - shape(b)                                                     (m < 0: s = 0)
+ *     w[n]       = sum over j = 0 .. N, ascending j, of h[j] * s[L n - j]
+ *     out[n]     = level * (mix * w[n] + (1 - mix) * x[n - T])
+ *   shape TANH: 1 - 2 / (exp2(2 log2(e) v) + 1) on the device's exp2 / reciprocal units (absolute error ~1e-7), the StdMath form of
+ *   the model kernels; CUBIC: 1.5 (v - v^3 / 3) for |v| < 1, otherwise +-1; HARD: min(max(v, -1), 1).  g = drive, b = bias, those of
+ *   base sample floor(m / L).  Each of the two sums is ONE f32 accumulator that starts at 0 and takes its terms in the stated order,
+ *   every step ONE FUSED multiply-add (fmaf); every other operation -- g u, + b, the subtraction, the shapes' own operations, mix w,
+ *   1 - mix, its product, the sum, level -- is rounded by itself (the unit is built without contraction).  The s a call reads behind
+ *   its first sample is recomputed from the 2 T input samples the stage keeps per row, so a sample's bits do not depend on how the
+ *   signal is cut into calls, on the stride or on the other streams.  Against the same formulas in double the row is within 2e-6 RMS
+ *   relative to max(1, level) on every 32-frame window (measured worst: DESIGN.md 2.21).
+ * Ramp: drive, bias, mix and level move linearly from the values in effect to the new ones over rampSamples; a NEW entry starts from
+ *   the drive and bias it is given, mix 0 and level 1 -- the delayed dry row.  k counts the samples since the LAST set call; a value is
+ *   `from` for k < 0, `to` for k >= R - 1 and from + (to - from) * w, w = (float)((double)(k + 1) / (double)R), between, k advanced by
+ *   whole calls and never accumulated.  The outputs between two set calls are those of the earlier call's ramp; the s of the 2 T
+ *   samples behind a set call that its first outputs still read are evaluated with its from-values.
+ *   A set call while a ramp runs is refused ("... ramp running").  shape and oversample belong to the entry for its life: a set call
+ *   that changes either on a stream that has a drive is refused by name.  The click-free route to another shape or factor, and to no
+ *   drive at all: ramp mix to 0 (level to 1), take the drive away, set the new one with a ramp -- and hide the 32-sample jump of the
+ *   row, which is the host's (the dry row jumps from delayed to undelayed), in a moment of silence or a cross-fade of its own.
+ * Limits (each refused with a message that names the field): shape in [0, 2]; oversample 2, 4 or 8; drive finite in [0, 1000]; bias
+ *   finite in [-4, 4]; mix in [0, 1]; level finite in [0, 16]; rampSamples in [0, 1 << 20].  reserved is ignored.
+ * NA_BatchEnableDriveStage is the set-up side (allocates; idempotent): the coefficients of the three factors, two history blocks of 64
+ *   samples and a row of the model-input block per row, and the stage's device + pinned tables; later NA_BatchAddStreams /
+ *   NA_BatchReserveStreams grow them, and a call longer than the block's rows (1024 samples at first) grows those first, like any
+ *   first use of a longer buffer.  Every call below fails ("drive stage not enabled (NA_BatchEnableDriveStage)") before it.  It is
+ *   refused on a resampling batch, and NA_BatchSetResampling with different rates is refused on a batch that enabled it.
+ * NA_BatchSetStreamDrive is REAL-TIME SAFE: host arithmetic on tables that exist; no memset travels with it.
+ *   The stream has no drive: the entry starts at the next sample, at position 0, with silence behind it.
+ *   The stream has a drive: its position and history go on; the four values ramp (rampSamples == 0: they change at once).
+ *   params == NULL: the drive goes AT ONCE, with its history: the model reads x[n] undelayed from the next call on.
+ * NA_BatchGetStreamDrive returns 1 and fills *out with the target, 0 when the stream has no drive, < 0 on a bad id or when the stage is
+ *   not enabled.  NA_BatchStreamDriveRampRemaining returns the samples the ramp still has to run (0: none), < 0 on an error.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a
+ * hand-over, drop the drive and its history at once.  Drives are not part of a NA_BatchSaveStreams blob; NA_BatchLoadStreams leaves
+ * them alone.
+ * While an entry exists a processing call behaves as it does with entries of the other stages: its launches run in order on one
+ * stream (no half-batch chains, no resident launch), host buffers go through the library's device staging block, and it enqueues one
+ * table upload from a ring of pinned tables and ONE launch, whatever n: no device or pinned allocation, no stream or event creation,
+ * no unbounded wait.  With the last entry the free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches, on the one-stream NeuralModel and in NA_RenderOffline; filters in front of the shaper
+ * (a pre-model EQ position is a change of its own). */
+#define NA_DRIVE_TAPS_PER_PHASE 32      /* T: also the stage's latency in samples, at every oversampling factor */
+enum { NA_DRIVE_SHAPE_TANH = 0, NA_DRIVE_SHAPE_CUBIC = 1, NA_DRIVE_SHAPE_HARD = 2 };
+typedef struct NA_DriveParams { int shape, oversample; float drive, bias, mix, level; int reserved[2]; } NA_DriveParams;
+typedef struct NA_DriveInfo   { int numDrives; long long deviceBytes; } NA_DriveInfo;
+NA_EXTERN int NA_BatchEnableDriveStage(NA_Batch* batch);                                   /* set-up side, allocates, idempotent */
+NA_EXTERN int NA_BatchGetDriveInfo(NA_Batch* batch, NA_DriveInfo* info);
+NA_EXTERN int NA_BatchSetStreamDrive(NA_Batch* batch, int stream, const NA_DriveParams* params, int rampSamples); /* REAL-TIME SAFE; NULL: the drive goes */
+NA_EXTERN int NA_BatchGetStreamDrive(NA_Batch* batch, int stream, NA_DriveParams* out);    /* 1 / 0 / < 0 as the tuner's */
+NA_EXTERN int NA_BatchStreamDriveRampRemaining(NA_Batch* batch, int stream);
 /* ---- the mix stage: per-session mix groups ----
  * Every stage above works on one row at a time.  A rig that runs two captures on one input, blended or panned left / right (dual amp),
  * an amp next to the dry DI (wet / dry), or wet / dry / wet needs rows to MEET, and the output rows never pass through host code that
@@ -1278,6 +1348,8 @@ NA_EXTERN long long NA_DebugModLaunches(void);
 NA_EXTERN long long NA_DebugGateLaunches(void);
 /* Tests: launches of the meter stage's two kernels so far (two per processing call with entries) */
 NA_EXTERN long long NA_DebugMeterLaunches(void);
+/* Tests: launches of the drive stage's kernel so far (one per call with entries) */
+NA_EXTERN long long NA_DebugDriveLaunches(void);
 /* Tests: launches of the tuner stage's two kernels so far (one append per piece of a call with entries, one evaluate where an evaluation ends) */
 NA_EXTERN long long NA_DebugTunerLaunches(void);
 /* Tests: launches of the EQ stage's kernel so far (one per processing call with entries) */

@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "mod_params_from_ms", "MOD_TRIANGLE", "MOD_SINE", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "mod_params_from_ms", "MOD_TRIANGLE", "MOD_SINE", "DRIVE_SHAPE_TANH", "DRIVE_SHAPE_CUBIC", "DRIVE_SHAPE_HARD", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -196,6 +196,23 @@ def _tuner_params(d):
 
 def _tuner_dict(p):
     return {name: int(getattr(p, name)) for name in TUNER_FIELDS}
+
+
+DRIVE_FIELDS = ("shape", "oversample", "drive", "bias", "mix", "level")
+DRIVE_SHAPE_TANH, DRIVE_SHAPE_CUBIC, DRIVE_SHAPE_HARD = capi.NA_DRIVE_SHAPE_TANH, capi.NA_DRIVE_SHAPE_CUBIC, capi.NA_DRIVE_SHAPE_HARD
+
+
+def _drive_params(d):
+    if isinstance(d, capi.NA_DriveParams):
+        return d
+    p = capi.NA_DriveParams()
+    for name in DRIVE_FIELDS:
+        setattr(p, name, (int if name in ("shape", "oversample") else float)(d[name]))
+    return p
+
+
+def _drive_dict(p):
+    return {name: (int if name in ("shape", "oversample") else float)(getattr(p, name)) for name in DRIVE_FIELDS}
 
 
 def _tuner_reading(r):
@@ -979,6 +996,39 @@ class Batch:
         if rc < 0:
             raise NeuralAudioError(capi.last_error())
         return _tuner_reading(out) if rc else None
+
+    # -- the drive stage: EnableDriveStage is set-up side; SetStreamDrive is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableDriveStage(self):
+        if self._lib.NA_BatchEnableDriveStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetDriveInfo(self):
+        info = capi.NA_DriveInfo()
+        if self._lib.NA_BatchGetDriveInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_DriveInfo._fields_}
+
+    def SetStreamDrive(self, stream, params, rampSamples=0):
+        """An oversampled boost or overdrive in front of the stream's model from the next sample on: `params` a dict of the
+        NA_DriveParams fields (shape, oversample, drive, bias, mix, level); drive, bias, mix and level ramp over rampSamples.  None
+        takes the drive away at once.  The driven stream is delayed by NA_DRIVE_TAPS_PER_PHASE (32) samples."""
+        p = None if params is None else C.byref(_drive_params(params))
+        if self._lib.NA_BatchSetStreamDrive(self._h, int(stream), p, int(rampSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamDrive(self, stream):
+        """The target constants as a dict; None: no drive."""
+        out = capi.NA_DriveParams()
+        rc = int(self._lib.NA_BatchGetStreamDrive(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _drive_dict(out) if rc else None
+
+    def StreamDriveRampRemaining(self, stream):
+        rc = int(self._lib.NA_BatchStreamDriveRampRemaining(self._h, int(stream)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return rc
 
     # -- the mix stage: EnableMixStage is set-up side; SetMixGroup and ClearMixGroup are real-time safe (include/neuralaudio_amd.h) ----
     def EnableMixStage(self):

@@ -60,6 +60,8 @@ NA_SYMBOLS = [
     "NA_DebugMeterLaunches",
     "NA_BatchEnableTunerStage", "NA_BatchGetTunerInfo", "NA_BatchSetStreamTuner", "NA_BatchGetStreamTuner", "NA_BatchReadStreamTuner",
     "NA_TunerParamsFromRange", "NA_TunerPitch", "NA_DebugTunerLaunches",
+    "NA_BatchEnableDriveStage", "NA_BatchGetDriveInfo", "NA_BatchSetStreamDrive", "NA_BatchGetStreamDrive", "NA_BatchStreamDriveRampRemaining",
+    "NA_DebugDriveLaunches",
     "NA_BatchEnableMixStage", "NA_BatchGetMixInfo", "NA_BatchSetMixGroup", "NA_BatchClearMixGroup", "NA_BatchGetStreamMix",
     "NA_BatchMixRampRemaining", "NA_MixGainsFromPan", "NA_DebugMixLaunches", "NA_DebugMixStashLaunches", "NA_DebugRunMixStage",
 ]
@@ -176,6 +178,21 @@ class NA_TunerReading(C.Structure):
 
 class NA_TunerInfo(C.Structure):
     _fields_ = [("numTuners", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+NA_DRIVE_TAPS_PER_PHASE = 32
+NA_DRIVE_SHAPE_TANH = 0
+NA_DRIVE_SHAPE_CUBIC = 1
+NA_DRIVE_SHAPE_HARD = 2
+
+
+class NA_DriveParams(C.Structure):
+    _fields_ = [("shape", C.c_int), ("oversample", C.c_int), ("drive", C.c_float), ("bias", C.c_float), ("mix", C.c_float), ("level", C.c_float),
+                ("reserved", C.c_int * 2)]
+
+
+class NA_DriveInfo(C.Structure):
+    _fields_ = [("numDrives", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 NA_MIX_MAX_MEMBERS = 8
@@ -347,6 +364,12 @@ def load_library():
         "NA_TunerParamsFromRange": (C.c_int, [C.c_double] * 4 + [C.POINTER(NA_TunerParams)]),
         "NA_TunerPitch": (C.c_int, [C.POINTER(NA_TunerReading), C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "NA_DebugTunerLaunches": (C.c_longlong, []),
+        "NA_BatchEnableDriveStage": (C.c_int, [vp]),
+        "NA_BatchGetDriveInfo": (C.c_int, [vp, C.POINTER(NA_DriveInfo)]),
+        "NA_BatchSetStreamDrive": (C.c_int, [vp, C.c_int, C.POINTER(NA_DriveParams), C.c_int]),
+        "NA_BatchGetStreamDrive": (C.c_int, [vp, C.c_int, C.POINTER(NA_DriveParams)]),
+        "NA_BatchStreamDriveRampRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_DebugDriveLaunches": (C.c_longlong, []),
         "NA_BatchEnableMixStage": (C.c_int, [vp]),
         "NA_BatchGetMixInfo": (C.c_int, [vp, C.POINTER(NA_MixInfo)]),
         "NA_BatchSetMixGroup": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int]),

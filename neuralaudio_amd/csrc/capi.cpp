@@ -1261,6 +1261,58 @@ int NA_TunerPitch(const NA_TunerReading* reading, double sampleRate, double* hz,
 long long NA_DebugTunerLaunches(void) { return (long long)na::TunerStageLaunches(); }
 #endif
 
+// ---- the drive stage (gpu_batch.h EnableDriveStage / SetStreamDrive) ----
+static_assert(sizeof(NA_DriveParams) == sizeof(na::DriveParams) && NA_DRIVE_TAPS_PER_PHASE == na::kDriveTaps, "NA_DriveParams is DriveParams, field for field");
+static_assert(NA_DRIVE_SHAPE_TANH == na::kDriveShapeTanh && NA_DRIVE_SHAPE_CUBIC == na::kDriveShapeCubic && NA_DRIVE_SHAPE_HARD == na::kDriveShapeHard, "the header's shapes are drive_stage.h's");
+
+int NA_BatchEnableDriveStage(NA_Batch* batch)
+{
+	return BatchCall(batch, "NA_BatchEnableDriveStage", [&](na::GpuBatch& b) { b.EnableDriveStage(); });
+}
+
+int NA_BatchGetDriveInfo(NA_Batch* batch, NA_DriveInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetDriveInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetDriveInfo: bad argument");
+		const na::DriveStageInfo i = b.GetDriveInfo();
+		info->numDrives = i.numDrives;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamDrive(NA_Batch* batch, int stream, const NA_DriveParams* params, int rampSamples)
+{
+	return BatchCall(batch, "NA_BatchSetStreamDrive", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamDrive(stream, nullptr, 0);
+			return;
+		}
+		na::DriveParams d;
+		memcpy(&d, params, sizeof(d));
+		b.SetStreamDrive(stream, &d, rampSamples);
+	});
+}
+
+int NA_BatchGetStreamDrive(NA_Batch* batch, int stream, NA_DriveParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamDrive", -1, [&](na::GpuBatch& b) {
+		na::DriveParams d;
+		const int has = b.GetStreamDrive(stream, d) ? 1 : 0;
+		if (has && out) memcpy(out, &d, sizeof(d));
+		return has;
+	});
+}
+
+int NA_BatchStreamDriveRampRemaining(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchStreamDriveRampRemaining", -1, [&](na::GpuBatch& b) { return b.StreamDriveRampRemaining(stream); });
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugDriveLaunches(void) { return (long long)na::DriveStageLaunches(); }
+#endif
+
 // ---- the mix stage (gpu_batch.h EnableMixStage / SetMixGroup) ----
 static_assert(NA_MIX_MAX_MEMBERS == na::kMixMaxMembers && NA_MIX_TAP_OUT == na::kMixTapOut && NA_MIX_TAP_DRY == na::kMixTapDry, "the header's mix constants are mix_stage.h's");
 

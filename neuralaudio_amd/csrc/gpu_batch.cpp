@@ -620,9 +620,9 @@ namespace na
 	}
 
 	// One processing call on `launch`, and the one place that states its order: what a stage runs in front of the models, in StageId
-	// order -- the gate detector, then the mix stage's stash of the input rows its DRY members name (2.16), then the meter's IN tap (2.14), then the tuner's append and evaluate launches (2.15):
+	// order -- the drive stage's launch, which fills the block the models of this call read in place of the caller's rows (everything else in front of the models keeps reading the caller's rows), then the gate detector, then the mix stage's stash of the input rows its DRY members name (2.16), then the meter's IN tap (2.14), then the tuner's append and evaluate launches (2.15):
 	// they read the input rows as the caller passed them, which may be the output rows, so before any model writes --, the up kernel, the model launches and the down kernel of a
-	// resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages (DESIGN.md 2.9 - 2.20) once per
+	// resampling batch (ProcessResampledOn) or the model launches alone, then the per-stream stages (DESIGN.md 2.9 - 2.21) once per
 	// call: behind everything the call has launched -- the join of the units, the graph replay, the down kernel -- on the same stream,
 	// outside any capture.  The stages' order is the order of StageId (gpu_batch.h), written there and nowhere else: every row is
 	// gated first, then runs through its own EQ cascade (the tone stack sits between amp and cabinet), then is convolved with its own
@@ -635,7 +635,12 @@ namespace na
 	{
 		for (auto& stage : stages)
 			if (stage && stage->HasEntries()) stage->BeforeModels(*this, launch, dIn, n, inStride);
+		// (a drive stage with entries has filled its block: the models read it; a resampling batch has no drive stage)
+		DriveStage* drive = static_cast<DriveStage*>(stages[kDriveStage].get());
+		const bool driven = drive && drive->filled;
+		if (driven) drive->filled = false;
 		if (Resamples()) ProcessResampledOn(launch, dIn, dOut, n, inStride, outStride);
+		else if (driven) LaunchModelsOn(launch, drive->block, dOut, n, (long)drive->blockSamples, outStride);
 		else LaunchModelsOn(launch, dIn, dOut, n, inStride, outStride);
 		RunStages(launch, dOut, n, outStride);
 	}

@@ -22,6 +22,7 @@
 #include "compressor_stage.h"
 #include "delay_stage.h"
 #include "device_resources.h"
+#include "drive_stage.h"
 #include "eq_stage.h"
 #include "gate_stage.h"
 #include "host_route.h"
@@ -124,6 +125,12 @@ namespace na
 	struct TunerStageInfo
 	{
 		int numTuners = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct DriveStageInfo
+	{
+		int numDrives = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -334,6 +341,22 @@ namespace na
 		bool GetStreamTuner(int stream, TunerParams& out) const;    // false: no tuner
 		bool ReadStreamTuner(int stream, TunerReading& out);        // false: no tuner, or no evaluation has arrived yet
 
+		// The drive stage (drive_stage.h): a per-stream boost or overdrive IN FRONT of the model -- the row a stream takes in,
+		// oversampled 2, 4 or 8 times, shaped (tanh, cubic or hard clip), decimated and mixed with the delayed dry row -- the one stage that
+		// changes what a model reads; the gate's detector, the tuner, the meter's IN tap and a mix group's DRY tap keep reading the rows the
+		// caller passed, which are never written.  EnableDriveStage is the set-up side: the coefficients, two history blocks of 64 samples
+		// and a row of the model-input block per row (CreateStreams grows them; a call longer than the block's rows grows those first, like
+		// any first use of a longer buffer) and the tables.  SetStreamDrive is host arithmetic on those tables; while an entry exists
+		// every processing call runs on the ordered path and enqueues ONE table upload and ONE launch, whatever n, that fills the block
+		// for every row -- driven rows processed, the others copied -- and the model launches read the block.  Without an entry the batch
+		// launches exactly what it launches without the stage.
+		void EnableDriveStage();
+		bool HasDriveStage() const { return stages[kDriveStage] != nullptr; }
+		DriveStageInfo GetDriveInfo() const;
+		void SetStreamDrive(int stream, const DriveParams* params, int rampSamples); // nullptr: the drive goes at once
+		bool GetStreamDrive(int stream, DriveParams& out) const;                     // the target; false: none
+		int StreamDriveRampRemaining(int stream) const;
+
 		// The mix stage (mix_stage.h): per-session mix groups -- the rows of up to 8 members (a stream's row as the output
 		// stage left it, or the input row the caller passed for it) summed through a ramped D x M gain matrix into the rows of the first
 		// D members -- behind the output stage and in front of the meter's OUT tap: the one stage in which rows meet.  EnableMixStage is
@@ -506,22 +529,22 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.20).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.21).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kGateStage, kEqStage, kCabinetStage, kCompressorStage, kModStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kDriveStage, kGateStage, kEqStage, kCabinetStage, kCompressorStage, kModStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
 			virtual bool HasEntries() const = 0;
 			virtual void EnsureRows(GpuBatch& batch, int rows) = 0; // set-up side: device blocks and tables for `rows` rows
 			virtual void Leave(int stream) = 0;                     // park / removal: nothing of the stream is carried over
-			// a call with entries: in front of its model launches (the gate's detector, the mix stage's stash, the meter's IN tap, the tuner), and behind them in chain order
+			// a call with entries: in front of its model launches (the drive, the gate's detector, the mix stage's stash, the meter's IN tap, the tuner), and behind them in chain order
 			virtual void BeforeModels(GpuBatch&, hipStream_t, const float*, size_t, long) {}
 			virtual void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) = 0;
 		};
 		template <class Book, class Entry> struct StageOf;
 		template <class Record> struct StageResults; // the result blocks of the stages that report to the host (meter, tuner)
-		struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct ModStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
+		struct DriveStage; struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct ModStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -299,7 +299,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the eleven stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the twelve stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -309,6 +309,29 @@ namespace na
 		explicit StageOf(const char* name) : tables(name) {}
 		bool HasEntries() const override { return book.HasEntries(); }
 	};
+
+	// the drive stage (drive_stage.h, drive_stage.cpp): the rows' history blocks, the coefficients of the three factors and
+	// the model-input block its launch fills in front of the model launches of a call with entries; everything a call enqueues is in
+	// BeforeModels, and -- until the call's model launches have been enqueued -- `filled` says that they read the block
+	struct GpuBatch::DriveStage : StageOf<DriveBook, DriveEntry>
+	{
+		static constexpr StageId kId = kDriveStage;
+		static constexpr const char* kNotEnabled = "drive stage not enabled (NA_BatchEnableDriveStage)";
+		float* history = nullptr;         // [rowCapacity][2][kDriveHistory]
+		float* block = nullptr;           // [rowCapacity][blockSamples]: what the models read (nothing of it outlives its call)
+		float* coefs = nullptr;           // [3][kDriveCoefFloats]
+		int rowCapacity = 0;
+		int blockSamples = kDriveMinBlockSamples; // a power of two
+		bool filled = false;              // this call's launch has filled the block
+		DriveStage() : StageOf("drive stage") {}
+		~DriveStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // its drive goes at once, its history dropped
+		void EnsureSamples(GpuBatch& batch, size_t n); // block rows of at least n samples (grows them: not real-time safe)
+		void BeforeModels(GpuBatch& batch, hipStream_t launch, const float* dIn, size_t n, long inStride) override; // table upload + launch + the host mirror's advance
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override;              // nothing
+	};
+	hipError_t LaunchDriveStage(const DriveLaunch& L, hipStream_t stream); // (drive_stage_kernels.hip)
 
 	// the gate stage (gate_stage.h, gate_stage.cpp): the rows' states and gain rows on the device, and -- between the
 	// detector and the apply launch of one call -- the table that call runs on

@@ -136,6 +136,8 @@ namespace na
 		std::unique_ptr<ResampleState> rs(new ResampleState());
 		rs->plan = PlanResampling(externalRate, modelRate, quantum);
 		const ResamplePlan& p = rs->plan;
+		if (!p.identity && stages[kDriveStage])
+			throw std::runtime_error("neuralaudio_amd: SetResampling: resampling is refused on a batch with the drive stage enabled (NA_BatchEnableDriveStage)");
 		if (!p.identity)
 		{
 			// the longest piece whose two windows (history ++ the piece's samples) fit the stages' LDS window
