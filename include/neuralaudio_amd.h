@@ -853,6 +853,73 @@ NA_EXTERN int NA_BatchGetDriveInfo(NA_Batch* batch, NA_DriveInfo* info);
 NA_EXTERN int NA_BatchSetStreamDrive(NA_Batch* batch, int stream, const NA_DriveParams* params, int rampSamples); /* REAL-TIME SAFE; NULL: the drive goes */
 NA_EXTERN int NA_BatchGetStreamDrive(NA_Batch* batch, int stream, NA_DriveParams* out);    /* 1 / 0 / < 0 as the tuner's */
 NA_EXTERN int NA_BatchStreamDriveRampRemaining(NA_Batch* batch, int stream);
+/* ---- the limiter stage: a per-stream look-ahead brickwall limiter on the row the caller receives ----
+ * The compressor stage sits in the middle of the chain and its follower has an attack time; the echo's feedback, the reverb, the output
+ * gain and a mix group that sums up to eight rows all come behind it.  This stage bounds what the caller RECEIVES: a thirteenth
+ * per-stream stage, off unless enabled, behind the mix stage and in front of the meter stage -- a session's chain is drive -> model ->
+ * gate -> EQ -> cabinet -> compressor -> modulation -> delay -> reverb -> output gain -> mix -> limiter, and the OUT tap of a meter
+ * reads the limited row.  A batch that enabled the stage and set no limiter launches exactly what it launched before and produces
+ * the same bits.  Rows are limited independently (no stereo linking across a mix group's outputs).
+ * LATENCY: a limited row is delayed by exactly `lookahead` samples.  Rows without a limiter are not delayed.
+ * Arithmetic.  Every operation is one separately rounded f32 operation fl(.), round to nearest even, no FMA contraction, subnormals
+ *   kept; the quotient is correctly rounded.  L = lookahead, H = hold, x the row as the mix stage left it.  Positions t = 0, 1, ...
+ *   count the samples of the row since the set call that created the entry; a position t < 0 counts as need = 1 and x = +0 -- decided
+ *   by position, never by what memory holds.  k counts the samples since the LAST set call (negative in front of it).
+ *     c[t]    = from for k < 0;  to for k >= R - 1;  else fl(from + fl(fl(to - from) * w)),  w = (float)(k + 1) / (float)R
+ *     need[t] = |x[t]| > c[t] ? fl(c[t] / |x[t]|) : 1
+ *     m[t]    = min(need[t - L - H .. t])
+ *     S_1[t]  = fl(m[t - 1] + m[t]),  S_(j+1)[t] = fl(S_j[t - 2^j] + S_j[t]),  S[t] = S_(log2 L)[t]
+ *               (the sum of m[t - L + 1 .. t] as a PAIRWISE TREE in index order)
+ *     g[t]    = fl(S[t] * (1 / L))
+ *     y[t]    = min(max(fl(x[t - L] * g[t]), -c[t]), c[t])
+ *   Why a tree: a tree sum of L copies of v is exactly L v, and rounding is monotone, so g[t] <= need[t - L] wherever the ceiling is
+ *   constant over the window: the gain does the limiting, and the clamp only removes the last ulp of fl(c / a) * a.  A row that never
+ *   exceeds c has g = 1 exactly and comes out bit for bit, L samples late.  Attack and release are linear over L samples; the gain
+ *   is held H samples behind a peak.  There is no recursive release: it would make the stage serial.
+ *   |y[t]| <= c[t] always (the clamp).  The outputs between two set calls are those of the earlier call's (from, to, R) and H, which
+ *   reach back over the 2 L + H samples an output reads: need of a sample in front of the set call is evaluated with `from`.  For the
+ *   L samples behind a set call that LOWERS the ceiling (and through a falling ramp) the clamp may therefore cut what the gain has not
+ *   yet reached: lower the ceiling with a ramp.  The stage keeps the last 2 L + H INPUT samples per row and recomputes from them, so a
+ *   sample's bits do not depend on how the signal is cut into calls, on the stride or on the other streams.
+ *   Non-finite samples: a NaN sample has need = 1 and comes out as -c[t] (min / max drop the NaN); an infinite sample has need = 0,
+ *   pulls the gain to 0 over its window and comes out as -c[t] as well (inf * 0).  Neither spreads beyond its window.
+ * Limits (each refused with a message that names the field): lookahead a power of two in [8, 512]; hold in [0, 4096]; ceiling finite
+ *   and > 0; rampSamples in [0, 1 << 20].  reserved is ignored.
+ * NA_BatchEnableLimiterStage is the set-up side (allocates; idempotent): a ring of the last 5120 input samples per row (20 KB a row:
+ *   20 MB for 1024 rows, NA_BatchGetLimiterInfo's deviceBytes) and the stage's device + pinned tables; later NA_BatchAddStreams /
+ *   NA_BatchReserveStreams grow them.  Every call below fails ("limiter stage not enabled (NA_BatchEnableLimiterStage)") before it.
+ *   It is refused on a resampling batch, and NA_BatchSetResampling with different rates is refused on a batch that enabled it.
+ * NA_BatchSetStreamLimiter is REAL-TIME SAFE: host arithmetic on tables that exist; no memset travels with it.
+ *   The stream has no limiter: the entry starts at the next sample, at position 0, with silence behind it, at the given ceiling
+ *     (rampSamples is ignored: there is nothing to ramp from).
+ *   The stream has a limiter: its position and history go on; the ceiling ramps over rampSamples from the ceiling of the last sample
+ *     produced (a set call during a ramp starts from where the ramp stands); `hold` acts at once -- any window of at least L + 1
+ *     samples keeps the bound --; a different `lookahead` is refused by name (it is the row's latency: take the limiter away first).
+ *   params == NULL: the limiter goes AT ONCE, with its history, as the drive stage's does: the row comes out undelayed from the next
+ *     call on, and the L samples in flight are dropped.  The jump is the host's to hide.
+ * NA_BatchGetStreamLimiter returns 1 and fills *out with the target, 0 when the stream has no limiter, < 0 on a bad id or when the
+ *   stage is not enabled.
+ * NA_LimiterParamsFromDb is host arithmetic in double, each value rounded once, no device: ceiling = 10^(ceilingDb / 20); lookahead =
+ *   the power of two in [8, 512] nearest to lookaheadMs * sampleRate / 1000 (a value v picks P while v <= 1.5 P); hold =
+ *   round(holdMs * sampleRate / 1000), refused beyond 4096.  It returns 0, or < 0 with a message.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a
+ * hand-over, drop the limiter and its history at once.  Limiters are not part of a NA_BatchSaveStreams blob.
+ * While an entry exists a processing call behaves as it does with entries of the other stages: its launches run in order on one
+ * stream, host buffers go through the library's device staging block, and it enqueues one table upload from a ring of pinned tables
+ * and one launch per piece of 1024 samples over the entries only: no device or pinned allocation, no stream or event creation, no
+ * unbounded wait.  With the last entry the free-running modes come back.
+ * Not provided: the stage on NA_Multi* batches, on the one-stream NeuralModel and in NA_RenderOffline; stereo linking; true-peak
+ * (oversampled) detection; a recursive release. */
+#define NA_LIMITER_MAX_LOOKAHEAD 512
+#define NA_LIMITER_MAX_HOLD 4096
+typedef struct NA_LimiterParams { int lookahead, hold; float ceiling; int reserved; } NA_LimiterParams;
+typedef struct NA_LimiterInfo   { int historySamples, pieceSamples, numLimiters; long long deviceBytes; } NA_LimiterInfo;
+NA_EXTERN int NA_BatchEnableLimiterStage(NA_Batch* batch);                                 /* set-up side, allocates, idempotent */
+NA_EXTERN int NA_BatchGetLimiterInfo(NA_Batch* batch, NA_LimiterInfo* info);
+NA_EXTERN int NA_BatchSetStreamLimiter(NA_Batch* batch, int stream, const NA_LimiterParams* params, int rampSamples); /* REAL-TIME SAFE; NULL: the limiter goes */
+NA_EXTERN int NA_BatchGetStreamLimiter(NA_Batch* batch, int stream, NA_LimiterParams* out); /* 1 / 0 / < 0 as the tuner's */
+NA_EXTERN int NA_LimiterParamsFromDb(int sampleRate, double ceilingDb, double lookaheadMs, double holdMs, NA_LimiterParams* out); /* host arithmetic */
 /* ---- the mix stage: per-session mix groups ----
  * Every stage above works on one row at a time.  A rig that runs two captures on one input, blended or panned left / right (dual amp),
  * an amp next to the dry DI (wet / dry), or wet / dry / wet needs rows to MEET, and the output rows never pass through host code that
@@ -1350,6 +1417,8 @@ NA_EXTERN long long NA_DebugGateLaunches(void);
 NA_EXTERN long long NA_DebugMeterLaunches(void);
 /* Tests: launches of the drive stage's kernel so far (one per call with entries) */
 NA_EXTERN long long NA_DebugDriveLaunches(void);
+/* Tests: launches of the limiter stage's kernel so far (one per piece of a call with entries) */
+NA_EXTERN long long NA_DebugLimiterLaunches(void);
 /* Tests: launches of the tuner stage's two kernels so far (one append per piece of a call with entries, one evaluate where an evaluation ends) */
 NA_EXTERN long long NA_DebugTunerLaunches(void);
 /* Tests: launches of the EQ stage's kernel so far (one per processing call with entries) */

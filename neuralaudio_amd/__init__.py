@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "mod_params_from_ms", "MOD_TRIANGLE", "MOD_SINE", "DRIVE_SHAPE_TANH", "DRIVE_SHAPE_CUBIC", "DRIVE_SHAPE_HARD", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "mod_params_from_ms", "MOD_TRIANGLE", "MOD_SINE", "DRIVE_SHAPE_TANH", "DRIVE_SHAPE_CUBIC", "DRIVE_SHAPE_HARD", "limiter_params_from_db", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -213,6 +213,30 @@ def _drive_params(d):
 
 def _drive_dict(p):
     return {name: (int if name in ("shape", "oversample") else float)(getattr(p, name)) for name in DRIVE_FIELDS}
+
+
+LIMITER_FIELDS = ("lookahead", "hold", "ceiling")
+
+
+def _limiter_params(d):
+    if isinstance(d, capi.NA_LimiterParams):
+        return d
+    p = capi.NA_LimiterParams()
+    p.lookahead, p.hold, p.ceiling = int(d["lookahead"]), int(d["hold"]), float(d["ceiling"])
+    return p
+
+
+def _limiter_dict(p):
+    return {"lookahead": int(p.lookahead), "hold": int(p.hold), "ceiling": float(p.ceiling)}
+
+
+def limiter_params_from_db(sample_rate, ceiling_db, lookahead_ms=1.5, hold_ms=0.0):
+    """The constants Batch.SetStreamLimiter takes, from dBFS and milliseconds (NA_LimiterParamsFromDb): the lookahead is rounded to the
+    nearest power of two in [8, 512] samples.  Host arithmetic: needs no device."""
+    out = capi.NA_LimiterParams()
+    if capi.load_library().NA_LimiterParamsFromDb(int(sample_rate), float(ceiling_db), float(lookahead_ms), float(hold_ms), C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _limiter_dict(out)
 
 
 def _tuner_reading(r):
@@ -1029,6 +1053,33 @@ class Batch:
         if rc < 0:
             raise NeuralAudioError(capi.last_error())
         return rc
+
+    # -- the limiter stage: EnableLimiterStage is set-up side; SetStreamLimiter is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableLimiterStage(self):
+        if self._lib.NA_BatchEnableLimiterStage(self._h) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetLimiterInfo(self):
+        info = capi.NA_LimiterInfo()
+        if self._lib.NA_BatchGetLimiterInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_LimiterInfo._fields_}
+
+    def SetStreamLimiter(self, stream, params, rampSamples=0):
+        """A look-ahead brickwall limiter on the row the caller receives for the stream, from the next sample on: `params` a dict of the
+        NA_LimiterParams fields (lookahead, hold, ceiling; limiter_params_from_db makes one); the ceiling of a stream that has a limiter
+        ramps over rampSamples.  None takes the limiter away at once.  The limited row is delayed by `lookahead` samples."""
+        p = None if params is None else C.byref(_limiter_params(params))
+        if self._lib.NA_BatchSetStreamLimiter(self._h, int(stream), p, int(rampSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamLimiter(self, stream):
+        """The target constants as a dict; None: no limiter."""
+        out = capi.NA_LimiterParams()
+        rc = int(self._lib.NA_BatchGetStreamLimiter(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _limiter_dict(out) if rc else None
 
     # -- the mix stage: EnableMixStage is set-up side; SetMixGroup and ClearMixGroup are real-time safe (include/neuralaudio_amd.h) ----
     def EnableMixStage(self):

@@ -62,6 +62,8 @@ NA_SYMBOLS = [
     "NA_TunerParamsFromRange", "NA_TunerPitch", "NA_DebugTunerLaunches",
     "NA_BatchEnableDriveStage", "NA_BatchGetDriveInfo", "NA_BatchSetStreamDrive", "NA_BatchGetStreamDrive", "NA_BatchStreamDriveRampRemaining",
     "NA_DebugDriveLaunches",
+    "NA_BatchEnableLimiterStage", "NA_BatchGetLimiterInfo", "NA_BatchSetStreamLimiter", "NA_BatchGetStreamLimiter", "NA_LimiterParamsFromDb",
+    "NA_DebugLimiterLaunches",
     "NA_BatchEnableMixStage", "NA_BatchGetMixInfo", "NA_BatchSetMixGroup", "NA_BatchClearMixGroup", "NA_BatchGetStreamMix",
     "NA_BatchMixRampRemaining", "NA_MixGainsFromPan", "NA_DebugMixLaunches", "NA_DebugMixStashLaunches", "NA_DebugRunMixStage",
 ]
@@ -193,6 +195,18 @@ class NA_DriveParams(C.Structure):
 
 class NA_DriveInfo(C.Structure):
     _fields_ = [("numDrives", C.c_int), ("deviceBytes", C.c_longlong)]
+
+
+NA_LIMITER_MAX_LOOKAHEAD = 512
+NA_LIMITER_MAX_HOLD = 4096
+
+
+class NA_LimiterParams(C.Structure):
+    _fields_ = [("lookahead", C.c_int), ("hold", C.c_int), ("ceiling", C.c_float), ("reserved", C.c_int)]
+
+
+class NA_LimiterInfo(C.Structure):
+    _fields_ = [("historySamples", C.c_int), ("pieceSamples", C.c_int), ("numLimiters", C.c_int), ("deviceBytes", C.c_longlong)]
 
 
 NA_MIX_MAX_MEMBERS = 8
@@ -370,6 +384,12 @@ def load_library():
         "NA_BatchGetStreamDrive": (C.c_int, [vp, C.c_int, C.POINTER(NA_DriveParams)]),
         "NA_BatchStreamDriveRampRemaining": (C.c_int, [vp, C.c_int]),
         "NA_DebugDriveLaunches": (C.c_longlong, []),
+        "NA_BatchEnableLimiterStage": (C.c_int, [vp]),
+        "NA_BatchGetLimiterInfo": (C.c_int, [vp, C.POINTER(NA_LimiterInfo)]),
+        "NA_BatchSetStreamLimiter": (C.c_int, [vp, C.c_int, C.POINTER(NA_LimiterParams), C.c_int]),
+        "NA_BatchGetStreamLimiter": (C.c_int, [vp, C.c_int, C.POINTER(NA_LimiterParams)]),
+        "NA_LimiterParamsFromDb": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(NA_LimiterParams)]),
+        "NA_DebugLimiterLaunches": (C.c_longlong, []),
         "NA_BatchEnableMixStage": (C.c_int, [vp]),
         "NA_BatchGetMixInfo": (C.c_int, [vp, C.POINTER(NA_MixInfo)]),
         "NA_BatchSetMixGroup": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_float), C.c_int]),

@@ -1313,6 +1313,65 @@ int NA_BatchStreamDriveRampRemaining(NA_Batch* batch, int stream)
 long long NA_DebugDriveLaunches(void) { return (long long)na::DriveStageLaunches(); }
 #endif
 
+// ---- the limiter stage (gpu_batch.h EnableLimiterStage / SetStreamLimiter) ----
+static_assert(sizeof(NA_LimiterParams) == sizeof(na::LimiterParams), "NA_LimiterParams is LimiterParams, field for field");
+static_assert(NA_LIMITER_MAX_LOOKAHEAD == na::kLimMaxLookahead && NA_LIMITER_MAX_HOLD == na::kLimMaxHold, "the header's limits are limiter_stage.h's");
+
+int NA_LimiterParamsFromDb(int sampleRate, double ceilingDb, double lookaheadMs, double holdMs, NA_LimiterParams* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_LimiterParamsFromDb: bad argument");
+		na::LimiterParams p;
+		if (const char* why = na::LimiterParamsFromDb(sampleRate, ceilingDb, lookaheadMs, holdMs, p)) throw std::runtime_error(std::string("NA_LimiterParamsFromDb: ") + why);
+		memcpy(out, &p, sizeof(p));
+	});
+}
+
+int NA_BatchEnableLimiterStage(NA_Batch* batch)
+{
+	return BatchCall(batch, "NA_BatchEnableLimiterStage", [&](na::GpuBatch& b) { b.EnableLimiterStage(); });
+}
+
+int NA_BatchGetLimiterInfo(NA_Batch* batch, NA_LimiterInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetLimiterInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetLimiterInfo: bad argument");
+		const na::LimiterStageInfo i = b.GetLimiterInfo();
+		info->historySamples = i.historySamples;
+		info->pieceSamples = i.pieceSamples;
+		info->numLimiters = i.numLimiters;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamLimiter(NA_Batch* batch, int stream, const NA_LimiterParams* params, int rampSamples)
+{
+	return BatchCall(batch, "NA_BatchSetStreamLimiter", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamLimiter(stream, nullptr, 0);
+			return;
+		}
+		na::LimiterParams p;
+		memcpy(&p, params, sizeof(p));
+		b.SetStreamLimiter(stream, &p, rampSamples);
+	});
+}
+
+int NA_BatchGetStreamLimiter(NA_Batch* batch, int stream, NA_LimiterParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamLimiter", -1, [&](na::GpuBatch& b) {
+		na::LimiterParams p;
+		const int has = b.GetStreamLimiter(stream, p) ? 1 : 0;
+		if (has && out) memcpy(out, &p, sizeof(p));
+		return has;
+	});
+}
+
+#ifndef NA_RELEASE
+long long NA_DebugLimiterLaunches(void) { return (long long)na::LimiterStageLaunches(); }
+#endif
+
 // ---- the mix stage (gpu_batch.h EnableMixStage / SetMixGroup) ----
 static_assert(NA_MIX_MAX_MEMBERS == na::kMixMaxMembers && NA_MIX_TAP_OUT == na::kMixTapOut && NA_MIX_TAP_DRY == na::kMixTapDry, "the header's mix constants are mix_stage.h's");
 

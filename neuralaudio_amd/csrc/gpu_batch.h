@@ -26,6 +26,7 @@
 #include "eq_stage.h"
 #include "gate_stage.h"
 #include "host_route.h"
+#include "limiter_stage.h"
 #include "launch_plan.h"
 #include "meter_stage.h"
 #include "mod_stage.h"
@@ -131,6 +132,12 @@ namespace na
 	struct DriveStageInfo
 	{
 		int numDrives = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct LimiterStageInfo
+	{
+		int historySamples = 0, pieceSamples = 0, numLimiters = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -357,6 +364,19 @@ namespace na
 		bool GetStreamDrive(int stream, DriveParams& out) const;                     // the target; false: none
 		int StreamDriveRampRemaining(int stream) const;
 
+		// The limiter stage (limiter_stage.h): a per-stream feed-forward look-ahead brickwall limiter on the row the caller
+		// receives -- a sliding minimum of the gain each sample needs, held, smoothed by a fixed-order sum over the lookahead, times the
+		// row delayed by the lookahead, clamped -- behind the mix stage and in front of the meter's OUT tap: the last thing that writes a
+		// row, so nothing behind it can exceed the ceiling.  EnableLimiterStage is the set-up side: a ring of the last 5120 input samples
+		// per row (CreateStreams grows the block) and the tables.  SetStreamLimiter is host arithmetic on those tables; while an entry
+		// exists every processing call runs on the ordered path and enqueues ONE table upload and one launch per piece of 1024 samples
+		// over the entries only.  Without an entry the batch launches exactly what it launches without the stage.
+		void EnableLimiterStage();
+		bool HasLimiterStage() const { return stages[kLimiterStage] != nullptr; }
+		LimiterStageInfo GetLimiterInfo() const;
+		void SetStreamLimiter(int stream, const LimiterParams* params, int rampSamples); // nullptr: the limiter goes at once
+		bool GetStreamLimiter(int stream, LimiterParams& out) const;                     // the target; false: none
+
 		// The mix stage (mix_stage.h): per-session mix groups -- the rows of up to 8 members (a stream's row as the output
 		// stage left it, or the input row the caller passed for it) summed through a ramped D x M gain matrix into the rows of the first
 		// D members -- behind the output stage and in front of the meter's OUT tap: the one stage in which rows meet.  EnableMixStage is
@@ -529,9 +549,9 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.21).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.22).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kDriveStage, kGateStage, kEqStage, kCabinetStage, kCompressorStage, kModStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kDriveStage, kGateStage, kEqStage, kCabinetStage, kCompressorStage, kModStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kLimiterStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
@@ -544,7 +564,7 @@ namespace na
 		};
 		template <class Book, class Entry> struct StageOf;
 		template <class Record> struct StageResults; // the result blocks of the stages that report to the host (meter, tuner)
-		struct DriveStage; struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct ModStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct MeterStage; struct TunerStage;
+		struct DriveStage; struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct ModStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct LimiterStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

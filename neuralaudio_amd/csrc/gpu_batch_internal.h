@@ -299,7 +299,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the twelve stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the thirteen stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -494,6 +494,21 @@ namespace na
 	};
 	hipError_t LaunchMixStash(const MixStashLaunch& L, hipStream_t stream); // (mix_stage_kernels.hip)
 	hipError_t LaunchMixStage(const MixLaunch& L, hipStream_t stream);
+
+	// the limiter stage (limiter_stage.h, limiter_stage.cpp): the rows' rings of input samples
+	struct GpuBatch::LimiterStage : StageOf<LimiterBook, LimiterEntry>
+	{
+		static constexpr StageId kId = kLimiterStage;
+		static constexpr const char* kNotEnabled = "limiter stage not enabled (NA_BatchEnableLimiterStage)";
+		float* history = nullptr;         // [rowCapacity][kLimHistory]
+		int rowCapacity = 0;
+		LimiterStage() : StageOf("limiter stage") {}
+		~LimiterStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // its limiter goes at once, its history dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + one launch per piece + the host mirror's advance
+	};
+	hipError_t LaunchLimiterStage(const LimiterLaunch& L, hipStream_t stream); // (limiter_stage_kernels.hip) the launch of one piece
 
 	// the meter stage (meter_stage.h, meter_stage.cpp): the rows' states on the device and the result blocks (StageResults
 	// above) the OUT launch writes a record per entry to

@@ -138,6 +138,8 @@ namespace na
 		const ResamplePlan& p = rs->plan;
 		if (!p.identity && stages[kDriveStage])
 			throw std::runtime_error("neuralaudio_amd: SetResampling: resampling is refused on a batch with the drive stage enabled (NA_BatchEnableDriveStage)");
+		if (!p.identity && stages[kLimiterStage])
+			throw std::runtime_error("neuralaudio_amd: SetResampling: resampling is refused on a batch with the limiter stage enabled (NA_BatchEnableLimiterStage)");
 		if (!p.identity)
 		{
 			// the longest piece whose two windows (history ++ the piece's samples) fit the stages' LDS window
