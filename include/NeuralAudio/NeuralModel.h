@@ -141,6 +141,12 @@ namespace NeuralAudio
 		// inf input samples are not cleaned
 		void SetWaveNetExactF32(bool on) { wavenetExactF32 = on; }
 		bool GetWaveNetExactF32() { return wavenetExactF32; }
+		// Gated layer arrays ("gated": true) in models wider than 16 channels, for the WaveNet models created next (default off: such a
+		// file is refused at load, which hosts use to route it elsewhere): up to 64 channels in every array, head and input, in plain
+		// f32 on the gated instantiations of WaveNetWideF32Kernel -- no input clamp, NaN / inf not cleaned.  Any other model is
+		// unaffected
+		void SetWaveNetWideGated(bool on) { wavenetWideGated = on; }
+		bool GetWaveNetWideGated() { return wavenetWideGated; }
 		void SetLSTMMathMode(EMathMode mode) { lstmMath = mode; }
 		EMathMode GetLSTMMathMode() { return lstmMath; }
 		// Opt-in (default off: the reference's behaviour): a model created while the external sample rate is neither its model-side rate
@@ -162,6 +168,7 @@ namespace NeuralAudio
 		EMathMode wavenetMath = EMathMode::FastMath;
 		EMathMode lstmMath = EMathMode::FastMath;
 		bool wavenetExactF32 = false;
+		bool wavenetWideGated = false;
 		bool resampleToExternalRate = false;
 	};
 }

@@ -39,6 +39,14 @@ NA_EXTERN void NA_SetLSTMMathMode(NeuralModelLoader* loader, int mathMode);
 // no range event is counted.  It costs several times the default kernels at those widths (README), and NaN / inf input samples are not
 // cleaned.  Models created before the call, or by a loader with the option off, are what they were; both kinds share a batch.
 NA_EXTERN void NA_SetWaveNetExactF32(NeuralModelLoader* loader, int on);
+// Gated layer arrays (the A1 key "gated") in models wider than 16 channels, for the WaveNet models this loader creates next (on != 0;
+// default off: such a file is refused at load).  With the option a model with at least one gated array and some channels, head_size or
+// input_size above 16 loads when every such dimension of every array, gated or plain, is at most 64 (beyond: refused, the message names
+// the array, the width and the limit), and runs in plain f32 on the gated instantiations of WaveNetWideF32Kernel whatever NA_WN_KERNEL
+// or NA_SetWaveNetExactF32 say: NA_ModelKernelInfo family "wide-f32", NA_ModelIsGated 1, input limit infinity, no range event, NaN / inf
+// input samples not cleaned.  Models without a gated array, and gated models of at most 16 channels everywhere (f32 frame kernel), are
+// what they are without the option.  The A2-format gating modes stay refused.
+NA_EXTERN void NA_SetWaveNetWideGated(NeuralModelLoader* loader, int on);
 /* ECompositeModelLoadMode (NeuralModel.h:27-31,166-174): 0 = LoadAll (default), 1 = OnDemand */
 NA_EXTERN void NA_SetCompositeModelLoadMode(NeuralModelLoader* loader, int loadMode);
 /* NeuralModel::IsQualityChangeRealtimeSafe (NeuralModel.h:54-59) */

@@ -583,6 +583,11 @@ class NeuralModelLoader:
         clamp (17 .. 128 channels: WaveNetWideF32Kernel, several times the default's cost; NaN / inf inputs are not cleaned)."""
         self._lib.NA_SetWaveNetExactF32(self._h, 1 if on else 0)
 
+    def SetWaveNetWideGated(self, on):
+        """Gated layer arrays in models wider than 16 channels, for the WaveNet models created next (default off: refused at load): up to 64
+        channels everywhere, plain f32 on the gated instantiations of WaveNetWideF32Kernel.  Any other model is unaffected."""
+        self._lib.NA_SetWaveNetWideGated(self._h, 1 if on else 0)
+
     def SetLSTMMathMode(self, mode):
         self._lib.NA_SetLSTMMathMode(self._h, int(mode))
 

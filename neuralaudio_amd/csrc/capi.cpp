@@ -272,6 +272,11 @@ void NA_SetWaveNetExactF32(NeuralModelLoader* loader, int on)
 	if (loader) loader->loader->SetWaveNetExactF32(on != 0);
 }
 
+void NA_SetWaveNetWideGated(NeuralModelLoader* loader, int on)
+{
+	if (loader) loader->loader->SetWaveNetWideGated(on != 0);
+}
+
 void NA_SetLSTMMathMode(NeuralModelLoader* loader, int mathMode)
 {
 	if (loader) loader->loader->SetLSTMMathMode(mathMode == 1 ? NeuralAudio::EMathMode::StdMath : NeuralAudio::EMathMode::FastMath);

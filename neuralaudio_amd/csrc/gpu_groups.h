@@ -407,7 +407,8 @@ namespace na
 					for (const WnPrewarmLayer& pw : plan.prewarm)
 					{
 						if (pw.kind != 0 || pw.ksize <= 1) continue;
-						const size_t base = (size_t)pw.wconv, K = (size_t)pw.ksize, CO = (size_t)pw.cout, CI = (size_t)pw.cin;
+						// (a gated layer's conv has a filter and a gate half: [2C][C][K] -> [K][2C][C])
+						const size_t base = (size_t)pw.wconv, K = (size_t)pw.ksize, CO = (size_t)pw.cout * (pw.gated ? 2 : 1), CI = (size_t)pw.cin;
 						for (size_t o = 0; o < CO; o++)
 							for (size_t c = 0; c < CI; c++)
 								for (size_t k = 0; k < K; k++) wg[base + (k * CO + o) * CI + c] = d->wavenet.weights[base + (o * CI + c) * K + k];
@@ -564,7 +565,7 @@ namespace na
 							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetGenericKernel");
 					else if (family == WN_FAMILY_WIDE_F32)
 						CheckHip(LaunchWaveNetWideF32(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
-							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
+							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, choice.gated, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
 							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetWideF32Kernel");
 					else
 					{

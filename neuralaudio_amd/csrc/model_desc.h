@@ -25,7 +25,8 @@ namespace na
 		int channels = 0;
 		bool hasHeadBias = false;
 		int activation = ACT_TANH;
-		// A1 key "gated": conv and mix-in are 2 * channels wide, z = act(rows 0 .. C-1) * sigmoid(rows C .. 2C-1); f32 frame kernel only
+		// A1 key "gated": conv and mix-in are 2 * channels wide, z = act(rows 0 .. C-1) * sigmoid(rows C .. 2C-1); f32 frame kernel (<= 16
+		// channels everywhere) or, on request, the wide-f32 kernel (WaveNetDesc::wideGated)
 		bool gated = false;
 		std::vector<int> kernelSizes;
 		std::vector<int> dilations;
@@ -38,6 +39,8 @@ namespace na
 		bool isStatic = false;      // matched one of the official architectures (InternalModel.h:12-20)
 		int mathMode = MATH_FAST;   // tanh policy of ACT_TANH layers
 		bool exactF32 = false;      // the loader asked for f32 arithmetic (NA_SetWaveNetExactF32): no f16-split kernel runs this model (wavenet_choice.h)
+		bool wideGated = false;     // the loader admits gated layer arrays in models wider than 16 channels (NA_SetWaveNetWideGated): up to 64 channels
+		                            // everywhere, on the gated instantiations of WaveNetWideF32Kernel; changes nothing for any other model
 
 		size_t ExpectedNumWeights() const;
 		int ReceptiveFieldSize() const; // WaveNet.h:534-542,674-684

@@ -234,6 +234,7 @@ namespace na
 			if (desc->wavenet.isStatic && layers.Size() == 1 && layers.At(0).Contains("kernel_sizes") && !NAMIsA2Standard(modelJson)) desc->wavenet.isStatic = false;
 			desc->wavenet.mathMode = opts.wavenetMath;
 			desc->wavenet.exactF32 = opts.wavenetExactF32;
+			desc->wavenet.wideGated = opts.wavenetWideGated;
 			// the reference throws "Wrong number of weights" inside CreateFromJson (WaveNet.h:704-709); so does this loader, together with
 			// the limits of the gfx950 kernels, instead of deferring them to the first device use on the audio thread
 			ValidateWaveNetDesc(desc->wavenet);

@@ -54,6 +54,7 @@ namespace na
 		int wavenetMath = MATH_FAST;    // WAVENET_MATH (NeuralAudio/CMakeLists.txt:82-84)
 		int lstmMath = MATH_FAST;       // LSTM_MATH (:94-96)
 		bool wavenetExactF32 = false;   // WaveNetDesc::exactF32 of the models created next
+		bool wavenetWideGated = false;  // WaveNetDesc::wideGated of the models created next
 	};
 
 	// `extension` is ".nam", ".json" or ".aidax".  Returns nullptr when no Internal-path engine accepts the

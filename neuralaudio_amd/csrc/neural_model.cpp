@@ -179,6 +179,7 @@ namespace NeuralAudio
 		opts.wavenetMath = (wavenetMath == EMathMode::StdMath) ? na::MATH_STD : na::MATH_FAST;
 		opts.lstmMath = (lstmMath == EMathMode::StdMath) ? na::MATH_STD : na::MATH_FAST;
 		opts.wavenetExactF32 = wavenetExactF32;
+		opts.wavenetWideGated = wavenetWideGated;
 		std::shared_ptr<na::LoadedModel> loaded = na::LoadModelFromText(jsonText, extension.string(), opts);
 		if (!loaded) return nullptr;
 		GpuModel* m = new GpuModel(loaded, this, doPrewarm);

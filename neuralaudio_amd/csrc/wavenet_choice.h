@@ -35,7 +35,7 @@ namespace na
 		LaunchKind kind = LaunchKind::Frame;
 		float inputLimit = INFINITY; // samples beyond +-limit are clamped by the kernel (f16-split arithmetic: split and generic families)
 		bool rangeProven = true, weightsOk = true; // the range proof of the real model (wavenet_plan.cpp)
-		bool gated = false;      // some layer array is gated (A1 key "gated"): the frame family whatever the knobs say
+		bool gated = false;      // some layer array is gated (A1 key "gated"): the frame family -- wider than 16 channels the wide-f32 family -- whatever the knobs say
 		WaveNetPlan plan;        // the plan the group runs, in its family's state format
 		WaveNetPlan realPlan;    // isVirtual: the real model's plan (bookkeeping: bytes / MACs per REAL stream); empty otherwise
 
@@ -96,6 +96,17 @@ namespace na
 			// already): like a failed range proof this outranks NA_WN_KERNEL
 			c.gated = true;
 			c.plan = std::move(real);
+			return c;
+		}
+		if (real.wideGated)
+		{
+			// Gated layer arrays in a model wider than 16 channels (loaded on request, NA_SetWaveNetWideGated): one kernel evaluates them,
+			// the gated instantiations of the exact-f32 kernel of the runtime-shaped family -- ahead of NA_WN_KERNEL and whether or not
+			// exact f32 was asked for.  Generic state format, no input limit, no pack, no padding
+			c.gated = true;
+			c.family = WN_FAMILY_WIDE_F32;
+			c.kind = LaunchKind::Own;
+			c.plan = BuildWaveNetPlan(wn, false);
 			return c;
 		}
 		if (wn.exactF32)

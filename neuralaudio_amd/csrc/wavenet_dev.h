@@ -139,7 +139,8 @@ namespace na
 		int rech_in;
 		int dilation;   // layer conv / head conv dilation (the generic block kernel walks this table; the prewarm kernel ignores it)
 		int gated;      // layer: conv / bias / mix-in have 2 * cout rows, z = act(rows 0 .. cout-1) * sigmoid(rows cout ..); 1 FastMath sigmoid, 2 StdMath
-		                // (prewarm kernel only: a gated model never runs on the runtime-shaped kernel)
+		                // (the prewarm kernel, and WaveNetWideF32Kernel<NB, true> for gated models wider than 16 channels; the f16-split
+		                // runtime-shaped kernel never sees one)
 	};
 
 	// Everything the kernels need about one model; passed by value.
@@ -168,7 +169,8 @@ namespace na
 		float cond_limit;     // f16-split kernels: input samples are clamped to +-cond_limit (WaveNetPlan::condLimit)
 		int compact_rings;    // f16-split state format: some ring is a compact one -- launches take WnCompactSafeFrames() lengths only
 		int saturate;         // f16-split kernels: 1 = no static range proof (WaveNetPlan::splitRangeProven): saturating split + range events
-		int gated;            // frame kernel: some layer stage has WN_FLAG_GATED -- its launches take the gated instantiations
+		int gated;            // some layer array is gated.  Frame family: some layer stage has WN_FLAG_GATED -- its launches take the gated
+		                      // instantiations; wide-f32 family (wider than 16 channels): the group's own launches do (the frame list never sees it)
 	};
 
 	enum WnSpecArch : int

@@ -245,8 +245,10 @@ namespace na
 
 	// The same models in exact f32 (wavenet_wide_f32_kernels.hip, family WN_FAMILY_WIDE_F32): every mat-mul on v_mfma_f32_16x16x4_f32 with plain
 	// f32 operands -- no clamp, no saturation, no range-event word; same table, same tap-major weight copy, same stream state.
+	// gated: the model has gated layer arrays (WnPrewarmLayer::gated; up to 64 channels) -- the gated instantiations
+	// (wavenet_wide_f32_gated_kernels.hip, wavenet_launch_choice.h WaveNetWideF32For)
 	hipError_t LaunchWaveNetWideF32(const WnPrewarmLayer* layers, int numLayers, const float* weights, const int* ringOffF4, const int* ringFrames, const int* ringG,
-		int nrings, int stateF4, int maxChannels, float headScale, float* state, const int* slots, const int* rows, int numStreams, int slot0, int row0,
+		int nrings, int stateF4, int maxChannels, float headScale, bool gated, float* state, const int* slots, const int* rows, int numStreams, int slot0, int row0,
 		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
 
 	// tuning aid: device buffer of long long[stages*4*waves] that workgroup 0 stamps with the shader clock (nullptr: off)

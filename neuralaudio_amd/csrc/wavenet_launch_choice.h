@@ -21,7 +21,7 @@ namespace na
 	// "frame" = the f32 4x4x1-MFMA kernel (wavenet_frame_kernels.hip), "generic" = the runtime-shaped kernel for layer arrays wider than 16
 	// channels (wavenet_generic_kernels.hip; frame-kernel state format).  A group stays in its family for life: the families keep
 	// different stream-state formats.  "wide-f32" = the same widths in exact f32 on request (wavenet_wide_f32_kernels.hip, WaveNetDesc::exactF32;
-	// the generic family's state format).  (Appended: the numeric codes of NA_DebugWaveNetKernel keep their meaning.)
+	// the generic family's state format), and gated layer arrays wider than 16 channels (WaveNetDesc::wideGated).  (Appended: the numeric codes of NA_DebugWaveNetKernel keep their meaning.)
 	enum WnFamily { WN_FAMILY_AUTO, WN_FAMILY_SPLIT, WN_FAMILY_FRAME, WN_FAMILY_GENERIC, WN_FAMILY_WIDE_F32 };
 
 	// the tuning knobs that take part in a choice (tuning.h: NA_WN_KERNEL, NA_WN_PACK, NA_WN_PAD, NA_WN_DENSE, NA_SP_T, NA_SP_SPB, NA_SP_GEN,
@@ -301,6 +301,24 @@ namespace na
 			if (!FrameLaunchFits(maxA4, c.wps, c.spb, c.pf)) return Refused(WN_REFUSED_INVALID_VALUE);
 			return c;
 		}
+	}
+
+	// The instantiation of WaveNetWideF32Kernel<NB, GATED> a launch of a wide-f32 group takes (its launches are the group's own, LaunchKind::Own:
+	// one model, every block length): NB = 16-channel blocks per matrix side from the model's widest dimension; a model with gated layer
+	// arrays takes the gated instantiations, which exist for <= 32 and <= 64 channels (a [2C x C] tap is one image of 2 NB x NB blocks).
+	// nb == 0: no instantiation takes the launch (hipErrorInvalidValue).
+	struct WaveNetWideF32Choice
+	{
+		int nb = 0;
+		bool gated = false;
+	};
+	inline WaveNetWideF32Choice WaveNetWideF32For(int maxChannels, bool gated)
+	{
+		WaveNetWideF32Choice c;
+		c.gated = gated;
+		if (maxChannels < 1 || maxChannels > (gated ? 64 : WN_GENERIC_MAX_CHANNELS)) return c;
+		c.nb = maxChannels <= 32 ? 2 : (maxChannels <= 64 ? 4 : (maxChannels <= 96 ? 6 : 8));
+		return c;
 	}
 
 	inline WaveNetLaunchChoice WaveNetLaunchFor(const WaveNetLaunchFacts& f, const WaveNetKnobs& k)

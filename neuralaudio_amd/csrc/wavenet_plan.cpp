@@ -65,7 +65,16 @@ namespace na
 			if (cfg.headKernelSize > 1 && (cfg.channels > 64 || cfg.headSize > 64))
 				throw std::runtime_error("WaveNet: a conv head on a layer array wider than 64 channels is not supported");
 			if (cfg.conditionSize != 1) throw std::runtime_error("WaveNet condition_size != 1 is not supported");
-			if (cfg.gated && cfg.channels > 16)
+			// Gated arrays wider than 16 channels on request (WaveNetDesc::wideGated, NA_SetWaveNetWideGated): the model runs on the gated
+			// instantiations of WaveNetWideF32Kernel, which stage a [2C x C] tap as one image of at most 128 rows -- 64 channels everywhere
+			if (desc.wideGated && anyGated && (cfg.channels > 64 || cfg.headSize > 64 || cfg.inputSize > 64))
+			{
+				std::stringstream str;
+				str << "WaveNet layer array " << a << ": " << std::max(cfg.channels, std::max(cfg.headSize, cfg.inputSize))
+				    << " channels (channels, head_size or input_size) in a model with gated layer arrays are not supported (with NA_SetWaveNetWideGated such a model runs on WaveNetWideF32Kernel: at most 64 channels everywhere)";
+				throw std::runtime_error(str.str());
+			}
+			if (!desc.wideGated && cfg.gated && cfg.channels > 16)
 			{
 				std::stringstream str;
 				str << "WaveNet layer array " << a << ": gated layers at " << cfg.channels << " channels are not supported (gated layer arrays run on the f32 frame kernel: at most 16 channels)";
@@ -73,7 +82,7 @@ namespace na
 			}
 			// ... and a model with ANY gated array is frame-only: every array of it, gated or plain, with its head and its input, must be
 			// one the frame kernel takes (the runtime-shaped kernels that run wider arrays have no gating and walk the plain weight count)
-			if (anyGated && (cfg.channels > 16 || cfg.headSize > 16 || cfg.inputSize > 16))
+			if (!desc.wideGated && anyGated && (cfg.channels > 16 || cfg.headSize > 16 || cfg.inputSize > 16))
 			{
 				std::stringstream str;
 				str << "WaveNet layer array " << a << ": " << std::max(cfg.channels, std::max(cfg.headSize, cfg.inputSize))
@@ -726,8 +735,9 @@ namespace na
 					const WnArrayCfg& cfg = desc.arrays[a];
 					const int C = cfg.channels;
 					const int numLayers = (int)cfg.kernelSizes.size();
+					const int C2 = cfg.gated ? 2 * C : C; // gated (plan.wideGated): rows 0 .. C-1 filter, C .. 2C-1 gate
 					const int rechOff = Take((size_t)C * cfg.inputSize);
-					RangeRechannel(a, cfg, rechOff);
+					if (!plan.wideGated) RangeRechannel(a, cfg, rechOff);
 					for (int l = 0; l < numLayers; l++)
 					{
 						const int K = cfg.kernelSizes[l];
@@ -735,9 +745,10 @@ namespace na
 						pw.kind = 0;
 						pw.cin = C; pw.cout = C; pw.ksize = K;
 						pw.act = (cfg.activation == ACT_LEAKYRELU) ? 1 : (desc.mathMode == MATH_STD ? 2 : 0);
-						pw.wconv = Take((size_t)C * C * K);
-						pw.bconv = Take((size_t)C);
-						pw.wmix = Take((size_t)C * cfg.conditionSize);
+						pw.gated = cfg.gated ? (desc.mathMode == MATH_STD ? 2 : 1) : 0;
+						pw.wconv = Take((size_t)C2 * C * K);
+						pw.bconv = Take((size_t)C2);
+						pw.wmix = Take((size_t)C2 * cfg.conditionSize);
 						pw.w1 = Take((size_t)C * C);
 						pw.b1 = Take((size_t)C);
 						pw.ring_id = AddRing(C, (K - 1) * cfg.dilations[l], cfg.dilations[l], l == 0);
@@ -747,7 +758,7 @@ namespace na
 						pw.rech_in = cfg.inputSize;
 						pw.dilation = cfg.dilations[l];
 						plan.prewarm.push_back(pw);
-						RangeLayer(a == 0 && l == 0, cfg, K, pw.wconv, pw.bconv, pw.wmix, pw.w1, pw.b1, !(l == numLayers - 1 && a == numArrays - 1));
+						if (!plan.wideGated) RangeLayer(a == 0 && l == 0, cfg, K, pw.wconv, pw.bconv, pw.wmix, pw.w1, pw.b1, !(l == numLayers - 1 && a == numArrays - 1));
 					}
 					WnPrewarmLayer pw = {};
 					pw.kind = 1;
@@ -759,11 +770,17 @@ namespace na
 					pw.rechannel = -1;
 					pw.dilation = cfg.headDilation;
 					plan.prewarm.push_back(pw);
-					RangeHead(cfg, pw.wconv, pw.bconv, a == numArrays - 1);
+					if (!plan.wideGated) RangeHead(cfg, pw.wconv, pw.bconv, a == numArrays - 1);
 				}
 				plan.headScale = W(Take(1));
 				plan.stateF4 = CeilDiv(plan.stateF4, 16) * 16;
-				FinishRange();
+				if (plan.wideGated)
+				{
+					// plain f32 on WaveNetWideF32Kernel, the only kernel of such a model: no f16 program, so no range walk and no proof
+					plan.splitRangeProven = false;
+					plan.genericOk = false; // (the f16-split runtime-shaped kernel has no gating)
+				}
+				else FinishRange();
 			}
 
 			void Build()
@@ -774,8 +791,17 @@ namespace na
 				plan.receptiveField = desc.ReceptiveFieldSize();
 				// A model with a gated layer array runs on the f32 frame kernel only: its state format whatever the caller asked for, no
 				// f16-split stage program (BuildSplit would walk the plain weight count), hence no range proof, no packing and no padding
-				for (const WnArrayCfg& cfg : desc.arrays) plan.frameOnly = plan.frameOnly || cfg.gated;
-				if (plan.frameOnly) exactRings = false;
+				// Wider than 16 channels (validated only with WaveNetDesc::wideGated) it runs on the gated instantiations of the wide-f32
+				// kernel only: the genericOnly route below, without the f16 range walk.
+				bool anyGated = false;
+				for (const WnArrayCfg& cfg : desc.arrays)
+				{
+					anyGated = anyGated || cfg.gated;
+					plan.maxChannels = std::max(plan.maxChannels, std::max(cfg.channels, std::max(cfg.headSize, cfg.inputSize)));
+				}
+				plan.frameOnly = anyGated && plan.maxChannels <= 16;
+				plan.wideGated = anyGated && plan.maxChannels > 16;
+				if (anyGated) exactRings = false;
 				compactOk = exactRings;
 				for (const WnArrayCfg& cfg : desc.arrays)
 				{
@@ -785,14 +811,10 @@ namespace na
 				}
 				plan.stateF4 = WN_HEADER_F4;
 				plan.genericOk = true;
-				for (const WnArrayCfg& cfg : desc.arrays)
-				{
-					plan.maxChannels = std::max(plan.maxChannels, std::max(cfg.channels, std::max(cfg.headSize, cfg.inputSize)));
-					(void)cfg; // (conv heads run on the runtime-shaped kernel too since round 3)
-				}
+				// (conv heads run on the runtime-shaped kernel too since round 3)
 				if (plan.maxChannels > 16)
 				{
-					if (plan.frameOnly) throw std::runtime_error("internal: a WaveNet with gated layer arrays wider than 16 channels passed validation");
+					if (plan.wideGated && !desc.wideGated) throw std::runtime_error("internal: a WaveNet with gated layer arrays wider than 16 channels passed validation");
 					plan.genericOnly = true;
 					BuildGenericOnly();
 					return;
@@ -1043,6 +1065,8 @@ namespace na
 		// Exact f32 on request (WaveNetDesc::exactF32): WaveNetWideF32Kernel runs the model, and neither the operand format nor the range
 		// bound concerns it.  (The shape limits -- ValidateWaveNetDesc, inside BuildWaveNetPlan above -- are the same.)
 		if (desc.exactF32) return;
+		// Gated arrays beside or above 16 channels (WaveNetPlan::wideGated): the gated instantiations of the same kernel, plain f32 as well
+		if (plan.wideGated) return;
 		const std::string who = "WaveNet with layer arrays wider than 16 channels (f16-split arithmetic only): ";
 		if (!plan.splitWeightsOk)
 			throw std::runtime_error(who + "the weights do not fit the (hi, lo) f16 operand format (a weight beyond 32752, or a weight matrix whose largest entry is below 2^-12)");

@@ -39,7 +39,9 @@ namespace na
 		std::vector<float> packedWeights;  // pack > 1: flat weights of the virtual model (reference order)
 		bool genericOnly = false;          // > 16 channels: only rings + the natural-layout table are built (runtime-shaped block kernel)
 		bool genericOk = false;            // the runtime-shaped block kernel can run it (dense heads only)
-		bool frameOnly = false;            // some layer array is gated: frame-kernel stages and state format only, no f16-split program, no range proof
+		bool frameOnly = false;            // some layer array is gated, none wider than 16 channels: frame-kernel stages and state format only, no f16-split program, no range proof
+		bool wideGated = false;            // some layer array is gated and some dimension is above 16 (WaveNetDesc::wideGated): genericOnly, the table's conv /
+		                                   // bias / mix-in have 2 C rows, NO f16 range walk (plain f32 on WaveNetWideF32Kernel<NB, true> only)
 		int stateF4 = 0;            // per-stream state in float4 units
 		int maxA4Floats = 0;        // largest per-stage A-operand block of the frame kernel (floats)
 		float headScale = 0.0f;

@@ -27,6 +27,23 @@
 // Sum order: acc[rb] += over kb ascending, s ascending, the MFMA's own four-way sum inside -- a function of the model alone, not of the
 // frame's place in the block, the block length or the other streams: call sizes do not change a sample's bits.  The unit is compiled
 // with -ffp-contract=off so that no instantiation fuses what another one rounds twice.
+//
+// Gated layer arrays (the A1 key "gated", WnPrewarmLayer::gated; loaded wider than 16 channels on request, NA_SetWaveNetWideGated):
+// WaveNetWideF32Kernel<NB, true>, NB = 2 / 4 (<= 32 / 64 channels), compiled in a translation unit of their own
+// (wavenet_wide_f32_gated_kernels.hip includes this file) so that the plain instantiations' code stays what it was.  A gated layer's
+// conv, bias and mix-in have 2 C rows: rows 0 .. C-1 the filter half, C .. 2C-1 the gate half, z = act(filter) * sigmoid(gate).
+//   One image per tap: the [2C x C] tap matrix as 2 nb x nb blocks -- filter rows in row blocks 0 .. nb-1, gate rows (from row C of the
+//     file) in row blocks nb .. 2 nb-1, each half zero-padded to whole blocks on its own, so C = 17, 24, 33 .. need no special case.
+//   The tap's B operands (the lane's quads of X or the ring) are fetched once and feed both halves; a lane's accumulator fragments
+//     acc[rb] and accg[rb] hold the filter and gate pre-activations of the SAME four channels of the SAME frame: the gating is
+//     lane-local -- no cross-lane move, no LDS.  MFMAs are issued in groups of two filter and two gate row blocks (four independent
+//     accumulators, four LDS quads in registers at a time); per accumulator the sum order is the plain one, kb ascending, s ascending.
+//   Epilogue: z = Activate(f + bc_f + wm_f cond) * sigmoid(g + bc_g + wm_g cond), the sigmoid 0.5 (FastTanh(0.5 g) + 1) or, under
+//     StdMath, rcp(1 + exp2(-g log2 e)) -- the prewarm kernel's expressions.  1x1, residual, head accumulate, rechannel and head
+//     stages are the plain ones; a plain array inside a gated model runs the plain layer body of the same instantiation (L.gated).
+//   LDS at NB = 4: X 32 KB + head 32 KB + two 8 x 4-block images 2 x 32 KB + the condition row = 131 584 bytes: double-imaged.
+//   Registers: 2 NB accumulator quads, b[] / zs[] stay NB, the staged matrix is 2 NB NB / 8 quads per thread; the bias / mix-in vectors
+//     of both halves are loaded ahead like the plain ones at NB = 2, at use at NB = 4 (profiles/wide_gated_isa.txt: no scratch).
 #include "device_once.h"
 
 #include <hip/hip_runtime.h>
@@ -135,6 +152,65 @@ namespace na
 			}
 		}
 
+		// The gated instantiations stage images of up to 2 NB x NB blocks (a gated layer's tap is [2C x C]).  gate: m describes ONE half ([cout x
+		// cin] of the [2 cout x cin] matrix at m.off); the image then has 2 nbo row blocks, row block nbo + rb <- rows cout + 16 rb .. of the
+		// matrix, each half zero-padded to whole blocks on its own.  !gate: the plain image of StageLoad.
+		template <int NB>
+		struct StagedRegsG
+		{
+			static constexpr int ITEMS = (2 * NB * NB * 64 + NTHREADS - 1) / NTHREADS;
+			f32x4 v[ITEMS];
+		};
+		template <int NB>
+		__device__ __forceinline__ void StageLoad(StagedRegsG<NB>& r, const float* __restrict__ w, const MatRef& m, bool gate = false)
+		{
+			const int half = m.nbo * m.nbk * 64;
+#pragma unroll
+			for (int it = 0; it < StagedRegsG<NB>::ITEMS; it++)
+			{
+				const int idx = threadIdx.x + it * NTHREADS;
+				const bool g = gate && idx >= half;              // an item of the gate half
+				const int idh = g ? idx - half : idx;
+				const int lane = idh & 63, blk = idh >> 6, rb = blk / m.nbk, kb = blk % m.nbk;
+				const int oh = 16 * rb + (lane & 15), c0 = 16 * kb + 4 * (lane >> 4);
+				const bool on = idh < half && oh < m.cout;
+				const float* p = w + m.off + (size_t)(g ? m.cout + oh : oh) * m.cin + c0;
+				f32x4 v = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+				if (on && c0 + 3 < m.cin)
+				{
+					const f32x4u t = *reinterpret_cast<const f32x4u*>(p);
+					v = f32x4{ t.x, t.y, t.z, t.w };
+				}
+				else if (on)
+				{
+					v.x = (c0 + 0 < m.cin) ? p[0] : 0.0f;
+					v.y = (c0 + 1 < m.cin) ? p[1] : 0.0f;
+					v.z = (c0 + 2 < m.cin) ? p[2] : 0.0f;
+				}
+				r.v[it] = v;
+			}
+		}
+		template <int NB>
+		__device__ __forceinline__ void StageCommit(f32x4* ops, const StagedRegsG<NB>& r, const MatRef& m, bool gate = false)
+		{
+#pragma unroll
+			for (int it = 0; it < StagedRegsG<NB>::ITEMS; it++)
+			{
+				const int idx = threadIdx.x + it * NTHREADS;
+				if (idx < (gate ? 2 : 1) * m.nbo * m.nbk * 64) ops[idx] = r.v[it];
+			}
+		}
+		template <int NB, bool GATED>
+		struct StagedOf
+		{
+			typedef StagedRegs<NB> T;
+		};
+		template <int NB>
+		struct StagedOf<NB, true>
+		{
+			typedef StagedRegsG<NB> T;
+		};
+
 		// acc[rb] += M[16 rb .. + 16][all k blocks] * b[kb]   (b[kb] = the quad of channels 16 kb + 4 q .. of the lane's frame); k block by
 		// k block, in groups of up to four row blocks: consecutive MFMAs write different accumulators, and a group's four LDS reads are all
 		// of the image that is in registers at a time (the scheduling barrier keeps the compiler from hoisting the reads of the whole
@@ -172,6 +248,52 @@ namespace na
 			}
 		}
 
+		// a gated tap: accf[rb] += F[16 rb .. + 16][.] * b, accg[rb] += G[16 rb .. + 16][.] * b from the image of 2 nb x nb blocks (StageLoad, gate) --
+		// ONE set of B operands for both halves.  Groups of two filter and two gate row blocks: four independent accumulators behind each
+		// other on the matrix pipe, four LDS quads in registers at a time.  Per accumulator: kb ascending, s ascending, as in MatMul.
+		template <int NB>
+		__device__ __forceinline__ void MatMulGated(const f32x4* ops, int nb, int lane, const f32x4 (&b)[NB], f32x4 (&accf)[NB], f32x4 (&accg)[NB])
+		{
+#pragma unroll
+			for (int kb = 0; kb < NB; kb++)
+			{
+				if (kb >= nb) break;
+#pragma unroll
+				for (int r0 = 0; r0 < NB; r0 += 2)
+				{
+					if (r0 >= nb) break;
+					const bool two = r0 + 1 < nb; // (NB is even; nb may be odd)
+					const f32x4 f0 = ops[((r0)*nb + kb) * 64 + lane], g0 = ops[((nb + r0) * nb + kb) * 64 + lane];
+					f32x4 f1 = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f }, g1 = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+					if (two)
+					{
+						f1 = ops[((r0 + 1) * nb + kb) * 64 + lane];
+						g1 = ops[((nb + r0 + 1) * nb + kb) * 64 + lane];
+					}
+#define NA_WF_GATED_STEP(S)                                                                                   \
+	accf[r0] = __builtin_amdgcn_mfma_f32_16x16x4f32(f0.S, b[kb].S, accf[r0], 0, 0, 0);                        \
+	accg[r0] = __builtin_amdgcn_mfma_f32_16x16x4f32(g0.S, b[kb].S, accg[r0], 0, 0, 0);                        \
+	if (two)                                                                                                  \
+	{                                                                                                         \
+		accf[r0 + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(f1.S, b[kb].S, accf[r0 + 1], 0, 0, 0);            \
+		accg[r0 + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(g1.S, b[kb].S, accg[r0 + 1], 0, 0, 0);            \
+	}
+					NA_WF_GATED_STEP(x)
+					NA_WF_GATED_STEP(y)
+					NA_WF_GATED_STEP(z)
+					NA_WF_GATED_STEP(w)
+#undef NA_WF_GATED_STEP
+					__builtin_amdgcn_sched_barrier(0);
+				}
+			}
+		}
+		// Activation.h:40-43,93-96 -- the gate's sigmoid by the model's math policy (mode 2: StdMath), the prewarm kernel's expressions
+		__device__ __forceinline__ float Sigmoid(float g, int mode)
+		{
+			if (mode == 2) return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(g * -1.4426950408889634f));
+			return 0.5f * (FastTanh(0.5f * g) + 1.0f);
+		}
+
 		__device__ __forceinline__ f32x4 Load4(const float* __restrict__ w, int off, int c0, int count)
 		{
 			f32x4 v;
@@ -185,22 +307,26 @@ namespace na
 		constexpr bool HeadInLds(int nb) { return nb <= 4; }   // up to 64 channels; in registers above
 		constexpr bool TwoImages(int nb) { return nb <= 6; }   // X + two images within 160 KB (96 channels: 48 + 72 KB; 128: 64 + 128)
 		constexpr bool LoadsAhead(int nb) { return nb <= 4; }  // bias vectors and the ring history of K <= 3 ahead of the taps (registers)
-		constexpr size_t LdsBytes(int nb, int gq)
+		constexpr size_t LdsBytes(int nb, int gq, bool gated = false)
 		{
-			return (size_t)(HeadInLds(nb) ? 2 : 1) * gq * FRAMES * 16 + (size_t)(TwoImages(nb) ? 2 : 1) * nb * nb * 64 * 16 + FRAMES * sizeof(float);
+			return (size_t)(HeadInLds(nb) ? 2 : 1) * gq * FRAMES * 16 + (size_t)(TwoImages(nb) ? 2 : 1) * (gated ? 2 : 1) * nb * nb * 64 * 16 + FRAMES * sizeof(float);
 		}
 
-		template <int NB>
+		template <int NB, bool GATED = false>
 		__global__ void __launch_bounds__(NTHREADS) __attribute__((amdgpu_waves_per_eu(2))) WaveNetWideF32Kernel(const Args a, const float* __restrict__ in, float* __restrict__ out,
 			long inStride, long outStride, int n)
 		{
-			constexpr bool HEAD_LDS = HeadInLds(NB), TWO = TwoImages(NB), AHEAD = LoadsAhead(NB);
-			constexpr int OPS_ONE = NB * NB * 64;
+			static_assert(!GATED || NB <= 4, "gated: a [2C x C] tap is one image of at most 8 x 4 blocks");
+			// (the gated <4> gives up the ahead loads -- bias vectors and ring history -- for its second accumulator set: with them it spills 25 VGPRs)
+			constexpr bool HEAD_LDS = HeadInLds(NB), TWO = TwoImages(NB), AHEAD = LoadsAhead(NB) && !(GATED && NB > 2);
+			constexpr bool AHEAD_G = GATED && AHEAD; // a gated layer's gate-half bias / mix-in vectors ahead as well
+			constexpr int RB = GATED ? 2 * NB : NB;     // row blocks of the largest image
+			constexpr int OPS_ONE = RB * NB * 64;
 			extern __shared__ __attribute__((aligned(16))) float lds[];
 			const int GQ = (a.maxC + 3) / 4;                          // channel groups of the widest array
 			f32x4* X = reinterpret_cast<f32x4*>(lds);                 // [GQ][FRAMES]
 			f32x4* HEAD = X + (size_t)GQ * FRAMES;                    // [GQ][FRAMES] (HEAD_LDS)
-			f32x4* ops0 = HEAD + (HEAD_LDS ? (size_t)GQ * FRAMES : 0); // [TWO ? 2 : 1][NB * NB][64]
+			f32x4* ops0 = HEAD + (HEAD_LDS ? (size_t)GQ * FRAMES : 0); // [TWO ? 2 : 1][RB * NB][64]
 			float* condL = reinterpret_cast<float*>(ops0 + (TWO ? 2 : 1) * OPS_ONE); // [FRAMES]
 			int par = 0; // mat-muls so far (workgroup-uniform)
 			const int tid = threadIdx.x;
@@ -226,7 +352,7 @@ namespace na
 			const float cond = condL[tf];
 
 			const float* __restrict__ w = a.w;
-			StagedRegs<NB> pre;   // weights of the next mat-mul, under way while the current one runs
+			typename StagedOf<NB, GATED>::T pre;   // weights of the next mat-mul, under way while the current one runs
 			bool havePre = false; // (workgroup-uniform)
 			// the image the next mat-mul reads.  Two images: the one the mat-mul before the last read -- every wave is past that one (the
 			// barrier in front of the last mat-mul).  One image: every wave must be past the LAST mat-mul first.
@@ -245,6 +371,7 @@ namespace na
 				{
 					const int cin = L.cin; // == cout
 					const int Gl = (cin + 3) / 4, nb = (cin + 15) / 16;
+					const bool lg = GATED && L.gated != 0;                   // a gated layer (workgroup-uniform): taps of [2 cin x cin], two accumulator sets
 					// AHEAD: the layer's bias / mix-in vectors for the rows this lane will hold, loaded now (they are used behind the mat-muls,
 					// where a load is a memory round trip on the critical path); the widest instantiations need the registers and load at use
 					f32x4 bcv[AHEAD ? NB : 1], wmv[AHEAD ? NB : 1], b1v[AHEAD ? NB : 1];
@@ -258,6 +385,19 @@ namespace na
 							bcv[AHEAD ? rb : 0] = on ? Load4(w, L.bconv, 4 * g, cin) : f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
 							wmv[AHEAD ? rb : 0] = on ? Load4(w, L.wmix, 4 * g, cin) : f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
 							b1v[AHEAD ? rb : 0] = on ? Load4(w, L.b1, 4 * g, cin) : f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+						}
+					}
+					// (gated layer: the gate half's bias and mix-in, rows cin .. 2 cin - 1 of both vectors)
+					f32x4 bgv[AHEAD_G ? NB : 1], wgv[AHEAD_G ? NB : 1];
+					if (AHEAD_G && lg)
+					{
+#pragma unroll
+						for (int rb = 0; rb < NB; rb++)
+						{
+							const int g = 4 * rb + q;
+							const bool on = rb < nb && g < Gl;
+							bgv[AHEAD_G ? rb : 0] = on ? Load4(w, L.bconv + cin, 4 * g, cin) : f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+							wgv[AHEAD_G ? rb : 0] = on ? Load4(w, L.wmix + cin, 4 * g, cin) : f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
 						}
 					}
 					if (L.rechannel >= 0)
@@ -310,6 +450,12 @@ namespace na
 					f32x4 acc[NB];
 #pragma unroll
 					for (int rb = 0; rb < NB; rb++) acc[rb] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+					f32x4 accg[GATED ? NB : 1]; // gated layer: the gate half's pre-activations, the same channels and frame as acc[]
+					if (GATED)
+					{
+#pragma unroll
+						for (int rb = 0; rb < NB; rb++) accg[GATED ? rb : 0] = f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
+					}
 					auto histOf = [&](int k, f32x4 (&h)[NB]) {
 						const int src = tf - L.dilation * (K - 1 - k);
 						int p = pos0 + src; // src >= -(R - FRAMES): one wrap
@@ -323,12 +469,25 @@ namespace na
 					};
 					auto tap = [&](int k, const f32x4 (&h)[NB]) {
 						f32x4* ops = nextImage();
-						const MatRef mk = { L.wconv + k * cin * cin, cin, cin, nb, nb };
-						if (!havePre) StageLoad<NB>(pre, w, mk); // (the first tap behind a rechannel / head stage: nothing was under way)
-						StageCommit<NB>(ops, pre, mk);
-						// the next mat-mul's weights set out now: the next tap's, or the 1x1's behind the last tap
-						const MatRef mn = (k + 1 < K) ? MatRef{ L.wconv + (k + 1) * cin * cin, cin, cin, nb, nb } : MatRef{ L.w1, cin, cin, nb, nb };
-						StageLoad<NB>(pre, w, mn);
+						if constexpr (GATED)
+						{
+							// the same with a gated layer's taps: [2 cin x cin] each in the tap-major copy, mk / mn describe the filter half
+							const int tapFloats = lg ? 2 * cin * cin : cin * cin;
+							const MatRef mk = { L.wconv + k * tapFloats, cin, cin, nb, nb };
+							if (!havePre) StageLoad<NB>(pre, w, mk, lg);
+							StageCommit<NB>(ops, pre, mk, lg);
+							const MatRef mn = (k + 1 < K) ? MatRef{ L.wconv + (k + 1) * tapFloats, cin, cin, nb, nb } : MatRef{ L.w1, cin, cin, nb, nb };
+							StageLoad<NB>(pre, w, mn, lg && k + 1 < K);
+						}
+						else
+						{
+							const MatRef mk = { L.wconv + k * cin * cin, cin, cin, nb, nb };
+							if (!havePre) StageLoad<NB>(pre, w, mk); // (the first tap behind a rechannel / head stage: nothing was under way)
+							StageCommit<NB>(ops, pre, mk);
+							// the next mat-mul's weights set out now: the next tap's, or the 1x1's behind the last tap
+							const MatRef mn = (k + 1 < K) ? MatRef{ L.wconv + (k + 1) * cin * cin, cin, cin, nb, nb } : MatRef{ L.w1, cin, cin, nb, nb };
+							StageLoad<NB>(pre, w, mn);
+						}
 						havePre = true;
 						LdsBarrier();
 						const int src = tf - L.dilation * (K - 1 - k); // tap k reads the frame d (K-1-k) back
@@ -339,7 +498,12 @@ namespace na
 							const int g = 4 * kb + q;
 							b[kb] = (kb < nb && g < Gl) ? (src >= 0 ? X[g * FRAMES + src] : h[kb]) : f32x4{ 0.0f, 0.0f, 0.0f, 0.0f };
 						}
-						MatMul<NB>(ops, nb, nb, lane, b, acc);
+						if constexpr (GATED)
+						{
+							if (lg) MatMulGated<NB>(ops, nb, lane, b, acc, accg);
+							else MatMul<NB>(ops, nb, nb, lane, b, acc);
+						}
+						else MatMul<NB>(ops, nb, nb, lane, b, acc);
 					};
 					if (AHEAD && K <= 3)
 					{
@@ -379,6 +543,20 @@ namespace na
 							zv.y = (4 * g + 1 < cin) ? Activate(acc[rb].y + bc.y + wm.y * cond, L.act) : 0.0f;
 							zv.z = (4 * g + 2 < cin) ? Activate(acc[rb].z + bc.z + wm.z * cond, L.act) : 0.0f;
 							zv.w = (4 * g + 3 < cin) ? Activate(acc[rb].w + bc.w + wm.w * cond, L.act) : 0.0f;
+							if constexpr (GATED)
+							{
+								if (lg)
+								{
+									// z = act(filter) * sigmoid(gate): the gate's pre-activation is in this lane, same channels, same frame
+									const f32x4 bg = AHEAD_G ? bgv[AHEAD_G ? rb : 0] : Load4(w, L.bconv + cin, 4 * g, cin);
+									const f32x4 wg = AHEAD_G ? wgv[AHEAD_G ? rb : 0] : Load4(w, L.wmix + cin, 4 * g, cin);
+									const f32x4 ag = accg[GATED ? rb : 0];
+									if (4 * g + 0 < cin) zv.x *= Sigmoid(ag.x + bg.x + wg.x * cond, L.gated);
+									if (4 * g + 1 < cin) zv.y *= Sigmoid(ag.y + bg.y + wg.y * cond, L.gated);
+									if (4 * g + 2 < cin) zv.z *= Sigmoid(ag.z + bg.z + wg.z * cond, L.gated);
+									if (4 * g + 3 < cin) zv.w *= Sigmoid(ag.w + bg.w + wg.w * cond, L.gated);
+								}
+							}
 							if (HEAD_LDS) HEAD[g * FRAMES + tf] += zv;
 							else head[rb] += zv;
 							zs[rb] = zv;
@@ -395,7 +573,8 @@ namespace na
 						if (N.kind == 0 && N.rechannel < 0)
 						{
 							const int nbn = (N.cin + 15) / 16;
-							StageLoad<NB>(pre, w, MatRef{ N.wconv, N.cin, N.cin, nbn, nbn });
+							if constexpr (GATED) StageLoad<NB>(pre, w, MatRef{ N.wconv, N.cin, N.cin, nbn, nbn }, N.gated != 0);
+							else StageLoad<NB>(pre, w, MatRef{ N.wconv, N.cin, N.cin, nbn, nbn });
 							havePre = true;
 						}
 					}
@@ -523,22 +702,36 @@ namespace na
 			}
 		}
 
-		template <int NB>
+		template <int NB, bool GATED = false>
 		hipError_t Launch(const Args& a, int numStreams, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
 		{
 			static PerDeviceOnce attr;
-			(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&WaveNetWideF32Kernel<NB>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
-			hipLaunchKernelGGL((WaveNetWideF32Kernel<NB>), dim3((unsigned)numStreams), dim3(NTHREADS), LdsBytes(NB, (a.maxC + 3) / 4), stream, a, in, out, inStride, outStride, n);
+			(void)attr.Run([] { return hipFuncSetAttribute(reinterpret_cast<const void*>(&WaveNetWideF32Kernel<NB, GATED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); });
+			hipLaunchKernelGGL((WaveNetWideF32Kernel<NB, GATED>), dim3((unsigned)numStreams), dim3(NTHREADS), LdsBytes(NB, (a.maxC + 3) / 4, GATED), stream, a, in, out, inStride, outStride, n);
 			return hipGetLastError();
 		}
+
+		// the gated instantiations <2, true> / <4, true> (wavenet_wide_f32_gated_kernels.hip)
+		hipError_t LaunchGated(const Args& a, int nb, int numStreams, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
+#ifdef NA_WIDE_F32_GATED_TU
+		// LDS at the widest model of each: 32 channels 49 664, 64: 131 584 bytes (of 163 840)
+		hipError_t LaunchGated(const Args& a, int nb, int numStreams, const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
+		{
+			if (nb == 2) return Launch<2, true>(a, numStreams, in, out, inStride, outStride, n, stream);
+			if (nb == 4) return Launch<4, true>(a, numStreams, in, out, inStride, outStride, n, stream);
+			return hipErrorInvalidValue;
+		}
+#endif
 	}
 
+#ifndef NA_WIDE_F32_GATED_TU
 	hipError_t LaunchWaveNetWideF32(const WnPrewarmLayer* layers, int numLayers, const float* weights, const int* ringOffF4, const int* ringFrames, const int* ringG,
-		int nrings, int stateF4, int maxChannels, float headScale, float* state, const int* slots, const int* rows, int numStreams, int slot0, int row0,
+		int nrings, int stateF4, int maxChannels, float headScale, bool gated, float* state, const int* slots, const int* rows, int numStreams, int slot0, int row0,
 		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
 	{
 		if (numStreams <= 0 || n <= 0) return hipSuccess;
-		if (n > WN_MAX_FRAMES || maxChannels < 1 || maxChannels > WN_GENERIC_MAX_CHANNELS) return hipErrorInvalidValue;
+		const WaveNetWideF32Choice c = WaveNetWideF32For(maxChannels, gated); // (nb == 0: no instantiation -- beyond 128 channels, gated beyond 64)
+		if (n > WN_MAX_FRAMES || c.nb == 0) return hipErrorInvalidValue;
 		wf::Args a;
 		a.layers = layers;
 		a.numLayers = numLayers;
@@ -555,10 +748,12 @@ namespace na
 		a.rows = rows;
 		a.slot0 = slot0;
 		a.row0 = row0;
+		if (c.gated) return wf::LaunchGated(a, c.nb, numStreams, in, out, inStride, outStride, n, stream);
 		// LDS at the widest model of each instantiation: 32 channels 41 472, 64: 98 816, 96: 123 392, 128: 131 584 bytes (of 163 840)
-		if (maxChannels <= 32) return wf::Launch<2>(a, numStreams, in, out, inStride, outStride, n, stream);
-		if (maxChannels <= 64) return wf::Launch<4>(a, numStreams, in, out, inStride, outStride, n, stream);
-		if (maxChannels <= 96) return wf::Launch<6>(a, numStreams, in, out, inStride, outStride, n, stream);
+		if (c.nb == 2) return wf::Launch<2>(a, numStreams, in, out, inStride, outStride, n, stream);
+		if (c.nb == 4) return wf::Launch<4>(a, numStreams, in, out, inStride, outStride, n, stream);
+		if (c.nb == 6) return wf::Launch<6>(a, numStreams, in, out, inStride, outStride, n, stream);
 		return wf::Launch<8>(a, numStreams, in, out, inStride, outStride, n, stream);
 	}
+#endif
 }
