@@ -516,6 +516,75 @@ NA_EXTERN int NA_BatchGetModInfo(NA_Batch* batch, NA_ModInfo* info);
 NA_EXTERN int NA_BatchSetStreamMod(NA_Batch* batch, int stream, const NA_ModParams* params, int fadeSamples);  /* params = NULL: the effect goes, click-free */
 NA_EXTERN int NA_BatchGetStreamMod(NA_Batch* batch, int stream, NA_ModParams* out); /* 1: *out filled (the target); 0: none (or a fade to none); < 0: stage not enabled / bad id */
 NA_EXTERN int NA_BatchStreamModFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's modulation fade; 0: none; < 0: stage not enabled / bad id */
+/* ---- the room stage: a per-stream algorithmic reverb, a feedback delay network ----
+ * The reverb stage below convolves with a measured room; its sound changes only by loading another impulse response.  This stage is
+ * the other kind of reverb an amp simulator ships -- room, plate, hall -- whose size, decay and damping are knobs turned while
+ * playing: eight delay lines of 128 .. maxLineSamples samples, a two-tap damping filter and an orthogonal mix that feeds every line
+ * into every other.  A fourteenth per-stream stage, off unless enabled, behind the delay stage and in front of the reverb stage: a
+ * session's chain is drive -> model -> gate -> EQ -> cabinet -> compressor -> modulation -> delay -> room -> reverb -> output gain ->
+ * mix -> limiter.  A batch that enabled the stage and set no room launches exactly what it launched before and produces the same bits.
+ * Arithmetic.  Every operation is one separately rounded f32 operation fl(.), round to nearest even, no FMA contraction, subnormals
+ *   kept.  len_i = lineSamples[i], fb_i = feedback[i], i = 0 .. 7.  L_i[t] is what line i took at position t; positions count the row's
+ *   samples from the set call that took the stream from no room, and L_i[t] = +0 for t < 0 -- decided by position, never by what
+ *   memory holds.  Per sample, x the row as the delay stage left it:
+ *     x'     = isnan(x) ? 0 : clamp(x, +-1e18)
+ *     r_i    = L_i[t - len_i],  q_i = L_i[t - len_i - 1]
+ *     keep   = fl(1 - damp)
+ *     d_i    = fl(fl(r_i * keep) + fl(q_i * damp))                    (the damping is a two-tap FIR: nothing recurs sample to sample)
+ *     h      = H8 d: three passes over pairs (a, b) -> (fl(a + b), fl(a - b)), the partners 1, then 2, then 4 indices apart (the
+ *              unnormalised Hadamard butterfly; its 1 / sqrt 8 is inside fb)
+ *     L_i[t] = fl(x' + fl(fb_i * h_i))
+ *     s      = fl(fl(fl(d_0 - d_1) + fl(d_2 - d_3)) + fl(fl(d_4 - d_5) + fl(d_6 - d_7)))
+ *     y      = fl(fl(dry * x') + fl(wet * s))
+ *   Fades: a set call moves from setting A to B over N = fadeSamples; k counts the samples since the set call; wk = 1 for k >= N - 1,
+ *   else (float)(k + 1) / (float)N.  fb_i, damp, wet and dry are B's where wk == 1, else fl(g_A + fl(fl(g_B - g_A) * wk)).  A line whose
+ *   length differs between A and B cross-fades its read head as the delay stage does: r_i is B's tap where wk == 1, else
+ *   fl(fl(fl(1 - wk) * tap_A) + fl(wk * tap_B)), and q_i likewise.  "No room" as A is B with wet = 0, dry = 1; "no room" as B is A
+ *   with wet = 0, dry = 1, and the entry retires with the sample at which the fade ends: later samples of the row are not touched.
+ *   Consequences: a sample's bits do not depend on how the signal is cut into calls, on alignment, on the stride, on in-place use, on
+ *   the other streams or on maxLineSamples; a row without an entry passes bit for bit; with damp = 0, fb_i = 0.25 and every line 128
+ *   long an impulse comes back as exact powers of two, 2^(2 - m) at t = 256 m, down through the subnormals.
+ * Limits (each refused with a message that names the field): lineSamples[i] in [128, maxLineSamples]; feedback[i] in [0, 1 / sqrt 8]
+ *   as an f32 (0.35355338f, which lies below 1 / sqrt 8); damp in [0, 0.5]; wet, dry finite and at most 1e6 in magnitude; NaN nowhere;
+ *   fadeSamples in [0, 1 << 20].  H8 / sqrt 8 is orthogonal and the FIR's gain is at most 1, so every accepted setting is stable.
+ * NA_BatchEnableRoomStage(maxLineSamples, a power of two in [256, 16384]) is the set-up side (allocates): per row of the batch's
+ *   capacity eight rings of ringSamples floats -- the power of two >= maxLineSamples + 129: 16 KB a row at 256, 1 MB a row at 16384 --,
+ *   a block of 160 bytes for the row's settings, and the stage's device + pinned tables; later NA_BatchAddStreams /
+ *   NA_BatchReserveStreams grow them.  Idempotent for an equal or smaller maximum; a larger one is refused while a stream has a room.
+ *   Every call below fails ("room stage not enabled (NA_BatchEnableRoomStage)") before it.  NA_BatchGetRoomInfo reports the sizes in
+ *   effect, the number of entries and the device bytes.
+ * NA_BatchSetStreamRoom, NA_BatchGetStreamRoom and NA_BatchStreamRoomFadeRemaining are REAL-TIME SAFE: host arithmetic on tables
+ *   that exist; no memset travels with them, and the settings travel to the device once, with the next processing call's table.
+ *   The stream has no room: the lines start empty at the next sample and wet / dry ramp in from 0 / 1 over fadeSamples.
+ *   The stream has a room: the lines go on; everything moves to the new setting over fadeSamples (0: at once).
+ *   params == NULL: wet / dry ramp to 0 / 1 over fadeSamples and the entry retires (0: at once); the lines are dropped.
+ *   A set call while a fade of the stream runs is refused ("a room fade of stream <s> is running (<k> samples left)"); the caller
+ *   polls NA_BatchStreamRoomFadeRemaining.  NA_BatchGetStreamRoom returns 1 and fills *out with the target, 0 when the stream has no
+ *   room (or fades to none), < 0 on a bad id or when the stage is not enabled.
+ * NA_RoomParamsFromSeconds is host arithmetic in double, each value rounded once, no device: lineSamples[i] is the smallest prime not
+ *   below sampleRate * sizeMs / 1000 * 2^(-i / 8), clamped to [128, 16384]; feedback[i] = 10^(-3 * lineSamples[i] / (decaySeconds *
+ *   sampleRate)) / sqrt 8 (the tail is 60 dB down after decaySeconds); wet = 10^(wetDb / 20) with -inf -> 0, dry likewise.  It returns
+ *   0, or < 0 with a message.
+ * Rules (each fails with a message that names it, NA_GetLastError): the stage must be enabled; the stream must be live (a parked one
+ * fails with "... is parked"); a broken batch refuses everything.  NA_BatchParkStream / NA_BatchRemoveStreams, and the park that ends a
+ * hand-over, drop the room and its lines at once.  Rooms are not part of a NA_BatchSaveStreams blob.
+ * While an entry exists a processing call behaves as it does with the other stages' entries: it takes the ordered path, host buffers
+ * go through the staging block, and it enqueues one table upload from the ring of pinned tables and ONE launch over the entries only,
+ * whatever the call's length: no allocation, no stream or event creation, no unbounded wait.  With the last entry the free-running
+ * modes come back.
+ * Not provided: the stage on NA_Multi* batches, on the one-stream NeuralModel and in NA_RenderOffline; a pre-delay (the delay stage in
+ * front provides it); modulated lines; more than eight lines; stereo decorrelation across the rows of a mix group. */
+#define NA_ROOM_LINES 8
+#define NA_ROOM_MIN_LINE_SAMPLES 128
+#define NA_ROOM_MAX_LINE_SAMPLES 16384
+typedef struct NA_RoomParams { int lineSamples[8]; float feedback[8]; float damp, wet, dry; } NA_RoomParams; /* 76 bytes */
+typedef struct NA_RoomInfo   { int maxLineSamples, ringSamples, pieceSamples, numRooms; long long deviceBytes; } NA_RoomInfo;
+NA_EXTERN int NA_RoomParamsFromSeconds(int sampleRate, double sizeMs, double decaySeconds, double damp, double wetDb, double dryDb, NA_RoomParams* out);
+NA_EXTERN int NA_BatchEnableRoomStage(NA_Batch* batch, int maxLineSamples);     /* a power of two in [256, 16384]; idempotent for equal or smaller; larger refused while entries exist */
+NA_EXTERN int NA_BatchGetRoomInfo(NA_Batch* batch, NA_RoomInfo* info);
+NA_EXTERN int NA_BatchSetStreamRoom(NA_Batch* batch, int stream, const NA_RoomParams* params, int fadeSamples); /* params = NULL: the room fades out and retires */
+NA_EXTERN int NA_BatchGetStreamRoom(NA_Batch* batch, int stream, NA_RoomParams* out); /* 1: *out filled (the target); 0: none (or a fade to none); < 0: stage not enabled / bad id */
+NA_EXTERN int NA_BatchStreamRoomFadeRemaining(NA_Batch* batch, int stream); /* samples left of the stream's room fade; 0: none; < 0: stage not enabled / bad id */
 /* ---- the gate stage: a per-stream noise gate ----
  * High-gain captures turn pickup hum into a loud hiss between notes.  A host of the reference gates that itself: it listens to the dry
  * input and scales the amp's output, because it holds both buffers.  Here the rows stay on the device, and a gate needs both ends of a
@@ -1425,6 +1494,10 @@ NA_EXTERN long long NA_DebugGateLaunches(void);
 NA_EXTERN long long NA_DebugMeterLaunches(void);
 /* Tests: launches of the drive stage's kernel so far (one per call with entries) */
 NA_EXTERN long long NA_DebugDriveLaunches(void);
+/* Tests: the room stage of a call of n samples on the host rows [NumStreams][stride], in place, synchronous (as NA_DebugRunModStage) */
+NA_EXTERN int NA_DebugRunRoomStage(NA_Batch* batch, float* hostRows, long stride, size_t n);
+/* Tests: launches of the room stage's kernel so far (one per processing call with entries, whatever its length) */
+NA_EXTERN long long NA_DebugRoomLaunches(void);
 /* Tests: launches of the limiter stage's kernel so far (one per piece of a call with entries) */
 NA_EXTERN long long NA_DebugLimiterLaunches(void);
 /* Tests: launches of the tuner stage's two kernels so far (one append per piece of a call with entries, one evaluate where an evaluation ends) */

@@ -15,7 +15,7 @@ from . import capi
 
 __all__ = ["NeuralModelLoader", "NeuralModel", "Batch", "MultiBatch", "EModelLoadMode", "EMathMode", "ECompositeModelLoadMode", "device_count",
            "NeuralAudioError", "render_offline", "render_plan", "debug_render_tap", "snapshot_bytes", "snapshot_fingerprint", "resample_plan", "resample_prototype",
-           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "mod_params_from_ms", "MOD_TRIANGLE", "MOD_SINE", "DRIVE_SHAPE_TANH", "DRIVE_SHAPE_CUBIC", "DRIVE_SHAPE_HARD", "limiter_params_from_db", "delay_params_from_ms", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
+           "resample_model_frames", "db_to_gain", "gate_params_from_db", "compressor_params_from_db", "mod_params_from_ms", "MOD_TRIANGLE", "MOD_SINE", "DRIVE_SHAPE_TANH", "DRIVE_SHAPE_CUBIC", "DRIVE_SHAPE_HARD", "limiter_params_from_db", "delay_params_from_ms", "room_params_from_seconds", "eq_section", "tuner_params_from_range", "tuner_pitch", "mix_gains_from_pan"]
 
 
 class NeuralAudioError(RuntimeError):
@@ -135,6 +135,33 @@ def mod_params_from_ms(sample_rate, base_ms, depth_ms, rate_hz, shape=MOD_SINE, 
                                               float(wet_db), float(dry_db), float(tremolo_depth), C.byref(out)) != 0:
         raise NeuralAudioError(capi.last_error())
     return _mod_dict(out)
+
+
+def _room_dict(p):
+    return {"lineSamples": [int(v) for v in p.lineSamples], "feedback": [float(v) for v in p.feedback], "damp": float(p.damp), "wet": float(p.wet),
+            "dry": float(p.dry)}
+
+
+def _room_params(d):
+    if isinstance(d, capi.NA_RoomParams):
+        return d
+    p = capi.NA_RoomParams()
+    for i in range(capi.NA_ROOM_LINES):
+        p.lineSamples[i] = int(d["lineSamples"][i])
+        p.feedback[i] = d["feedback"][i]
+    p.damp, p.wet, p.dry = d["damp"], d["wet"], d["dry"]
+    return p
+
+
+def room_params_from_seconds(sample_rate, size_ms, decay_seconds, damp=0.2, wet_db=-12.0, dry_db=0.0):
+    """The constants Batch.SetStreamRoom takes, from a size, a decay time and decibels (NA_RoomParamsFromSeconds): eight prime line
+    lengths from size_ms down to 2^(-7/8) of it, each line's feedback such that the tail is 60 dB down after decay_seconds; -inf dB is
+    0.  Host arithmetic: needs no device."""
+    out = capi.NA_RoomParams()
+    if capi.load_library().NA_RoomParamsFromSeconds(int(sample_rate), float(size_ms), float(decay_seconds), float(damp), float(wet_db), float(dry_db),
+                                                    C.byref(out)) != 0:
+        raise NeuralAudioError(capi.last_error())
+    return _room_dict(out)
 
 
 DELAY_FIELDS = ("delaySamples", "feedback", "lowpassCoeff", "highpassCoeff", "wet", "dry")
@@ -878,6 +905,42 @@ class Batch:
     def DebugRunModStage(self, rows, n=None):
         """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunModStage)."""
         return self._debug_run_stage(self._lib.NA_DebugRunModStage, rows, n)
+
+    # -- the room stage: EnableRoomStage is set-up side; SetStreamRoom is real-time safe (include/neuralaudio_amd.h) ----
+    def EnableRoomStage(self, maxLineSamples):
+        if self._lib.NA_BatchEnableRoomStage(self._h, int(maxLineSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetRoomInfo(self):
+        info = capi.NA_RoomInfo()
+        if self._lib.NA_BatchGetRoomInfo(self._h, C.byref(info)) != 0:
+            raise NeuralAudioError(capi.last_error())
+        return {name: int(getattr(info, name)) for name, _ in capi.NA_RoomInfo._fields_}
+
+    def SetStreamRoom(self, stream, params, fadeSamples=0):
+        """An algorithmic reverb (a feedback delay network of eight lines) on the stream from the next sample on: `params` a dict of the
+        NA_RoomParams fields (room_params_from_seconds makes one), reached over fadeSamples.  None fades the room out and retires it."""
+        p = None if params is None else C.byref(_room_params(params))
+        if self._lib.NA_BatchSetStreamRoom(self._h, int(stream), p, int(fadeSamples)) != 0:
+            raise NeuralAudioError(capi.last_error())
+
+    def GetStreamRoom(self, stream):
+        """The target constants as a dict; None: no room (or a fade to none)."""
+        out = capi.NA_RoomParams()
+        rc = int(self._lib.NA_BatchGetStreamRoom(self._h, int(stream), C.byref(out)))
+        if rc < 0:
+            raise NeuralAudioError(capi.last_error())
+        return _room_dict(out) if rc else None
+
+    def StreamRoomFadeRemaining(self, stream):
+        left = int(self._lib.NA_BatchStreamRoomFadeRemaining(self._h, int(stream)))
+        if left < 0:
+            raise NeuralAudioError(capi.last_error())
+        return left
+
+    def DebugRunRoomStage(self, rows, n=None):
+        """Test hook: the stage of a call of n samples, in place on the float32 array rows[NumStreams, stride] (NA_DebugRunRoomStage)."""
+        return self._debug_run_stage(self._lib.NA_DebugRunRoomStage, rows, n)
 
     # -- the compressor stage: EnableCompressorStage is set-up side; SetStreamCompressor is real-time safe (include/neuralaudio_amd.h) ----
     def EnableCompressorStage(self):

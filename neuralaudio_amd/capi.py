@@ -52,6 +52,8 @@ NA_SYMBOLS = [
     "NA_DebugCompressorLaunches",
     "NA_ModParamsFromMs", "NA_BatchEnableModStage", "NA_BatchGetModInfo", "NA_BatchSetStreamMod", "NA_BatchGetStreamMod",
     "NA_BatchStreamModFadeRemaining", "NA_DebugRunModStage", "NA_DebugModLaunches",
+    "NA_RoomParamsFromSeconds", "NA_BatchEnableRoomStage", "NA_BatchGetRoomInfo", "NA_BatchSetStreamRoom", "NA_BatchGetStreamRoom",
+    "NA_BatchStreamRoomFadeRemaining", "NA_DebugRunRoomStage", "NA_DebugRoomLaunches",
     "NA_GateParamsFromDb", "NA_BatchEnableGateStage", "NA_BatchGetGateInfo", "NA_BatchSetStreamGate", "NA_BatchGetStreamGate",
     "NA_BatchStreamGateGain", "NA_DebugGateLaunches",
     "NA_EqSectionFromDesign", "NA_BatchEnableEqStage", "NA_BatchGetEqInfo", "NA_BatchSetStreamEq", "NA_BatchGetStreamEq",
@@ -127,6 +129,20 @@ class NA_ModParams(C.Structure):
 
 class NA_ModInfo(C.Structure):
     _fields_ = [("maxDelaySamples", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numMods", C.c_int),
+                ("deviceBytes", C.c_longlong)]
+
+
+NA_ROOM_LINES = 8
+NA_ROOM_MIN_LINE_SAMPLES = 128
+NA_ROOM_MAX_LINE_SAMPLES = 16384
+
+
+class NA_RoomParams(C.Structure):
+    _fields_ = [("lineSamples", C.c_int * 8), ("feedback", C.c_float * 8), ("damp", C.c_float), ("wet", C.c_float), ("dry", C.c_float)]
+
+
+class NA_RoomInfo(C.Structure):
+    _fields_ = [("maxLineSamples", C.c_int), ("ringSamples", C.c_int), ("pieceSamples", C.c_int), ("numRooms", C.c_int),
                 ("deviceBytes", C.c_longlong)]
 
 
@@ -357,6 +373,14 @@ def load_library():
         "NA_BatchStreamModFadeRemaining": (C.c_int, [vp, C.c_int]),
         "NA_DebugRunModStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
         "NA_DebugModLaunches": (C.c_longlong, []),
+        "NA_RoomParamsFromSeconds": (C.c_int, [C.c_int] + [C.c_double] * 5 + [C.POINTER(NA_RoomParams)]),
+        "NA_BatchEnableRoomStage": (C.c_int, [vp, C.c_int]),
+        "NA_BatchGetRoomInfo": (C.c_int, [vp, C.POINTER(NA_RoomInfo)]),
+        "NA_BatchSetStreamRoom": (C.c_int, [vp, C.c_int, C.POINTER(NA_RoomParams), C.c_int]),
+        "NA_BatchGetStreamRoom": (C.c_int, [vp, C.c_int, C.POINTER(NA_RoomParams)]),
+        "NA_BatchStreamRoomFadeRemaining": (C.c_int, [vp, C.c_int]),
+        "NA_DebugRunRoomStage": (C.c_int, [vp, fp, C.c_long, C.c_size_t]),
+        "NA_DebugRoomLaunches": (C.c_longlong, []),
         "NA_GateParamsFromDb": (C.c_int, [C.c_int] + [C.c_float] * 7 + [C.POINTER(NA_GateParams)]),
         "NA_BatchEnableGateStage": (C.c_int, [vp]),
         "NA_BatchGetGateInfo": (C.c_int, [vp, C.POINTER(NA_GateInfo)]),

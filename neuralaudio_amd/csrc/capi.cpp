@@ -1037,6 +1037,79 @@ int NA_DebugRunModStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
 long long NA_DebugModLaunches(void) { return (long long)na::ModStageLaunches(); }
 #endif
 
+// ---- the room stage (gpu_batch.h EnableRoomStage / SetStreamRoom) ----
+static_assert(sizeof(NA_RoomParams) == sizeof(na::RoomParams) && sizeof(NA_RoomParams) == 76, "NA_RoomParams is RoomParams, field for field");
+static_assert(NA_ROOM_LINES == na::kRoomLines && NA_ROOM_MIN_LINE_SAMPLES == na::kRoomMinLineSamples && NA_ROOM_MAX_LINE_SAMPLES == na::kRoomMaxLineSamples,
+	"the header's limits are room_stage.h's");
+
+int NA_RoomParamsFromSeconds(int sampleRate, double sizeMs, double decaySeconds, double damp, double wetDb, double dryDb, NA_RoomParams* out)
+{
+	return Guard([&] {
+		if (!out) throw std::runtime_error("NA_RoomParamsFromSeconds: bad argument");
+		na::RoomParams p;
+		if (const char* why = na::RoomParamsFromSeconds(sampleRate, sizeMs, decaySeconds, damp, wetDb, dryDb, p)) throw std::runtime_error(std::string("NA_RoomParamsFromSeconds: ") + why);
+		memcpy(out, &p, sizeof(p));
+	});
+}
+
+int NA_BatchEnableRoomStage(NA_Batch* batch, int maxLineSamples)
+{
+	return BatchCall(batch, "NA_BatchEnableRoomStage", [&](na::GpuBatch& b) { b.EnableRoomStage(maxLineSamples); });
+}
+
+int NA_BatchGetRoomInfo(NA_Batch* batch, NA_RoomInfo* info)
+{
+	return BatchCall(batch, "NA_BatchGetRoomInfo", [&](na::GpuBatch& b) {
+		if (!info) throw std::runtime_error("NA_BatchGetRoomInfo: bad argument");
+		const na::RoomStageInfo i = b.GetRoomInfo();
+		info->maxLineSamples = i.maxLineSamples;
+		info->ringSamples = i.ringSamples;
+		info->pieceSamples = i.pieceSamples;
+		info->numRooms = i.numRooms;
+		info->deviceBytes = i.deviceBytes;
+	});
+}
+
+int NA_BatchSetStreamRoom(NA_Batch* batch, int stream, const NA_RoomParams* params, int fadeSamples)
+{
+	return BatchCall(batch, "NA_BatchSetStreamRoom", [&](na::GpuBatch& b) {
+		if (!params)
+		{
+			b.SetStreamRoom(stream, nullptr, fadeSamples);
+			return;
+		}
+		na::RoomParams p;
+		memcpy(&p, params, sizeof(p));
+		b.SetStreamRoom(stream, &p, fadeSamples);
+	});
+}
+
+int NA_BatchGetStreamRoom(NA_Batch* batch, int stream, NA_RoomParams* out)
+{
+	return BatchValue(batch, "NA_BatchGetStreamRoom", -1, [&](na::GpuBatch& b) {
+		na::RoomParams p;
+		const int has = b.GetStreamRoom(stream, p) ? 1 : 0;
+		if (has && out) memcpy(out, &p, sizeof(p));
+		return has;
+	});
+}
+
+int NA_BatchStreamRoomFadeRemaining(NA_Batch* batch, int stream)
+{
+	return BatchValue(batch, "NA_BatchStreamRoomFadeRemaining", -1, [&](na::GpuBatch& b) { return b.StreamRoomFadeRemaining(stream); });
+}
+
+#ifndef NA_RELEASE
+int NA_DebugRunRoomStage(NA_Batch* batch, float* hostRows, long stride, size_t n)
+{
+	return Guard([&] {
+		if (!batch) throw std::runtime_error("NA_DebugRunRoomStage: null batch");
+		batch->batch->DebugRunRoomStage(hostRows, stride, n);
+	});
+}
+long long NA_DebugRoomLaunches(void) { return (long long)na::RoomStageLaunches(); }
+#endif
+
 // ---- the gate stage (gpu_batch.h EnableGateStage / SetStreamGate) ----
 namespace
 {

@@ -31,6 +31,7 @@
 #include "meter_stage.h"
 #include "mod_stage.h"
 #include "mix_stage.h"
+#include "room_stage.h"
 #include "tuner_stage.h"
 #include "model_loader.h"
 #include "output_stage.h"
@@ -132,6 +133,12 @@ namespace na
 	struct DriveStageInfo
 	{
 		int numDrives = 0;
+		long long deviceBytes = 0;
+	};
+
+	struct RoomStageInfo
+	{
+		int maxLineSamples = 0, ringSamples = 0, pieceSamples = 0, numRooms = 0;
 		long long deviceBytes = 0;
 	};
 
@@ -289,6 +296,21 @@ namespace na
 		int StreamModFadeRemaining(int stream) const;
 		// test hook (NA_DebugRunModStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
 		void DebugRunModStage(float* hostRows, long stride, size_t n);
+
+		// The room stage (room_stage.h): a per-stream algorithmic reverb -- a feedback delay network of eight lines of
+		// 128 .. maxLineSamples samples, a two-tap damping FIR and an 8-point Hadamard mix -- behind the delay stage and in front of the
+		// reverb stage.  EnableRoomStage is the set-up side: eight rings and a setting block per row (CreateStreams grows them) and the
+		// tables.  SetStreamRoom is host arithmetic on those tables; while an entry exists -- a stream with a room, or a fade towards none --
+		// every processing call runs on the ordered path and enqueues ONE table upload and ONE launch over the entries only, whatever the
+		// call's length.  Without an entry the batch launches exactly what it launches without the stage.
+		void EnableRoomStage(int maxLineSamples);
+		bool HasRoomStage() const { return stages[kRoomStage] != nullptr; }
+		RoomStageInfo GetRoomInfo() const;
+		void SetStreamRoom(int stream, const RoomParams* params, int fadeSamples); // nullptr: no room
+		bool GetStreamRoom(int stream, RoomParams& out) const;                     // the target; false: none
+		int StreamRoomFadeRemaining(int stream) const;
+		// test hook (NA_DebugRunRoomStage): the stage of a call of n samples on host rows [NumStreams()][stride]; synchronous, set-up side
+		void DebugRunRoomStage(float* hostRows, long stride, size_t n);
 
 		// The gate stage (gate_stage.h): a per-stream noise gate that listens to the stream's input row and scales the row
 		// the models produced for it -- the detector launch in front of everything of the call, the apply launch first of the stages, in
@@ -549,9 +571,9 @@ namespace na
 		std::vector<int> pendingHistoryZero; // resampling batch: rows activated since the last processing call
 		int CreateStreams(const std::shared_ptr<const LoadedModel>& model, float quality, int count, bool prewarm, bool onDemand, bool pool);
 		void FlushRearms(); // top of every processing entry point, outside any graph capture
-		// The per-stream stages (DESIGN.md 2.9 - 2.22).  StageId is THE place that states the chain: a processing call runs the stages with
+		// The per-stream stages (DESIGN.md 2.9 - 2.23).  StageId is THE place that states the chain: a processing call runs the stages with
 		// entries in this order, and what the batch does for every stage is a loop over `stages` (null until the stage's Enable call).
-		enum StageId { kDriveStage, kGateStage, kEqStage, kCabinetStage, kCompressorStage, kModStage, kDelayStage, kReverbStage, kOutputStage, kMixStage, kLimiterStage, kMeterStage, kTunerStage, kNumStages };
+		enum StageId { kDriveStage, kGateStage, kEqStage, kCabinetStage, kCompressorStage, kModStage, kDelayStage, kRoomStage, kReverbStage, kOutputStage, kMixStage, kLimiterStage, kMeterStage, kTunerStage, kNumStages };
 		struct Stage // what the batch needs from any stage (the stages: gpu_batch_internal.h)
 		{
 			virtual ~Stage() = default;
@@ -564,7 +586,7 @@ namespace na
 		};
 		template <class Book, class Entry> struct StageOf;
 		template <class Record> struct StageResults; // the result blocks of the stages that report to the host (meter, tuner)
-		struct DriveStage; struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct ModStage; struct DelayStage; struct ReverbStage; struct OutputStage; struct MixStage; struct LimiterStage; struct MeterStage; struct TunerStage;
+		struct DriveStage; struct GateStage; struct EqStage; struct CabinetStage; struct CompressorStage; struct ModStage; struct DelayStage; struct RoomStage; struct ReverbStage; struct OutputStage; struct MixStage; struct LimiterStage; struct MeterStage; struct TunerStage;
 		std::unique_ptr<Stage> stages[kNumStages];
 		template <class S> S& Require(const char* who) const;             // throws "<who>: <stage> not enabled (...)"
 		template <class S> S& EnableStage();                              // every Enable*Stage call

@@ -299,7 +299,7 @@ namespace na
 		if (samples < 0 || samples > kOutStageMaxRamp) throw std::runtime_error(std::string("neuralaudio_amd: ") + who + ": " + argument + " must lie in [0, 1 << 20]");
 	}
 
-	// What the thirteen stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
+	// What the fourteen stages share (GpuBatch::Stage, gpu_batch.h): the host mirror `book` (its own header, host-compilable) and the ring of
 	// entry tables.
 	template <class Book, class Entry>
 	struct GpuBatch::StageOf : GpuBatch::Stage
@@ -421,6 +421,22 @@ namespace na
 		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + one launch per piece + the host mirror's advance
 	};
 	hipError_t LaunchModStage(const ModLaunch& L, hipStream_t stream); // (mod_stage_kernels.hip) the launch of one piece
+
+	// the room stage (room_stage.h, room_stage.cpp): the rows' lines (eight rings a row) and the settings the kernel reads
+	struct GpuBatch::RoomStage : StageOf<RoomBook, RoomEntry>
+	{
+		static constexpr StageId kId = kRoomStage;
+		static constexpr const char* kNotEnabled = "room stage not enabled (NA_BatchEnableRoomStage)";
+		float* rings = nullptr;           // [ringRows][kRoomLines][book.RingSamples()]
+		RoomSetting* settings = nullptr;  // [settingRows]: filed by the launch of the call behind a set call
+		int ringRows = 0, settingRows = 0;
+		RoomStage() : StageOf("room stage") {}
+		~RoomStage() override;
+		void EnsureRows(GpuBatch& batch, int rows) override;
+		void Leave(int s) override { if (s < book.Rows()) book.Leave(s); } // no room at once, its history dropped
+		void Run(GpuBatch& batch, hipStream_t launch, float* dOut, size_t n, long outStride) override; // table upload + one launch + the host mirror's advance
+	};
+	hipError_t LaunchRoomStage(const RoomLaunch& L, hipStream_t stream); // (room_stage_kernels.hip) the launch of one call
 
 	// the delay stage (delay_stage.h, delay_stage.cpp): the rows' delay lines (rings) and filter states
 	struct GpuBatch::DelayStage : StageOf<DelayBook, DelayEntry>

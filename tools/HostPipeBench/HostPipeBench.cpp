@@ -57,6 +57,11 @@
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --limit N [--limit-lookahead L=64 --limit-hold H=0]
 //       the plain run below with the limiter stage enabled and a limiter (ceiling 0.05) on the first N streams (N = 0: enabled, nothing
 //       set: must cost nothing); the histories fill first.
+//   HostPipeBench <model file> [streams] [frames] [buffers=2000] --room N [--room-size-ms S=80 --room-decay D=1.5]
+//       the plain run below with the room stage enabled (maxLineSamples: the power of two that holds the longest line) and a room on the
+//       first N streams: eight prime lines from S ms down at 48 kHz, a tail of D seconds, damp 0.2, wet -12 dB, dry 0 dB
+//       (NA_RoomParamsFromSeconds) -- (N = 0: enabled, nothing set: must cost nothing).  With N > 0 the run first feeds the longest
+//       line, so that every ring read is a read of a sample the stage wrote.  Times every buffer period like --tuner.
 //   HostPipeBench <model file> [streams] [frames] [buffers=2000] --mod N [--mod-base-ms B=7 --mod-depth-ms 3 --mod-rate-hz 0.8 --mod-voices 3 --mod-fb 0]
 //       the plain run below with the modulation stage enabled (maxDelaySamples = 4096) and a modulation on the first N streams: voices a
 //       1 / voices of a cycle apart around B ms at 48 kHz, "sine" shape, wet -3 dB, dry 0 dB (NA_ModParamsFromMs); the defaults are a
@@ -624,6 +629,8 @@ int main(int argc, char** argv)
 	int comp = -1;
 	int mod = -1, modVoices = -1;
 	int limit = -1, limitLookahead = 64, limitHold = 0;
+	int room = -1;
+	double roomSizeMs = 80.0, roomDecay = 1.5;
 	double modBaseMs = 7.0, modDepthMs = -1.0, modRateHz = 0.8, modFb = 0.0;
 	float compAttackMs = 5.0f, compReleaseMs = 100.0f;
 	bool churnLegacy = false, tunerStagger = false, mixDry = false;
@@ -655,6 +662,9 @@ int main(int argc, char** argv)
 		else if (!std::strcmp(argv[i], "--comp") && i + 1 < argc) comp = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--mod") && i + 1 < argc) mod = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--limit") && i + 1 < argc) limit = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--room") && i + 1 < argc) room = std::atoi(argv[++i]);
+		else if (!std::strcmp(argv[i], "--room-size-ms") && i + 1 < argc) roomSizeMs = std::atof(argv[++i]);
+		else if (!std::strcmp(argv[i], "--room-decay") && i + 1 < argc) roomDecay = std::atof(argv[++i]);
 		else if (!std::strcmp(argv[i], "--limit-lookahead") && i + 1 < argc) limitLookahead = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--limit-hold") && i + 1 < argc) limitHold = std::atoi(argv[++i]);
 		else if (!std::strcmp(argv[i], "--mod-base-ms") && i + 1 < argc) modBaseMs = std::atof(argv[++i]);
@@ -861,6 +871,22 @@ int main(int argc, char** argv)
 		CHECK(NA_BatchGetLimiterInfo(batch, &info) == 0);
 		limitBytes = info.deviceBytes;
 	}
+	long long roomBytes = 0;
+	int roomLongest = 0;
+	if (room >= 0)
+	{
+		NA_RoomParams rp;
+		CHECK(NA_RoomParamsFromSeconds(48000, roomSizeMs, roomDecay, 0.2, -12.0, 0.0, &rp) == 0);
+		for (int i = 0; i < NA_ROOM_LINES; i++) roomLongest = std::max(roomLongest, rp.lineSamples[i]);
+		int maxLine = 256;
+		while (maxLine < roomLongest) maxLine *= 2;
+		CHECK(NA_BatchEnableRoomStage(batch, maxLine) == 0);
+		room = std::min(room, streams);
+		for (int s = 0; s < room; s++) CHECK(NA_BatchSetStreamRoom(batch, s, &rp, 0) == 0);
+		NA_RoomInfo info;
+		CHECK(NA_BatchGetRoomInfo(batch, &info) == 0);
+		roomBytes = info.deviceBytes;
+	}
 	long long delayBytes = 0;
 	if (delay >= 0)
 	{
@@ -878,7 +904,7 @@ int main(int argc, char** argv)
 	unsigned long long meterWindows = 0; // (--meter: `windows` of the last reading of stream 0 in the pipelined loop)
 	unsigned long long tunerEvaluations = 0; // (--tuner: `evaluations` of the last reading of stream 0 in the pipelined loop)
 	std::vector<double> periods;             // (--tuner, --mix N: every buffer period of the pipelined loop)
-	const bool marks = gate >= 0 || comp >= 0 || mod >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0 || limit >= 0; // (the plain run stays what it was)
+	const bool marks = gate >= 0 || comp >= 0 || mod >= 0 || eq >= 0 || meter >= 0 || tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0 || limit >= 0 || room >= 0; // (the plain run stays what it was)
 	const size_t count = (size_t)streams * frames;
 	std::vector<float> in(count), out(count);
 	for (size_t i = 0; i < count; i++) in[i] = 0.25f * (float)((i * 2654435761u) >> 8 & 0xffff) / 65536.0f - 0.125f;
@@ -892,6 +918,8 @@ int main(int argc, char** argv)
 		for (long long fed = 0; fed < 4096; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 	if (limit > 0)
 		for (long long fed = 0; fed < 2 * limitLookahead + limitHold; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
+	if (room > 0)
+		for (long long fed = 0; fed <= roomLongest; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 	if (delay > 0)
 		for (long long fed = 0; fed < delaySamples; fed += frames) CHECK(NA_BatchProcess(batch, in.data(), out.data(), (size_t)frames) == 0);
 
@@ -969,7 +997,7 @@ int main(int argc, char** argv)
 			CHECK(have >= 0);
 			if (have) tunerEvaluations = reading.evaluations;
 		}
-		if (tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0 || comp >= 0 || mod >= 0 || limit >= 0) periods.push_back(Now());
+		if (tuner >= 0 || mixGroups >= 0 || reverb >= 0 || delay >= 0 || comp >= 0 || mod >= 0 || limit >= 0 || room >= 0) periods.push_back(Now());
 	}
 	CHECK(NA_BatchCollect(batch, pending, out.data()) == 0);
 	const double usCopy = (Now() - t0) * 1e6 / buffers;
@@ -1026,9 +1054,9 @@ int main(int argc, char** argv)
 		usZero[depth - 2] = (Now() - t0) * 1e6 / buffers;
 	}
 
-	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"reverb\": %d, \"reverb_taps\": %d, \"reverb_irs\": %d, \"reverb_device_bytes\": %lld, \"reverb_load_irs_ms\": %.1f, \"reverb_input_spectrum_bytes_per_buffer\": %lld, \"reverb_distinct_ir_spectrum_bytes\": %lld, \"delay\": %d, \"delay_samples\": %d, \"delay_device_bytes\": %lld, \"comp\": %d, \"mod\": %d, \"mod_voices\": %d, \"mod_feedback\": %.3g, \"mod_device_bytes\": %lld, \"limit\": %d, \"limit_lookahead\": %d, \"limit_hold\": %d, \"limit_device_bytes\": %lld, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
+	std::printf("{\"streams\": %d, \"frames\": %d, \"buffers\": %d, \"gate\": %d, \"eq\": %d, \"eq_sections\": %d, \"meter\": %d, \"meter_window\": %d, \"meter_windows_read\": %llu, \"tuner\": %d, \"tuner_hop\": %d, \"tuner_stagger\": %d, \"tuner_evaluations_read\": %llu, \"mix_groups\": %d, \"mix_dry\": %d, \"reverb\": %d, \"reverb_taps\": %d, \"reverb_irs\": %d, \"reverb_device_bytes\": %lld, \"reverb_load_irs_ms\": %.1f, \"reverb_input_spectrum_bytes_per_buffer\": %lld, \"reverb_distinct_ir_spectrum_bytes\": %lld, \"delay\": %d, \"delay_samples\": %d, \"delay_device_bytes\": %lld, \"comp\": %d, \"mod\": %d, \"mod_voices\": %d, \"mod_feedback\": %.3g, \"mod_device_bytes\": %lld, \"limit\": %d, \"limit_lookahead\": %d, \"limit_hold\": %d, \"limit_device_bytes\": %lld, \"room\": %d, \"room_size_ms\": %.3g, \"room_decay_s\": %.3g, \"room_device_bytes\": %lld, \"pipelined_period_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"us_per_buffer_copying_between_marks\": %.3f, \"us_per_buffer_zero_copy\": %.3f, \"us_per_buffer_zero_copy_3_in_flight\": %.3f, \"us_per_buffer_copying\": %.3f, "
 		"\"blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f, \"max\": %.1f}, \"in_place_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"registered_blocking_latency_us\": {\"p50\": %.1f, \"p99\": %.1f}, \"checksum\": %.6g}\n",
-		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, reverb, reverb >= 0 ? reverbTaps : 0, reverb > 0 ? reverbIRs : 0, reverbBytes, reverbLoadMs, reverbInputSpectrumBytes, reverbDistinctIRBytes, delay, delay >= 0 ? delaySamples : 0, delayBytes, comp, mod, mod >= 0 ? modVoices : 0, mod >= 0 ? modFb : 0.0, modBytes, limit, limit >= 0 ? limitLookahead : 0, limit >= 0 ? limitHold : 0, limitBytes, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
+		streams, frames, buffers, gate, eq, eq >= 0 ? eqSections : 0, meter, meter >= 0 ? meterWindow : 0, meterWindows, tuner, tuner >= 0 ? tunerHop : 0, tunerStagger ? 1 : 0, tunerEvaluations, mixGroups, mixGroups >= 0 && mixDry ? 1 : 0, reverb, reverb >= 0 ? reverbTaps : 0, reverb > 0 ? reverbIRs : 0, reverbBytes, reverbLoadMs, reverbInputSpectrumBytes, reverbDistinctIRBytes, delay, delay >= 0 ? delaySamples : 0, delayBytes, comp, mod, mod >= 0 ? modVoices : 0, mod >= 0 ? modFb : 0.0, modBytes, limit, limit >= 0 ? limitLookahead : 0, limit >= 0 ? limitHold : 0, limitBytes, room, room >= 0 ? roomSizeMs : 0.0, room >= 0 ? roomDecay : 0.0, roomBytes, periodP50, periodP99, periodMax, usMarked, usZero[0], usZero[1], usCopy, lat[lat.size() / 2], lat[(size_t)(lat.size() * 0.99)], lat.back(), latInPlace[latInPlace.size() / 2], latInPlace[(size_t)(latInPlace.size() * 0.99)], latReg[latReg.size() / 2], latReg[(size_t)(latReg.size() * 0.99)], checksum);
 	NA_BatchDestroy(batch);
 	DeleteModel(model);
 	DeleteLoader(loader);
