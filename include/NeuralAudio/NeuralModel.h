@@ -137,7 +137,7 @@ namespace NeuralAudio
 		void SetWaveNetMathMode(EMathMode mode) { wavenetMath = mode; }
 		EMathMode GetWaveNetMathMode() { return wavenetMath; }
 		// Exact f32 arithmetic for the WaveNet models created next (default off): no f16-split kernel runs them -- no load refusal of the
-		// f16 operand format, no input clamp, no saturation; several times the cost at 17 .. 128 channels (WaveNetWideF32Kernel), and NaN /
+		// f16 operand format, no input clamp, no saturation; several times the cost at 17 .. 128 channels (WaveNetWideF32Kernel); 129 .. 256 channels load with this option only (WaveNetPanelF32Kernel); NaN /
 		// inf input samples are not cleaned
 		void SetWaveNetExactF32(bool on) { wavenetExactF32 = on; }
 		bool GetWaveNetExactF32() { return wavenetExactF32; }

@@ -34,8 +34,8 @@ NA_EXTERN void NA_SetDevice(NeuralModelLoader* loader, int device);
 NA_EXTERN void NA_SetWaveNetMathMode(NeuralModelLoader* loader, int mathMode);
 NA_EXTERN void NA_SetLSTMMathMode(NeuralModelLoader* loader, int mathMode);
 // Exact f32 arithmetic for the WaveNet models this loader creates next (on != 0; default off).  Such a model never runs on an f16-split
-// kernel: up to 16 channels it runs on the f32 frame kernel, at 17 .. 128 channels on WaveNetWideF32Kernel (NA_ModelKernelInfo family
-// "wide-f32") -- the weights need not fit the f16 operand format, the input is not clamped (input limit: infinity), nothing saturates and
+// kernel: up to 16 channels it runs on the f32 frame kernel, at 17 .. 128 channels on WaveNetWideF32Kernel, at 129 .. 256 channels --
+// which load with this option only, the default limit is 128 -- on WaveNetPanelF32Kernel (NA_ModelKernelInfo family "wide-f32") -- the weights need not fit the f16 operand format, the input is not clamped (input limit: infinity), nothing saturates and
 // no range event is counted.  It costs several times the default kernels at those widths (README), and NaN / inf input samples are not
 // cleaned.  Models created before the call, or by a loader with the option off, are what they were; both kinds share a batch.
 NA_EXTERN void NA_SetWaveNetExactF32(NeuralModelLoader* loader, int on);

@@ -564,9 +564,10 @@ namespace na
 							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, plan.condLimit, !plan.splitRangeProven, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
 							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetGenericKernel");
 					else if (family == WN_FAMILY_WIDE_F32)
-						CheckHip(LaunchWaveNetWideF32(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
+						// (beyond 128 channels the panel kernel: the chunk goes out as ordered launches of at most 64 frames, wavenet_launch.h)
+						CheckHip(LaunchWaveNetExactF32(dPrewarm.Get(), (int)plan.prewarm.size(), dWeightsGen.Get(), dRingOff.Get(), dRingFrames.Get(), dRingG.Get(),
 							(int)plan.rings.size(), plan.stateF4, plan.maxChannels, plan.headScale, choice.gated, state.Get(), contiguous ? nullptr : dSlots.Get(), dRows.Get(), numActive,
-							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), "WaveNetWideF32Kernel");
+							contiguous ? hSlots[0] : 0, contiguous ? hRows[0] : 0, dIn + offset, dOut + offset, inStride, outStride, chunk, launchStream), choice.KernelName(true));
 					else
 					{
 						// a launch of this group alone (sharing 1; split family: the state of this group's streams alone beyond the Infinity Cache

@@ -44,7 +44,7 @@ namespace na
 		const char* KernelName(bool specOn) const
 		{
 			if (family == WN_FAMILY_SPLIT) return (specArch != WN_SPEC_NONE && specOn) ? "WaveNetSpecKernel" : "WaveNetSplitKernel";
-			if (family == WN_FAMILY_WIDE_F32) return "WaveNetWideF32Kernel";
+			if (family == WN_FAMILY_WIDE_F32) return plan.maxChannels > WN_GENERIC_MAX_CHANNELS ? "WaveNetPanelF32Kernel" : "WaveNetWideF32Kernel";
 			return family == WN_FAMILY_GENERIC ? (plan.maxChannels > 64 ? "WaveNetWideKernel" : "WaveNetGenericKernel") : "WaveNetFrameKernel";
 		}
 		const char* FamilyName() const
@@ -113,8 +113,8 @@ namespace na
 		{
 			// Exact f32 on request (NA_SetWaveNetExactF32): the same rule as a failed range proof, and like it this outranks NA_WN_KERNEL -- no
 			// f16-split kernel, hence no pack and no padding.  Up to 16 channels that is the frame kernel; wider models run the f32 kernel of
-			// the runtime-shaped family (wavenet_wide_f32_kernels.hip), on the generic state format (genericOnly plans have no other), with
-			// no input limit
+			// the runtime-shaped family (wavenet_wide_f32_kernels.hip; 129 .. 256 channels, which only this option loads:
+			// wavenet_panel_f32_kernels.hip), on the generic state format (genericOnly plans have no other), with no input limit
 			c.family = real.genericOnly ? WN_FAMILY_WIDE_F32 : WN_FAMILY_FRAME;
 			c.kind = real.genericOnly ? LaunchKind::Own : LaunchKind::Frame;
 			c.plan = BuildWaveNetPlan(wn, false);

@@ -120,7 +120,8 @@ namespace na
 	static_assert(sizeof(WnSplitStage) == 64, "split stage descriptors are 64-byte records");
 
 	constexpr int WN_GENERIC_MAX_CHANNELS = 128; // runtime-shaped block kernels (wavenet_generic_kernels.hip): channels per layer array (65 .. 128: WaveNetWideKernel)
-	constexpr int WN_COL_STRIDE = 128;          // floats per ring in the steady-state column table
+	constexpr int WN_PANEL_MAX_CHANNELS = 256;   // ... in exact f32 on request (WaveNetDesc::exactF32): 129 .. 256 on WaveNetPanelF32Kernel (wavenet_panel_f32_kernels.hip)
+	constexpr int WN_COL_STRIDE = 256;          // floats per ring in the steady-state column table (the widest array any kernel runs)
 
 	// Natural-layout tensor table used by the prewarm kernel and the runtime-shaped block kernel (one entry per conv ring).
 	struct WnPrewarmLayer

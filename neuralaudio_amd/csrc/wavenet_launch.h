@@ -251,6 +251,32 @@ namespace na
 		int nrings, int stateF4, int maxChannels, float headScale, bool gated, float* state, const int* slots, const int* rows, int numStreams, int slot0, int row0,
 		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
 
+	// Exact f32 for plain models of 129 .. 256 channels (wavenet_panel_f32_kernels.hip, WaveNetPanelF32Kernel): the same table, weight copy
+	// and stream state; one launch holds at most WN_PANEL_MAX_FRAMES frames (hipErrorInvalidValue beyond)
+	hipError_t LaunchWaveNetPanelF32(const WnPrewarmLayer* layers, int numLayers, const float* weights, const int* ringOffF4, const int* ringFrames, const int* ringG,
+		int nrings, int stateF4, int maxChannels, float headScale, float* state, const int* slots, const int* rows, int numStreams, int slot0, int row0,
+		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream);
+	// A chunk of n <= WN_MAX_FRAMES frames of a wide-f32 group on the kernel WaveNetExactF32LaunchFor names, as ordered launches of at most
+	// its maxFrames on `stream` (a launch of the panel kernel never reads a ring position it wrote: AddRing's history + 128 covers 64)
+	inline hipError_t LaunchWaveNetExactF32(const WnPrewarmLayer* layers, int numLayers, const float* weights, const int* ringOffF4, const int* ringFrames, const int* ringG,
+		int nrings, int stateF4, int maxChannels, float headScale, bool gated, float* state, const int* slots, const int* rows, int numStreams, int slot0, int row0,
+		const float* in, float* out, long inStride, long outStride, int n, hipStream_t stream)
+	{
+		const WaveNetExactF32LaunchChoice c = WaveNetExactF32LaunchFor(maxChannels, gated);
+		if (c.maxFrames <= 0) return hipErrorInvalidValue;
+		for (int at = 0; at < n; at += c.maxFrames)
+		{
+			const int piece = std::min(c.maxFrames, n - at);
+			const hipError_t err = c.panelNb != 0
+				? LaunchWaveNetPanelF32(layers, numLayers, weights, ringOffF4, ringFrames, ringG, nrings, stateF4, maxChannels, headScale, state, slots, rows, numStreams,
+					  slot0, row0, in + at, out + at, inStride, outStride, piece, stream)
+				: LaunchWaveNetWideF32(layers, numLayers, weights, ringOffF4, ringFrames, ringG, nrings, stateF4, maxChannels, headScale, gated, state, slots, rows,
+					  numStreams, slot0, row0, in + at, out + at, inStride, outStride, piece, stream);
+			if (err != hipSuccess) return err;
+		}
+		return hipSuccess;
+	}
+
 	// tuning aid: device buffer of long long[stages*4*waves] that workgroup 0 stamps with the shader clock (nullptr: off)
 	void SetWaveNetTraceBuffer(long long* deviceBuffer);
 	long long* GetWaveNetTraceBuffer();

@@ -321,6 +321,32 @@ namespace na
 		return c;
 	}
 
+	// Which kernel takes a launch of a wide-f32 group, and how many frames one launch holds.  Up to 128 channels (gated: 64) that is
+	// WaveNetWideF32Kernel<wideNb> with blocks of WN_MAX_FRAMES; plain models of 129 .. 256 channels (WaveNetDesc::exactF32) run
+	// WaveNetPanelF32Kernel (wavenet_panel_f32_kernels.hip), whose B image and weight panels leave room for 64 frames: panelNb = 16-channel
+	// blocks per matrix side of the instantiation, 12 (<= 192 channels) or 16 (<= 256).  The caller cuts a longer chunk into ordered
+	// launches of at most maxFrames (wavenet_launch.h LaunchWaveNetExactF32).  wideNb == 0 && panelNb == 0: no kernel takes the launch.
+	constexpr int WN_PANEL_MAX_FRAMES = 64;
+	struct WaveNetExactF32LaunchChoice
+	{
+		int wideNb = 0, panelNb = 0;
+		bool gated = false;
+		int maxFrames = 0;
+	};
+	inline WaveNetExactF32LaunchChoice WaveNetExactF32LaunchFor(int maxChannels, bool gated)
+	{
+		WaveNetExactF32LaunchChoice c;
+		c.gated = gated;
+		c.wideNb = WaveNetWideF32For(maxChannels, gated).nb;
+		if (c.wideNb != 0) c.maxFrames = WN_MAX_FRAMES;
+		else if (!gated && maxChannels > WN_GENERIC_MAX_CHANNELS && maxChannels <= WN_PANEL_MAX_CHANNELS)
+		{
+			c.panelNb = maxChannels <= 192 ? 12 : 16;
+			c.maxFrames = WN_PANEL_MAX_FRAMES;
+		}
+		return c;
+	}
+
 	inline WaveNetLaunchChoice WaveNetLaunchFor(const WaveNetLaunchFacts& f, const WaveNetKnobs& k)
 	{
 		using namespace choice_detail;

@@ -60,8 +60,16 @@ namespace na
 		{
 			const WnArrayCfg& cfg = desc.arrays[a];
 			if (cfg.channels < 1 || cfg.headSize < 1 || cfg.inputSize < 1) throw std::runtime_error("WaveNet layer array with a zero-sized dimension");
-			if (cfg.channels > WN_GENERIC_MAX_CHANNELS || cfg.headSize > WN_GENERIC_MAX_CHANNELS || cfg.inputSize > WN_GENERIC_MAX_CHANNELS)
-				throw std::runtime_error("WaveNet channels > 128 are not supported");
+			// 128 channels by default; 256 with exact f32 on request (WaveNetDesc::exactF32: WaveNetPanelF32Kernel runs 129 .. 256)
+			const int widest = std::max(cfg.channels, std::max(cfg.headSize, cfg.inputSize));
+			if (!desc.exactF32 && widest > WN_GENERIC_MAX_CHANNELS) throw std::runtime_error("WaveNet channels > 128 are not supported");
+			if (widest > WN_PANEL_MAX_CHANNELS)
+			{
+				std::stringstream str;
+				str << "WaveNet layer array " << a << ": " << widest << " channels (channels, head_size or input_size) are not supported: the limit is "
+				    << WN_PANEL_MAX_CHANNELS << " with exact f32 (NA_SetWaveNetExactF32), " << WN_GENERIC_MAX_CHANNELS << " without";
+				throw std::runtime_error(str.str());
+			}
 			if (cfg.headKernelSize > 1 && (cfg.channels > 64 || cfg.headSize > 64))
 				throw std::runtime_error("WaveNet: a conv head on a layer array wider than 64 channels is not supported");
 			if (cfg.conditionSize != 1) throw std::runtime_error("WaveNet condition_size != 1 is not supported");

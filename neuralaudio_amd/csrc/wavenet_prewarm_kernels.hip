@@ -32,7 +32,7 @@ namespace na
 	__global__ void __launch_bounds__(WN_COL_STRIDE) WaveNetPrewarmColumnsKernel(const WnPrewarmLayer* __restrict__ layers, int numLayers,
 		const float* __restrict__ w, float* __restrict__ cols /* [ring][WN_COL_STRIDE] */)
 	{
-		constexpr int CW = WN_COL_STRIDE; // 128 = one thread per channel
+		constexpr int CW = WN_COL_STRIDE; // 256 = one thread per channel of the widest array that loads (WN_PANEL_MAX_CHANNELS)
 		__shared__ float x[CW], z[CW], head[CW], lin[CW];
 		const int i = threadIdx.x;
 		x[i] = 0.0f; z[i] = 0.0f; head[i] = 0.0f; lin[i] = 0.0f; // condition = 0 (:748), headArray zero (:750)
